@@ -372,6 +372,34 @@ def emit_line(out):
         sys.stdout.flush()
 
 
+DUMP_LIMIT_BYTES = 64 << 20    # --dump-outputs: all files of one run together
+
+
+def dump_outputs(path, eng, best, world=1, rank=0):
+    """--dump-outputs DIR: what the timed path computed in its last step, as its caller receives it, in float64 --
+    best_index.npy / best_ei.npy (spx_get_best, after the collective; rank 0) and this rank's ei_mean.npy [M] and
+    ei_draws.npy [M, H] (spx_get_ei_mean / spx_get_ei_draws; with N > 1 ranks every rank writes its own shard as
+    <name>_rank<r>.npy).  Past DUMP_LIMIT_BYTES in all, the candidate rows are a fixed seeded sample whose row indices
+    (into this rank's shard) go to candidate_rows.npy.  The inputs are seeded, so two builds run with the same arguments
+    can be compared file for file."""
+    os.makedirs(path, exist_ok=True)
+    sfx = "_rank%d" % rank if world > 1 else ""
+    mean = np.asarray(eng.ei_mean(), dtype=np.float64)
+    draws = np.asarray(eng.ei_draws(), dtype=np.float64).reshape(mean.shape[0], -1)
+    M = mean.shape[0]
+    row_bytes = 8 * (1 + draws.shape[1])
+    budget = DUMP_LIMIT_BYTES // world - (1 << 16)          # room for the .npy headers and the two scalars
+    rows = np.arange(M)
+    if M * row_bytes > budget:
+        rows = np.sort(np.random.RandomState(12345).choice(M, budget // (row_bytes + 8), replace=False))
+        np.save(os.path.join(path, "candidate_rows%s.npy" % sfx), rows.astype(np.float64))
+    np.save(os.path.join(path, "ei_mean%s.npy" % sfx), mean[rows])
+    np.save(os.path.join(path, "ei_draws%s.npy" % sfx), draws[rows])
+    if rank == 0:
+        np.save(os.path.join(path, "best_index.npy"), np.array([best[0]], dtype=np.float64))
+        np.save(os.path.join(path, "best_ei.npy"), np.array([best[1]], dtype=np.float64))
+
+
 def engine_class():
     """The engine the bench drives: spearmint_amd.engine.Engine (libspx.so, no fallback).  TEST HOOK, never set by the
     driver: SPX_BENCH_ENGINE="module:Class" substitutes another class with the same methods, so that the launch / rank /
@@ -396,15 +424,20 @@ def free_port():
 
 def self_launch(args, argv):
     """`python bench.py --gpus N` with N > 1 and no launcher around it (WORLD_SIZE unset): start the N ranks ourselves --
-    re-exec this very command under `python -m torch.distributed.run --nnodes=1 --nproc-per-node N` (one process per
-    GPU, rendezvous on 127.0.0.1, a free port) -- so that the one command the driver runs for the scaling curve yields
-    N ranks, not one.  Refuses (non-zero exit, no JSON line) when the node has fewer than N devices: a line whose
+    run this very command as a child under `python -m torch.distributed.run --nnodes=1 --nproc-per-node N` (one process
+    per GPU, rendezvous on 127.0.0.1, a free port) and exit with its status -- so that the one command the driver runs
+    for the scaling curve yields N ranks, not one.  This process never opens a GPU itself: the device count comes from a
+    short-lived child.  Refuses (non-zero exit, no JSON line) when the node has fewer than N devices: a line whose
     n_gpus differs from --gpus is never printed."""
     n = int(args.gpus)
     single = bool(os.environ.get("SPX_BENCH_SINGLE_DEVICE"))
     if not single and not os.environ.get("SPX_BENCH_ENGINE"):
-        from spearmint_amd import engine as _e
-        have = _e.device_count()
+        probe = subprocess.run([sys.executable, "-c", "from spearmint_amd import engine; print(engine.device_count())"],
+                               cwd=ROOT, stdout=subprocess.PIPE, stderr=subprocess.PIPE, timeout=120)
+        try:
+            have = int(probe.stdout.decode().strip().splitlines()[-1])
+        except (ValueError, IndexError):
+            have = 0
         if have < n:
             raise SystemExit("bench.py: --gpus %d but this node shows %d GPU(s); refusing to run fewer ranks than asked "
                              "for (SPX_BENCH_SINGLE_DEVICE=1 puts all ranks on device 0: a plumbing test, not a measurement)"
@@ -415,7 +448,7 @@ def self_launch(args, argv):
     env.setdefault("HSA_ENABLE_IPC_MODE_LEGACY", "0")      # RCCL across processes needs dmabuf IPC on this pool
     sys.stdout.flush()
     sys.stderr.flush()
-    os.execve(sys.executable, cmd, env)
+    sys.exit(subprocess.call(cmd, env=env))
 
 
 def weak_problem(w, rank):
@@ -481,6 +514,8 @@ def main_in_process(args):
     if args.warmup:
         run(args.warmup)
     dt, best = run(args.steps)
+    if args.dump_outputs:
+        dump_outputs(args.dump_outputs, eng, best)
     out = {
         "metric": "EI candidate evaluations per second (N_cand x mcmc_iters / wall time)",
         "value": n * float(M) * H * args.steps / dt, "unit": "EI evals/s", "n_gpus": n, "ranks_seen": eng.stat("ranks_seen"),
@@ -578,15 +613,20 @@ def main():
                          "RCCL all-gather inside the library) instead of one process per GPU; what the unmodified "
                          "single-process Spearmint driver uses with --method-args=ndev=N")
     ap.add_argument("--devices", default="", help="with --in-process: comma-separated device ids (default 0..gpus-1)")
+    ap.add_argument("--dump-outputs", default="", metavar="DIR",
+                    help="after the timed steps write what the last one computed (best index / EI, per-candidate EI mean "
+                         "and per-draw EI) as float64 DIR/<name>.npy, at most 64 MB in all")
     args = ap.parse_args()
     if args.gpus < 1:
         raise SystemExit("--gpus must be >= 1")
+    if args.steps < 1 or args.warmup < 0:
+        raise SystemExit("--steps must be >= 1 and --warmup >= 0")
     if args.next_baseline:
         return emit_line(next_baseline())
     if args.in_process:
         return main_in_process(args)
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ:
-        return self_launch(args, sys.argv[1:])          # does not return: exec of the launcher
+        return self_launch(args, sys.argv[1:])          # does not return: exits with the launcher's status
 
     world = int(os.environ.get("WORLD_SIZE", "1"))
     rank = int(os.environ.get("RANK", "0"))
@@ -639,6 +679,12 @@ def main():
     N, M, D, H = w["N"], w["M"], w["D"], w["H"]
     flags = FLAG_PER_SEC if w["per_sec"] else 0
     prob, comp, vals, hypers, shard = weak_problem(w, rank)
+
+    # the rocprofv3 passes of roofline.traffic run before this process opens the GPU, so that the profiled children are not
+    # started from a process that holds a device
+    live = None
+    if world == 1 and not args.no_live_traffic and engine_name == "libspx":
+        live = live_traffic(args.workload)
 
     eng = EngineCls(local_rank)
     eng.set_observations(comp, vals)
@@ -713,6 +759,8 @@ def main():
     if args.warmup:
         run_steps(eng, flags, args.warmup)
     dt, best = run_steps(eng, flags, args.steps, tag="headline")
+    if args.dump_outputs:
+        dump_outputs(args.dump_outputs, eng, best, world, rank)
     evals_per_step = float(M) * H
     value = world * evals_per_step * args.steps / dt
 
@@ -732,8 +780,8 @@ def main():
         achieved = flops_per_eval * evals_per_launch / avg_s / 1e12
         traffic, traffic_src, traffic_note = None, None, None
         if world == 1:
-            if not args.no_live_traffic:
-                traffic, traffic_src = live_traffic(args.workload)
+            if live is not None:
+                traffic, traffic_src = live
                 if traffic is None:
                     traffic_note = traffic_src
             if traffic is None:

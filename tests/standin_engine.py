@@ -54,6 +54,9 @@ class Engine(object):
     def best(self):
         return self._best
 
+    def ei_mean(self):
+        return np.mean(self._draws, axis=1)
+
     def ei_draws(self):
         return self._draws
 

@@ -37,6 +37,16 @@ def test_pick_best_numpy_rule():
         assert sd.pick_best(recs)[0] == int(np.argmax(v))
 
 
+def _spawn_context():
+    """torch.distributed runs in spawned children only: torch is never imported into the test process itself, whose HIP
+    runtime and librccl (bound by libspx.so) the GPU tests of the same session go on to use."""
+    import importlib.util
+    import multiprocessing
+    if importlib.util.find_spec("torch") is None:
+        pytest.skip("torch is not installed")
+    return multiprocessing.get_context("spawn")
+
+
 def _free_port():
     s = socket.socket(); s.bind(("127.0.0.1", 0)); p = s.getsockname()[1]; s.close()
     return p
@@ -61,9 +71,7 @@ def _worker(rank, world, port, q):
 
 
 def test_exchange_best_gloo_world2():
-    torch = pytest.importorskip("torch")
-    import torch.multiprocessing as mp
-    ctx = mp.get_context("spawn")
+    ctx = _spawn_context()
     q = ctx.Queue()
     port = _free_port()
     procs = [ctx.Process(target=_worker, args=(r, 2, port, q)) for r in range(2)]
@@ -78,8 +86,19 @@ def test_exchange_best_gloo_world2():
         assert o2[0] == 900 and np.isnan(o2[1])
 
 
+def _exchange_alone(q):
+    q.put(sd.exchange_best(1.5, 42))
+
+
 def test_allreduce_without_group_is_identity():
-    assert sd.exchange_best(1.5, 42) == (42, 1.5)
+    ctx = _spawn_context()
+    q = ctx.Queue()
+    p = ctx.Process(target=_exchange_alone, args=(q,))
+    p.start()
+    out = q.get(timeout=120)
+    p.join(60)
+    assert p.exitcode == 0
+    assert out == (42, 1.5)
 
 
 def test_strong_scaling_grid_does_not_depend_on_world_size():
@@ -127,11 +146,9 @@ def _worker_2d(rank, world, port, q):
 def test_2d_partition_allreduce_gloo_world4():
     """draws x candidates over 4 ranks (2 x 2): one all-reduce(SUM) of the M-vector, every rank ends with the mean EI
     of every candidate and the reference's argmax."""
-    torch = pytest.importorskip("torch")
-    import torch.multiprocessing as mp
     from oracle import gp_ei_oracle as orc
     from spearmint_amd.synthetic import synthetic_problem
-    ctx = mp.get_context("spawn")
+    ctx = _spawn_context()
     q = ctx.Queue()
     port = _free_port()
     procs = [ctx.Process(target=_worker_2d, args=(r, 4, port, q)) for r in range(4)]
@@ -204,3 +221,60 @@ def test_bench_refuses_a_line_whose_n_gpus_is_not_what_was_asked_for():
     assert rc != 0 and out is None and "--gpus 2" in err and "GPU" in err
     rc, out, err = _bench(["--gpus", "2"] + SMALL, dict(STANDIN, WORLD_SIZE="1", RANK="0"))
     assert rc != 0 and out is None and "WORLD_SIZE=1" in err
+
+
+def test_bench_dump_outputs_writes_the_last_timed_step(tmp_path):
+    """--dump-outputs DIR: the last timed step's results as float64 .npy files (best index / EI as the line reports them,
+    the per-candidate EI mean and the per-draw EI), identical for two runs with the same arguments; --steps is the number
+    of timed steps the line reports, with its ms_per_step."""
+    from oracle import gp_ei_oracle as orc
+    import bench
+    runs = []
+    for k in range(2):
+        d = str(tmp_path / ("run%d" % k))
+        rc, out, err = _bench(["--gpus", "1"] + SMALL[:4] + ["--steps", "2"] + SMALL[6:] + ["--dump-outputs", d], STANDIN)
+        assert rc == 0 and out is not None, err[-2000:]
+        assert out["steps"] == 2 and out["ms_per_step"] > 0
+        got = {f[:-4]: np.load(os.path.join(d, f)) for f in os.listdir(d)}
+        assert sorted(got) == ["best_ei", "best_index", "ei_draws", "ei_mean"]
+        assert all(a.dtype == np.float64 for a in got.values())
+        assert got["best_index"][0] == out["best_index"] and got["best_ei"][0] == out["best_ei"]
+        runs.append(got)
+    assert all(np.array_equal(runs[0][n], runs[1][n]) for n in runs[0])
+    w = dict(bench.WORKLOADS["c2"], M=1500)
+    _, comp, vals, hypers, s0 = bench.weak_problem(w, 0)
+    ei = orc.ei_over_hypers(comp, s0, vals, hypers)
+    assert runs[0]["ei_draws"].shape == (1500, w["H"]) and np.allclose(runs[0]["ei_draws"], ei, rtol=1e-9, atol=0)
+    assert np.allclose(runs[0]["ei_mean"], np.mean(ei, axis=1), rtol=1e-9, atol=0)
+    assert int(runs[0]["best_index"][0]) == int(np.argmax(runs[0]["ei_mean"]))
+
+
+def test_bench_dump_outputs_samples_rows_past_the_limit(tmp_path, monkeypatch):
+    """Past DUMP_LIMIT_BYTES the candidate rows are a fixed seeded sample, the same rows of ei_mean and ei_draws, with
+    their indices stored beside them."""
+    import bench
+
+    class Done(object):
+        def __init__(self, draws):
+            self.draws = draws
+
+        def ei_mean(self):
+            return np.mean(self.draws, axis=1)
+
+        def ei_draws(self):
+            return self.draws
+
+    draws = np.random.RandomState(1).rand(5000, 4)
+    monkeypatch.setattr(bench, "DUMP_LIMIT_BYTES", 100000 + (1 << 16))
+    for k in range(2):
+        d = str(tmp_path / ("run%d" % k))
+        bench.dump_outputs(d, Done(draws), (7, 0.5))
+        total = sum(os.path.getsize(os.path.join(d, f)) for f in os.listdir(d))
+        assert total <= bench.DUMP_LIMIT_BYTES
+        rows = np.load(os.path.join(d, "candidate_rows.npy")).astype(np.int64)
+        assert 0 < rows.size < 5000 and np.all(np.diff(rows) > 0)
+        assert np.array_equal(np.load(os.path.join(d, "ei_draws.npy")), draws[rows])
+        assert np.array_equal(np.load(os.path.join(d, "ei_mean.npy")), np.mean(draws, axis=1)[rows])
+        if k:
+            assert np.array_equal(rows, first)
+        first = rows
