@@ -58,6 +58,10 @@ typedef struct spx_handle spx_handle;
                                     computed (spx_get_time_mean); no EI, no winner.  The per-second chooser's pending
                                     branch needs exactly that from its first pass (GPEIperSecChooser.py:492-548: the two
                                     GPs have different observation sets there)                                      */
+#define SPX_FLAG_CONSTRAINED 16  /* multiply every draw's EI by the constraint model's P_d(x) = Phi(gain_d k_c(x,X_c)' alpha_c)
+                                    (GPConstrainedEIChooser.py:816-842, :931-940) before the mean over draws; needs
+                                    spx_set_constraint_model().  SPX_ERR_ARG with SPX_FLAG_PER_SEC, on a multi-device
+                                    handle and with a communicator attached                                          */
 
 /* ---- lifetime ---------------------------------------------------------- */
 /* Create an engine on HIP device `device_id` (lazy: the first call that needs
@@ -142,6 +146,15 @@ int spx_set_hypers(spx_handle* h, const double* hypers, int32_t H);
  * log_durs (N), time_hypers H x (3+D).  Pass NULLs to clear.                  */
 int spx_set_time_model(spx_handle* h, const double* log_durs,
                        const double* time_hypers);
+/* Probit constraint GP (GPConstrainedEIChooser.py:816-842): Nc points comp_c (Nc x D, all completed jobs, Nc independent
+ * of the objective's N), their latent values ff (Nc) and H rows c_hypers [gain, noise_c, amp2_c, ls_c...] (H and D as
+ * spx_set_hypers set them).  alpha_c = (amp2_c (k(X_c,X_c) + 1e-6 I) + noise_c I)^-1 ff -- no mean term -- is factored
+ * by the next spx_factor / spx_ei_step, before the objective draws, on an internal handle of the same device (same
+ * factorisation path, SPX_ERR_NOT_PD as for the objective; spx_not_pd_info reports draw 2H + d).  Nc = 0 is the
+ * all-valid case (comp_c / ff may be NULL): P_d = Phi(gain_d).  All three pointers NULL clears the model.
+ * SPX_ERR_ARG on a multi-device handle.                                                                            */
+int spx_set_constraint_model(spx_handle* h, const double* comp_c, const double* ff, int64_t Nc,
+                             const double* c_hypers);
 
 /* Hot path, stage 1: for every draw build K(X,X)+noise (gp.py:34-54,120-127;
  * GPEIChooser.py:186,190), factor it (:191), and form what the solves need
@@ -276,10 +289,22 @@ int spx_get_moments(spx_handle* h, int32_t draw, double* func_m, double* func_v)
 /* exp(predicted log duration) of every candidate under time draw `draw`
  * (func_time_m, GPEIperSecChooser.py:452-458); needs SPX_FLAG_PER_SEC | SPX_FLAG_KEEP_MOMENTS. */
 int spx_get_time_mean(spx_handle* h, int32_t draw, double* out /* M */);
+/* P_d(x) of every candidate under draw `draw` of the constraint model; needs SPX_FLAG_CONSTRAINED | SPX_FLAG_KEEP_MOMENTS
+ * on the last pass (spx_get_ei_draws then holds EI_d * P_d).                                                          */
+int spx_get_constraint_prob(spx_handle* h, int32_t draw, double* out /* M */);
 /* GP marginal log-likelihood data term  -sum(log diag L) - 0.5 r' K^-1 r  for
  * each resident draw (GPEIChooser.py:281-285): out has H entries, -inf where
  * the covariance is not PD.  Needs spx_set_observations + spx_set_hypers.      */
 int spx_gp_logprob(spx_handle* h, double* out);
+/* The same data term with a right-hand side of its own per hyper row (the probit constraint GP's [amp2_c, ff] slice move,
+ * GPConstrainedEIChooser.py:1159-1201, where every proposal carries its own ff): n_rows (1 .. 32, one launch) rows
+ * [mean, noise, amp2, ls...] -- [0, noise_c, amp2_c, ls_c...] for that move -- and rhs (n_rows x N, row-major); row k's
+ * residual is rhs[k] - mean_k.  The points are THIS handle's resident observations (spx_set_observations; their values
+ * are not read): the constrained chooser keeps a handle of its own holding the completed points.  Replaces the
+ * resident hypers as spx_set_hypers does.  With rhs[k] = vals - mean_k for every row the result equals spx_gp_logprob
+ * bit for bit.  lp_out: n_rows values, -inf where not PD.  SPX_ERR_ARG on a multi-device handle.                 */
+int spx_gp_logprob_rhs(spx_handle* h, const double* rows, const double* rhs /* n_rows x N */, int32_t n_rows,
+                       double* lp_out);
 /* Objective of the local refinement (GPEIOptChooser.py:360-525 grad_optimize_ei_over_hypers;
  * "next" row 3) at P points in ONE call -- the reference runs grid_subset (20) L-BFGS-B problems,
  * one objective evaluation at a time (:265-291): points (P x D) -> neg_ei[p] = the summed

@@ -1091,6 +1091,7 @@ struct FlowCov {
     const double* comp; const double* hyp; const double* vals;   // observations [N][D], raw hyper rows [nh][hs], values [N]
     int D, hs;
     double* lp_out; int* info_out;
+    int64_t vals_stride;          // 0: one vector of values for every draw; N: draw h reads vals[h N ..] (spx_gp_logprob_rhs)
 };
 
 template <int KIND>
@@ -1247,7 +1248,7 @@ __device__ __forceinline__ void flow_rhs_tile(const FlowCov& cv, int h, int J, d
     for (int nt = 0; nt < 4; ++nt) {
         const int col = J * NB + 16 * nt + li;
         acc[nt] = (d4){0.0, 0.0, 0.0, 0.0};
-        if (wave == 0 && g == 0 && col < cv.N) acc[nt][0] = cv.vals[col] - mean;
+        if (wave == 0 && g == 0 && col < cv.N) acc[nt][0] = cv.vals[(size_t)h * cv.vals_stride + col] - mean;
     }
 }
 
@@ -1502,9 +1503,10 @@ void launch_lean_flow(hipStream_t s, double* Lt, double* Dinv, int* info, double
                       const double* Xs, const double* X2s, const double* s1, const double* htab, int N, int Dp, int kind,
                       int* cu_busy, int spin_limit, const FlowFused* fused)
 {
-    FlowCov cov{Xs, X2s, s1, htab, N, Dp, kind, nullptr, nullptr, nullptr, 0, 0, nullptr, nullptr};
+    FlowCov cov{Xs, X2s, s1, htab, N, Dp, kind, nullptr, nullptr, nullptr, 0, 0, nullptr, nullptr, 0};
     if (fused) {
         cov.comp = fused->comp; cov.hyp = fused->hyp; cov.vals = fused->vals; cov.D = fused->D; cov.hs = fused->hs;
+        cov.vals_stride = fused->vals_stride;
         cov.lp_out = fused->lp_out; cov.info_out = fused->info_out;
     }
     const int nblk = Np / NB;
@@ -1669,7 +1671,7 @@ void launch_lean_trsm(hipStream_t s, double* Lt, const double* Dinv, double* rhs
 __global__ __launch_bounds__(256) void k_lean_rhs_init(const double* __restrict__ vals,
                                                        const double* __restrict__ htab,
                                                        double* __restrict__ rhs, int N, int Np,
-                                                       int* __restrict__ info, int* __restrict__ flags)
+                                                       int* __restrict__ info, int* __restrict__ flags, int64_t vals_stride)
 {
     const int h = blockIdx.y;
     const int idx = blockIdx.x * 256 + threadIdx.x;      // over [nblk][4096]
@@ -1683,14 +1685,15 @@ __global__ __launch_bounds__(256) void k_lean_rhs_init(const double* __restrict_
     const int wave = t >> 6, lane = t & 63, r = q & 3, nt = q >> 2;
     const int rowi = 16 * wave + (lane >> 4) + 4 * r, col = J * NB + 16 * nt + (lane & 15);
     double v = 0.0;
-    if (rowi == 0 && col < N) v = vals[col] - htab[h * SPX_HT + 0];
+    if (rowi == 0 && col < N) v = vals[(size_t)h * vals_stride + col] - htab[h * SPX_HT + 0];
     rhs[(size_t)h * NB * Np + idx] = v;
 }
 
 void launch_lean_rhs_init(hipStream_t s, const double* vals, const double* htab, double* rhs, int N, int Np, int nh,
-                          int* info, int* flags)
+                          int* info, int* flags, int64_t vals_stride)
 {
-    hipLaunchKernelGGL(k_lean_rhs_init, dim3((NB * Np + 255) / 256, nh), dim3(256), 0, s, vals, htab, rhs, N, Np, info, flags);
+    hipLaunchKernelGGL(k_lean_rhs_init, dim3((NB * Np + 255) / 256, nh), dim3(256), 0, s, vals, htab, rhs, N, Np, info, flags,
+                       vals_stride);
 }
 
 // lp = -sum log diag(L) - 0.5 |y|^2 (GPEIChooser.py:284) from the diagonal the diag blocks left in diagL
@@ -1927,20 +1930,21 @@ void launch_alpha(hipStream_t s, const double* WT, const double* gamma, double* 
 // block that k_chol_panel carries through the factorisation (log-likelihood path)
 __global__ __launch_bounds__(256) void k_rhs_init(const double* __restrict__ vals,
                                                   const double* __restrict__ htab,
-                                                  double* __restrict__ rhs, int N, int Np)
+                                                  double* __restrict__ rhs, int N, int Np, int64_t vals_stride)
 {
     const int h = blockIdx.y;
     const int idx = blockIdx.x * 256 + threadIdx.x;      // over [64][Np]
     if (idx >= NB * Np) return;
     const int row = idx / Np, j = idx - row * Np;
     double v = 0.0;
-    if (row == 0 && j < N) v = vals[j] - htab[h * SPX_HT + 0];
+    if (row == 0 && j < N) v = vals[(size_t)h * vals_stride + j] - htab[h * SPX_HT + 0];
     rhs[(size_t)h * NB * Np + idx] = v;
 }
 
-void launch_rhs_init(hipStream_t s, const double* vals, const double* htab, double* rhs, int N, int Np, int nh)
+void launch_rhs_init(hipStream_t s, const double* vals, const double* htab, double* rhs, int N, int Np, int nh,
+                     int64_t vals_stride)
 {
-    hipLaunchKernelGGL(k_rhs_init, dim3((NB * Np + 255) / 256, nh), dim3(256), 0, s, vals, htab, rhs, N, Np);
+    hipLaunchKernelGGL(k_rhs_init, dim3((NB * Np + 255) / 256, nh), dim3(256), 0, s, vals, htab, rhs, N, Np, vals_stride);
 }
 
 // lp = -sum log diag(L) - 0.5 |gamma|^2   (GPEIChooser.py:284); -inf if not PD

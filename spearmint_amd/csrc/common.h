@@ -51,7 +51,7 @@ void launch_scale_rows(hipStream_t s, const double* x, int64_t n, int64_t n_pad,
 // the log-likelihood path's prologue in ONE launch: launch_scale_rows (factor 1, with the doubled copy) + launch_lean_rhs_init
 void launch_lean_prologue(hipStream_t s, const double* x, int64_t n, int64_t n_pad, int D, int Dp, const double* ls,
                           int ls_stride, int nh, double* xs, double* sumsq, double* xs2, const double* vals,
-                          const double* htab, double* rhs, int* info, int* flags);
+                          const double* htab, double* rhs, int* info, int* flags, int64_t vals_stride = 0);
 void launch_cov_self(hipStream_t s, const double* Xs, const double* s1, const double* X2s,
                      const double* htab, double* K, int N, int Np, int Dp, int nh, bool tiled = false,
                      int kind = SPX_COV_MATERN52);
@@ -62,6 +62,10 @@ void launch_cov_cross(hipStream_t s, const double* Xs, const double* s1, const d
 void launch_cross_mean(hipStream_t s, const double* Xs, const double* s1, const double* Cs,
                        const double* s2, const double* htab, const double* alpha, double* out,
                        int N, int Np, int Mc, int Dp, int nh, int kind = SPX_COV_MATERN52);
+void launch_constraint_prob(hipStream_t s, const double* Xs, const double* s1, const double* Cs,
+                            const double* s2, const double* htab, const double* alpha, double* out,
+                            int N, int Np, int Mc, int Dp, int nh, int kind);
+void launch_constraint_const(hipStream_t s, const double* htab, double* out, int Mc, int nh);
 
 // chol_kernels.hip
 void launch_chol_diag(hipStream_t s, double* L, double* Dinv, int* info, int Np, int k, int nh, int updated = 0);
@@ -76,13 +80,14 @@ void launch_lean_step_ps(hipStream_t s, double* Lt, double* Dinv, int* info, dou
 struct FlowFused {
     const double* comp; const double* hyp; const double* vals; int D, hs;
     double* lp_out; int* info_out;
+    int64_t vals_stride;   // 0: vals shared by every draw; N: a right-hand side per draw (spx_gp_logprob_rhs)
 };
 void launch_lean_flow(hipStream_t s, double* Lt, double* Dinv, int* info, double* rhs, double* diagL, int* lflags,
                       int* dflags, unsigned* tickets, int Np, int nh, int gen, bool alone,
                       const double* Xs, const double* X2s, const double* s1, const double* htab, int N, int Dp, int kind,
                       int* cu_busy, int spin_limit = 0, const FlowFused* fused = nullptr);
 void launch_lean_rhs_init(hipStream_t s, const double* vals, const double* htab, double* rhs, int N, int Np, int nh,
-                          int* info, int* flags);
+                          int* info, int* flags, int64_t vals_stride = 0);
 void launch_lean_logprob(hipStream_t s, const double* diagL, const double* rhs, const int* info, double* out, int* info_out,
                          int N, int Np, int nh);
 void launch_trinv(hipStream_t s, const double* L, const double* Dinv, double* WT, int Np, int nh, bool tiled = false);
@@ -92,7 +97,8 @@ void launch_gamma_multi(hipStream_t s, const double* WT_h, const double* rhs, co
                         double* gamma, int N, int Np, int S);
 void launch_gemv_lower(hipStream_t s, const double* WT, const double* rhs, double* out, int Np, int nh);
 void launch_alpha(hipStream_t s, const double* WT, const double* gamma, double* alpha, int Np, int nh);
-void launch_rhs_init(hipStream_t s, const double* vals, const double* htab, double* rhs, int N, int Np, int nh);
+void launch_rhs_init(hipStream_t s, const double* vals, const double* htab, double* rhs, int N, int Np, int nh,
+                     int64_t vals_stride = 0);
 void launch_logprob(hipStream_t s, const double* L, const double* gamma, size_t gstride, const int* info,
                     double* out, int Np, int nh);
 
@@ -112,7 +118,7 @@ void launch_point_finish(hipStream_t s, const double* Xs, const double* hyp, con
 
 // fused_kernels.hip: the whole EI pass of a chunk for N <= 128 in one launch (no K* / beta in memory)
 void launch_ei_fused128(hipStream_t s, int kind, const double* WT, const double* gamma, const double* Xs, const double* s1,
-                        const double* Cs, const double* s2, const double* htab, const double* time_m, double best,
+                        const double* Cs, const double* s2, const double* htab, const double* time_m, const double* cprob, double best,
                         double* ei_draw, double* mom_m, double* mom_v, int N, int Mc, int Dp, int nh, int64_t c0,
                         int64_t M, int64_t Mp, int n_cu);
 
@@ -126,11 +132,11 @@ void launch_predict_gemm(hipStream_t s, int variant, const double* WT, const dou
 bool predict_gemm_variant_ok(int v);
 int predict_gemm_padding_plan(int variant, int N, int Np);
 void launch_ei_finalize_fant(hipStream_t s, const double* part_ss, const double* part_bgS,
-                             const double* htab, const double* bests, const double* time_m,
+                             const double* htab, const double* bests, const double* time_m, const double* cprob,
                              double* ei_draw, int nrb, int Mc, int nh, int S, int64_t c0, int64_t M,
                              int64_t Mp, int h0, double* ei_s);
 void launch_ei_finalize(hipStream_t s, const double* part_ss, const double* part_bg,
-                        const double* htab, const double* time_m, double best, double* ei_draw,
+                        const double* htab, const double* time_m, const double* cprob, double best, double* ei_draw,
                         double* mom_m, double* mom_v, int nrb, int Mc, int nh, int64_t c0,
                         int64_t M, int64_t Mp, int h0);
 void launch_mean_over_draws(hipStream_t s, const double* ei_draw, double* ei_mean, int64_t M,

@@ -12,6 +12,7 @@
 // norm / Matern part is the epilogue on the accumulator registers, so the
 // squared-distance matrix never exists in memory.
 #include "common.h"
+#include "ei_device.h"   // ndtr_dev: the constraint probability (MODE 4)
 
 #ifndef SPX_COV_HOIST
 #define SPX_COV_HOIST 1   // keep the column-side fragments in registers across row tiles
@@ -100,7 +101,7 @@ __global__ __launch_bounds__(256) void k_lean_prologue(
     const double* __restrict__ ls, int ls_stride,
     double* __restrict__ xs, double* __restrict__ sumsq, double* __restrict__ xs2, int nsb,
     const double* __restrict__ vals, const double* __restrict__ htab, double* __restrict__ rhs,
-    int* __restrict__ info, int* __restrict__ flags)
+    int* __restrict__ info, int* __restrict__ flags, int64_t vals_stride)
 {
     const int h = blockIdx.y;
     if ((int)blockIdx.x < nsb) {
@@ -120,23 +121,23 @@ __global__ __launch_bounds__(256) void k_lean_prologue(
     const int wave = t >> 6, lane = t & 63, r = q & 3, nt = q >> 2;
     const int rowi = 16 * wave + (lane >> 4) + 4 * r, col = J * SPX_NB + 16 * nt + (lane & 15);
     double v = 0.0;
-    if (rowi == 0 && col < N) v = vals[col] - htab[h * SPX_HT + 0];
+    if (rowi == 0 && col < N) v = vals[(size_t)h * vals_stride + col] - htab[h * SPX_HT + 0];
     rhs[(size_t)h * SPX_NB * Np + idx] = v;
 }
 
 void launch_lean_prologue(hipStream_t s, const double* x, int64_t n, int64_t n_pad, int D, int Dp, const double* ls,
                           int ls_stride, int nh, double* xs, double* sumsq, double* xs2, const double* vals,
-                          const double* htab, double* rhs, int* info, int* flags)
+                          const double* htab, double* rhs, int* info, int* flags, int64_t vals_stride)
 {
     const int nrhs = (int)((SPX_NB * n_pad + 255) / 256);
     if (((n_pad + 255) / 256) * nh < 512) {
         const int nsb = (int)((n_pad + 63) / 64);
         hipLaunchKernelGGL(k_lean_prologue<64>, dim3(nsb + nrhs, nh), dim3(256), 0, s, x, n, n_pad, D, Dp, ls, ls_stride, xs, sumsq,
-                           xs2, nsb, vals, htab, rhs, info, flags);
+                           xs2, nsb, vals, htab, rhs, info, flags, vals_stride);
     } else {
         const int nsb = (int)((n_pad + 255) / 256);
         hipLaunchKernelGGL(k_lean_prologue<256>, dim3(nsb + nrhs, nh), dim3(256), 0, s, x, n, n_pad, D, Dp, ls, ls_stride, xs, sumsq,
-                           xs2, nsb, vals, htab, rhs, info, flags);
+                           xs2, nsb, vals, htab, rhs, info, flags, vals_stride);
     }
 }
 
@@ -200,7 +201,7 @@ __device__ __forceinline__ void cov_run(
         }
     }
 
-    // MODE 2 accumulates sum_j k[j][c] alpha[j] for this lane's column(s)
+    // MODE 2 / 4 accumulate sum_j k[j][c] alpha[j] for this lane's column(s)
     double colsum[4] = {0.0, 0.0, 0.0, 0.0};
 
     // Matern epilogue of one 16 x 64 tile on the accumulator layout: row = j0 + g + 4 r,
@@ -211,7 +212,7 @@ __device__ __forceinline__ void cov_run(
             const int j = j0 + g + 4 * r;
             const double s1v = s1h[j];
             double av = 0.0;
-            if (MODE == 2) av = alpha[(size_t)h * Np + j];
+            if (MODE == 2 || MODE == 4) av = alpha[(size_t)h * Np + j];
             const double amp_j = (j < N) ? amp2 : 0.0;
             double gv[4], cv[4];
 #pragma unroll
@@ -293,9 +294,9 @@ __device__ __forceinline__ void cov_run(
         epilogue(acc, j0);
     }
 
-    if (MODE == 2) {
+    if (MODE == 2 || MODE == 4) {
         __shared__ double red[4][64];
-        const double mean = htab[h * SPX_HT + 0];
+        const double mean = htab[h * SPX_HT + 0];   // MODE 4: the constraint model's gain (its table, not the factor's)
 #pragma unroll
         for (int nt = 0; nt < 4; ++nt) {
             double v = colsum[nt];
@@ -307,7 +308,9 @@ __device__ __forceinline__ void cov_run(
         if (threadIdx.x < 64) {
             const int c = threadIdx.x;
             const double dot = ((red[0][c] + red[1][c]) + red[2][c]) + red[3][c];
-            out[(size_t)h * Mc + c0 + c] = exp(dot + mean);
+            // MODE 2: exp(predicted log duration), GPEIperSecChooser.py:452-458; MODE 4: the probability of not violating a
+            // constraint, sps.norm.cdf(gain * K*_c' alpha_c) (GPConstrainedEIChooser.py:837-842)
+            out[(size_t)h * Mc + c0 + c] = (MODE == 2) ? exp(dot + mean) : ndtr_dev(mean * dot);
         }
     }
 }
@@ -322,8 +325,8 @@ __global__ __launch_bounds__(256, 2) void k_cov(
     // live_rows (MODE 0, a multiple of 16, >= N): the rows from there on are padding whose consumer skips them
     // (k_predict_gemm_tri<true>): they are not computed and not written
     const int jtop = (MODE == 0 && live_rows > 0) ? live_rows : Np;
-    const int jbeg = (MODE == 2) ? 0 : blockIdx.y * rows_per_wg;
-    const int jend = (MODE == 2) ? Np : min(jtop, jbeg + rows_per_wg);
+    const int jbeg = (MODE == 2 || MODE == 4) ? 0 : blockIdx.y * rows_per_wg;
+    const int jend = (MODE == 2 || MODE == 4) ? Np : min(jtop, jbeg + rows_per_wg);
     cov_run<MODE, QC, KIND>(Xs, s1, Cs, s2, htab, alpha, out, N, Np, Mc, Dp, nchunks, ldo, blockIdx.z, blockIdx.x * 64, jbeg, jend);
 }
 
@@ -366,7 +369,7 @@ static void launch_cov_kind(hipStream_t s, const double* Xs, const double* s1, c
     if (rpw && MODE == 3) rows_per_wg = atoi(rpw);
 #endif
     const int row_top = (MODE == 0 && live_rows > 0) ? live_rows : Np;     // (MODE 0: rows past live_rows are left alone)
-    dim3 grid(Mc / 64, (MODE == 2) ? 1 : (row_top + rows_per_wg - 1) / rows_per_wg, nh);
+    dim3 grid(Mc / 64, (MODE == 2 || MODE == 4) ? 1 : (row_top + rows_per_wg - 1) / rows_per_wg, nh);
     dim3 block(256);
     if (MODE == 0) {
         // a launch of several residency rounds: whole rounds, equal shares (k_cov_flat); `places` = 2 workgroups per CU
@@ -430,4 +433,28 @@ void launch_cross_mean(hipStream_t s, const double* Xs, const double* s1, const 
                        int N, int Np, int Mc, int Dp, int nh, int kind)
 {
     launch_cov_mode<2>(s, kind, Xs, s1, Cs, s2, htab, alpha, out, N, Np, Mc, Dp, nh, Mc);
+}
+
+// The constraint model's P_d(x) for every (candidate of the chunk, draw): the fused k_c(x, X_c)' alpha_c of launch_cross_mean
+// over the Nc constraint points (K*_c is never stored), then Phi(gain_d * m) in the epilogue.  htab: [gain, noise_c, amp2_c,
+// .] per draw (slot 0 holds the gain here, where the factor's table holds the zero mean).  out[nh][Mc].
+void launch_constraint_prob(hipStream_t s, const double* Xs, const double* s1, const double* Cs,
+                            const double* s2, const double* htab, const double* alpha, double* out,
+                            int N, int Np, int Mc, int Dp, int nh, int kind)
+{
+    launch_cov_mode<4>(s, kind, Xs, s1, Cs, s2, htab, alpha, out, N, Np, Mc, Dp, nh, Mc);
+}
+
+// No constraint violation observed yet (all labels 1): the reference squashes the scalar 1 (GPConstrainedEIChooser.py:
+// 816-819, 836-837), so every candidate of draw d gets Phi(gain_d).
+__global__ __launch_bounds__(256) void k_constraint_const(const double* __restrict__ htab, double* __restrict__ out, int Mc)
+{
+    const int c = blockIdx.x * 256 + threadIdx.x;
+    const int h = blockIdx.y;
+    if (c < Mc) out[(size_t)h * Mc + c] = ndtr_dev(htab[h * SPX_HT + 0] * 1.0);
+}
+
+void launch_constraint_const(hipStream_t s, const double* htab, double* out, int Mc, int nh)
+{
+    hipLaunchKernelGGL(k_constraint_const, dim3((Mc + 255) / 256, nh), dim3(256), 0, s, htab, out, Mc);
 }

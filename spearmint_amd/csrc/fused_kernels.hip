@@ -135,7 +135,8 @@ __global__ __launch_bounds__(FU_THREADS, 1) void k_ei_fused128(
     const double* __restrict__ WT /*[nh][128][128]*/, const double* __restrict__ gamma /*[nh][128]*/,
     const double* __restrict__ Xs /*[nh][128][Dp]*/, const double* __restrict__ s1 /*[nh][128]*/,
     const double* __restrict__ Cs /*[nh][Mc][Dp]*/, const double* __restrict__ s2 /*[nh][Mc]*/,
-    const double* __restrict__ htab, const double* __restrict__ time_m /*[nh][Mc] or null*/, double best,
+    const double* __restrict__ htab, const double* __restrict__ time_m /*[nh][Mc] or null*/,
+    const double* __restrict__ cprob /*[nh][Mc] or null*/, double best,
     double* __restrict__ ei_draw /*[H][Mp]*/, double* __restrict__ mom_m, double* __restrict__ mom_v,
     int N, int Mc, int Dp, int nchunks, int wgs_per_draw, int64_t c0g, int64_t M, int64_t Mp)
 {
@@ -206,6 +207,7 @@ __global__ __launch_bounds__(FU_THREADS, 1) void k_ei_fused128(
             const double func_v = prior_v - kss[slot];
             double ei = ei_dev(func_m, func_v, best);
             if (time_m) ei = ei / time_m[(size_t)h * Mc + c];
+            if (cprob) ei = ei * cprob[(size_t)h * Mc + c];   // GPConstrainedEIChooser.py:878
             const size_t o = (size_t)h * Mp + c0g + c;
             ei_draw[o] = ei;
             if (mom_m) {
@@ -218,7 +220,7 @@ __global__ __launch_bounds__(FU_THREADS, 1) void k_ei_fused128(
 
 template <int KIND>
 static void launch_fused_kind(hipStream_t s, const double* WT, const double* gamma, const double* Xs, const double* s1,
-                              const double* Cs, const double* s2, const double* htab, const double* time_m, double best,
+                              const double* Cs, const double* s2, const double* htab, const double* time_m, const double* cprob, double best,
                               double* ei_draw, double* mom_m, double* mom_v, int N, int Mc, int Dp, int nh, int64_t c0,
                               int64_t M, int64_t Mp, int n_cu)
 {
@@ -242,7 +244,7 @@ static void launch_fused_kind(hipStream_t s, const double* WT, const double* gam
     do {                                                                                                                  \
         SPX_LDS_ATTR((k_ei_fused128<QC_, KIND, ONE_>), lds);                                  \
         hipLaunchKernelGGL((k_ei_fused128<QC_, KIND, ONE_>), grid, dim3(FU_THREADS), lds, s, WT, gamma, Xs, s1, Cs, s2, htab,   \
-                           time_m, best, ei_draw, mom_m, mom_v, N, Mc, Dp, Q / QC_, per, c0, M, Mp);                      \
+                           time_m, cprob, best, ei_draw, mom_m, mom_v, N, Mc, Dp, Q / QC_, per, c0, M, Mp);                      \
     } while (0)
     if (Q == 1) SPX_FU_LAUNCH(1, true);
     else if (Q == 2) SPX_FU_LAUNCH(2, true);
@@ -254,14 +256,14 @@ static void launch_fused_kind(hipStream_t s, const double* WT, const double* gam
 
 // EI of every (candidate of the chunk, draw): N <= 128 (Np = 128), no fantasies.  ei_draw[h][c0 + c].
 void launch_ei_fused128(hipStream_t s, int kind, const double* WT, const double* gamma, const double* Xs, const double* s1,
-                        const double* Cs, const double* s2, const double* htab, const double* time_m, double best,
+                        const double* Cs, const double* s2, const double* htab, const double* time_m, const double* cprob, double best,
                         double* ei_draw, double* mom_m, double* mom_v, int N, int Mc, int Dp, int nh, int64_t c0,
                         int64_t M, int64_t Mp, int n_cu)
 {
     if (kind == SPX_COV_MATERN32)
-        launch_fused_kind<SPX_COV_MATERN32>(s, WT, gamma, Xs, s1, Cs, s2, htab, time_m, best, ei_draw, mom_m, mom_v, N, Mc, Dp, nh, c0, M, Mp, n_cu);
+        launch_fused_kind<SPX_COV_MATERN32>(s, WT, gamma, Xs, s1, Cs, s2, htab, time_m, cprob, best, ei_draw, mom_m, mom_v, N, Mc, Dp, nh, c0, M, Mp, n_cu);
     else if (kind == SPX_COV_ARDSE)
-        launch_fused_kind<SPX_COV_ARDSE>(s, WT, gamma, Xs, s1, Cs, s2, htab, time_m, best, ei_draw, mom_m, mom_v, N, Mc, Dp, nh, c0, M, Mp, n_cu);
+        launch_fused_kind<SPX_COV_ARDSE>(s, WT, gamma, Xs, s1, Cs, s2, htab, time_m, cprob, best, ei_draw, mom_m, mom_v, N, Mc, Dp, nh, c0, M, Mp, n_cu);
     else
-        launch_fused_kind<SPX_COV_MATERN52>(s, WT, gamma, Xs, s1, Cs, s2, htab, time_m, best, ei_draw, mom_m, mom_v, N, Mc, Dp, nh, c0, M, Mp, n_cu);
+        launch_fused_kind<SPX_COV_MATERN52>(s, WT, gamma, Xs, s1, Cs, s2, htab, time_m, cprob, best, ei_draw, mom_m, mom_v, N, Mc, Dp, nh, c0, M, Mp, n_cu);
 }

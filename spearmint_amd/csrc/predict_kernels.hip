@@ -747,6 +747,7 @@ void launch_predict_gemm(hipStream_t s, int variant, const double* WT, const dou
 __global__ __launch_bounds__(256) void k_ei_finalize(
     const double* __restrict__ part_ss, const double* __restrict__ part_bg,
     const double* __restrict__ htab, const double* __restrict__ time_m /*[nh][Mc] or null*/,
+    const double* __restrict__ cprob /*[nh][Mc] or null*/,
     double best, double* __restrict__ ei_draw /*[H][Mp]*/, double* __restrict__ mom_m,
     double* __restrict__ mom_v, int nrb, int Mc, int nh, int64_t c0, int64_t M, int64_t Mp, int h0)
 {
@@ -766,6 +767,7 @@ __global__ __launch_bounds__(256) void k_ei_finalize(
     const double func_v = prior_v - ss;
     double ei = ei_dev(func_m, func_v, best);
     if (time_m) ei = ei / time_m[(size_t)h * Mc + c];
+    if (cprob) ei = ei * cprob[(size_t)h * Mc + c];   // constrained_ei = ei*func_constraint_m (GPConstrainedEIChooser.py:878)
     const size_t o = (size_t)(h0 + h) * Mp + c0 + c;
     ei_draw[o] = ei;
     if (mom_m) {
@@ -775,12 +777,12 @@ __global__ __launch_bounds__(256) void k_ei_finalize(
 }
 
 void launch_ei_finalize(hipStream_t s, const double* part_ss, const double* part_bg,
-                        const double* htab, const double* time_m, double best, double* ei_draw,
+                        const double* htab, const double* time_m, const double* cprob, double best, double* ei_draw,
                         double* mom_m, double* mom_v, int nrb, int Mc, int nh, int64_t c0,
                         int64_t M, int64_t Mp, int h0)
 {
     hipLaunchKernelGGL(k_ei_finalize, dim3((Mc + 255) / 256, nh), dim3(256), 0, s, part_ss, part_bg,
-                       htab, time_m, best, ei_draw, mom_m, mom_v, nrb, Mc, nh, c0, M, Mp, h0);
+                       htab, time_m, cprob, best, ei_draw, mom_m, mom_v, nrb, Mc, nh, c0, M, Mp, h0);
 }
 
 
@@ -812,6 +814,7 @@ __global__ __launch_bounds__(256) void k_ei_fant_values(
 }
 
 __global__ __launch_bounds__(256) void k_ei_fant_mean(const double* __restrict__ ei_s, const double* __restrict__ time_m,
+                                                      const double* __restrict__ cprob,
                                                       double* __restrict__ ei_draw, int Mc, int S, int64_t c0, int64_t M,
                                                       int64_t Mp, int h0)
 {
@@ -822,17 +825,18 @@ __global__ __launch_bounds__(256) void k_ei_fant_mean(const double* __restrict__
     const double res = np_pairwise(ei_s + (size_t)h * S * Mc + c, Mc, S);
     double out = (0.0 + res) / (double)S;
     if (time_m) out = out / time_m[(size_t)h * Mc + c];
+    if (cprob) out = out * cprob[(size_t)h * Mc + c];   // np.mean(ei, axis=1)*func_constraint_m (GPConstrainedEIChooser.py:940)
     ei_draw[(size_t)(h0 + h) * Mp + c0 + c] = out;
 }
 
 void launch_ei_finalize_fant(hipStream_t s, const double* part_ss, const double* part_bgS,
-                             const double* htab, const double* bests, const double* time_m,
+                             const double* htab, const double* bests, const double* time_m, const double* cprob,
                              double* ei_draw, int nrb, int Mc, int nh, int S, int64_t c0, int64_t M,
                              int64_t Mp, int h0, double* ei_s)
 {
     hipLaunchKernelGGL(k_ei_fant_values, dim3((Mc + 255) / 256, nh * S), dim3(256), 0, s, part_ss, part_bgS, htab, bests, nrb,
                        Mc, nh, S, c0, M, ei_s);
-    hipLaunchKernelGGL(k_ei_fant_mean, dim3((Mc + 255) / 256, nh), dim3(256), 0, s, ei_s, time_m, ei_draw, Mc, S, c0, M, Mp, h0);
+    hipLaunchKernelGGL(k_ei_fant_mean, dim3((Mc + 255) / 256, nh), dim3(256), 0, s, ei_s, time_m, cprob, ei_draw, Mc, S, c0, M, Mp, h0);
 }
 
 // ---------------------------------------------------------------------------

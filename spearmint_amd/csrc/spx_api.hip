@@ -154,6 +154,7 @@ void spx_destroy(spx_handle* h)
     if (!h) return;
     if (h->multi) { spx_multi_destroy(h->multi); delete h; return; }
     spx_comm_release(h);
+    if (h->con) { spx_destroy(h->con); h->con = nullptr; }
     if (h->inited) {
         (void)hipSetDevice(h->device);
         (void)hipStreamSynchronize(h->stream);
@@ -166,7 +167,9 @@ void spx_destroy(spx_handle* h)
                           &h->pt_x, &h->pt_k, &h->pt_dk, &h->pt_t, &h->pt_z, &h->pt_out, &h->pt_kt, &h->pt_dkt,
                           &h->ei_draw, &h->ei_mean, &h->mom_m, &h->mom_v, &h->mom_t, &h->am_val, &h->am_idx,
                           &h->am_out_val, &h->am_out_idx, &h->scratch, &h->sobol_dirs, &h->sobol_out, &h->rhs, &h->diagL, &h->ps_flags, &h->flow_flags,
-                          &h->alphaS, &h->pt_u, &h->rec_send, &h->rec_recv, &h->rec_out, &h->ei_sum_full};
+                          &h->alphaS, &h->pt_u, &h->rec_send, &h->rec_recv, &h->rec_out, &h->ei_sum_full,
+                          &h->con_tab, &h->con_Cs[0], &h->con_Cs[1], &h->con_s2[0], &h->con_s2[1], &h->con_p[0], &h->con_p[1],
+                          &h->mom_c, &h->rhs_rows};
         for (DevBuf* b : bufs) b->release();
         h->pin_up.release();
         h->pin_res.release();
@@ -411,6 +414,71 @@ int spx_set_time_model(spx_handle* h, const double* log_durs, const double* time
 // ---------------------------------------------------------------------------
 static int finish_factor(spx_handle* h, const std::vector<int>& info, bool tolerate_not_pd, bool lean);
 
+int spx_set_constraint_model(spx_handle* h, const double* comp_c, const double* ff, int64_t Nc, const double* c_hypers)
+{
+    if (!h) return fail(SPX_ERR_ARG, "spx_set_constraint_model: null handle");
+    if (h->multi) return fail(SPX_ERR_ARG, "spx_set_constraint_model: the constraint model is single-device only "
+                                           "(multi-device handles and hyper_shards > 1 are not supported)");
+    if (!comp_c && !ff && !c_hypers) { h->have_con = false; h->con_factored = false; h->ran_con = false; return SPX_OK; }
+    if (!h->have_obs || !h->have_hyp)
+        return fail(SPX_ERR_ARG, "spx_set_constraint_model: set observations and hypers first");
+    if (!c_hypers || Nc < 0 || Nc > (1 << 20) || (Nc > 0 && (!comp_c || !ff)))
+        return fail(SPX_ERR_ARG, "spx_set_constraint_model: bad arguments (Nc=%lld)", (long long)Nc);
+    int rc = ensure_init(h);
+    if (rc) return rc;
+    const int H = h->H, D = h->D, hs = 3 + D;
+    if (Nc > 0) {
+        if (!h->con) {
+            if ((rc = spx_create(h->device, &h->con))) return rc;
+            h->con->stage_copies = h->stage_copies;
+        }
+        h->con->cov_kind = h->cov_kind;
+        // the factor's rows: [0, noise_c, amp2_c, ls_c...] -- alpha_c = K_c^-1 (ff - 0): no mean term (:819-842)
+        std::vector<double> rows(c_hypers, c_hypers + (size_t)H * hs);
+        for (int i = 0; i < H; ++i) rows[(size_t)i * hs] = 0.0;
+        if ((rc = spx_set_observations(h->con, comp_c, ff, Nc, D))) return rc;
+        if ((rc = spx_set_hypers(h->con, rows.data(), H))) return rc;
+    }
+    h->con_tab_host.assign((size_t)H * SPX_HT, 0.0);
+    for (int i = 0; i < H; ++i) {
+        const double* r = c_hypers + (size_t)i * hs;
+        double* t = &h->con_tab_host[(size_t)i * SPX_HT];
+        t[0] = r[0]; t[1] = r[1]; t[2] = r[2]; t[3] = r[2];
+    }
+    if ((rc = h->con_tab.reserve(h->con_tab_host.size() * 8))) return rc;
+    stage_begin(h);
+    if ((rc = stage_h2d(h, h->con_tab.p, h->con_tab_host.data(), h->con_tab_host.size() * 8, h->stream))) return rc;
+    HIPCHK(hipStreamSynchronize(h->stream));
+    h->con_n = Nc;
+    h->have_con = true; h->con_factored = false; h->ran_con = false; h->ran = false;
+    return SPX_OK;
+}
+
+// The constraint model's alpha_c, before the objective's factorisation (spx_factor / spx_ei_step).  Its own handle, its own
+// synchronisation: a not-PD constraint covariance is reported as draw 2H + d.
+static int factor_constraint(spx_handle* h)
+{
+    if (!h->have_con || h->con_n == 0) return SPX_OK;
+    spx_handle* c = h->con;
+    // option "covar" changed since the last factorisation: alpha_c, the scaled rows and (SE) the unit length scales of the
+    // internal handle belong to the old kernel
+    if (c->cov_kind != h->cov_kind) { c->cov_kind = h->cov_kind; c->factored = false; h->con_factored = false; }
+    if (h->con_factored) return SPX_OK;
+    if (c->H != h->H || c->D != h->D)
+        return fail(SPX_ERR_ARG, "spx_factor: the constraint model has H=%d, D=%d but the objective H=%d, D=%d "
+                                 "(call spx_set_constraint_model again)", c->H, c->D, h->H, h->D);
+    int rc = spx_factor(c);
+    if (rc == SPX_ERR_NOT_PD) {
+        h->not_pd_draw = 2 * h->H + c->not_pd_draw;
+        h->not_pd_pivot = c->not_pd_pivot;
+        return fail(SPX_ERR_NOT_PD, "%d-th leading minor of the array is not positive definite (draw %d, constraint model)",
+                    c->not_pd_pivot + 1, c->not_pd_draw);
+    }
+    if (rc) return rc;
+    h->con_factored = true;
+    return SPX_OK;
+}
+
 // A hand-off of k_lean_flow timed out (its polls are bounded: an error, never a hang; not seen on a healthy device -- a
 // preempted or badly oversubscribed GPU could produce one).  The call is repeated with one launch per block column -- the
 // same arithmetic, the same bits -- and the handle STAYS there for `flow_rearm_after` clean factorisations (default 16), then
@@ -603,6 +671,9 @@ static int do_factor(spx_handle* h, bool tolerate_not_pd, bool lean = false, boo
     // lean: the right-hand side vals - mean rides through the factorisation as an extra row block,
     // so y = L^-1 (vals - mean) is ready when the last column is
     double* rhs = nullptr;
+    // (spx_gp_logprob_rhs: draw h's right-hand side is row h of rhs_rows instead of the shared values)
+    const double* vsrc = h->rhs_rows_on ? h->rhs_rows.d() : h->vals.d();
+    const int64_t vstride = h->rhs_rows_on ? N : 0;
     if (lean) {
         if ((rc = h->rhs.reserve((size_t)nh * SPX_NB * Np * 8))) return rc;
         rhs = h->rhs.d();
@@ -611,17 +682,19 @@ static int do_factor(spx_handle* h, bool tolerate_not_pd, bool lean = false, boo
             if (fused) {}            // (nothing to launch)
             else if (merged_prologue)     // (implies flow and cov_in_flow: nothing before this point read x / ls)
                 TIMED(ST_SCALE, launch_lean_prologue(s, h->comp.d(), N, Np, D, Dp, ls, hs, nh, h->Xs.d(), h->s1.d(), h->X2s.d(),
-                                                     h->vals.d(), h->htab.d(), rhs, (int*)h->info.p, ps ? (int*)h->ps_flags.p : nullptr));
+                                                     vsrc, h->htab.d(), rhs, (int*)h->info.p, ps ? (int*)h->ps_flags.p : nullptr,
+                                                     vstride));
             else
-                TIMED(ST_GAMMA_ALPHA, launch_lean_rhs_init(s, h->vals.d(), h->htab.d(), rhs, (int)N, Np, nh, (int*)h->info.p,
-                                                           ps ? (int*)h->ps_flags.p : nullptr));
+                TIMED(ST_GAMMA_ALPHA, launch_lean_rhs_init(s, vsrc, h->htab.d(), rhs, (int)N, Np, nh, (int*)h->info.p,
+                                                           ps ? (int*)h->ps_flags.p : nullptr, vstride));
         } else {
-            TIMED(ST_GAMMA_ALPHA, launch_rhs_init(s, h->vals.d(), h->htab.d(), rhs, (int)N, Np, nh));
+            TIMED(ST_GAMMA_ALPHA, launch_rhs_init(s, vsrc, h->htab.d(), rhs, (int)N, Np, nh, vstride));
         }
         h->lean_tiled = rl != 0;
     }
     h->factor_tiled = !lean && flow;
-    FlowFused ff{h->comp.d(), zero_copy ? (const double*)h->pin_up.p : h->hyp.d(), h->vals.d(), D, hs, h->fused_lp, h->fused_info};
+    FlowFused ff{h->comp.d(), zero_copy ? (const double*)h->pin_up.p : h->hyp.d(), vsrc, D, hs, h->fused_lp, h->fused_info,
+                 lean ? vstride : 0};
     const double* htab_dev = zero_copy ? (const double*)h->pin_up.p + (size_t)nh * hs : h->htab.d();
     if (flow)
         TIMED(ST_CHOL_DIAG, launch_lean_flow(s, h->Lm.d(), h->Dinv.d(), (int*)h->info.p, rhs, lean ? h->diagL.d() : nullptr, lflags, dflags, tickets, Np, nh, h->flow_gen, flow_alone,
@@ -693,8 +766,10 @@ int spx_factor(spx_handle* h)
 {
     if (!h) return fail(SPX_ERR_ARG, "spx_factor: null handle");
     if (h->multi) return spx_multi_factor(h->multi);
+    int rc = factor_constraint(h);
+    if (rc) return rc;
     h->handoff_timeout = false;
-    int rc = do_factor(h, false);
+    rc = do_factor(h, false);
     if (rc == SPX_ERR_HIP && h->handoff_timeout && h->flow_used) {   // as in spx_gp_logprob: never seen; bounded, then the launches
         note_flow_timeout(h);
         rc = do_factor(h, false);
@@ -787,12 +862,23 @@ static int check_run_flags(const spx_handle* h, int32_t flags, int nmodels)
     if (time_only && h->comm) return fail(SPX_ERR_ARG, "spx_ei_run: SPX_FLAG_TIME_ONLY has no winner to exchange (communicator attached)");
     if (per_sec && nmodels != 2)
         return fail(SPX_ERR_ARG, "spx_ei_run: SPX_FLAG_PER_SEC needs spx_set_time_model before spx_factor");
+    if (flags & SPX_FLAG_CONSTRAINED) {
+        if (per_sec) return fail(SPX_ERR_ARG, "spx_ei_run: SPX_FLAG_CONSTRAINED cannot be combined with SPX_FLAG_PER_SEC");
+        if (!h->have_con) return fail(SPX_ERR_ARG, "spx_ei_run: SPX_FLAG_CONSTRAINED needs spx_set_constraint_model");
+        if (h->comm) return fail(SPX_ERR_ARG, "spx_ei_run: SPX_FLAG_CONSTRAINED is single-device only (communicator attached)");
+        if (h->con_n > 0 && (h->con->H != h->H || h->con->D != h->D))
+            return fail(SPX_ERR_ARG, "spx_ei_run: the constraint model does not match the objective's H / D");
+        if ((int64_t)h->con_tab_host.size() != (int64_t)h->H * SPX_HT)
+            return fail(SPX_ERR_ARG, "spx_ei_run: the constraint model has a different number of draws");
+    }
     return SPX_OK;
 }
 
 int spx_ei_run(spx_handle* h, int32_t flags)
 {
     if (!h) return fail(SPX_ERR_ARG, "spx_ei_run: null handle");
+    if (h->multi && (flags & SPX_FLAG_CONSTRAINED))
+        return fail(SPX_ERR_ARG, "spx_ei_run: SPX_FLAG_CONSTRAINED is single-device only (multi-device handle)");
     if (h->multi) return spx_multi_ei_run(h->multi, flags & ~SPX_FLAG_TIME_ONLY);   // (several GPUs: the full pass; the durations are a by-product)
     return ei_run_impl(h, flags, false);
 }
@@ -804,6 +890,8 @@ int spx_ei_run(spx_handle* h, int32_t flags)
 int spx_ei_step(spx_handle* h, int32_t flags)
 {
     if (!h) return fail(SPX_ERR_ARG, "spx_ei_step: null handle");
+    if (h->multi && (flags & SPX_FLAG_CONSTRAINED))
+        return fail(SPX_ERR_ARG, "spx_ei_step: SPX_FLAG_CONSTRAINED is single-device only (multi-device handle)");
     if (h->multi) {
         int rc = spx_multi_factor(h->multi);
         return rc ? rc : spx_multi_ei_run(h->multi, flags & ~SPX_FLAG_TIME_ONLY);
@@ -815,6 +903,7 @@ int spx_ei_step(spx_handle* h, int32_t flags)
     // the pass's argument checks BEFORE anything is queued (ei_run_impl repeats them for spx_ei_run)
     int rc = check_run_flags(h, flags, h->have_time ? 2 : 1);
     if (rc) return rc;
+    if ((rc = factor_constraint(h))) return rc;
     h->handoff_timeout = false;
     rc = do_factor(h, false, false, true);
     if (rc) return rc;
@@ -846,9 +935,12 @@ static int ei_run_impl(spx_handle* h, int32_t flags, bool factor_pending)
     const bool per_sec = (flags & SPX_FLAG_PER_SEC) != 0;
     const bool keep_mom = (flags & SPX_FLAG_KEEP_MOMENTS) != 0;
     const bool time_only = (flags & SPX_FLAG_TIME_ONLY) != 0;
+    const bool constrained = (flags & SPX_FLAG_CONSTRAINED) != 0;
     int rc = check_run_flags(h, flags, h->nmodels);
     if (rc) return rc;
     if ((rc = ensure_init(h))) return rc;
+    if (constrained && h->con_n > 0 && (!h->con_factored || h->con->cov_kind != h->cov_kind))
+        return fail(SPX_ERR_ARG, "spx_ei_run: the constraint model is not factored (spx_factor after spx_set_constraint_model)");
     const int H = h->H, D = h->D, Dp = h->Dp, Np = h->Np, hs = 3 + D;
     const int64_t N = h->N, M = h->M, Mp = round_up(M, SPX_BN);
     const int nrb = Np / SPX_BM;
@@ -898,6 +990,9 @@ static int ei_run_impl(spx_handle* h, int32_t flags, bool factor_pending)
         if ((rc = h->Cs[b].reserve((size_t)H * Mc * Dp * 8))) return rc;
         if ((rc = h->s2[b].reserve((size_t)H * Mc * 8))) return rc;
         if (per_sec && (rc = h->time_m[b].reserve((size_t)H * Mc * 8))) return rc;
+        if (constrained && (rc = h->con_p[b].reserve((size_t)H * Mc * 8))) return rc;
+        if (constrained && h->con_n > 0 && (rc = h->con_Cs[b].reserve((size_t)H * Mc * Dp * 8))) return rc;
+        if (constrained && h->con_n > 0 && (rc = h->con_s2[b].reserve((size_t)H * Mc * 8))) return rc;
         if (b < ns && !fused && !time_only) {
             if ((rc = h->Kst[b].reserve((size_t)Hb * Np * Mc * 8))) return rc;
             if (S > 0 && (rc = h->part_bgS[b].reserve((size_t)nrb * 2 * Hb * S * Mc * 8))) return rc;
@@ -914,6 +1009,7 @@ static int ei_run_impl(spx_handle* h, int32_t flags, bool factor_pending)
         if ((rc = h->mom_m.reserve((size_t)H * Mp * 8))) return rc;
         if ((rc = h->mom_v.reserve((size_t)H * Mp * 8))) return rc;
         if (per_sec && (rc = h->mom_t.reserve((size_t)H * Mp * 8))) return rc;
+        if (constrained && (rc = h->mom_c.reserve((size_t)H * Mp * 8))) return rc;
     }
     const int nab = argmax_blocks(M);
     if ((rc = h->am_val.reserve((size_t)nab * 8))) return rc;
@@ -981,6 +1077,25 @@ static int ei_run_impl(spx_handle* h, int32_t flags, bool factor_pending)
                                         (size_t)std::min<int64_t>(mc, Mp - c0) * 8, (size_t)H, hipMemcpyDeviceToDevice, T));
         }
         if (time_only) continue;      // (the predicted durations of the chunk are in mom_t: nothing else was asked for)
+        double* cp = constrained ? h->con_p[par].d() : nullptr;
+        if (constrained) {
+            // P_d(x) of the chunk, all draws, on the producer stream ahead of the objective's work there: with one stream P is G,
+            // with two the EI epilogues on G wait for K(X*,X) recorded on P after it.  alpha_c was made (and synchronised) by
+            // factor_constraint.
+            if (h->con_n > 0) {
+                spx_handle* c = h->con;
+                TIMED_S(ST_SCALE, P, launch_scale_rows(P, xc, nreal, mc, D, Dp, c->hyp.d() + 3, hs, H, 2.0, h->con_Cs[par].d(),
+                                                       h->con_s2[par].d()));
+                TIMED_S(ST_CROSS_MEAN, P, launch_constraint_prob(P, c->Xs.d(), c->s1.d(), h->con_Cs[par].d(), h->con_s2[par].d(),
+                                                                 h->con_tab.d(), c->alpha.d(), cp, (int)c->N, c->Np, mc, Dp, H,
+                                                                 dev_kind(h)));
+            } else {
+                TIMED_S(ST_CROSS_MEAN, P, launch_constraint_const(P, h->con_tab.d(), cp, mc, H));
+            }
+            if (keep_mom)   // P_d [H][mc] -> [H][Mp] for spx_get_constraint_prob
+                HIPCHK(hipMemcpy2DAsync(h->mom_c.d() + c0, (size_t)Mp * 8, cp, (size_t)mc * 8,
+                                        (size_t)std::min<int64_t>(mc, Mp - c0) * 8, (size_t)H, hipMemcpyDeviceToDevice, P));
+        }
         // 2 * cand / ls and |cand / ls|^2 for every draw (one launch per chunk)
         hipStream_t Pc = (chunk == 0) ? P0 : P;       // (the first chunk's producer work of a step: beside the factorisation)
         TIMED_S(ST_SCALE, Pc, launch_scale_rows(Pc, xc, nreal, mc, D, Dp, ls, hs, H, 2.0, Cs, s2));
@@ -990,7 +1105,7 @@ static int ei_run_impl(spx_handle* h, int32_t flags, bool factor_pending)
         }
         if (fused)
             TIMED_S(ST_PREDICT_GEMM, G, launch_ei_fused128(G, dev_kind(h), h->WT.d(), h->gamma.d(), h->Xs.d(), h->s1.d(), Cs, s2,
-                                                           h->htab.d(), tm, h->best, h->ei_draw.d(), keep_mom ? h->mom_m.d() : nullptr,
+                                                           h->htab.d(), tm, cp, h->best, h->ei_draw.d(), keep_mom ? h->mom_m.d() : nullptr,
                                                            keep_mom ? h->mom_v.d() : nullptr, (int)N, mc, Dp, H, c0, M, Mp, h->n_cu));
         for (int h0 = 0; h0 < (fused ? 0 : H); h0 += Hb, ++item) {
             const int nhb = std::min(Hb, H - h0);
@@ -1019,17 +1134,18 @@ static int ei_run_impl(spx_handle* h, int32_t flags, bool factor_pending)
                                                                    h->htab.d() + (size_t)h0 * SPX_HT,
                                                                    h->bests.d() + (size_t)h0 * S,
                                                                    per_sec ? tm + (size_t)h0 * mc : nullptr,
+                                                                   constrained ? cp + (size_t)h0 * mc : nullptr,
                                                                    h->ei_draw.d(), nrb, mc, nhb, S, c0, M, Mp, h0,
                                                                    h->scratch.d()));
             if (ns == 2) HIPCHK(hipEventRecord(h->ev_sync[2 + k], G));
         }
         if (S == 0 && !fused)   // every draw of the chunk in one launch
-            TIMED_S(ST_EI_FINALIZE, G, launch_ei_finalize(G, h->part_ss[0].d(), h->part_bg[0].d(), h->htab.d(), tm, h->best,
+            TIMED_S(ST_EI_FINALIZE, G, launch_ei_finalize(G, h->part_ss[0].d(), h->part_bg[0].d(), h->htab.d(), tm, cp, h->best,
                                                           h->ei_draw.d(), keep_mom ? h->mom_m.d() : nullptr,
                                                           keep_mom ? h->mom_v.d() : nullptr, nrb, mc, H, c0, M, Mp, 0));
         if (ns == 2) HIPCHK(hipEventRecord(h->ev_sync[4 + par], G));
     }
-    if (ns == 2 && per_sec && keep_mom) {   // the duration copies ran on P
+    if (ns == 2 && (per_sec || constrained) && keep_mom) {   // the duration / probability copies ran on P
         HIPCHK(hipEventRecord(h->ev_sync[0], P));
         HIPCHK(hipStreamWaitEvent(G, h->ev_sync[0], 0));
     }
@@ -1060,6 +1176,7 @@ static int ei_run_impl(spx_handle* h, int32_t flags, bool factor_pending)
     h->ran_time = time_only;
     h->ran_2d = false;
     h->ran_moments = keep_mom && S == 0 && !time_only;
+    h->ran_con = constrained && keep_mom && !time_only;
     if (h->comm) return spx_comm_exchange(h);   // one process per GPU: the winner over all ranks
     return SPX_OK;
 }
@@ -1123,6 +1240,19 @@ int spx_get_time_mean(spx_handle* h, int32_t draw, double* out)
     if (rc) return rc;
     const int64_t Mp = round_up(h->M, SPX_BN);
     HIPCHK(hipMemcpy(out, h->mom_t.d() + (size_t)draw * Mp, (size_t)h->M * 8, hipMemcpyDeviceToHost));
+    return SPX_OK;
+}
+
+int spx_get_constraint_prob(spx_handle* h, int32_t draw, double* out)
+{
+    if (h && h->multi) return fail(SPX_ERR_ARG, "spx_get_constraint_prob: the constraint model is single-device only");
+    if (!h || !out || !h->ran || !h->ran_con)
+        return fail(SPX_ERR_ARG, "spx_get_constraint_prob: run spx_ei_run with SPX_FLAG_CONSTRAINED | SPX_FLAG_KEEP_MOMENTS first");
+    if (draw < 0 || draw >= h->H) return fail(SPX_ERR_ARG, "spx_get_constraint_prob: draw out of range");
+    int rc = ensure_init(h);
+    if (rc) return rc;
+    const int64_t Mp = round_up(h->M, SPX_BN);
+    HIPCHK(hipMemcpy(out, h->mom_c.d() + (size_t)draw * Mp, (size_t)h->M * 8, hipMemcpyDeviceToHost));
     return SPX_OK;
 }
 
@@ -1274,6 +1404,27 @@ int spx_gp_logprob(spx_handle* h, double* out)
         rc = gp_logprob_once(h, out);
         if (!rc) warn_flow_fallback(h);
     }
+    return rc;
+}
+
+int spx_gp_logprob_rhs(spx_handle* h, const double* rows, const double* rhs, int32_t n_rows, double* lp_out)
+{
+    if (!h || !rows || !rhs || !lp_out) return fail(SPX_ERR_ARG, "spx_gp_logprob_rhs: null argument");
+    if (h->multi) return fail(SPX_ERR_ARG, "spx_gp_logprob_rhs: single-device only (multi-device handle)");
+    if (n_rows < 1 || n_rows > 32) return fail(SPX_ERR_ARG, "spx_gp_logprob_rhs: 1 .. 32 rows per call (got %d)", n_rows);
+    if (!h->have_obs) return fail(SPX_ERR_ARG, "spx_gp_logprob_rhs: call spx_set_observations first (the points)");
+    int rc = spx_set_hypers(h, rows, n_rows);
+    if (rc) return rc;
+    const size_t bytes = (size_t)n_rows * h->N * 8;
+    if ((rc = h->rhs_rows.reserve(bytes))) return rc;
+    stage_begin(h);
+    if ((rc = stage_h2d(h, h->rhs_rows.p, rhs, bytes, h->stream))) return rc;
+    // (the copy is ordered in front of the factorisation on the same stream; the staging buffer is the caller's until the
+    // stream has drained, which spx_gp_logprob waits for before it returns)
+    h->rhs_rows_on = true;
+    rc = spx_gp_logprob(h, lp_out);
+    h->rhs_rows_on = false;
+    (void)hipStreamSynchronize(h->stream);
     return rc;
 }
 

@@ -155,6 +155,16 @@ struct spx_handle {
     bool ran_2d = false;
     DevBuf ei_sum_full;
     DevBuf sobol_dirs, sobol_out;                                   // spx_sobol_grid
+    // probit constraint model (spx_set_constraint_model): an internal handle on the same device factors
+    // (amp2_c (K_c + 1e-6 I) + noise_c I) alpha_c = ff over its own Nc points; the EI pass reads its scaled rows and alpha_c
+    spx_handle* con = nullptr;
+    bool have_con = false, con_factored = false, ran_con = false;
+    int64_t con_n = 0;                                              // Nc (0: all valid, P_d = Phi(gain_d))
+    std::vector<double> con_tab_host;                               // [H][SPX_HT]: gain, noise_c, amp2_c, amp2_c
+    DevBuf con_tab, con_Cs[2], con_s2[2], con_p[2], mom_c;
+    // spx_gp_logprob_rhs: a right-hand side per hyper row, [H][N], read in place of the resident values while set
+    DevBuf rhs_rows;
+    bool rhs_rows_on = false;
     DevBuf rhs;                                                     // spx_gp_logprob: [H][64][Np] right-hand-side rows
     DevBuf diagL;                                                   // spx_gp_logprob (tile-major path): diag(L), [H][Np]
     int lean_np = 0;                                                // padded size of the last lean factorisation (a multiple of 64, not of 128)

@@ -30,6 +30,7 @@ FLAG_PER_SEC = 1
 FLAG_KEEP_MOMENTS = 2
 FLAG_TIMING = 4
 FLAG_TIME_ONLY = 8
+FLAG_CONSTRAINED = 16
 
 _c_double_p = ctypes.POINTER(ctypes.c_double)
 _c_int64_p = ctypes.POINTER(ctypes.c_int64)
@@ -88,6 +89,7 @@ ABI = {
     "spx_set_candidates": (ctypes.c_int, [_vp, _c_double_p, ctypes.c_int64, ctypes.c_int32, ctypes.c_int64]),
     "spx_set_hypers": (ctypes.c_int, [_vp, _c_double_p, ctypes.c_int32]),
     "spx_set_time_model": (ctypes.c_int, [_vp, _c_double_p, _c_double_p]),
+    "spx_set_constraint_model": (ctypes.c_int, [_vp, _c_double_p, _c_double_p, ctypes.c_int64, _c_double_p]),
     "spx_factor": (ctypes.c_int, [_vp]),
     "spx_set_fantasies": (ctypes.c_int, [_vp, _c_double_p, _c_double_p, ctypes.c_int32]),
     "spx_ei_run": (ctypes.c_int, [_vp, ctypes.c_int32]),
@@ -107,7 +109,9 @@ ABI = {
     "spx_get_cross_cov": (ctypes.c_int, [_vp, ctypes.c_int32, ctypes.c_int64, ctypes.c_int64, _c_double_p]),
     "spx_get_moments": (ctypes.c_int, [_vp, ctypes.c_int32, _c_double_p, _c_double_p]),
     "spx_get_time_mean": (ctypes.c_int, [_vp, ctypes.c_int32, _c_double_p]),
+    "spx_get_constraint_prob": (ctypes.c_int, [_vp, ctypes.c_int32, _c_double_p]),
     "spx_gp_logprob": (ctypes.c_int, [_vp, _c_double_p]),
+    "spx_gp_logprob_rhs": (ctypes.c_int, [_vp, _c_double_p, _c_double_p, ctypes.c_int32, _c_double_p]),
     "spx_ei_grad": (ctypes.c_int, [_vp, _c_double_p, _c_double_p, _c_double_p]),
     "spx_ei_grad_batch": (ctypes.c_int, [_vp, _c_double_p, ctypes.c_int32, _c_double_p, _c_double_p]),
     "spx_sobol_grid": (ctypes.c_int, [_vp, ctypes.POINTER(ctypes.c_uint32), ctypes.c_int32, ctypes.c_int32,
@@ -331,6 +335,21 @@ class Engine(object):
             raise ValueError("log_durs must be (N,), time_hypers (H, 3 + D)")
         self._check(self._lib.spx_set_time_model(self._h, _dp(log_durs), _dp(time_hypers)))
 
+    def set_constraint_model(self, comp_c, ff, c_hypers):
+        """Probit constraint GP (spx_set_constraint_model): comp_c (Nc, D) -- Nc = 0 for the all-valid case --, latent
+        values ff (Nc,), rows c_hypers (H, 3 + D) [gain, noise_c, amp2_c, ls_c...].  comp_c None clears the model."""
+        if comp_c is None:
+            self._check(self._lib.spx_set_constraint_model(self._h, None, None, 0, None))
+            return
+        comp_c = _f64(np.asarray(comp_c, dtype=np.float64).reshape(-1, self.D))
+        ff = _f64(ff).ravel()
+        c_hypers = _f64(np.atleast_2d(c_hypers))
+        nc = comp_c.shape[0]
+        if ff.shape[0] != nc or c_hypers.shape != (self.H, 3 + self.D):
+            raise ValueError("comp_c must be (Nc, D), ff (Nc,), c_hypers (H, 3 + D)")
+        self._check(self._lib.spx_set_constraint_model(self._h, _dp(comp_c) if nc else None, _dp(ff) if nc else None,
+                                                       nc, _dp(c_hypers)))
+
     def set_option(self, name, value):
         self._check(self._lib.spx_set_option(self._h, name.encode("ascii"), int(value)))
 
@@ -447,6 +466,24 @@ class Engine(object):
     def get_time_mean(self, draw):
         out = np.empty(self.M)
         self._check(self._lib.spx_get_time_mean(self._h, int(draw), _dp(out)))
+        return out
+
+    def gp_logprob_rhs(self, rows, rhs):
+        """spx_gp_logprob_rhs: the data term of every row [mean, noise, amp2, ls...] (<= 32) with its own right-hand side
+        rhs[k] (N,) over the resident observations; -inf where the covariance is not positive definite."""
+        rows = _f64(np.atleast_2d(rows))
+        rhs = _f64(np.atleast_2d(rhs))
+        n = rows.shape[0]
+        if rows.shape[1] != 3 + self.D or rhs.shape != (n, self.N):
+            raise ValueError("rows must be (k, 3 + D) and rhs (k, N)")
+        out = np.empty(n)
+        self._check(self._lib.spx_gp_logprob_rhs(self._h, _dp(rows), _dp(rhs), n, _dp(out)))
+        self.H = n
+        return out
+
+    def get_constraint_prob(self, draw):
+        out = np.empty(self.M)
+        self._check(self._lib.spx_get_constraint_prob(self._h, int(draw), _dp(out)))
         return out
 
     def gp_logprob(self, raise_not_pd=False):
