@@ -2,9 +2,17 @@
 """bench.py -- EI-candidate evaluations / second of the GP-EI hot path on MI355X.
 
     python bench.py --gpus 1 --steps 3 --warmup 1
+    python bench.py --gpus 1 --steps 3 --warmup 1 --full   (the headline and everything else described below)
     python bench.py --gpus N --steps K --warmup W          (N > 1, no launcher: starts its own N ranks, see self_launch)
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 \
            --master-port P bench.py --gpus N --steps K --warmup W
+
+A plain run does only what its headline needs: it sets the problem up, runs the W warm-up and the K timed steps,
+writes --dump-outputs if asked, and prints the line (metric, value, unit, ms_per_step, the winner, the launch
+plumbing).  Everything else described below -- the strong-scaling sub-records, the per-launch event pass with
+`roofline`, `roofline_hbm` and the stage table, the live traffic passes, `platform`, `host_inclusive_value`,
+`in_process_n1`, `next_call` and `cpu_baseline` -- runs only with --full; --no-cpu-baseline, --no-live-traffic and
+--skip-extras trim a --full run.
 
 Whichever way it is started, the JSON line's `n_gpus` is the number of ranks that TOOK PART in the collective
 (`ranks_seen`: the size of the communicator the all-gather of the 16-byte records ran on -- one record per rank in its
@@ -24,7 +32,7 @@ metric's target is quoted on): synthetic 32-D, N_obs=2048, 200 000 candidates
 per GPU, mcmc_iters=20, fp64.  Per-GPU work is fixed as N grows ("weak"
 scaling): N GPUs score N x 200 000 candidates of one grid.
 
-The same run also times, as sub-records "c4" and "c5", the two multi-GPU
+With --full the same run also times, as sub-records "c4" and "c5", the two multi-GPU
 configurations of BASELINE.json at their FULL size with the candidate grid split
 over the WORLD_SIZE ranks ("strong" scaling: total work fixed):
   c4  N_obs=2048, 32-D, 1 000 000 candidates, mcmc_iters=20
@@ -42,7 +50,7 @@ variant that cannot run records its error string instead of ending the run, and
 all that ran must agree on the winner.  `--in-process` runs the same headline
 and strong-scaling lines through ONE multi-device handle (spx_create_multi).
 
-Rank 0 prints ONE JSON line.  `roofline` is for the dominant kernel
+Rank 0 prints ONE JSON line.  With --full, `roofline` is for the dominant kernel
 (k_predict_gemm_tri: beta = L^-1 K* as an fp64 MFMA GEMM over the lower triangle of
 L^-1, with the variance/mean reduction fused in its epilogue): achieved = algorithmic flops per launch
 (N^2 + 4N per (candidate, draw) evaluation) / the kernel's mean
@@ -134,7 +142,7 @@ def live_traffic(workload, timeout_s=240):
     work = tempfile.mkdtemp(prefix="spx_traffic_", dir="/tmp")
     env = dict(os.environ, TMPDIR="/tmp")
     child = [sys.executable, os.path.join(ROOT, "bench.py"), "--workload", workload, "--steps", "1", "--warmup", "0",
-             "--no-cpu-baseline", "--skip-extras", "--no-live-traffic", "--event-steps", "0"]
+             "--full", "--no-cpu-baseline", "--skip-extras", "--no-live-traffic", "--event-steps", "0"]
     try:
         for counter in ("FETCH_SIZE", "WRITE_SIZE"):
             out = os.path.join(work, counter)
@@ -527,8 +535,8 @@ def main_in_process(args):
                    "devices": devs, "transport": eng.transport()},
         "best_index": best[0], "best_ei": best[1]}
     # strong scaling through the same handle: the full C4 / C5 grids sharded by the library over the n devices
-    # (and, with --hyper-shards, C4 in the library's 2-D partition: one ncclAllReduce of the EI-sum vector)
-    if not args.skip_extras:
+    # (and, with --hyper-shards, C4 in the library's 2-D partition: one ncclAllReduce of the EI-sum vector); --full only
+    if args.full and not args.skip_extras:
         esteps = max(args.extra_steps, 5 if n > 1 else 2)
         variants = [("c4", "c4", 1), ("c5", "c5", 1)]
         if args.hyper_shards > 1:
@@ -586,6 +594,10 @@ def main():
     ap.add_argument("--workload", default="c3", choices=sorted(WORKLOADS))
     ap.add_argument("--candidates", type=int, default=0,
                     help="candidates per GPU of the headline instead of the workload's own (plumbing tests only: the line says so)")
+    ap.add_argument("--full", action="store_true",
+                    help="besides the headline, run everything else this bench measures and checks: the event pass (roofline, "
+                         "stage times), live traffic, platform, host-inclusive and in-process figures, next_call, the strong-"
+                         "scaling sub-records and the CPU baseline (the switches below trim it); off: headline only")
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--next-baseline", action="store_true",
                     help="instead of the EI-grid bench: time one whole GPEIOptChooser.next() of the reference (CPU) and of this "
@@ -683,7 +695,7 @@ def main():
     # the rocprofv3 passes of roofline.traffic run before this process opens the GPU, so that the profiled children are not
     # started from a process that holds a device
     live = None
-    if world == 1 and not args.no_live_traffic and engine_name == "libspx":
+    if args.full and world == 1 and not args.no_live_traffic and engine_name == "libspx":
         live = live_traffic(args.workload)
 
     eng = EngineCls(local_rank)
@@ -764,7 +776,57 @@ def main():
     evals_per_step = float(M) * H
     value = world * evals_per_step * args.steps / dt
 
-    # ---- second pass: the same steps with HIP events around every launch (stage breakdown, roofline)
+    # ---- the line as a plain run prints it; --full adds its records below ------------------------
+    out = None
+    ranks_seen = seen.get("headline")
+    if ranks_seen != args.gpus:      # never a line whose n_gpus is not what was asked for and what took part
+        raise SystemExit("bench.py: --gpus %d but the collective returned %r records per step" % (args.gpus, ranks_seen))
+    if rank == 0:
+        versions = {}
+        if engine_name == "libspx" and (world > 1 or lib_collective):
+            try:
+                from spearmint_amd import engine as _e
+                versions["libspx_binding"] = _e.rccl_version()          # ncclGetVersion of the librccl libspx dlopens
+            except Exception as ex:
+                versions["libspx_binding"] = "unavailable: %s" % ex
+        if world > 1 and backend == "nccl":
+            try:
+                versions["torch_backend"] = ".".join(str(v) for v in torch.cuda.nccl.version())
+            except Exception as ex:
+                versions["torch_backend"] = "unavailable: %s" % ex
+        out = {
+            "metric": "EI candidate evaluations per second (N_cand x mcmc_iters / wall time)",
+            "value": value, "unit": "EI evals/s", "n_gpus": ranks_seen, "ranks_seen": ranks_seen,
+            "launcher": ("self: bench.py re-executed itself under torch.distributed.run" if os.environ.get("SPX_BENCH_SELF_LAUNCHED")
+                         else ("external torch.distributed.run" if world > 1 else "none (one rank)")),
+            "backend": (backend if world > 1 else None), "rccl_version": versions or None, "engine": engine_name,
+            "steps": args.steps,
+            "warmup": args.warmup, "ms_per_step": dt / args.steps * 1e3,
+            "higher_is_better": True, "scaling": "weak", "vs_baseline": None,
+            "dtype": "f64", "data": "synthetic",
+            "config": {"workload": w["desc"], "N_obs": N, "candidates_per_gpu": M, "D": D,
+                       "mcmc_iters": H, "per_sec": w["per_sec"],
+                       "sharding": "candidates sharded contiguously over ranks, draws replicated; "
+                                   "one collective of (best EI, index) records",
+                       "collective": "libspx ncclAllGather (spx_comm_attach)" if lib_collective
+                                     else "torch.distributed all_gather_into_tensor"},
+            "best_index": best[0], "best_ei": best[1],
+            "rank_step_ms": rank_times.get("headline"),
+        }
+
+    def finish():
+        # teardown FIRST, the line LAST: librccl (torch's, or the one libspx binds) prints a version banner through C stdio,
+        # which a pipe buffers until the process ends -- behind the JSON line if that were printed earlier
+        if world > 1:
+            tdist.barrier()
+            tdist.destroy_process_group()
+        eng.close()
+        emit_line(out if rank == 0 else None)
+
+    if not args.full:           # a plain run: the headline is all it measures
+        return finish()
+
+    # ---- --full: a second pass of the same steps with HIP events around every launch (stage breakdown, roofline)
     ev_steps = max(1, min(args.event_steps, args.steps))
     eng.set_option("timing", 1)
     dt_ev, _ = run_steps(eng, flags, ev_steps)
@@ -838,46 +900,13 @@ def main():
 
     if roofline_hbm and roofline_hbm.get("ms_per_step"):
         roofline_hbm["frac_of_fma_unit_bound"] = roofline_hbm["fma_unit_bound_ms_per_step"] / roofline_hbm["ms_per_step"]
-    out = None
-    ranks_seen = seen.get("headline")
-    if ranks_seen != args.gpus:      # never a line whose n_gpus is not what was asked for and what took part
-        raise SystemExit("bench.py: --gpus %d but the collective returned %r records per step" % (args.gpus, ranks_seen))
     if rank == 0:
-        versions = {}
-        if engine_name == "libspx" and (world > 1 or lib_collective):
-            try:
-                from spearmint_amd import engine as _e
-                versions["libspx_binding"] = _e.rccl_version()          # ncclGetVersion of the librccl libspx dlopens
-            except Exception as ex:
-                versions["libspx_binding"] = "unavailable: %s" % ex
-        if world > 1 and backend == "nccl":
-            try:
-                versions["torch_backend"] = ".".join(str(v) for v in torch.cuda.nccl.version())
-            except Exception as ex:
-                versions["torch_backend"] = "unavailable: %s" % ex
-        out = {
-            "metric": "EI candidate evaluations per second (N_cand x mcmc_iters / wall time)",
-            "value": value, "unit": "EI evals/s", "n_gpus": ranks_seen, "ranks_seen": ranks_seen,
-            "launcher": ("self: bench.py re-executed itself under torch.distributed.run" if os.environ.get("SPX_BENCH_SELF_LAUNCHED")
-                         else ("external torch.distributed.run" if world > 1 else "none (one rank)")),
-            "backend": (backend if world > 1 else None), "rccl_version": versions or None, "engine": engine_name,
-            "steps": args.steps,
-            "warmup": args.warmup, "ms_per_step": dt / args.steps * 1e3,
-            "higher_is_better": True, "scaling": "weak", "vs_baseline": None,
-            "dtype": "f64", "data": "synthetic",
-            "config": {"workload": w["desc"], "N_obs": N, "candidates_per_gpu": M, "D": D,
-                       "mcmc_iters": H, "per_sec": w["per_sec"],
-                       "sharding": "candidates sharded contiguously over ranks, draws replicated; "
-                                   "one collective of (best EI, index) records",
-                       "collective": "libspx ncclAllGather (spx_comm_attach)" if lib_collective
-                                     else "torch.distributed all_gather_into_tensor"},
+        out.update({
             "roofline": roofline, "roofline_hbm": roofline_hbm,
             "platform": platform_info(eng if engine_name == "libspx" else None, local_rank),
             "ms_per_step_with_events": dt_ev / ev_steps * 1e3,
             "stages_ms_per_step": {k: v[0] / ev_steps for k, v in tm.items() if v[1]},
-            "best_index": best[0], "best_ei": best[1],
-            "rank_step_ms": rank_times.get("headline"),
-        }
+        })
 
     # ---- the metric as SURVEY 8(d) defines it: host buffers in, result out (PCIe included) ------
     if world == 1:
@@ -1099,13 +1128,7 @@ def main():
 
     if rank == 0 and world == 1 and not args.no_cpu_baseline:
         out["cpu_baseline"] = cpu_baseline(w, args.cpu_candidates, args.cpu_reps)
-    # teardown FIRST, the line LAST: librccl (torch's, or the one libspx binds) prints a version banner through C stdio,
-    # which a pipe buffers until the process ends -- behind the JSON line if that were printed earlier
-    if world > 1:
-        tdist.barrier()
-        tdist.destroy_process_group()
-    eng.close()
-    emit_line(out if rank == 0 else None)
+    finish()
 
 
 if __name__ == "__main__":

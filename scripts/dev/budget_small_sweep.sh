@@ -3,7 +3,7 @@
 cd $GRAFT_REPO_ROOT
 for wl in ${WLS:-c3}; do
   for mb in ${MBS:-0 384 256 192 128 96 64}; do
-    python bench.py --workload $wl --skip-extras --no-cpu-baseline --no-live-traffic --steps 5 --warmup 2 --kstar-budget-mb $mb 2>/dev/null | python -c "
+    python bench.py --full --workload $wl --skip-extras --no-cpu-baseline --no-live-traffic --steps 5 --warmup 2 --kstar-budget-mb $mb 2>/dev/null | python -c "
 import sys, json
 o = json.loads([l for l in sys.stdin if l.startswith('{')][-1])
 st = o.get('stages_ms_per_step', {})

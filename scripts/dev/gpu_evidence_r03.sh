@@ -3,9 +3,9 @@
 cd $GRAFT_REPO_ROOT
 O=$PWD/gpurun_out/evidence; mkdir -p $O
 if [ "$1" = a ]; then
-echo "== bench c3 (default)"; timeout 600 python bench.py > $O/r03_c3_bench_line.json 2> $O/bench_c3.err; tail -c 600 $O/r03_c3_bench_line.json; echo
-echo "== bench c2"; timeout 300 python bench.py --workload c2 --skip-extras > $O/r03_c2_bench_line.json 2>> $O/bench_c2.err
-echo "== bench c5"; timeout 300 python bench.py --workload c5 --skip-extras > $O/r03_c5_bench_line.json 2>> $O/bench_c5.err
+echo "== bench c3 (default)"; timeout 600 python bench.py --full > $O/r03_c3_bench_line.json 2> $O/bench_c3.err; tail -c 600 $O/r03_c3_bench_line.json; echo
+echo "== bench c2"; timeout 300 python bench.py --full --workload c2 --skip-extras > $O/r03_c2_bench_line.json 2>> $O/bench_c2.err
+echo "== bench c5"; timeout 300 python bench.py --full --workload c5 --skip-extras > $O/r03_c5_bench_line.json 2>> $O/bench_c5.err
 echo "== time_lean"; timeout 300 python scripts/time_lean.py > $O/r03_time_lean.log 2>&1; cat $O/r03_time_lean.log
 echo "== flow A/B"; timeout 300 python scripts/dev/flow_ab.py 2>&1 | grep -v Warn > $O/r03_flow_ab.log; head -8 $O/r03_flow_ab.log
 echo "== flow modes"; timeout 300 python scripts/dev/flow_modes.py > $O/r03_flow_modes.log 2>&1; head -8 $O/r03_flow_modes.log

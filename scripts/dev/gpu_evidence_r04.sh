@@ -3,9 +3,9 @@
 cd $GRAFT_REPO_ROOT
 O=$PWD/gpurun_out/evidence; mkdir -p $O
 if [ "$1" = a ]; then
-echo "== bench c3 (default)"; timeout 900 python bench.py > $O/r04_c3_bench_line.json 2> $O/bench_c3.err; tail -c 400 $O/r04_c3_bench_line.json; echo
-echo "== bench c2"; timeout 300 python bench.py --workload c2 --skip-extras --steps 20 --warmup 3 > $O/r04_c2_bench_line.json 2>> $O/bench_c2.err
-echo "== bench c5"; timeout 300 python bench.py --workload c5 --skip-extras --steps 10 --warmup 2 > $O/r04_c5_bench_line.json 2>> $O/bench_c5.err
+echo "== bench c3 (default)"; timeout 900 python bench.py --full > $O/r04_c3_bench_line.json 2> $O/bench_c3.err; tail -c 400 $O/r04_c3_bench_line.json; echo
+echo "== bench c2"; timeout 300 python bench.py --full --workload c2 --skip-extras --steps 20 --warmup 3 > $O/r04_c2_bench_line.json 2>> $O/bench_c2.err
+echo "== bench c5"; timeout 300 python bench.py --full --workload c5 --skip-extras --steps 10 --warmup 2 > $O/r04_c5_bench_line.json 2>> $O/bench_c5.err
 echo "== time_lean"; timeout 300 python scripts/time_lean.py 2>&1 | grep -v amdgpu.ids > $O/r04_time_lean.log; cat $O/r04_time_lean.log
 echo "== small n"; timeout 300 python scripts/dev/time_small_n.py 2>&1 | grep -v amdgpu.ids > $O/r04_small_n.log; cut -c1-200 $O/r04_small_n.log
 echo "== small lp"; timeout 300 python scripts/dev/time_small_lp.py 2>&1 | grep -v amdgpu.ids > $O/r04_small_lp.log; cat $O/r04_small_lp.log

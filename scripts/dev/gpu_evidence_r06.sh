@@ -4,9 +4,9 @@ cd $GRAFT_REPO_ROOT
 O=$PWD/gpurun_out/evidence; mkdir -p $O
 A="mcmc_iters=10,burnin=10,grid_subset=20"
 if [ "$1" = a ]; then
-echo "== bench c3 (the driver's command)"; timeout 900 python bench.py --gpus 1 --steps 20 --warmup 5 > $O/r06_c3_bench_line.json 2> $O/bench_c3.err; tail -c 700 $O/r06_c3_bench_line.json; echo
-echo "== bench c2"; timeout 300 python bench.py --workload c2 --skip-extras --steps 20 --warmup 3 > $O/r06_c2_bench_line.json 2>> $O/bench_c2.err
-echo "== bench c5"; timeout 300 python bench.py --workload c5 --skip-extras --steps 10 --warmup 2 > $O/r06_c5_bench_line.json 2>> $O/bench_c5.err
+echo "== bench c3 (the driver's command)"; timeout 900 python bench.py --full --gpus 1 --steps 20 --warmup 5 > $O/r06_c3_bench_line.json 2> $O/bench_c3.err; tail -c 700 $O/r06_c3_bench_line.json; echo
+echo "== bench c2"; timeout 300 python bench.py --full --workload c2 --skip-extras --steps 20 --warmup 3 > $O/r06_c2_bench_line.json 2>> $O/bench_c2.err
+echo "== bench c5"; timeout 300 python bench.py --full --workload c5 --skip-extras --steps 10 --warmup 2 > $O/r06_c5_bench_line.json 2>> $O/bench_c5.err
 echo "== next() vs the reference"; timeout 400 python bench.py --next-baseline > $O/r06_next_vs_reference.json 2>/dev/null; tail -c 300 $O/r06_next_vs_reference.json; echo
 echo "== next() phases"; { for shape in "256 20000 8" "64 20000 8" "1024 20000 16"; do for v in "sampler=python,lookahead=6,follow=0:0" "sampler=native,lookahead=6,follow=0:0" "sampler=native"; do echo "=== $shape $v"; timeout 300 python scripts/dev/next_phases.py $shape "$A,$v" 2>&1 | grep -v amdgpu.ids; done; done; echo "=== C3 size"; for v in "sampler=python,lookahead=6,follow=0:0" "sampler=native"; do timeout 600 python scripts/dev/next_phases.py 2048 200000 32 "mcmc_iters=20,burnin=2,grid_subset=20,$v" 2>&1 | grep -v amdgpu.ids; done; } > $O/r06_next_phases.log 2>&1; grep "^===\|^next()" $O/r06_next_phases.log
 echo "== log-likelihood call forms"; timeout 400 python scripts/dev/lean_one_ab.py 2>&1 | grep -v amdgpu.ids > $O/r06_lean_one_ab.log; tail -4 $O/r06_lean_one_ab.log

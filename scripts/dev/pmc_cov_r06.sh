@@ -16,7 +16,7 @@ for lib in shipped covabl2; do
              "TCC_WRITE_sum TCC_EA0_WRREQ_sum TCC_EA0_RDREQ_sum"; do
     d=$R/gpurun_out/pmc_cov_tmp
     rm -rf $d
-    rocprofv3 --pmc $set --kernel-include-regex "k_cov" --output-format csv -d $d -- python $R/bench.py --steps 1 --warmup 0 --no-cpu-baseline --skip-extras --no-live-traffic > /dev/null 2>&1
+    rocprofv3 --pmc $set --kernel-include-regex "k_cov" --output-format csv -d $d -- python $R/bench.py --full --steps 1 --warmup 0 --no-cpu-baseline --skip-extras --no-live-traffic > /dev/null 2>&1
     f=$(find $d -name "*counter_collection.csv" | head -1)
     if [ -z "$f" ]; then echo "(pass failed: $set)" >> $OUT; continue; fi
     python - "$f" >> $OUT <<'PY'

@@ -223,6 +223,24 @@ def test_bench_refuses_a_line_whose_n_gpus_is_not_what_was_asked_for():
     assert rc != 0 and out is None and "WORLD_SIZE=1" in err
 
 
+def test_bench_plain_run_is_the_headline_and_full_adds_the_rest():
+    """A plain run stops after its timed steps: the line carries the headline (same winner as --full) and none of the
+    records that take runs of their own.  --full still runs them (here the event pass, platform and the host-inclusive
+    one-shot, trimmed by the usual switches; the stand-in has no per-launch timings, so its roofline is null)."""
+    head = ["--gpus", "1", "--workload", "c2", "--candidates", "1500", "--steps", "1", "--warmup", "0"]
+    rc, out, err = _bench(head, STANDIN)
+    assert rc == 0 and out is not None, err[-2000:]
+    assert out["unit"] == "EI evals/s" and out["dtype"] == "f64" and out["higher_is_better"] is True
+    assert out["value"] > 0 and out["ms_per_step"] > 0 and out["steps"] == 1
+    extras = {"roofline", "roofline_hbm", "platform", "ms_per_step_with_events", "stages_ms_per_step", "host_inclusive_value",
+              "in_process_n1", "next_call", "c4", "c5", "cpu_baseline"}
+    assert not extras & set(out)
+    rc, full, err = _bench(head + ["--full", "--no-cpu-baseline", "--no-live-traffic", "--skip-extras"], STANDIN)
+    assert rc == 0 and full is not None, err[-2000:]
+    assert {"roofline", "platform", "stages_ms_per_step", "host_inclusive_value"} <= set(full) and set(out) <= set(full)
+    assert (full["best_index"], full["best_ei"]) == (out["best_index"], out["best_ei"])
+
+
 def test_bench_dump_outputs_writes_the_last_timed_step(tmp_path):
     """--dump-outputs DIR: the last timed step's results as float64 .npy files (best index / EI as the line reports them,
     the per-candidate EI mean and the per-draw EI), identical for two runs with the same arguments; --steps is the number

@@ -173,7 +173,7 @@ def test_bench_two_ranks_equals_one_rank_over_concatenated_candidates(eng):
     env = dict(os.environ, SPX_BENCH_BACKEND="gloo", SPX_BENCH_SINGLE_DEVICE="1")
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "2",
            "--master-addr", "127.0.0.1", "--master-port", str(_free_port()), os.path.join(ROOT, "bench.py"),
-           "--gpus", "2", "--steps", "1", "--warmup", "0", "--workload", "c2", "--no-cpu-baseline",
+           "--gpus", "2", "--steps", "1", "--warmup", "0", "--workload", "c2", "--full", "--no-cpu-baseline",
            "--extra-steps", "1", "--c4-candidates", "30000", "--c5-candidates", "20000", "--hyper-shards", "2"]
     res = subprocess.run(cmd, env=env, cwd=ROOT, stdout=subprocess.PIPE, stderr=subprocess.PIPE, timeout=850)
     assert res.returncode == 0, res.stderr.decode()[-2000:]
@@ -226,7 +226,8 @@ def test_bench_gpus_2_with_no_launcher_starts_two_ranks_on_libspx(eng):
     for k in ("WORLD_SIZE", "RANK", "LOCAL_RANK", "MASTER_ADDR", "MASTER_PORT"):
         env.pop(k, None)
     cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", "2", "--warmup", "1", "--workload", "c2",
-           "--no-cpu-baseline", "--no-live-traffic", "--extra-steps", "1", "--c4-candidates", "30000", "--c5-candidates", "20000"]
+           "--full", "--no-cpu-baseline", "--no-live-traffic", "--extra-steps", "1", "--c4-candidates", "30000",
+           "--c5-candidates", "20000"]
     res = subprocess.run(cmd, env=env, cwd=ROOT, stdout=subprocess.PIPE, stderr=subprocess.PIPE, timeout=850)
     assert res.returncode == 0, res.stderr.decode()[-2000:]
     out = json.loads([l for l in res.stdout.decode().splitlines() if l.startswith("{")][-1])
@@ -358,7 +359,7 @@ def test_bench_in_process_mode_matches_the_default_mode(eng):
     """bench.py --in-process: the weak-scaling headline through one multi-device handle (the RCCL path of
     libspx; here a communicator of one device) must pick the same candidate as the default mode."""
     cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--in-process", "--gpus", "1", "--steps", "1", "--warmup", "0",
-           "--workload", "c2", "--c4-candidates", "30000", "--c5-candidates", "20000", "--hyper-shards", "2"]
+           "--workload", "c2", "--full", "--c4-candidates", "30000", "--c5-candidates", "20000", "--hyper-shards", "2"]
     res = subprocess.run(cmd, cwd=ROOT, stdout=subprocess.PIPE, stderr=subprocess.PIPE, timeout=800)
     assert res.returncode == 0, res.stderr.decode()[-2000:]
     out = json.loads([l for l in res.stdout.decode().splitlines() if l.startswith("{")][-1])
@@ -417,7 +418,7 @@ def test_process_group_communicator_attached_to_a_handle(eng):
     # bench.py with the library collective (one rank)
     env = dict(os.environ, SPX_BENCH_COLLECTIVE="lib")
     cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--steps", "1", "--warmup", "0", "--workload", "c2",
-           "--no-cpu-baseline", "--skip-extras"]
+           "--full", "--no-cpu-baseline", "--no-live-traffic", "--skip-extras"]
     res = subprocess.run(cmd, env=env, cwd=ROOT, stdout=subprocess.PIPE, stderr=subprocess.PIPE, timeout=800)
     assert res.returncode == 0, res.stderr.decode()[-2000:]
     out = json.loads([l for l in res.stdout.decode().splitlines() if l.startswith("{")][-1])
