@@ -1,0 +1,647 @@
+"""The SPX_FLAG_CONSTRAINED pass (EI x P(feasible)) on every execution path of ei_run_impl, at the shapes and edges where
+its own buffers (con_p / con_Cs / con_s2 by chunk parity, mom_c, the cprob offset of a draw group) can go wrong, in the
+tails of P against a 50-digit reference, and through the handle's state machine.  Sorted after test_gpu_j_constrained.py,
+whose plain parity tests should be read first when both fail."""
+import contextlib
+import functools
+import os
+
+import numpy as np
+import pytest
+from numpy.linalg import LinAlgError
+
+from spearmint_amd import hostgp
+from spearmint_amd.engine import FLAG_CONSTRAINED, FLAG_KEEP_MOMENTS
+from tests import constrained_mp as cm
+from tests import constrained_oracle as co
+from tests.test_gpu_j_constrained import _oracle, _problem, assert_product_close
+
+pytestmark = pytest.mark.gpu
+KEEP = FLAG_CONSTRAINED | FLAG_KEEP_MOMENTS
+OPTION_DEFAULTS = {"kstar_budget_bytes": 0, "streams": 1, "step_overlap": -1, "ei_fused": -1, "gemm_partial": -1,
+                   "timing": 0}
+
+
+@pytest.fixture()
+def eng():
+    from spearmint_amd.engine import Engine
+    e = Engine(0)
+    yield e
+    e.close()
+
+
+@contextlib.contextmanager
+def options(eng, **kw):
+    try:
+        for k, v in kw.items():
+            eng.set_option(k, v)
+        yield
+    finally:
+        for k in kw:
+            eng.set_option(k, OPTION_DEFAULTS[k])
+
+
+def plan_chunks(M, n_obs, H, budget):
+    """plan_chunks of csrc/spx_api.hip: (number of candidate chunks, draws per group) for a staging budget in bytes."""
+    up = lambda a, b: (a + b - 1) // b * b      # noqa: E731
+    Np, Mp = up(n_obs, 128), up(M, 128)
+    mc_budget = max(budget // (8 * Np) // 128 * 128, 128)
+    mc = min(mc_budget, Mp)
+    nchunks = (Mp + mc - 1) // mc
+    mc = up((Mp + nchunks - 1) // nchunks, 128)
+    if nchunks > 1:
+        if up(mc, 1024) <= mc_budget:
+            mc = up(mc, 1024)
+        elif mc >= 2048:
+            mc = mc // 1024 * 1024
+    return (Mp + mc - 1) // mc, min(max(budget // (8 * Np * mc), 1), H)
+
+
+def load(eng, covar, prob, pend=None):
+    """Everything resident: the valid observations (+ pending points), candidates, both sets of hyper rows."""
+    comp, vals, labels, cand, rows, crows, ff = prob
+    good = labels > 0
+    eng.set_covar(covar)
+    if pend is None:
+        eng.set_observations(comp[good], vals[good])
+    else:
+        eng.set_observations(np.concatenate((comp[good], pend)), np.concatenate((vals[good], np.zeros(len(pend)))))
+    eng.set_candidates(cand)
+    eng.set_hypers(rows)
+    if np.all(good):
+        eng.set_constraint_model(np.zeros((0, comp.shape[1])), np.zeros(0), crows)
+    else:
+        eng.set_constraint_model(comp, ff, crows)
+
+
+def collect(eng, want_P=True):
+    out = {"draws": eng.ei_draws(), "mean": eng.ei_mean(), "best": eng.best()}
+    if want_P:
+        out["P"] = np.stack([eng.get_constraint_prob(h) for h in range(eng.H)], axis=1)
+    return out
+
+
+def step(eng, flags=KEEP):
+    eng.ei_step(flags)
+    return collect(eng, (flags & KEEP) == KEEP)
+
+
+def assert_same(a, b, what=""):
+    """Bit for bit (a NaN equal to a NaN): per-draw values, mean over draws, P of every draw, the winner and its value."""
+    for k in ("draws", "mean", "P"):
+        if k in a and k in b:
+            assert np.array_equal(a[k], b[k], equal_nan=True), (what, k, int(np.sum(a[k] != b[k])))
+    assert a["best"][0] == b["best"][0], what
+    assert a["best"][1] == b["best"][1] or (np.isnan(a["best"][1]) and np.isnan(b["best"][1])), what
+
+
+def assert_winner(idx, mean_o):
+    """The oracle's argmax of the mean over draws.  Where the oracle's two best means are closer than its own tolerance
+    (1e-9 relative, the rule of the product) either is a right answer; the seeds below are ones where that does not
+    happen on the oracle's side, so the first branch is what runs."""
+    top = int(np.argmax(mean_o))
+    if idx == top:
+        return
+    assert not np.isnan(mean_o[top]) and mean_o[idx] >= mean_o[top] * (1 - 1e-9), (idx, top, mean_o[idx], mean_o[top])
+
+
+def assert_oracle(res, ei_o, P_o):
+    np.testing.assert_allclose(res["P"], P_o, rtol=1e-9, atol=0)
+    assert_product_close(res["draws"], ei_o)
+    assert_winner(res["best"][0], np.mean(ei_o, axis=1))
+    assert np.array_equal(res["mean"], np.mean(res["draws"], axis=1), equal_nan=True)
+    assert res["best"][1] == res["mean"][res["best"][0]] or np.isnan(res["best"][1])
+
+
+def scramble(eng, covar, prob):
+    """Another problem of the same sizes through the default path, so that every buffer the next pass should write holds
+    WRONG values of the right shape: a variant that skips a store, or stores it at the wrong place, cannot pass on what the
+    run before it left behind."""
+    comp, vals, labels, cand, rows, crows, ff = prob
+    rows2 = rows[::-1].copy()
+    rows2[:, 2] *= 1.3
+    crows2 = crows[::-1].copy()
+    crows2[:, 0] *= -0.7
+    load(eng, covar, (comp, vals, labels, cand[::-1].copy(), rows2, crows2, -ff))
+    eng.ei_step(KEEP)
+    load(eng, covar, prob)
+
+
+# ---- 1. path equivalence, bit for bit, anchored to the oracle ------------------------------------------------------------
+#                name: (seed, N_full, N_bad, M, D, H, small staging budget)
+BASES = {"general": (101, 300, 57, 5000, 7, 5, 256 * 1024 * 8),          # three-stage path, Np = 256
+         "fused": (102, 129, 40, 9001, 4, 6, 8 * 128 * 2048),            # k_ei_fused128
+         "allvalid": (103, 200, 0, 5000, 5, 4, 256 * 1024 * 8),          # k_constraint_const, three-stage
+         "allvalid_fused": (104, 37, 0, 2500, 2, 3, 8 * 128 * 512)}      # k_constraint_const, fused
+IS_FUSED = {"general": False, "fused": True, "allvalid": False, "allvalid_fused": True}
+
+
+@functools.lru_cache(maxsize=None)
+def base_problem(name):
+    seed, n_full, n_bad, M, D, H, budget = BASES[name]
+    prob = _problem(seed, n_full, n_bad, M, D, H)
+    ei_o, P_o = _oracle("Matern52", *prob)
+    return prob, ei_o, P_o, budget
+
+
+def default_run(eng, name):
+    prob, ei_o, P_o, budget = base_problem(name)
+    load(eng, "Matern52", prob)
+    base = step(eng)
+    assert_oracle(base, ei_o, P_o)
+    assert eng.stat("last_step_fused") == int(IS_FUSED[name])
+    n_valid = int(np.sum(prob[2] > 0))
+    nchunks, hb = plan_chunks(prob[3].shape[0], n_valid, prob[4].shape[0], budget)
+    assert nchunks >= 5 and hb == 1, (nchunks, hb)       # what "small budget" means below
+    scramble(eng, "Matern52", prob)
+    return prob, base, budget, nchunks
+
+
+VARIANTS = {"chunks": dict(kstar_budget_bytes=True),
+            "streams2": dict(streams=2),
+            "streams2+chunks": dict(streams=2, kstar_budget_bytes=True),
+            "no_overlap": dict(step_overlap=0),
+            "no_overlap+chunks": dict(step_overlap=0, kstar_budget_bytes=True),
+            "no_overlap+streams2+chunks": dict(step_overlap=0, streams=2, kstar_budget_bytes=True)}
+
+
+def _opts(variant, budget):
+    kw = dict(VARIANTS[variant])
+    if kw.get("kstar_budget_bytes"):
+        kw["kstar_budget_bytes"] = budget
+    return kw
+
+
+@pytest.mark.parametrize("variant", sorted(VARIANTS))
+@pytest.mark.parametrize("name", sorted(BASES))
+def test_step_variants_do_not_change_bits(eng, name, variant):
+    prob, base, budget, _ = default_run(eng, name)
+    with options(eng, **_opts(variant, budget)):
+        got = step(eng)
+        assert eng.stat("last_step_fused") == int(IS_FUSED[name])
+    assert_same(got, base, (name, variant))
+
+
+@pytest.mark.parametrize("variant", ["default", "chunks", "streams2", "streams2+chunks"])
+@pytest.mark.parametrize("name", sorted(BASES))
+def test_factor_plus_run_equals_step(eng, name, variant):
+    prob, base, budget, _ = default_run(eng, name)
+    with options(eng, **({} if variant == "default" else _opts(variant, budget))):
+        eng.factor()
+        eng.ei_run(KEEP)
+        got = collect(eng)
+    assert_same(got, base, (name, variant))
+
+
+@pytest.mark.parametrize("name", sorted(BASES))
+def test_small_budget_really_chunks(eng, name):
+    """The timed form of the pass (stage timers bracket every launch) with the small budget: the launch counts say how
+    many chunks and draw groups ran, and its results are the default's."""
+    prob, base, budget, nchunks = default_run(eng, name)
+    H = prob[4].shape[0]
+    with options(eng, kstar_budget_bytes=budget, timing=1):
+        eng.factor()
+        eng.ei_run(KEEP)
+        got = collect(eng)
+        t = eng.timings()
+    assert_same(got, base, name)
+    n_con = 0 if np.all(prob[2] > 0) else 1
+    if IS_FUSED[name]:
+        assert t["predict_gemm"][1] == nchunks and t["ei_finalize"][1] == 0 and t["cov_cross"][1] == 0
+    else:
+        assert t["ei_finalize"][1] == nchunks
+        assert t["predict_gemm"][1] == nchunks * H and t["cov_cross"][1] == nchunks * H      # one draw per group
+    assert t["cross_mean"][1] == nchunks                                 # P of a chunk: one launch, every draw
+    assert t["scale_rows"][1] >= nchunks * (1 + n_con)                   # (+ the factorisation's own)
+
+
+@pytest.mark.parametrize("name", ["fused", "allvalid_fused"])
+@pytest.mark.parametrize("chunks", [False, True])
+def test_unfused_multiply_equals_fused(eng, name, chunks):
+    """The multiply by P in k_ei_fused128 against the one in k_ei_finalize."""
+    prob, base, budget, _ = default_run(eng, name)
+    kw = dict(ei_fused=0)
+    if chunks:
+        kw["kstar_budget_bytes"] = budget
+    with options(eng, **kw):
+        got = step(eng)
+        assert eng.stat("last_step_fused") == 0
+    assert_same(got, base, name)
+    with options(eng, ei_fused=1, **({"kstar_budget_bytes": budget} if chunks else {})):
+        again = step(eng)
+        assert eng.stat("last_step_fused") == 1
+    assert_same(again, base, name)
+
+
+@pytest.mark.parametrize("name", ["general", "allvalid"])
+def test_gemm_padding_skip_does_not_change_bits(eng, name):
+    """The predict GEMM with and without the padding of N (16-row steps past N: 200 valid observations leave three of
+    them inside Np = 256, 243 leave none -- there the option has nothing to skip and the two runs are one path)."""
+    prob, base, budget, _ = default_run(eng, name)
+    n_valid = int(np.sum(prob[2] > 0))
+    has_padding_steps = (n_valid + 15) // 16 * 16 < (n_valid + 127) // 128 * 128
+    assert has_padding_steps == (name == "allvalid")
+    for on in (0, 1):
+        with options(eng, gemm_partial=on, kstar_budget_bytes=budget):
+            got = step(eng)
+            assert eng.stat("last_step_skipped_padding") == int(on and has_padding_steps)
+        assert_same(got, base, (name, on))
+
+
+@pytest.mark.parametrize("name", sorted(BASES))
+def test_without_keep_moments(eng, name):
+    prob, base, budget, _ = default_run(eng, name)
+    for kw in ({}, dict(kstar_budget_bytes=budget), dict(kstar_budget_bytes=budget, streams=2)):
+        with options(eng, **kw):
+            got = step(eng, FLAG_CONSTRAINED)
+            with pytest.raises(ValueError, match="KEEP_MOMENTS"):
+                eng.get_constraint_prob(0)
+        assert_same(got, base, (name, sorted(kw)))
+        scramble(eng, "Matern52", prob)
+
+
+@pytest.mark.parametrize("name", sorted(BASES))
+def test_plain_pass_between_constrained_passes(eng, name):
+    """FLAG_CONSTRAINED, then a pass without it on the same handle, and back: no stale cprob in the plain pass."""
+    from spearmint_amd.engine import Engine
+    prob, base, budget, _ = default_run(eng, name)
+    comp, vals, labels, cand, rows, crows, ff = prob
+    good = labels > 0
+    fresh = Engine(0)
+    try:
+        idx, val, mean, draws = fresh.ei_grid(comp[good], vals[good], cand, rows, want_draws=True)
+    finally:
+        fresh.close()
+    for kw in ({}, dict(kstar_budget_bytes=budget)):
+        with options(eng, **kw):
+            assert_same(step(eng), base, name)
+            plain = step(eng, FLAG_KEEP_MOMENTS)
+            with pytest.raises(ValueError):
+                eng.get_constraint_prob(0)
+            assert np.array_equal(plain["draws"], draws) and np.array_equal(plain["mean"], mean)
+            assert plain["best"] == (idx, val)
+            assert_same(step(eng), base, name)
+    assert not np.array_equal(draws, base["draws"])
+
+
+def _fantasy_problem():
+    prob = _problem(105, 300, 57, 5000, 3, 5)
+    pend = np.random.RandomState(6).rand(4, 3)
+    rs = np.random.RandomState(7)
+    randn = [rs.randn(4, 12) for _ in range(5)]
+    return prob, pend, randn
+
+
+def _fantasy_run(eng, prob, pend, randn):
+    comp, vals, labels, cand, rows, crows, ff = prob
+    good = labels > 0
+    n, H, S = int(np.sum(good)), rows.shape[0], randn[0].shape[1]
+    eng.factor()
+    fant, bests = np.empty((H, n + len(pend), S)), np.empty((H, S))
+    for h in range(H):
+        l_rows, gam = eng.get_factor_rows(h, n, len(pend))
+        fant[h], bests[h] = hostgp.fantasize_from_factor_rows(vals[good], rows[h], l_rows, gam, randn[h])
+    eng.set_fantasies(fant, bests)
+    eng.ei_run(FLAG_CONSTRAINED)
+    return collect(eng, False)
+
+
+def test_fantasies_chunks_draw_groups_and_streams(eng):
+    """Pending jobs (the three-stage path only): 243 valid + 4 pending observations, 12 fantasies, 5 draws.  The small
+    budget gives several chunks AND one draw per group, so k_ei_fant_mean reads cprob + h0 * mc for h0 > 0."""
+    prob, pend, randn = _fantasy_problem()
+    budget = 256 * 1024 * 8
+    nchunks, hb = plan_chunks(5000, 247, 5, budget)
+    assert nchunks >= 5 and hb == 1
+    load(eng, "Matern52", prob, pend)
+    base = _fantasy_run(eng, prob, pend, randn)
+    ei_o, _ = _oracle("Matern52", *prob, pend=pend, randn=randn)
+    assert_product_close(base["draws"], ei_o)
+    assert_winner(base["best"][0], np.mean(ei_o, axis=1))
+    for kw in (dict(kstar_budget_bytes=budget), dict(streams=2), dict(streams=2, kstar_budget_bytes=budget)):
+        scramble(eng, "Matern52", prob)
+        load(eng, "Matern52", prob, pend)
+        with options(eng, **kw):
+            got = _fantasy_run(eng, prob, pend, randn)
+        assert_same(got, base, sorted(kw))
+    with options(eng, kstar_budget_bytes=budget, timing=1):
+        got = _fantasy_run(eng, prob, pend, randn)
+        t = eng.timings()
+    assert_same(got, base, "timed")
+    assert t["ei_finalize"][1] == nchunks * 5 and t["cross_mean"][1] == nchunks
+
+
+# ---- 2. shapes and edges against the oracle --------------------------------------------------------------------------------
+#         (N_full, N_valid, M, D, H)
+SHAPES = [(128, 127, 700, 3, 3), (129, 128, 700, 3, 3), (130, 129, 700, 3, 3), (257, 128, 700, 3, 3), (257, 129, 700, 3, 3),
+          (300, 2, 700, 3, 3), (65, 64, 700, 3, 3), (3, 2, 700, 3, 3), (201, 200, 700, 3, 3),
+          (150, 120, 600, 1, 3), (150, 120, 600, 33, 3), (260, 200, 600, 1, 3), (260, 200, 600, 33, 3),
+          (150, 120, 600, 3, 1), (260, 200, 600, 3, 1), (90, 70, 300, 3, 130), (200, 150, 300, 3, 130),
+          (150, 120, 1, 3, 3), (150, 120, 127, 3, 3), (150, 120, 128, 3, 3), (150, 120, 129, 3, 3),
+          (260, 200, 1, 3, 3), (260, 200, 127, 3, 3), (260, 200, 128, 3, 3), (260, 200, 129, 3, 3)]
+
+
+@pytest.mark.parametrize("n_full,n_valid,M,D,H", SHAPES)
+def test_shapes_match_oracle(eng, n_full, n_valid, M, D, H):
+    """Pad boundaries of the objective's handle (N_valid) and of the constraint model's (N_full) independently, a single
+    violation, D = 1 / 33 (the Dp padding of con_Cs), H = 1 / 130 (more draws than one block of the mean), M around 128."""
+    prob = _problem(7 * n_full + 3 * n_valid + M + D + H, n_full, n_full - n_valid, M, D, H)
+    load(eng, "Matern52", prob)
+    res = step(eng)
+    ei_o, P_o = _oracle("Matern52", *prob)
+    assert_oracle(res, ei_o, P_o)
+    assert eng.stat("last_step_fused") == int(n_valid <= 128)
+
+
+@pytest.mark.parametrize("covar", ["Matern52", "Matern32", "ARDSE", "SE"])
+def test_every_covar_with_several_chunks(eng, covar):
+    prob = _problem(40 + len(covar), 300, 57, 5000, 3, 4)
+    budget = 256 * 1024 * 8
+    nchunks, hb = plan_chunks(5000, 243, 4, budget)
+    assert nchunks >= 5 and hb == 1
+    ei_o, P_o = _oracle(covar, *prob)
+    load(eng, covar, prob)
+    with options(eng, kstar_budget_bytes=budget):
+        assert_oracle(step(eng), ei_o, P_o)
+    with options(eng, kstar_budget_bytes=budget, streams=2):
+        assert_oracle(step(eng), ei_o, P_o)
+
+
+@pytest.mark.parametrize("name", ["general", "fused", "allvalid"])
+@pytest.mark.parametrize("chunks", [False, True])
+def test_nan_candidate(eng, name, chunks):
+    """One candidate with a NaN coordinate.  The oracle: constraint_prob propagates the NaN through K*' alpha (the
+    all-valid constant does not look at the candidate), and EI of a NaN point is NaN (the oracle's triangular solve refuses
+    non-finite input, so its EI is taken at the finite candidates and the NaN row set by that rule); np.argmax of the mean
+    returns the first NaN."""
+    (comp, vals, labels, cand, rows, crows, ff), ei_o, P_o, budget = base_problem(name)
+    H, bad_at = rows.shape[0], cand.shape[0] * 2 // 3 + 1
+    bad = cand.copy()
+    bad[bad_at, cand.shape[1] - 1] = np.nan
+    all_valid = bool(np.all(labels > 0))
+    P_bad = np.stack([np.broadcast_to(co.constraint_prob("Matern52", comp, ff, crows[h], bad, all_valid), (len(bad),))
+                      for h in range(H)], axis=1)
+    assert np.all(np.isnan(P_bad[bad_at])) == (not all_valid)
+    ei_bad = ei_o.copy()
+    ei_bad[bad_at] = np.nan
+    with options(eng, **({"kstar_budget_bytes": budget} if chunks else {})):
+        load(eng, "Matern52", (comp, vals, labels, cand, rows, crows, ff))
+        clean = step(eng)
+        load(eng, "Matern52", (comp, vals, labels, bad, rows, crows, ff))
+        res = step(eng)
+    assert np.array_equal(np.isnan(res["P"]), np.isnan(P_bad))
+    assert np.all(np.isnan(res["draws"][bad_at])) and np.isnan(res["mean"][bad_at])
+    assert res["best"][0] == int(np.argmax(np.mean(ei_bad, axis=1))) == bad_at and np.isnan(res["best"][1])
+    keep = np.arange(len(cand)) != bad_at
+    assert np.array_equal(res["draws"][keep], clean["draws"][keep])
+    assert np.array_equal(res["mean"][keep], clean["mean"][keep])
+    assert np.array_equal(res["P"][keep], clean["P"][keep])
+    if all_valid:
+        assert np.array_equal(res["P"], clean["P"])
+    np.testing.assert_allclose(res["P"][keep], P_bad[keep], rtol=1e-9, atol=0)
+    assert_product_close(res["draws"], ei_bad)
+
+
+# ---- 3. the tails of P against the 50-digit reference ----------------------------------------------------------------------
+FLOOR = 16 * np.finfo(float).eps      # 3.6e-15: a band where the oracle happens to be exact is not an impossible bar
+
+
+def _tail_run(eng, g, **kw):
+    good = g["labels"] > 0
+    eng.set_covar("Matern52")
+    eng.set_observations(g["comp"][good], g["vals"][good])
+    eng.set_candidates(g["cand"])
+    eng.set_hypers(g["rows"])
+    eng.set_constraint_model(g["comp"], g["ff"], g["crows"])
+    with options(eng, **kw):
+        return step(eng)
+
+
+def test_tail_probability_against_50_digits(eng, golden_dir):
+    """P from 1 down past 1e-300 (tests/golden/constrained_tail_mp.npz; mpmath is not needed here).  Per draw and band of
+    log10 P -- [-3, 0], [-20, -3), [-100, -20), [-300, -100) -- the device's max relative error against the 50-digit value
+    is at most 4 x the float64 oracle's own (numpy / scipy on the same inputs, computed here), floor 16 ulp.
+
+    Measured on an MI355X, device error / oracle error = ratio per band (bar: 4):
+        draw 0 (gain 3):     1.64e-10 / 9.75e-11 = 1.68, 5.37e-10 / 2.99e-10 = 1.80, 1.16e-9 / 1.05e-9 = 1.11,
+                             1.86e-9 / 9.40e-10 = 1.98
+        draw 1 (gain 0.75):  1.99e-11 / 3.35e-11 = 0.60, 8.11e-11 / 4.53e-11 = 1.79, 2.45e-11 / 5.13e-11 = 0.48 (no
+                             candidate below 1e-22)
+    and, through Phi^-1 of both, the largest relative error of u = gain m itself (taken where u is smallest, so a figure
+    for the sum K*' alpha_c and not for P): device 5.2e-9 against the oracle's 1.5e-9 in draw 0, 6.0e-11 against 2.1e-10
+    in draw 1.  The error of P is that of the sum, amplified by u^2 in the tail, on either side; ndtr_dev adds nothing that
+    shows."""
+    g = np.load(os.path.join(golden_dir, "constrained_tail_mp.npz"))
+    res = _tail_run(eng, g)
+    P = res["P"]
+    H = g["crows"].shape[0]
+    report, failures = [], []
+    for h in range(H):
+        lp, ref = g["log10P"][:, h], g["P_ref"][:, h]
+        P_o = co.constraint_prob("Matern52", g["comp"], g["ff"], g["crows"][h], g["cand"], False)
+        e_o, e_d = cm.band_errors(P_o, ref, lp), cm.band_errors(P[:, h], ref, lp)
+        for band, o, d in zip(cm.TAIL_BANDS, e_o, e_d):
+            if o is None:
+                continue
+            bar = max(4 * o, FLOOR)
+            report.append("draw %d band %s: device %.3g oracle %.3g ratio %.3g" % (h, band, d, o, d / o if o else np.inf))
+            if not d <= bar:
+                failures.append(report[-1])
+        # below 1e-300 (denormals and beyond): a condition, not a measurement
+        deep = lp < -300
+        assert np.mean(deep) <= 0.15
+        assert np.all((P[deep, h] >= 0) & (P[deep, h] <= 1e-290))
+        # the upper tail: never above 1, within one ulp of the rounded reference
+        top = 1.0 - ref <= 1e-12
+        assert top.any() or h > 0
+        assert np.all(P[:, h] <= 1.0) and np.all(P[:, h] >= 0.0)
+        assert np.all(np.abs(P[top, h] - ref[top]) <= np.spacing(ref[top]))
+        # where the error comes from: Phi^-1 of both against the 50-digit u = gain m
+        import scipy.special as sp
+        mid = (lp > -300) & (lp < -1e-3)
+        du_dev = np.max(np.abs(sp.ndtri(P[mid, h]) - g["u_ref"][mid, h]) / np.abs(g["u_ref"][mid, h]))
+        du_orc = np.max(np.abs(sp.ndtri(P_o[mid]) - g["u_ref"][mid, h]) / np.abs(g["u_ref"][mid, h]))
+        report.append("draw %d: max relative error of u = gain m, device %.3g oracle %.3g" % (h, du_dev, du_orc))
+    print("\n".join(report))
+    assert not failures, "\n".join(report)
+
+
+def test_tail_product_against_50_digits(eng, golden_dir):
+    """EI x P per draw against ei_nopend x the 50-digit P (rounded to float64 after the product): the banded rule of the
+    test above, bands by log10 P; never negative, never above the EI of the same pass without the factor.
+
+    Measured on an MI355X, device error / oracle error per band (bar: 4) -- P's own, the EI factor adds nothing visible:
+        draw 0 (gain 3):     1.67, 1.80, 1.11, 1.98
+        draw 1 (gain 0.75):  0.60, 1.79, 0.48"""
+    g = np.load(os.path.join(golden_dir, "constrained_tail_mp.npz"))
+    good = g["labels"] > 0
+    res = _tail_run(eng, g)
+    plain = step(eng, FLAG_KEEP_MOMENTS)
+    unfused = _tail_run(eng, g, ei_fused=0)
+    assert_same(unfused, res, "ei_fused=0")
+    draws = res["draws"]
+    assert np.all(draws >= 0) and np.all(draws <= plain["draws"])
+    report, failures = [], []
+    for h in range(g["crows"].shape[0]):
+        lp, ref = g["log10P"][:, h].copy(), g["prod_ref"][:, h]
+        ei = co.ei_nopend("Matern52", g["comp"][good], g["vals"][good], g["rows"][h], g["cand"])
+        np.testing.assert_allclose(ei, g["ei_ref"][:, h], rtol=1e-11, atol=0)
+        prod_o = ei * co.constraint_prob("Matern52", g["comp"], g["ff"], g["crows"][h], g["cand"], False)
+        tiny = ref < 1e-300
+        assert np.all((draws[tiny, h] >= 0) & (draws[tiny, h] <= 1e-290))
+        lp[tiny] = -1e9                                        # (in no band)
+        ref1 = np.where(tiny, 1.0, ref)
+        e_o, e_d = cm.band_errors(prod_o, ref1, lp), cm.band_errors(draws[:, h], ref1, lp)
+        for band, o, d in zip(cm.TAIL_BANDS, e_o, e_d):
+            if o is None:
+                continue
+            report.append("draw %d band %s: device %.3g oracle %.3g ratio %.3g" % (h, band, d, o, d / o if o else np.inf))
+            if not d <= max(4 * o, FLOOR):
+                failures.append(report[-1])
+    print("\n".join(report))
+    assert not failures, "\n".join(report)
+
+
+# ---- 4. the handle's state machine -----------------------------------------------------------------------------------------
+def fresh_result(covar, prob, flags=KEEP, check_oracle=False):
+    """What a new engine gives for the final state alone."""
+    from spearmint_amd.engine import Engine
+    e = Engine(0)
+    try:
+        load(e, covar, prob)
+        res = step(e, flags)
+    finally:
+        e.close()
+    if check_oracle:
+        assert_oracle(res, *_oracle(covar, *prob))
+    return res
+
+
+def test_new_objective_hypers_reuse_the_cached_constraint_factor(eng):
+    prob = _problem(201, 300, 57, 5000, 4, 4)
+    comp, vals, labels, cand, rows, crows, ff = prob
+    load(eng, "Matern52", prob)
+    first = step(eng)
+    assert_same(first, fresh_result("Matern52", prob, check_oracle=True), "first")
+    rows2 = rows.copy()
+    rows2[:, 2] *= 1.7
+    rows2[:, 3:] *= 0.8
+    eng.set_hypers(rows2)                       # no second set_constraint_model: alpha_c stays
+    got = step(eng)
+    want = fresh_result("Matern52", (comp, vals, labels, cand, rows2, crows, ff))
+    assert_same(got, want, "new objective hypers")
+    assert np.array_equal(got["P"], first["P"]) and not np.array_equal(got["draws"], first["draws"])
+    # a new ff, same Nc: results change and match
+    ff2 = ff[::-1].copy()
+    eng.set_constraint_model(comp, ff2, crows)
+    got2 = step(eng)
+    assert_same(got2, fresh_result("Matern52", (comp, vals, labels, cand, rows2, crows, ff2), check_oracle=True), "new ff")
+    assert not np.array_equal(got2["P"], got["P"])
+
+
+def test_constraint_model_shrinks_and_grows(eng):
+    """Nc 300 -> 129 -> 40 -> 300 (stale rows of the internal handle past the new Np) with N_valid crossing 128 both ways
+    (fused <-> general with the constraint buffers kept), then Nc > 0 -> all valid -> Nc > 0."""
+    D, H, M = 3, 3, 3000
+    seq = [(300, 243), (129, 100), (40, 33), (300, 128), (300, 129), (129, 129), (200, 150), (129, 127)]
+    fused_seen = set()
+    for i, (n_full, n_valid) in enumerate(seq):
+        prob = _problem(300 + i, n_full, n_full - n_valid, M, D, H)
+        load(eng, "Matern52", prob)
+        got = step(eng)
+        fused_seen.add(eng.stat("last_step_fused"))
+        assert eng.stat("last_step_fused") == int(n_valid <= 128)
+        assert_same(got, fresh_result("Matern52", prob, check_oracle=(i in (0, 2))), (n_full, n_valid))
+    assert fused_seen == {0, 1}
+
+
+def test_all_valid_between_two_constraint_models(eng):
+    D, H, M = 3, 3, 3000
+    for i, (n_full, n_valid) in enumerate([(200, 150), (200, 200), (129, 100), (100, 100), (260, 190)]):
+        prob = _problem(320 + i, n_full, n_full - n_valid, M, D, H)
+        load(eng, "Matern52", prob)
+        got = step(eng)
+        assert_same(got, fresh_result("Matern52", prob, check_oracle=(i in (1, 4))), (n_full, n_valid))
+        if n_full == n_valid:
+            assert np.all(got["P"] == got["P"][0])
+
+
+def test_candidate_count_changes_between_constrained_passes(eng):
+    """M 5000 -> 300 -> 9001: con_p / mom_c re-reserved; get_constraint_prob returns M values of THIS grid."""
+    prob = _problem(340, 300, 57, 9001, 3, 4)
+    comp, vals, labels, cand, rows, crows, ff = prob
+    load(eng, "Matern52", prob)
+    for i, M in enumerate([5000, 300, 9001]):
+        sub = cand[(9001 - M) // 2:(9001 - M) // 2 + M][::-1].copy()
+        eng.set_candidates(sub)
+        got = step(eng)
+        assert got["P"].shape == (M, 4) and got["draws"].shape == (M, 4)
+        assert_same(got, fresh_result("Matern52", (comp, vals, labels, sub, rows, crows, ff), check_oracle=(i == 1)), M)
+
+
+def test_draw_count_mismatch_is_refused_and_the_handle_survives(eng):
+    """The seed: a comparison with the float64 oracle at rtol 1e-9 needs an oracle that is itself well inside 1e-9.  With
+    seed 350 it is not: at the two deepest candidates of draw 0 (P = 7.9e-52 and 1.7e-47) the oracle is 8.3e-10 and 6.1e-10
+    off the 50-digit value (tests/constrained_mp.py), the MI355X 3.1e-10 and 4.0e-10 off it -- and 1.14e-9 and 1.00e-9 off
+    the oracle, two roundings apart and no error of either.  The rule kept here, from the oracle's side alone: its own
+    error over the 40 deepest candidates of every draw stays below half the tolerance (seed 351: 2.1e-10 at worst)."""
+    prob = _problem(351, 200, 40, 2000, 3, 4)
+    comp, vals, labels, cand, rows, crows, ff = prob
+    load(eng, "Matern52", prob)
+    first = step(eng)
+    eng.set_hypers(rows[:3])                     # H 4 -> 3, the constraint model still has 4 rows
+    with pytest.raises(ValueError, match="H|draws"):
+        eng.ei_step(KEEP)
+    eng.factor()                                 # (the cached constraint factor is not looked at again)
+    with pytest.raises(ValueError, match="H|draws"):
+        eng.ei_run(KEEP)
+    plain = step(eng, FLAG_KEEP_MOMENTS)         # the objective alone is fine
+    assert plain["draws"].shape == (2000, 3)
+    eng.set_constraint_model(comp, ff, crows[:3])
+    got = step(eng)
+    assert_same(got, fresh_result("Matern52", (comp, vals, labels, cand, rows[:3], crows[:3], ff), check_oracle=True), "H=3")
+    eng.set_hypers(rows)
+    eng.set_constraint_model(comp, ff, crows)
+    assert_same(step(eng), first, "back to H=4")
+    # the all-valid model keeps no internal handle: its table of gains is what is counted
+    eng.set_constraint_model(np.zeros((0, 3)), np.zeros(0), crows)
+    step(eng)
+    eng.set_hypers(rows[:2])
+    with pytest.raises(ValueError, match="draws"):
+        eng.ei_step(KEEP)
+
+
+@pytest.mark.parametrize("entry", ["step", "factor", "step_timed"])
+@pytest.mark.parametrize("n_valid", [100, 243])
+def test_not_pd_constraint_model_is_draw_2H_plus_d(eng, entry, n_valid):
+    """A negative amp2_c in draw d: LinAlgError, spx_not_pd_info = (2H + d, pivot) as include/spx.h documents; the handle
+    is usable once a valid model is set, and its results are a fresh engine's."""
+    H, d = 4, 2
+    prob = _problem(360 + n_valid, 300, 300 - n_valid, 3000, 3, H)
+    comp, vals, labels, cand, rows, crows, ff = prob
+    good = labels > 0
+    load(eng, "Matern52", prob)
+    first = step(eng)
+    bad = crows.copy()
+    bad[d, 2] = -1.0
+    eng.set_constraint_model(comp, ff, bad)
+    with options(eng, **({"timing": 1} if entry == "step_timed" else {})):
+        with pytest.raises(LinAlgError, match="constraint"):
+            eng.factor() if entry == "factor" else eng.ei_step(KEEP)
+    draw, pivot = eng.not_pd_info()
+    assert draw == 2 * H + d and 0 <= pivot < 300
+    with pytest.raises(ValueError):
+        eng.ei_draws()                           # no results of a pass that did not run
+    # the objective's own model is untouched: without the constraint model the plain pass is a fresh engine's
+    eng.set_constraint_model(None, None, None)
+    plain = step(eng, FLAG_KEEP_MOMENTS)
+    from spearmint_amd.engine import Engine
+    fresh = Engine(0)
+    try:
+        idx, val, mean, draws = fresh.ei_grid(comp[good], vals[good], cand, rows, want_draws=True)
+    finally:
+        fresh.close()
+    assert np.array_equal(plain["draws"], draws) and plain["best"] == (idx, val)
+    eng.set_constraint_model(comp, ff, crows)
+    assert_same(step(eng), first, "after a valid model")
+    assert_same(first, fresh_result("Matern52", prob, check_oracle=True), "fresh")
