@@ -14,6 +14,10 @@
  * i.e. per hyper-parameter draw:  gp.Matern52/dist2 (gp.py:34-54,120-127),
  * chooser cov (GPEIChooser.py:117-122), spla.cholesky (:191), cho_solve (:194),
  * solve_triangular (:195), predictive mean/variance (:198-199), EI (:202-206).
+ * and, for the local refinement that follows that block, the L-BFGS-B objectives
+ * grad_optimize_ei_over_hypers of GPEIOptChooser.py:360-525 / GPEIperSecChooser.py:322-434
+ * (spx_ei_grad_batch) and of GPConstrainedEIChooser.py:471-803, EI times the probability of
+ * feasibility (spx_constrained_ei_grad_batch), at a batch of points per call.
  * The Python choosers in spearmint_amd/chooser/ bind it with ctypes
  * (see INTEGRATION.md for the stub a maintainer would add to the reference).
  *
@@ -150,7 +154,8 @@ int spx_set_time_model(spx_handle* h, const double* log_durs,
  * of the objective's N), their latent values ff (Nc) and H rows c_hypers [gain, noise_c, amp2_c, ls_c...] (H and D as
  * spx_set_hypers set them).  alpha_c = (amp2_c (k(X_c,X_c) + 1e-6 I) + noise_c I)^-1 ff -- no mean term -- is factored
  * by the next spx_factor / spx_ei_step, before the objective draws, on an internal handle of the same device (same
- * factorisation path, SPX_ERR_NOT_PD as for the objective; spx_not_pd_info reports draw 2H + d).  Nc = 0 is the
+ * factorisation path, SPX_ERR_NOT_PD as for the objective; spx_not_pd_info reports draw 2H + d; 3H + d is the objective's
+ * draw d over these Nc points, factored by spx_constrained_ei_grad_batch).  Nc = 0 is the
  * all-valid case (comp_c / ff may be NULL): P_d = Phi(gain_d).  All three pointers NULL clears the model.
  * SPX_ERR_ARG on a multi-device handle.                                                                            */
 int spx_set_constraint_model(spx_handle* h, const double* comp_c, const double* ff, int64_t Nc,
@@ -318,6 +323,26 @@ int spx_ei_grad_batch(spx_handle* h, const double* points, int32_t P, double* ne
                       double* grad /* P x D */);
 /* == spx_ei_grad_batch with P = 1 */
 int spx_ei_grad(spx_handle* h, const double* point, double* neg_ei_sum, double* grad /* D */);
+/* Objective of the CONSTRAINED chooser's local refinement (GPConstrainedEIChooser.py:471-501 grad_optimize_ei_over_hypers
+ * over :529-690 / :692-803) at P points in one call: neg_cei[p] = -(sum over the resident draws of EI_d x P_d), grad (P x D)
+ * its gradient in the reference's scaling (factor one half, as spx_ei_grad_batch).  Needs spx_factor / spx_ei_step and a
+ * factored constraint model (spx_set_constraint_model before that spx_factor); SPX_ERR_ARG otherwise, with a time model,
+ * and on a multi-device handle.  `best` is the caller's np.min of the VALID values (:655): neither the values the handle
+ * holds nor the `bests` of spx_set_fantasies are read.  The reference's arithmetic, quirks included:
+ *   no fantasies, Nc > 0   the predictive mean comes from the handle's own factor (the valid points), the variance and its
+ *                          part of the gradient from the SAME hypers over ALL completed points X_c:
+ *                          amp2 (k(X_c,X_c) + 1e-6 I) + noise I is factored on an internal handle on the first call (the
+ *                          ordinary factorisation path; SPX_ERR_NOT_PD, spx_not_pd_info reporting draw 3H + d) and kept
+ *                          until observations, hypers, the constraint model or option "covar" change.
+ *                          value_d = -EI_d P_d, grad_d = P_d grad(-EI_d) + EI_d gcm_d with
+ *                          gcm_d = 0.5 amp2_c gain phi(gain m_c) (alpha_c . dk_c/dx)   (the reference's sign)
+ *   no fantasies, Nc = 0   P = 1: equal to spx_ei_grad_batch bit for bit (given best = the handle's own minimum)
+ *   fantasies set          observations = [valid; pend]: every fantasy is scored against `best`, and EI and its gradient
+ *                          are SUMMED over the S fantasies (spx_ei_grad_batch averages): -(sum_s EI_s) P,
+ *                          P sum_s grad(-EI_s) + (sum_s EI_s) gcm.
+ * A point's result does not depend on the other points of the call.                                                  */
+int spx_constrained_ei_grad_batch(spx_handle* h, const double* points, int32_t P, double best,
+                                  double* neg_cei /* P */, double* grad /* P x D */);
 /* Sobol candidate grid on the device (ExperimentGrid.py:192-196 -> sobol_lib.py:125-157
  * i4_sobol_generate; "next" row 4): grid (n x dim, row-major) = transpose(i4_sobol_generate(dim,
  * n, skip)), bit-identical to the reference.  dirs = its scaled direction integers V[d][b]

@@ -5,8 +5,9 @@ spearmint/spearmint/chooser/GPConstrainedEIChooser.py.
 A job "violates the constraint" when its value is NaN, +-inf or equal to ``constraint_violating_value``.
 The EI grid (EI_d x P_d for every candidate and draw, the mean over draws, the argmax) is one libspx pass with
 SPX_FLAG_CONSTRAINED; the constraint GP's [amp2_c, ff] move evaluates through spx_gp_logprob_rhs and the objective's
-length-scale sweep through spx_gp_logprob; the rest of both samplers and the 20-point refinement run on the host
-(constrained.py).
+length-scale sweep through spx_gp_logprob; the 20-point refinement evaluates -(EI x P) and its gradient for all waiting
+points and draws in one spx_constrained_ei_grad_batch call (gpu_refine=0: constrained.RefineModel on the host, the
+oracle of that call); the rest of both samplers runs on the host (constrained.py).
 
 Reference behaviour reproduced on purpose (each changes proposals):
   1. constraint_hyper_samples is never cleared: draw d pairs hyper_samples[d] with the d-th constraint sample
@@ -224,7 +225,34 @@ class GPConstrainedEIChooser(GPEIBase):
         self.last_overall_ei = overall
         return overall
 
+    def _refine_gpu(self, points, comp, pend, vals, labels):
+        """The 20 L-BFGS-B problems against what the grid pass left resident: every waiting point of every instance goes
+        through one spx_constrained_ei_grad_batch call (valid points or [valid; pend] factored, the constraint model
+        factored).  With pending jobs the objective's fantasies are not the grid pass's: they restart from the RNG state
+        of the first _real_init (quirk 5), the same normals for every draw, on a private generator."""
+        eng = self.engine()
+        good = labels > 0
+        valsv = vals[good]
+        if pend.shape[0] > 0:
+            rows, _crows = self._draw_rows()
+            rs = npr.RandomState()
+            rs.set_state(self.randomstate)
+            randn = rs.randn(pend.shape[0], self.pending_samples)
+            n, H = valsv.shape[0], rows.shape[0]
+            fant = np.empty((H, n + pend.shape[0], self.pending_samples))
+            bests = np.empty((H, self.pending_samples))
+            for h in range(H):
+                l_rows, gam = eng.get_factor_rows(h, n, pend.shape[0])
+                fant[h], bests[h] = hostgp.fantasize_from_factor_rows(valsv, rows[h], l_rows, gam, randn)
+            eng.set_fantasies(fant, bests)
+        best = np.min(valsv)
+        return refine.lbfgs_many(lambda X: eng.constrained_ei_grad_batch(X, best), points, [(0, 1)] * comp.shape[1],
+                                 log=log)
+
     def _refine(self, points, comp, pend, vals, labels):
+        # (covar=SE: the reference's refinement raises AttributeError -- gp has no grad_SE -- and the host path does)
+        if self.covar != "SE" and self._use_gpu_refine(int(np.sum(labels > 0))):
+            return self._refine_gpu(points, comp, pend, vals, labels)
         rows = self.hyper_samples[:self.mcmc_iters]
         crows = self.constraint_hyper_samples[:self.mcmc_iters]
         models = [con.RefineModel(comp, pend, vals, labels, h, c, self.cst.ff, self.covar, self.pending_samples,

@@ -115,6 +115,13 @@ void launch_point_finish(hipStream_t s, const double* Xs, const double* hyp, con
                          double* out, int N, int Np, int D, int Dp, int nh, int P, const double* kt,
                          const double* dkt, int S, const double* gammaS, const double* alphaS,
                          const double* bests, double* uvec);
+// the constrained chooser's refinement objective: mean side (N rows), variance side (Nv rows), constraint side (Nc rows; 0 = none)
+void launch_point_finish_con(hipStream_t s, const double* Xs, const double* hyp, const double* htab, const double* alpha,
+                             const double* kvec, const double* dkdr2, int N, int Np, const double* XsV, const double* dkV,
+                             const double* tV, const double* zV, int Nv, int Npv, const double* XsC, const double* hypC,
+                             const double* conTab, const double* alphaC, const double* kC, const double* dkC, int Nc,
+                             int Npc, const double* x, double best, double* out, int D, int Dp, int nh, int P, int S,
+                             const double* gammaS, const double* alphaS, double* uvec);
 
 // fused_kernels.hip: the whole EI pass of a chunk for N <= 128 in one launch (no K* / beta in memory)
 void launch_ei_fused128(hipStream_t s, int kind, const double* WT, const double* gamma, const double* Xs, const double* s1,

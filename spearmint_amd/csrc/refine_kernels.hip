@@ -415,3 +415,208 @@ void launch_point_finish(hipStream_t s, const double* Xs, const double* hyp, con
                        htab, alpha, kvec, dkdr2, tvec, zvec, x, best, out, N, Np, D, Dp, P, nh, kt, dkt, S,
                        gammaS, alphaS, bests, uvec);
 }
+
+// ---- the constrained chooser's refinement objective (GPConstrainedEIChooser.py:471-803) -----------------------------
+// -(EI x P(feasible)) and its gradient per (draw, point); summed over the draws on the host.  Three sets of rows meet in
+// one workgroup, each with its own count and padding:
+//   mean side      the handle's own factor (N rows: the valid points, or [valid; pend]): func_m = k . alpha + mean, alpha . G
+//   variance side  without fantasies the SAME hypers over ALL completed points X_c (Nv = Nc rows; :692-803 -- the reference
+//                  takes obsv_chol_full here): func_v = amp2 (1 + 1e-6) - |t_f|^2, (-2 z_f) . G_f;  with fantasies the
+//                  handle's own rows again (Nv = N)
+//   constraint     the probit GP over X_c (Nc rows, its own length scales): m_c = k_c . alpha_c, P = Phi(gain m_c),
+//                  gcm[d] = 0.5 amp2_c gain (alpha_c . G_c[:, d]) phi(gain m_c)                       (:682-688)
+// value = EI P,  grad[d] = P grad(-EI)[d] + EI gcm[d]  -- the sign of the second term is the reference's (:688, :801).
+// With S fantasies (:529-690) every fantasy is scored against the one `best` and EI, its gradient and the weights u are
+// SUMS over the fantasies (GPEIOptChooser averages; this chooser does not).  Nc = 0: P = 1 and gcm = 0 (use_vanilla_ei).
+
+// acc[q] = sum_j w[j] dk[j] * 2 (X[j][d0 + q] - x[d0 + q] / ls) / ls over this thread's rows, then over the wavefront
+__device__ __forceinline__ void grad_pass(const double* __restrict__ Xh, int Dp, const double* __restrict__ ls,
+                                          const double* __restrict__ xp, const double* __restrict__ dk,
+                                          const double* __restrict__ w, int n, int d0, int nd, double* acc /*[GD]*/)
+{
+    double xc[GD], il[GD];
+#pragma unroll
+    for (int q = 0; q < GD; ++q) {
+        acc[q] = 0.0;
+        const int d = d0 + (q < nd ? q : 0);
+        xc[q] = xp[d] / ls[d];
+        il[q] = 1.0 / ls[d];
+    }
+    for (int j = threadIdx.x; j < n; j += 256) {
+        const double* xr = Xh + (size_t)j * Dp + d0;
+        const double dj = dk[j], wj = w[j];
+#pragma unroll
+        for (int q = 0; q < GD; ++q)
+            if (q < nd) acc[q] += wj * (dj * (2.0 * (xr[q] - xc[q]) * il[q]));
+    }
+#pragma unroll
+    for (int q = 0; q < GD; ++q) {
+#pragma unroll
+        for (int off = 32; off > 0; off >>= 1) acc[q] += __shfl_xor(acc[q], off);
+    }
+}
+
+__global__ __launch_bounds__(256) void k_point_finish_con(
+    // mean side
+    const double* __restrict__ Xs, const double* __restrict__ hyp, const double* __restrict__ htab,
+    const double* __restrict__ alpha, const double* __restrict__ kvec, const double* __restrict__ dkdr2, int N, int Np,
+    // variance side (length scales and amplitude are the mean side's)
+    const double* __restrict__ XsV, const double* __restrict__ dkV, const double* __restrict__ tV,
+    const double* __restrict__ zV, int Nv, int Npv,
+    // constraint side; conTab rows [gain, noise_c, amp2_c, amp2_c]
+    const double* __restrict__ XsC, const double* __restrict__ hypC, const double* __restrict__ conTab,
+    const double* __restrict__ alphaC, const double* __restrict__ kC, const double* __restrict__ dkC, int Nc, int Npc,
+    const double* __restrict__ x, double best, double* __restrict__ out, int D, int Dp, int P,
+    // fantasies (mean side == variance side then)
+    int S, const double* __restrict__ gammaS /*[H][S][Np]*/, const double* __restrict__ alphaS /*[H][S][Np]*/,
+    double* __restrict__ uvec /*[H][P][Np] work vector*/)
+{
+    extern __shared__ double dyn[];        // S > 0: [3][S]
+    __shared__ double red[4];
+    __shared__ double redv[4][3 * GD];
+    __shared__ double sh_ei, sh_gm, sh_gs2, sh_pc, sh_c1, sh_pdfc;
+    const int h = blockIdx.x, p = blockIdx.y;
+    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    const size_t vo = ((size_t)h * P + p) * Np, vv = ((size_t)h * P + p) * Npv, vc = ((size_t)h * P + p) * Npc;
+    const double* ah = alpha + (size_t)h * Np;
+    const double* th = tV + vv;
+    const double* xp = x + (size_t)p * D;
+    const double* ls = hyp + (size_t)h * (3 + D) + 3;
+    const double mean = htab[h * SPX_HT + 0], amp2 = htab[h * SPX_HT + 2], prior_v = htab[h * SPX_HT + 3];
+    double* o = out + ((size_t)h * P + p) * (1 + D);
+
+    double tt = 0.0;
+    for (int j = tid; j < Nv; j += 256) tt += th[j] * th[j];
+    tt = block_sum(tt, red);
+    if (S == 0) {
+        const double* kh = kvec + vo;
+        double ka = 0.0;
+        for (int j = tid; j < N; j += 256) ka += kh[j] * ah[j];
+        ka = block_sum(ka, red);
+        if (tid == 0) {
+#pragma clang fp contract(off)
+            const double func_m = ka + mean;
+            const double func_v = prior_v - tt;
+            const double func_s = sqrt(func_v);
+            const double u = (best - func_m) / func_s;
+            const double cdf = ndtr_r(u);
+            const double pdf = exp(-(u * u) / 2.0) / 2.50662827463100050242;
+            sh_ei = func_s * (u * cdf + pdf);
+            sh_gm = -cdf;
+            sh_gs2 = 0.5 * pdf / func_s;
+        }
+        __syncthreads();
+    } else {
+        // every fantasy against the one `best` (:645): func_m[s] = t . Gamma_s + mean; one wavefront per s
+        double* gmS = dyn;                 // [S]  -Phi_s
+        double* eiS = dyn + S;             // [S]
+        double* gsS = dyn + 2 * S;         // [S]  0.5 phi_s / func_s
+        const double func_v = prior_v - tt;
+        const double func_s = sqrt(func_v);
+        for (int sidx = wave; sidx < S; sidx += 4) {
+            const double* gs = gammaS + ((size_t)h * S + sidx) * Np;
+            double m = 0.0;
+            for (int j = lane; j < N; j += 64) m += th[j] * gs[j];
+#pragma unroll
+            for (int off = 32; off > 0; off >>= 1) m += __shfl_xor(m, off);
+            if (lane == 0) {
+#pragma clang fp contract(off)
+                const double func_m = m + mean;
+                const double u = (best - func_m) / func_s;
+                const double cdf = ndtr_r(u);
+                const double pdf = exp(-(u * u) / 2.0) / 2.50662827463100050242;
+                eiS[sidx] = func_s * (u * cdf + pdf);
+                gmS[sidx] = -cdf;
+                gsS[sidx] = 0.5 * pdf / func_s;
+            }
+        }
+        __syncthreads();
+        if (tid == 0) {
+            double e = 0.0, g2 = 0.0;
+            for (int sidx = 0; sidx < S; ++sidx) { e += eiS[sidx]; g2 += gsS[sidx]; }
+            sh_ei = e;
+            sh_gs2 = g2;
+            sh_gm = 1.0;
+        }
+        // u[j] = sum_s( -Phi_s alpha_s[j] )
+        double* uh = uvec + vo;
+        for (int j = tid; j < Np; j += 256) {
+            double a = 0.0;
+            if (j < N)
+                for (int sidx = 0; sidx < S; ++sidx) a += gmS[sidx] * alphaS[((size_t)h * S + sidx) * Np + j];
+            uh[j] = a;
+        }
+        __syncthreads();
+        ah = uh;     // the mean-gradient weights of the fantasy branch (g_m folded in)
+    }
+    if (Nc > 0) {
+        const double* kc = kC + vc;
+        const double* ac = alphaC + (size_t)h * Npc;
+        double mc = 0.0;
+        for (int j = tid; j < Nc; j += 256) mc += kc[j] * ac[j];
+        mc = block_sum(mc, red);
+        if (tid == 0) {
+#pragma clang fp contract(off)
+            const double gain = conTab[h * SPX_HT + 0], camp2 = conTab[h * SPX_HT + 2];
+            const double a = gain * mc;
+            sh_pc = ndtr_r(a);
+            sh_pdfc = exp(-(a * a) / 2.0) / 2.50662827463100050242;
+            sh_c1 = 0.5 * camp2 * gain;
+        }
+        __syncthreads();
+    }
+    const double g_m = sh_gm, g_s2 = sh_gs2, ei = sh_ei;
+    const double* lsC = Nc > 0 ? hypC + (size_t)h * (3 + D) + 3 : ls;
+
+    for (int d0 = 0; d0 < D; d0 += GD) {
+        const int nd = min(GD, D - d0);
+        double a1[GD], a2[GD], a3[GD];
+        grad_pass(Xs + (size_t)h * Np * Dp, Dp, ls, xp, dkdr2 + vo, ah, N, d0, nd, a1);
+        grad_pass(XsV + (size_t)h * Npv * Dp, Dp, ls, xp, dkV + vv, zV + vv, Nv, d0, nd, a2);
+        if (Nc > 0) {
+            grad_pass(XsC + (size_t)h * Npc * Dp, Dp, lsC, xp, dkC + vc, alphaC + (size_t)h * Npc, Nc, d0, nd, a3);
+        } else {
+#pragma unroll
+            for (int q = 0; q < GD; ++q) a3[q] = 0.0;
+        }
+        __syncthreads();
+        if (lane == 0) {
+#pragma unroll
+            for (int q = 0; q < GD; ++q) {
+                redv[wave][q] = a1[q];
+                redv[wave][GD + q] = a2[q];
+                redv[wave][2 * GD + q] = a3[q];
+            }
+        }
+        __syncthreads();
+        if (tid < nd) {
+#pragma clang fp contract(off)
+            const int q = tid;
+            const double s1v = ((redv[0][q] + redv[1][q]) + redv[2][q]) + redv[3][q];
+            const double s2v = ((redv[0][GD + q] + redv[1][GD + q]) + redv[2][GD + q]) + redv[3][GD + q];
+            double gd = 0.5 * amp2 * (s1v * g_m + (-2.0 * s2v) * g_s2);
+            if (Nc > 0) {
+                const double s3v = ((redv[0][2 * GD + q] + redv[1][2 * GD + q]) + redv[2][2 * GD + q]) + redv[3][2 * GD + q];
+                const double gcm = sh_c1 * s3v * sh_pdfc;
+                gd = sh_pc * gd + ei * gcm;
+            }
+            o[1 + d0 + q] = gd;
+        }
+    }
+    if (tid == 0) o[0] = Nc > 0 ? ei * sh_pc : ei;
+}
+
+void launch_point_finish_con(hipStream_t s, const double* Xs, const double* hyp, const double* htab, const double* alpha,
+                             const double* kvec, const double* dkdr2, int N, int Np, const double* XsV, const double* dkV,
+                             const double* tV, const double* zV, int Nv, int Npv, const double* XsC, const double* hypC,
+                             const double* conTab, const double* alphaC, const double* kC, const double* dkC, int Nc,
+                             int Npc, const double* x, double best, double* out, int D, int Dp, int nh, int P, int S,
+                             const double* gammaS, const double* alphaS, double* uvec)
+{
+    const size_t lds = (size_t)3 * S * sizeof(double);   // up to 96 KB at S = 4096: above the 64 KB default limit
+    if (lds > 48 * 1024)
+        SPX_LDS_ATTR(k_point_finish_con, lds);
+    hipLaunchKernelGGL(k_point_finish_con, dim3(nh, P), dim3(256), lds, s, Xs, hyp, htab, alpha, kvec, dkdr2, N, Np, XsV,
+                       dkV, tV, zV, Nv, Npv, XsC, hypC, conTab, alphaC, kC, dkC, Nc, Npc, x, best, out, D, Dp, P, S, gammaS,
+                       alphaS, uvec);
+}

@@ -155,6 +155,7 @@ void spx_destroy(spx_handle* h)
     if (h->multi) { spx_multi_destroy(h->multi); delete h; return; }
     spx_comm_release(h);
     if (h->con) { spx_destroy(h->con); h->con = nullptr; }
+    if (h->full) { spx_destroy(h->full); h->full = nullptr; }
     if (h->inited) {
         (void)hipSetDevice(h->device);
         (void)hipStreamSynchronize(h->stream);
@@ -204,7 +205,7 @@ int spx_set_option(spx_handle* h, const char* name, int64_t value)
     if (!strcmp(name, "covar")) {   // SPX_COVAR_*: the reference's covar= (gp.py:87-132)
         if (value < SPX_COVAR_MATERN52 || value > SPX_COVAR_SE)
             return fail(SPX_ERR_ARG, "spx_set_option: covar=%lld is not one of SPX_COVAR_*", (long long)value);
-        if (h->cov_kind != (int)value) { h->factored = false; h->ran = false; h->ran_time = false; h->S = 0; }
+        if (h->cov_kind != (int)value) { h->factored = false; h->ran = false; h->ran_time = false; h->S = 0; h->full_valid = false; }
         h->cov_kind = (int)value;
         return SPX_OK;
     }
@@ -358,6 +359,7 @@ int spx_set_observations(spx_handle* h, const double* comp, const double* vals, 
     h->best = b;
     HIPCHK(hipStreamSynchronize(h->stream));
     h->have_obs = true; h->have_time = false; h->factored = false; h->ran = false; h->ran_time = false; h->S = 0;
+    h->full_valid = false;
     return SPX_OK;
 }
 
@@ -390,6 +392,7 @@ int spx_set_hypers(spx_handle* h, const double* hypers, int32_t H)
     h->H = H;
     h->hyp_host.assign(hypers, hypers + (size_t)H * (3 + h->D));
     h->have_hyp = true; h->have_time = false; h->factored = false; h->ran = false; h->ran_time = false; h->S = 0;
+    h->full_valid = false;
     return SPX_OK;
 }
 
@@ -419,7 +422,7 @@ int spx_set_constraint_model(spx_handle* h, const double* comp_c, const double* 
     if (!h) return fail(SPX_ERR_ARG, "spx_set_constraint_model: null handle");
     if (h->multi) return fail(SPX_ERR_ARG, "spx_set_constraint_model: the constraint model is single-device only "
                                            "(multi-device handles and hyper_shards > 1 are not supported)");
-    if (!comp_c && !ff && !c_hypers) { h->have_con = false; h->con_factored = false; h->ran_con = false; return SPX_OK; }
+    if (!comp_c && !ff && !c_hypers) { h->have_con = false; h->con_factored = false; h->ran_con = false; h->full_valid = false; return SPX_OK; }
     if (!h->have_obs || !h->have_hyp)
         return fail(SPX_ERR_ARG, "spx_set_constraint_model: set observations and hypers first");
     if (!c_hypers || Nc < 0 || Nc > (1 << 20) || (Nc > 0 && (!comp_c || !ff)))
@@ -438,7 +441,9 @@ int spx_set_constraint_model(spx_handle* h, const double* comp_c, const double* 
         for (int i = 0; i < H; ++i) rows[(size_t)i * hs] = 0.0;
         if ((rc = spx_set_observations(h->con, comp_c, ff, Nc, D))) return rc;
         if ((rc = spx_set_hypers(h->con, rows.data(), H))) return rc;
+        h->con_comp_host.assign(comp_c, comp_c + (size_t)Nc * D);
     }
+    h->full_valid = false;
     h->con_tab_host.assign((size_t)H * SPX_HT, 0.0);
     for (int i = 0; i < H; ++i) {
         const double* r = c_hypers + (size_t)i * hs;
@@ -1636,6 +1641,138 @@ int spx_ei_grad_batch(spx_handle* h, const double* points, int32_t P, double* ne
 int spx_ei_grad(spx_handle* h, const double* point, double* neg_ei_sum, double* grad)
 {
     return spx_ei_grad_batch(h, point, 1, neg_ei_sum, grad);
+}
+
+// W_f = L_f^-1, L_f L_f^T = amp2 (corr(ls; X_c, X_c) + 1e-6 I) + noise I: the objective's draws over the constraint model's
+// points, through the ordinary factorisation path on an internal handle.  Not positive definite: draw 3H + d.
+static int ensure_full_factor(spx_handle* h)
+{
+    if (h->full_valid && h->full && h->full->factored && h->full->cov_kind == h->cov_kind) return SPX_OK;
+    h->full_valid = false;
+    int rc;
+    if (!h->full) {
+        if ((rc = spx_create(h->device, &h->full))) return rc;
+        h->full->stage_copies = h->stage_copies;
+    }
+    spx_handle* f = h->full;
+    f->cov_kind = h->cov_kind;
+    const std::vector<double> zeros((size_t)h->con_n, 0.0);   // (the values are not read: only W_f and the scaled rows are)
+    if ((rc = spx_set_observations(f, h->con_comp_host.data(), zeros.data(), h->con_n, h->D))) return rc;
+    if ((rc = spx_set_hypers(f, h->hyp_host.data(), h->H))) return rc;
+    rc = spx_factor(f);
+    if (rc == SPX_ERR_NOT_PD) {
+        h->not_pd_draw = 3 * h->H + f->not_pd_draw;
+        h->not_pd_pivot = f->not_pd_pivot;
+        return fail(SPX_ERR_NOT_PD, "%d-th leading minor of the array is not positive definite (draw %d, objective over the "
+                                    "constraint model's points)", f->not_pd_pivot + 1, f->not_pd_draw);
+    }
+    if (rc) return rc;
+    h->full_valid = true;
+    return SPX_OK;
+}
+
+int spx_constrained_ei_grad_batch(spx_handle* h, const double* points, int32_t P, double best, double* neg_cei, double* grad)
+{
+    if (!h || !points || !neg_cei || !grad || P < 1) return fail(SPX_ERR_ARG, "spx_constrained_ei_grad_batch: bad argument");
+    if (h->multi) return fail(SPX_ERR_ARG, "spx_constrained_ei_grad_batch: the constraint model is single-device only "
+                                           "(multi-device handle)");
+    if (!h->factored) return fail(SPX_ERR_ARG, "spx_constrained_ei_grad_batch: call spx_factor (or spx_ei_step) first");
+    if (!h->have_con) return fail(SPX_ERR_ARG, "spx_constrained_ei_grad_batch: needs spx_set_constraint_model");
+    if (h->nmodels == 2) return fail(SPX_ERR_ARG, "spx_constrained_ei_grad_batch: not defined with a time model");
+    if ((int64_t)h->con_tab_host.size() != (int64_t)h->H * SPX_HT)
+        return fail(SPX_ERR_ARG, "spx_constrained_ei_grad_batch: the constraint model has a different number of draws");
+    const int64_t Nc = h->con_n;
+    spx_handle* c = Nc > 0 ? h->con : nullptr;
+    if (c && (c->H != h->H || c->D != h->D))
+        return fail(SPX_ERR_ARG, "spx_constrained_ei_grad_batch: the constraint model does not match the objective's H / D");
+    if (c && (!h->con_factored || !c->factored || c->cov_kind != h->cov_kind))
+        return fail(SPX_ERR_ARG, "spx_constrained_ei_grad_batch: the constraint model is not factored (spx_factor after "
+                                 "spx_set_constraint_model)");
+    int rc = ensure_init(h);
+    if (rc) return rc;
+    const int S = h->S;
+    const bool two_factor = (S == 0 && Nc > 0);      // variance over X_c (the quirk of :692-803)
+    if (two_factor && (rc = ensure_full_factor(h))) return rc;
+    spx_handle* f = two_factor ? h->full : nullptr;
+    const int H = h->H, D = h->D, Dp = h->Dp, Np = h->Np;
+    const int64_t N = h->N;
+    const int Npc = c ? c->Np : 0;
+    const size_t vec = (size_t)H * P * Np * 8, vecc = (size_t)H * P * Npc * 8;
+    if ((rc = h->pt_x.reserve((size_t)P * D * 8))) return rc;
+    if ((rc = h->pt_k.reserve(vec))) return rc;
+    if ((rc = h->pt_dk.reserve(vec))) return rc;
+    if ((rc = h->pt_out.reserve((size_t)H * P * (1 + D) * 8))) return rc;
+    if (!two_factor) {
+        if ((rc = h->pt_t.reserve(vec))) return rc;
+        if ((rc = h->pt_z.reserve(vec))) return rc;
+    } else {
+        if ((rc = f->pt_k.reserve(vecc))) return rc;
+        if ((rc = f->pt_dk.reserve(vecc))) return rc;
+        if ((rc = f->pt_t.reserve(vecc))) return rc;
+        if ((rc = f->pt_z.reserve(vecc))) return rc;
+    }
+    if (c) {
+        if ((rc = c->pt_k.reserve(vecc))) return rc;
+        if ((rc = c->pt_dk.reserve(vecc))) return rc;
+    }
+    hipStream_t s = h->stream;
+    if (S > 0) {
+        if ((rc = h->pt_u.reserve(vec))) return rc;
+        if (!h->alphaS_valid) {   // alpha_s = W^T Gamma_s = K^-1 (fant_s - mean) for every fantasy column
+            if ((rc = h->alphaS.reserve((size_t)H * S * Np * 8))) return rc;
+            launch_trimvT_multi(s, h->WT.d(), h->gammaS.d(), h->alphaS.d(), Np, H, S);
+            h->alphaS_valid = true;
+        }
+    }
+    stage_begin(h);
+    if ((rc = stage_h2d(h, h->pt_x.p, points, (size_t)P * D * 8, s))) return rc;
+    const int kind = dev_kind(h);
+    launch_point_cov(s, h->Xs.d(), h->s1.d(), h->hyp.d(), h->htab.d(), h->pt_x.d(), h->pt_k.d(), h->pt_dk.d(),
+                     (int)N, Np, D, Dp, H, P, kind);
+    if (!two_factor) {
+        launch_trimv_multi(s, h->WT.d(), h->pt_k.d(), h->pt_t.d(), Np, H, P);        // t = W k
+        launch_trimvT_multi(s, h->WT.d(), h->pt_t.d(), h->pt_z.d(), Np, H, P);       // z = W^T t = K^-1 k
+    } else {
+        // k_f, dk_f: the objective's length scales against X_c; t_f = W_f k_f, z_f = W_f^T t_f
+        launch_point_cov(s, f->Xs.d(), f->s1.d(), f->hyp.d(), f->htab.d(), h->pt_x.d(), f->pt_k.d(), f->pt_dk.d(),
+                         (int)Nc, Npc, D, Dp, H, P, kind);
+        launch_trimv_multi(s, f->WT.d(), f->pt_k.d(), f->pt_t.d(), Npc, H, P);
+        launch_trimvT_multi(s, f->WT.d(), f->pt_t.d(), f->pt_z.d(), Npc, H, P);
+    }
+    if (c)   // k_c, dk_c: the constraint GP's own length scales and amplitude
+        launch_point_cov(s, c->Xs.d(), c->s1.d(), c->hyp.d(), c->htab.d(), h->pt_x.d(), c->pt_k.d(), c->pt_dk.d(),
+                         (int)Nc, Npc, D, Dp, H, P, kind);
+    if (S == 0 && !c) {
+        // no violation seen, no pending job: comp == compfull and P = 1 -- spx_ei_grad_batch's own launch
+        launch_point_finish(s, h->Xs.d(), h->hyp.d(), h->htab.d(), h->alpha.d(), h->pt_k.d(), h->pt_dk.d(),
+                            h->pt_t.d(), h->pt_z.d(), h->pt_x.d(), best, h->pt_out.d(), (int)N, Np, D, Dp, H, P,
+                            nullptr, nullptr, 0, nullptr, nullptr, nullptr, nullptr);
+    } else {
+        const spx_handle* v = two_factor ? f : h;     // whose rows the variance runs over
+        launch_point_finish_con(s, h->Xs.d(), h->hyp.d(), h->htab.d(), h->alpha.d(), h->pt_k.d(), h->pt_dk.d(), (int)N, Np,
+                                v->Xs.d(), v->pt_dk.d(), v->pt_t.d(), v->pt_z.d(), (int)v->N, v->Np,
+                                c ? c->Xs.d() : nullptr, c ? c->hyp.d() : nullptr, h->con_tab.d(),
+                                c ? c->alpha.d() : nullptr, c ? c->pt_k.d() : nullptr, c ? c->pt_dk.d() : nullptr,
+                                (int)Nc, Npc, h->pt_x.d(), best, h->pt_out.d(), D, Dp, H, P, S,
+                                S > 0 ? h->gammaS.d() : nullptr, S > 0 ? h->alphaS.d() : nullptr,
+                                S > 0 ? h->pt_u.d() : nullptr);
+    }
+    std::vector<double> out((size_t)H * P * (1 + D));
+    if ((rc = stage_d2h(h, out.data(), h->pt_out.p, out.size() * 8, s))) return rc;
+    LAUNCHCHK();
+    // sum over draws in draw order, as grad_optimize_ei_over_hypers does (:471-501)
+    for (int p = 0; p < P; ++p) {
+        double fsum = 0.0;
+        double* g = grad + (size_t)p * D;
+        for (int d = 0; d < D; ++d) g[d] = 0.0;
+        for (int i = 0; i < H; ++i) {
+            const double* o = &out[((size_t)i * P + p) * (1 + D)];
+            fsum += -o[0];
+            for (int d = 0; d < D; ++d) g[d] = g[d] + o[1 + d];
+        }
+        neg_cei[p] = fsum;
+    }
+    return SPX_OK;
 }
 
 int spx_get_stat(spx_handle* h, const char* name, int64_t* value)

@@ -162,6 +162,12 @@ struct spx_handle {
     int64_t con_n = 0;                                              // Nc (0: all valid, P_d = Phi(gain_d))
     std::vector<double> con_tab_host;                               // [H][SPX_HT]: gain, noise_c, amp2_c, amp2_c
     DevBuf con_tab, con_Cs[2], con_s2[2], con_p[2], mom_c;
+    // spx_constrained_ei_grad_batch: the objective's hypers over the constraint model's points X_c (the variance of the
+    // reference's no-pending refinement objective, GPConstrainedEIChooser.py:692-803) -- a third internal handle, factored
+    // on the first call and kept until observations, hypers, the constraint points or option "covar" change
+    spx_handle* full = nullptr;
+    bool full_valid = false;
+    std::vector<double> con_comp_host;                              // X_c as spx_set_constraint_model received it
     // spx_gp_logprob_rhs: a right-hand side per hyper row, [H][N], read in place of the resident values while set
     DevBuf rhs_rows;
     bool rhs_rows_on = false;

@@ -114,6 +114,8 @@ ABI = {
     "spx_gp_logprob_rhs": (ctypes.c_int, [_vp, _c_double_p, _c_double_p, ctypes.c_int32, _c_double_p]),
     "spx_ei_grad": (ctypes.c_int, [_vp, _c_double_p, _c_double_p, _c_double_p]),
     "spx_ei_grad_batch": (ctypes.c_int, [_vp, _c_double_p, ctypes.c_int32, _c_double_p, _c_double_p]),
+    "spx_constrained_ei_grad_batch": (ctypes.c_int, [_vp, _c_double_p, ctypes.c_int32, ctypes.c_double, _c_double_p,
+                                                     _c_double_p]),
     "spx_sobol_grid": (ctypes.c_int, [_vp, ctypes.POINTER(ctypes.c_uint32), ctypes.c_int32, ctypes.c_int32,
                                       ctypes.c_int64, ctypes.c_int64, _c_double_p, ctypes.c_int32, _c_double_p]),
     "spx_not_pd_info": (ctypes.c_int, [_vp, _c_int32_p, _c_int32_p]),
@@ -540,6 +542,19 @@ class Engine(object):
         f = np.empty(x.shape[0])
         g = np.empty(x.shape)
         self._check(self._lib.spx_ei_grad_batch(self._h, _dp(x), x.shape[0], _dp(f), _dp(g)))
+        return f, g
+
+    def constrained_ei_grad_batch(self, points, best):
+        """-(sum over draws of EI x P(feasible)) and its gradient at P points: (f[P], grad[P, D]) -- the refinement
+        objective of GPConstrainedEIChooser.py:471-803 against the resident factorisation and constraint model
+        (include/spx.h: spx_constrained_ei_grad_batch).  `best` is np.min of the valid values.  LinAlgError when the
+        objective's covariance over the constraint model's points is not positive definite."""
+        x = _f64(np.atleast_2d(points))
+        if x.ndim != 2 or x.shape[1] != self.D:
+            raise ValueError("points must be (P, D)")
+        f = np.empty(x.shape[0])
+        g = np.empty(x.shape)
+        self._check(self._lib.spx_constrained_ei_grad_batch(self._h, _dp(x), x.shape[0], float(best), _dp(f), _dp(g)))
         return f, g
 
     def sobol_grid(self, dirs, dim, n, skip, fetch=True, as_candidates=False):
