@@ -172,7 +172,10 @@ int spx_factor(spx_handle* h);
  *         pend_fant);   bests H x S: np.min(fant_vals, axis=0) (:249).   1 <= S <= 4096.
  * The next spx_ei_run scores every candidate against every fantasy (:253-263) and averages
  * over S in numpy's summation order (:265).  NULL / S = 0 clears; so does any call that
- * invalidates the factorisation.                                                      */
+ * invalidates the factorisation.  SPX_FLAG_PER_SEC with fantasies set is defined: the mean over S
+ * of every draw is divided by the predicted duration of a time model over the SAME n resident rows
+ * (log_durs of length n); no chooser of the reference forms it.  SPX_FLAG_KEEP_MOMENTS then keeps
+ * the predicted durations (spx_get_time_mean) but no func_m / func_v: spx_get_moments refuses. */
 int spx_set_fantasies(spx_handle* h, const double* fant, const double* bests, int32_t S);
 
 /* Hot path, stage 2: K(X*,X) (:187), triangular solve (:195), predictive

@@ -1181,6 +1181,7 @@ static int ei_run_impl(spx_handle* h, int32_t flags, bool factor_pending)
     h->ran_time = time_only;
     h->ran_2d = false;
     h->ran_moments = keep_mom && S == 0 && !time_only;
+    h->ran_tmean = keep_mom && per_sec;       // (with fantasies the pass keeps no func_m / func_v, but mom_t is written all the same)
     h->ran_con = constrained && keep_mom && !time_only;
     if (h->comm) return spx_comm_exchange(h);   // one process per GPU: the winner over all ranks
     return SPX_OK;
@@ -1238,7 +1239,7 @@ int spx_get_moments(spx_handle* h, int32_t draw, double* func_m, double* func_v)
 int spx_get_time_mean(spx_handle* h, int32_t draw, double* out)
 {
     if (h && h->multi) return spx_multi_get_time_mean(h->multi, draw, out);
-    if (!h || !out || !((h->ran && h->ran_moments) || h->ran_time) || h->nmodels != 2)
+    if (!h || !out || !((h->ran && (h->ran_moments || h->ran_tmean)) || h->ran_time) || h->nmodels != 2)
         return fail(SPX_ERR_ARG, "spx_get_time_mean: run spx_ei_run with SPX_FLAG_PER_SEC | SPX_FLAG_KEEP_MOMENTS first");
     if (draw < 0 || draw >= h->H) return fail(SPX_ERR_ARG, "spx_get_time_mean: draw out of range");
     int rc = ensure_init(h);
