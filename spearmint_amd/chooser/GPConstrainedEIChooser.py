@@ -205,13 +205,8 @@ class GPConstrainedEIChooser(GPEIBase):
             eng.set_constraint_model(comp, self.cst.ff, crows)     # quirk 2: self.ff, the same for every draw
         if pend.shape[0] > 0:
             eng.factor()
-            S = self.pending_samples
-            n = compv.shape[0]
-            fant = np.empty((H, n + pend.shape[0], S))
-            bests = np.empty((H, S))
-            for h in range(H):
-                l_rows, gam = eng.get_factor_rows(h, n, pend.shape[0])
-                fant[h], bests[h] = hostgp.fantasize_from_factor_rows(valsv, rows[h], l_rows, gam, randn[h])
+            fant, bests = hostgp.fantasies_from_engine(eng, valsv, rows, compv.shape[0], pend.shape[0],
+                                                       self.pending_samples, randn, per_draw=True)
             eng.set_fantasies(fant, bests)
             eng.ei_run(FLAG_CONSTRAINED)
         else:
@@ -238,12 +233,8 @@ class GPConstrainedEIChooser(GPEIBase):
             rs = npr.RandomState()
             rs.set_state(self.randomstate)
             randn = rs.randn(pend.shape[0], self.pending_samples)
-            n, H = valsv.shape[0], rows.shape[0]
-            fant = np.empty((H, n + pend.shape[0], self.pending_samples))
-            bests = np.empty((H, self.pending_samples))
-            for h in range(H):
-                l_rows, gam = eng.get_factor_rows(h, n, pend.shape[0])
-                fant[h], bests[h] = hostgp.fantasize_from_factor_rows(valsv, rows[h], l_rows, gam, randn)
+            fant, bests = hostgp.fantasies_from_engine(eng, valsv, rows, valsv.shape[0], pend.shape[0],
+                                                       self.pending_samples, randn, per_draw=False)
             eng.set_fantasies(fant, bests)
         best = np.min(valsv)
         return refine.lbfgs_many(lambda X: eng.constrained_ei_grad_batch(X, best), points, [(0, 1)] * comp.shape[1],

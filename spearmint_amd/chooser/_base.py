@@ -530,7 +530,7 @@ class GPEIBase(object):
         (`randn[h]` is the (P, S) standard-normal matrix of draw h, drawn by the
         caller at the point where the reference consumes the RNG)."""
         hyper_rows = np.ascontiguousarray(np.atleast_2d(hyper_rows), dtype=np.float64)
-        H, n_comp, n_pend = hyper_rows.shape[0], comp.shape[0], pend.shape[0]
+        n_comp, n_pend = comp.shape[0], pend.shape[0]
         eng = self.engine()
         self._lp_key = None
         comp_pend = np.concatenate((comp, pend))
@@ -538,14 +538,8 @@ class GPEIBase(object):
         eng.set_candidates(cand)
         eng.set_hypers(hyper_rows)
         eng.factor()
-        S = randn[0].shape[1]
-        fant = np.empty((H, n_comp + n_pend, S))
-        bests = np.empty((H, S))
-        for h in range(H):
-            # the bottom P rows of the factor and gamma are all the posterior of the pending points needs (hostgp:
-            # fantasize_from_factor_rows) -- not the N x N sub-Cholesky and two O(N^2 P) host solves against it
-            l_rows, gam = eng.get_factor_rows(h, n_comp, n_pend)
-            fant[h], bests[h] = hostgp.fantasize_from_factor_rows(vals, hyper_rows[h], l_rows, gam, randn[h])
+        fant, bests = hostgp.fantasies_from_engine(eng, vals, hyper_rows, n_comp, n_pend, randn[0].shape[1], randn,
+                                                   per_draw=True)
         eng.set_fantasies(fant, bests)
         eng.ei_run()
         idx, _ = eng.best()

@@ -109,19 +109,37 @@ void launch_point_cov(hipStream_t s, const double* Xs, const double* s1, const d
                       int D, int Dp, int nh, int P, int kind = SPX_COV_MATERN52);
 void launch_trimv_multi(hipStream_t s, const double* WT, const double* rhs, double* out, int Np, int nh, int P);
 void launch_trimvT_multi(hipStream_t s, const double* WT, const double* rhs, double* out, int Np, int nh, int P);
-void launch_point_finish(hipStream_t s, const double* Xs, const double* hyp, const double* htab,
-                         const double* alpha, const double* kvec, const double* dkdr2,
-                         const double* tvec, const double* zvec, const double* x, double best,
-                         double* out, int N, int Np, int D, int Dp, int nh, int P, const double* kt,
-                         const double* dkt, int S, const double* gammaS, const double* alphaS,
-                         const double* bests, double* uvec);
-// the constrained chooser's refinement objective: mean side (N rows), variance side (Nv rows), constraint side (Nc rows; 0 = none)
-void launch_point_finish_con(hipStream_t s, const double* Xs, const double* hyp, const double* htab, const double* alpha,
-                             const double* kvec, const double* dkdr2, int N, int Np, const double* XsV, const double* dkV,
-                             const double* tV, const double* zV, int Nv, int Npv, const double* XsC, const double* hypC,
-                             const double* conTab, const double* alphaC, const double* kC, const double* dkC, int Nc,
-                             int Npc, const double* x, double best, double* out, int D, int Dp, int nh, int P, int S,
-                             const double* gammaS, const double* alphaS, double* uvec);
+// The finish of the refinement objective (k_point_finish): EI and its gradient per (draw, point) from up to three sets of
+// rows, each with its own count and padding.
+struct FinishSide {
+    const double* Xs;    // [nh][Np][Dp] rows scaled by this side's length scales
+    const double* hyp;   // [nh][3 + D]  this side's hyper rows (length scales at +3)
+    const double* dk;    // [nh][P][Np]  dk/dr2 at the points (launch_point_cov)
+    const double* w;     // weights of the gradient sum: alpha [nh][Np] (mean and third side), z = W^T t [nh][P][Np] (variance)
+    int n, Np;
+};
+struct FinishArgs {
+    FinishSide m;          // mean side: func_m = k . alpha + mean
+    FinishSide v;          // variance side: func_v = amp2 (1 + 1e-6) - |t|^2 with the mean side's length scales and amplitude;
+                           // the mean side's rows again (v.Xs == m.Xs) unless the constrained objective's variance runs over X_c
+    FinishSide c;          // third side, n = 0: none.  Plain: the time model (EI per second).  Constrained: the constraint model
+    const double* htab;    // [nh][SPX_HT] the mean side's table rows
+    const double* k;       // [nh][P][m.Np] k at the points, mean side
+    const double* t;       // [nh][P][v.Np] t = W k, variance side
+    const double* k3;      // [nh][P][c.Np] k at the points, third side
+    const double* tab3;    // [nh][SPX_HT] third side: the time model's table rows / [gain, noise_c, amp2_c, amp2_c]
+    const double* x;       // [P][D]
+    double best;           // (with fantasies the plain objective reads bests[h][s] instead)
+    double* out;           // [nh][P][1 + D]
+    int D, Dp, nh, P;
+    int S;                 // fantasies per draw (0: none); then mean side == variance side
+    const double* gammaS;  // [nh][S][Np]
+    const double* alphaS;  // [nh][S][Np]
+    const double* bests;   // [nh][S], plain objective only
+    double* uvec;          // [nh][P][Np] work vector
+};
+// constrained = false: EI, averaged over the fantasies; true: EI x P(feasible), summed over them (refine_kernels.hip)
+void launch_point_finish(hipStream_t s, const FinishArgs& a, bool constrained);
 
 // fused_kernels.hip: the whole EI pass of a chunk for N <= 128 in one launch (no K* / beta in memory)
 void launch_ei_fused128(hipStream_t s, int kind, const double* WT, const double* gamma, const double* Xs, const double* s1,

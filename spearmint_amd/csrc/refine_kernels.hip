@@ -18,6 +18,23 @@
 // Gamma_s = W (fant_s - mean) (equal to k . alpha_s), EI_s against bests[s], and
 //   grad[d] = 0.5 amp2 ( sum_j G[j][d] u[j] + (-2 z . G[:,d]) mean_s(0.5 phi_s / s) ),
 //   u[j] = mean_s( -Phi_s alpha_s[j] ),  alpha_s = W^T Gamma_s                    (:505-523)
+// The finish (k_point_finish, one workgroup per draw and point) exists once and serves two objectives as its cases.  It
+// meets up to three sets of rows, each with its own count and padding (FinishSide in common.h):
+//   mean side      the handle's own factor (N rows: the valid points, or [valid; pend]): func_m = k . alpha + mean, alpha . G
+//   variance side  func_v = amp2 (1 + 1e-6) - |t|^2, (-2 z) . G with the mean side's length scales: the mean side's rows
+//                  again, except in the constrained objective without fantasies, where the SAME hypers run over ALL
+//                  completed points X_c (GPConstrainedEIChooser.py:692-803 takes obsv_chol_full here)
+//   third side     absent, or one more GP over its own rows and length scales (below)
+// plain (spx_ei_grad_batch):  the formulas above; fantasies are AVERAGED, each against its own bests[s]; the third side is
+//   the log-duration GP: time_m = exp(k_t . alpha_t + mean_t), value EI / time_m, gradient by the quotient rule.
+// constrained (spx_constrained_ei_grad_batch; GPConstrainedEIChooser.py:471-803):  -(EI x P(feasible)); fantasies are SUMMED,
+//   every one against the one `best` (:529-690, :645); the third side is the probit constraint GP over X_c:
+//   m_c = k_c . alpha_c, P = Phi(gain m_c), gcm[d] = 0.5 amp2_c gain (alpha_c . G_c[:, d]) phi(gain m_c)  (:682-688),
+//   value = EI P, grad[d] = P grad(-EI)[d] + EI gcm[d] -- the sign of the second term is the reference's (:688, :801).
+//   No violation seen and no fantasies (P = 1, gcm = 0: use_vanilla_ei): the plain case's arithmetic.
+// Shared, each written once: the EI terms, the fantasy block (divisor S or 1, bests[s] or best), the gradient pass, the
+// reduction over the four waves, the third side's mean.  NOT shared: the last per-dimension combine (combine_plain,
+// combine_con), whose two roundings both stand.
 // Every point's numbers are computed by its own threads in a fixed order, so a result does not
 // depend on which other points share the call.
 #include "common.h"
@@ -200,6 +217,9 @@ void launch_trimvT_multi(hipStream_t s, const double* WT, const double* rhs, dou
     hipLaunchKernelGGL(k_trimvT_multi, dim3(Np / 4, nh, (P + PB - 1) / PB), dim3(256), 0, s, WT, rhs, out, Np, P);
 }
 
+// ---- the finish: one workgroup per (draw, point) -------------------------------------------------------------------
+// The pieces below are each written once; k_point_finish<CON> puts them together for the two objectives (header comment).
+
 __device__ __forceinline__ double ndtr_r(double a)
 {
 #pragma clang fp contract(off)
@@ -222,401 +242,271 @@ __device__ __forceinline__ double block_sum(double v, double* red /*[4]*/)
     return ((red[0] + red[1]) + red[2]) + red[3];
 }
 
+// a . b over n rows, every thread gets the result
+__device__ __forceinline__ double block_dot(const double* __restrict__ a, const double* __restrict__ b, int n, double* red)
+{
+    double v = 0.0;
+    for (int j = threadIdx.x; j < n; j += 256) v += a[j] * b[j];
+    return block_sum(v, red);
+}
+
+// EI against `best` and the weights of its gradient: d(-EI)/d func_m = -Phi, d(-EI)/d func_v = 0.5 phi / func_s  (:420-430)
+__device__ __forceinline__ void ei_terms(double best, double func_m, double func_s, double& ei, double& g_m, double& g_s2)
+{
+#pragma clang fp contract(off)
+    const double u = (best - func_m) / func_s;
+    const double cdf = ndtr_r(u);
+    const double pdf = exp(-(u * u) / 2.0) / 2.50662827463100050242;
+    ei = func_s * (u * cdf + pdf);
+    g_m = -cdf;
+    g_s2 = 0.5 * pdf / func_s;
+}
+
+// the S fantasies of draw h: func_m[s] = t . Gamma_s + mean (one wavefront per s), EI_s against bests[s] (null: the one
+// `best`), then over the fantasies  ei = sum_s EI_s / div,  g_s2 = sum_s (0.5 phi_s / func_s) / div  and the mean-gradient
+// weights  u[j] = sum_s( -Phi_s alpha_s[j] ) / div  with -Phi_s folded in (so g_m = 1).  div = S averages, div = 1 sums.
+__device__ __forceinline__ void fantasy_terms(double* dyn /*[3][S]*/, int S, double div, const double* __restrict__ th,
+                                              const double* __restrict__ gammaS /*[S][Np]*/,
+                                              const double* __restrict__ alphaS /*[S][Np]*/,
+                                              const double* __restrict__ bests /*[S] or null*/, double best, double mean,
+                                              double func_s, int N, int Np, double* __restrict__ uh /*[Np]*/, double& ei,
+                                              double& g_m, double& g_s2)
+{
+    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    double* gmS = dyn;                 // [S]  -Phi_s
+    double* eiS = dyn + S;             // [S]
+    double* gsS = dyn + 2 * S;         // [S]  0.5 phi_s / func_s
+    for (int sidx = wave; sidx < S; sidx += 4) {
+        const double* gs = gammaS + (size_t)sidx * Np;
+        double m = 0.0;
+        for (int j = lane; j < N; j += 64) m += th[j] * gs[j];
+#pragma unroll
+        for (int off = 32; off > 0; off >>= 1) m += __shfl_xor(m, off);
+        if (lane == 0) {
+#pragma clang fp contract(off)
+            ei_terms(bests ? bests[sidx] : best, m + mean, func_s, eiS[sidx], gmS[sidx], gsS[sidx]);
+        }
+    }
+    __syncthreads();
+    if (tid == 0) {
+        double e = 0.0, g2 = 0.0;
+        for (int sidx = 0; sidx < S; ++sidx) { e += eiS[sidx]; g2 += gsS[sidx]; }
+        ei = e / div;
+        g_s2 = g2 / div;
+        g_m = 1.0;
+    }
+    for (int j = tid; j < Np; j += 256) {
+        double a = 0.0;
+        if (j < N)
+            for (int sidx = 0; sidx < S; ++sidx) a += gmS[sidx] * alphaS[(size_t)sidx * Np + j];
+        uh[j] = a / div;
+    }
+    __syncthreads();
+}
+
 #define GD 8   // input dimensions per gradient pass
 
-// one workgroup per (draw, point): out[h][p][0] = EI_h(x_p) (mean over fantasies if S > 0),
-// out[h][p][1 + d] = d(-EI_h)/dx_d in the reference's scaling
-__global__ __launch_bounds__(256) void k_point_finish(
-    const double* __restrict__ Xs, const double* __restrict__ hyp, const double* __restrict__ htab,
-    const double* __restrict__ alpha, const double* __restrict__ kvec, const double* __restrict__ dkdr2,
-    const double* __restrict__ tvec, const double* __restrict__ zvec, const double* __restrict__ x,
-    double best, double* __restrict__ out, int N, int Np, int D, int Dp, int P,
-    // EI per second (GPEIperSecChooser.py:349-434): rows H..2H-1 of the tables hold the log-duration
-    // GP; kt / dkt are its k and dk/dr2 at the points.  Null -> plain EI.
-    int H, const double* __restrict__ kt, const double* __restrict__ dkt,
-    // pending-experiment fantasies (GPEIOptChooser.py:441-525): S right-hand sides per draw
-    int S, const double* __restrict__ gammaS /*[H][S][Np]*/, const double* __restrict__ alphaS /*[H][S][Np]*/,
-    const double* __restrict__ bests /*[H][S]*/, double* __restrict__ uvec /*[H][P][Np] scratch*/)
-{
-    extern __shared__ double dyn[];        // S > 0: [S] -Phi_s / S
-    __shared__ double red[4];
-    __shared__ double redv[4][3 * GD];
-    __shared__ double sh_ei, sh_gm, sh_gs2;
-    const int h = blockIdx.x, p = blockIdx.y;
-    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-    const size_t vo = ((size_t)h * P + p) * Np;
-    const double* ah = alpha + (size_t)h * Np;
-    const double* kh = kvec + vo;
-    const double* th = tvec + vo;
-    const double* zh = zvec + vo;
-    const double* dh = dkdr2 + vo;
-    const double* xp = x + (size_t)p * D;
-    const double* ls = hyp + (size_t)h * (3 + D) + 3;
-    const double mean = htab[h * SPX_HT + 0], amp2 = htab[h * SPX_HT + 2], prior_v = htab[h * SPX_HT + 3];
-    double* o = out + ((size_t)h * P + p) * (1 + D);
-
-    double ka = 0.0, tt = 0.0;
-    for (int j = tid; j < N; j += 256) {
-        ka += kh[j] * ah[j];
-        tt += th[j] * th[j];
-    }
-    tt = block_sum(tt, red);
-    if (S == 0) {
-        ka = block_sum(ka, red);
-        if (tid == 0) {
-#pragma clang fp contract(off)
-            const double func_m = ka + mean;
-            const double func_v = prior_v - tt;
-            const double func_s = sqrt(func_v);
-            const double u = (best - func_m) / func_s;
-            const double cdf = ndtr_r(u);
-            const double pdf = exp(-(u * u) / 2.0) / 2.50662827463100050242;
-            sh_ei = func_s * (u * cdf + pdf);
-            sh_gm = -cdf;
-            sh_gs2 = 0.5 * pdf / func_s;
-        }
-        __syncthreads();
-    } else {
-        // every fantasy: func_m[s] = t . Gamma_s + mean; one wavefront per s
-        double* gmS = dyn;                 // [S]  -Phi_s
-        double* eiS = dyn + S;             // [S]
-        double* gsS = dyn + 2 * S;         // [S]  0.5 phi_s / func_s
-        const double func_v = prior_v - tt;
-        const double func_s = sqrt(func_v);
-        for (int sidx = wave; sidx < S; sidx += 4) {
-            const double* gs = gammaS + ((size_t)h * S + sidx) * Np;
-            double m = 0.0;
-            for (int j = lane; j < N; j += 64) m += th[j] * gs[j];
-#pragma unroll
-            for (int off = 32; off > 0; off >>= 1) m += __shfl_xor(m, off);
-            if (lane == 0) {
-#pragma clang fp contract(off)
-                const double func_m = m + mean;
-                const double u = (bests[(size_t)h * S + sidx] - func_m) / func_s;
-                const double cdf = ndtr_r(u);
-                const double pdf = exp(-(u * u) / 2.0) / 2.50662827463100050242;
-                eiS[sidx] = func_s * (u * cdf + pdf);
-                gmS[sidx] = -cdf;
-                gsS[sidx] = 0.5 * pdf / func_s;
-            }
-        }
-        __syncthreads();
-        if (tid == 0) {
-            double e = 0.0, g2 = 0.0;
-            for (int sidx = 0; sidx < S; ++sidx) { e += eiS[sidx]; g2 += gsS[sidx]; }
-            sh_ei = e / (double)S;
-            sh_gs2 = g2 / (double)S;
-            sh_gm = 1.0;
-        }
-        // u[j] = mean_s( -Phi_s alpha_s[j] )
-        double* uh = uvec + vo;
-        for (int j = tid; j < Np; j += 256) {
-            double a = 0.0;
-            if (j < N)
-                for (int sidx = 0; sidx < S; ++sidx) a += gmS[sidx] * alphaS[((size_t)h * S + sidx) * Np + j];
-            uh[j] = a / (double)S;
-        }
-        __syncthreads();
-        ah = uh;     // the mean-gradient weights of the fantasy branch (g_m folded in)
-    }
-    const double g_m = sh_gm, g_s2 = sh_gs2, ei = sh_ei;
-
-    // time model of this draw (row h + H)
-    const int ht = h + H;
-    double time_m = 1.0, amp2t = 0.0;
-    const double *lst = nullptr, *aht = nullptr, *dht = nullptr;
-    if (kt) {
-        lst = hyp + (size_t)ht * (3 + D) + 3;
-        aht = alpha + (size_t)ht * Np;
-        dht = dkt + vo;
-        amp2t = htab[ht * SPX_HT + 2];
-        const double* kht = kt + vo;
-        double kat = 0.0;
-        for (int j = tid; j < N; j += 256) kat += kht[j] * aht[j];
-        kat = block_sum(kat, red);
-        time_m = exp(kat + htab[ht * SPX_HT + 0]);
-    }
-    for (int d0 = 0; d0 < D; d0 += GD) {
-        const int nd = min(GD, D - d0);
-        double a1[GD], a2[GD], a3[GD], xc[GD], il[GD], xct[GD], ilt[GD];
-#pragma unroll
-        for (int q = 0; q < GD; ++q) {
-            a1[q] = a2[q] = a3[q] = 0.0;
-            const int d = d0 + (q < nd ? q : 0);
-            xc[q] = xp[d] / ls[d];
-            il[q] = 1.0 / ls[d];
-            xct[q] = kt ? xp[d] / lst[d] : 0.0;
-            ilt[q] = kt ? 1.0 / lst[d] : 0.0;
-        }
-        for (int j = tid; j < N; j += 256) {
-            const double* xr = Xs + ((size_t)h * Np + j) * Dp + d0;
-            const double dj = dh[j], aj = ah[j], zj = zh[j];
-#pragma unroll
-            for (int q = 0; q < GD; ++q)
-                if (q < nd) {
-                    const double gj = dj * (2.0 * (xr[q] - xc[q]) * il[q]);
-                    a1[q] += aj * gj;
-                    a2[q] += zj * gj;
-                }
-            if (kt) {
-                const double* xt = Xs + ((size_t)ht * Np + j) * Dp + d0;
-                const double djt = dht[j], ajt = aht[j];
-#pragma unroll
-                for (int q = 0; q < GD; ++q)
-                    if (q < nd) a3[q] += ajt * (djt * (2.0 * (xt[q] - xct[q]) * ilt[q]));
-            }
-        }
-#pragma unroll
-        for (int q = 0; q < GD; ++q) {
-#pragma unroll
-            for (int off = 32; off > 0; off >>= 1) {
-                a1[q] += __shfl_xor(a1[q], off);
-                a2[q] += __shfl_xor(a2[q], off);
-                a3[q] += __shfl_xor(a3[q], off);
-            }
-        }
-        __syncthreads();
-        if (lane == 0) {
-#pragma unroll
-            for (int q = 0; q < GD; ++q) {
-                redv[wave][q] = a1[q];
-                redv[wave][GD + q] = a2[q];
-                redv[wave][2 * GD + q] = a3[q];
-            }
-        }
-        __syncthreads();
-        if (tid < nd) {
-            const int q = tid;
-            const double s1v = ((redv[0][q] + redv[1][q]) + redv[2][q]) + redv[3][q];
-            const double s2v = ((redv[0][GD + q] + redv[1][GD + q]) + redv[2][GD + q]) + redv[3][GD + q];
-            double gd = 0.5 * amp2 * (s1v * g_m + (-2.0 * s2v) * g_s2);
-            if (kt) {
-                const double s3v = ((redv[0][2 * GD + q] + redv[1][2 * GD + q]) + redv[2][2 * GD + q]) + redv[3][2 * GD + q];
-                const double gtd = 0.5 * amp2t * s3v * time_m;
-                gd = (time_m * gd - ei * gtd) / (time_m * time_m);
-            }
-            o[1 + d0 + q] = gd;
-        }
-    }
-    if (tid == 0) o[0] = kt ? ei / time_m : ei;
-}
-
-void launch_point_finish(hipStream_t s, const double* Xs, const double* hyp, const double* htab,
-                         const double* alpha, const double* kvec, const double* dkdr2,
-                         const double* tvec, const double* zvec, const double* x, double best,
-                         double* out, int N, int Np, int D, int Dp, int nh, int P, const double* kt,
-                         const double* dkt, int S, const double* gammaS, const double* alphaS,
-                         const double* bests, double* uvec)
-{
-    const size_t lds = (size_t)3 * S * sizeof(double);   // up to 96 KB at S = 4096: above the 64 KB default limit
-    if (lds > 48 * 1024)
-        SPX_LDS_ATTR(k_point_finish, lds);
-    hipLaunchKernelGGL(k_point_finish, dim3(nh, P), dim3(256), lds, s, Xs, hyp,
-                       htab, alpha, kvec, dkdr2, tvec, zvec, x, best, out, N, Np, D, Dp, P, nh, kt, dkt, S,
-                       gammaS, alphaS, bests, uvec);
-}
-
-// ---- the constrained chooser's refinement objective (GPConstrainedEIChooser.py:471-803) -----------------------------
-// -(EI x P(feasible)) and its gradient per (draw, point); summed over the draws on the host.  Three sets of rows meet in
-// one workgroup, each with its own count and padding:
-//   mean side      the handle's own factor (N rows: the valid points, or [valid; pend]): func_m = k . alpha + mean, alpha . G
-//   variance side  without fantasies the SAME hypers over ALL completed points X_c (Nv = Nc rows; :692-803 -- the reference
-//                  takes obsv_chol_full here): func_v = amp2 (1 + 1e-6) - |t_f|^2, (-2 z_f) . G_f;  with fantasies the
-//                  handle's own rows again (Nv = N)
-//   constraint     the probit GP over X_c (Nc rows, its own length scales): m_c = k_c . alpha_c, P = Phi(gain m_c),
-//                  gcm[d] = 0.5 amp2_c gain (alpha_c . G_c[:, d]) phi(gain m_c)                       (:682-688)
-// value = EI P,  grad[d] = P grad(-EI)[d] + EI gcm[d]  -- the sign of the second term is the reference's (:688, :801).
-// With S fantasies (:529-690) every fantasy is scored against the one `best` and EI, its gradient and the weights u are
-// SUMS over the fantasies (GPEIOptChooser averages; this chooser does not).  Nc = 0: P = 1 and gcm = 0 (use_vanilla_ei).
-
-// acc[q] = sum_j w[j] dk[j] * 2 (X[j][d0 + q] - x[d0 + q] / ls) / ls over this thread's rows, then over the wavefront
+// acc[q] = sum_j w[j] dk[j] * 2 (X[j][d0 + q] - x[d0 + q] / ls) / ls over this thread's rows, then over the wavefront;
+// TWO: w2 is a second weight vector over the same rows, into acc2 (else both null) -- each sum runs over its own j in
+// increasing order.  (A compile-time choice: tested at run time it put a branch and a select per row into the loop.)
+template <bool TWO>
 __device__ __forceinline__ void grad_pass(const double* __restrict__ Xh, int Dp, const double* __restrict__ ls,
                                           const double* __restrict__ xp, const double* __restrict__ dk,
-                                          const double* __restrict__ w, int n, int d0, int nd, double* acc /*[GD]*/)
+                                          const double* __restrict__ w, const double* __restrict__ w2, int n, int d0,
+                                          int nd, double* acc /*[GD]*/, double* acc2 /*[GD]*/)
 {
     double xc[GD], il[GD];
 #pragma unroll
     for (int q = 0; q < GD; ++q) {
         acc[q] = 0.0;
+        if (TWO) acc2[q] = 0.0;
         const int d = d0 + (q < nd ? q : 0);
         xc[q] = xp[d] / ls[d];
         il[q] = 1.0 / ls[d];
     }
     for (int j = threadIdx.x; j < n; j += 256) {
         const double* xr = Xh + (size_t)j * Dp + d0;
-        const double dj = dk[j], wj = w[j];
+        const double dj = dk[j], wj = w[j], w2j = TWO ? w2[j] : 0.0;
 #pragma unroll
         for (int q = 0; q < GD; ++q)
-            if (q < nd) acc[q] += wj * (dj * (2.0 * (xr[q] - xc[q]) * il[q]));
+            if (q < nd) {
+                const double gj = dj * (2.0 * (xr[q] - xc[q]) * il[q]);
+                acc[q] += wj * gj;
+                if (TWO) acc2[q] += w2j * gj;
+            }
     }
 #pragma unroll
     for (int q = 0; q < GD; ++q) {
 #pragma unroll
-        for (int off = 32; off > 0; off >>= 1) acc[q] += __shfl_xor(acc[q], off);
+        for (int off = 32; off > 0; off >>= 1) {
+            acc[q] += __shfl_xor(acc[q], off);
+            if (TWO) acc2[q] += __shfl_xor(acc2[q], off);
+        }
     }
 }
 
-__global__ __launch_bounds__(256) void k_point_finish_con(
+// the wave sums of the three accumulators meet in redv; redv_sum adds a column over the four waves in the fixed order
+__device__ __forceinline__ void redv_store(double (*redv)[3 * GD], const double* a1, const double* a2, const double* a3)
+{
+    __syncthreads();
+    if ((threadIdx.x & 63) == 0) {
+        double* r = redv[threadIdx.x >> 6];
+#pragma unroll
+        for (int q = 0; q < GD; ++q) {
+            r[q] = a1[q];
+            r[GD + q] = a2[q];
+            r[2 * GD + q] = a3[q];
+        }
+    }
+    __syncthreads();
+}
+__device__ __forceinline__ double redv_sum(const double (*redv)[3 * GD], int i)
+{
+    return ((redv[0][i] + redv[1][i]) + redv[2][i]) + redv[3][i];
+}
+
+// The two per-dimension combines.  Both start from  0.5 amp2 (s1v g_m + (-2 s2v) g_s2); they round differently and each
+// keeps its own bits: the plain one carries the fused multiply-adds its earliest build was compiled to, spelled out so that
+// no compiler or flag moves them; the constrained one fuses nothing.
+// plain / per second: d(-EI)/dx_d, with a time model (ei, time_m, gtd) the quotient rule of GPEIperSecChooser.py:425-432
+__device__ __forceinline__ double combine_plain(double amp2, double s1v, double s2v, double g_m, double g_s2, bool per_sec,
+                                                double amp2t, double s3v, double time_m, double ei)
+{
+#pragma clang fp contract(off)
+    const double t = g_s2 * (s2v + s2v);
+    double gd = (0.5 * amp2) * fma(g_m, s1v, -t);
+    if (per_sec) {
+        const double gtd = 0.5 * amp2t * s3v * time_m;
+        gd = fma(time_m, gd, -(ei * gtd)) / (time_m * time_m);
+    }
+    return gd;
+}
+// constrained: P grad(-EI)[d] + EI gcm[d], gcm[d] = c1 s3v phi(gain m_c)  (GPConstrainedEIChooser.py:682-688, :801)
+__device__ __forceinline__ double combine_con(double amp2, double s1v, double s2v, double g_m, double g_s2, bool with_con,
+                                              double c1, double s3v, double pdfc, double pc, double ei)
+{
+#pragma clang fp contract(off)
+    double gd = 0.5 * amp2 * (s1v * g_m + (-2.0 * s2v) * g_s2);
+    if (with_con) {
+        const double gcm = c1 * s3v * pdfc;
+        gd = pc * gd + ei * gcm;
+    }
+    return gd;
+}
+
+// out[h][p][0] = the objective's value for draw h at point p, out[h][p][1 + d] = its gradient, in the reference's scaling
+//   CON = false  EI (mean over the fantasies against bests[s] if S > 0); third side = time model: EI per second
+//   CON = true   EI x P(feasible) (sum over the fantasies against the one `best`); third side = constraint model
+// (positional __restrict__ parameters, not the FinishArgs struct itself: __restrict__ does not carry through struct members,
+// and with the struct as the kernel's argument the compiler spilled 23 / 16 SGPRs, none this way; launch_finish unpacks it.)
+template <bool CON>
+__global__ __launch_bounds__(256) void k_point_finish(
     // mean side
     const double* __restrict__ Xs, const double* __restrict__ hyp, const double* __restrict__ htab,
     const double* __restrict__ alpha, const double* __restrict__ kvec, const double* __restrict__ dkdr2, int N, int Np,
-    // variance side (length scales and amplitude are the mean side's)
+    // variance side (length scales and amplitude are the mean side's); XsV == Xs: the mean side's rows
     const double* __restrict__ XsV, const double* __restrict__ dkV, const double* __restrict__ tV,
     const double* __restrict__ zV, int Nv, int Npv,
-    // constraint side; conTab rows [gain, noise_c, amp2_c, amp2_c]
-    const double* __restrict__ XsC, const double* __restrict__ hypC, const double* __restrict__ conTab,
-    const double* __restrict__ alphaC, const double* __restrict__ kC, const double* __restrict__ dkC, int Nc, int Npc,
+    // third side (N3 = 0: none): time model / constraint model, tab3 rows [gain, noise_c, amp2_c, amp2_c]
+    const double* __restrict__ Xs3, const double* __restrict__ hyp3, const double* __restrict__ tab3,
+    const double* __restrict__ alpha3, const double* __restrict__ k3, const double* __restrict__ dk3, int N3, int Np3,
     const double* __restrict__ x, double best, double* __restrict__ out, int D, int Dp, int P,
     // fantasies (mean side == variance side then)
     int S, const double* __restrict__ gammaS /*[H][S][Np]*/, const double* __restrict__ alphaS /*[H][S][Np]*/,
-    double* __restrict__ uvec /*[H][P][Np] work vector*/)
+    const double* __restrict__ bests /*[H][S], plain only*/, double* __restrict__ uvec /*[H][P][Np] work vector*/)
 {
     extern __shared__ double dyn[];        // S > 0: [3][S]
     __shared__ double red[4];
     __shared__ double redv[4][3 * GD];
     __shared__ double sh_ei, sh_gm, sh_gs2, sh_pc, sh_c1, sh_pdfc;
-    const int h = blockIdx.x, p = blockIdx.y;
-    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-    const size_t vo = ((size_t)h * P + p) * Np, vv = ((size_t)h * P + p) * Npv, vc = ((size_t)h * P + p) * Npc;
+    const int h = blockIdx.x, p = blockIdx.y, tid = threadIdx.x;
+    const bool own_v = CON && XsV != Xs;      // the variance runs over rows of its own (constrained, no fantasies)
+    // the plain objective's variance side is its mean side: its launches pass Nv == N and Npv == Np
+    const int nv = CON ? Nv : N, npv = CON ? Npv : Np;
+    const size_t hp = (size_t)h * P + p, vo = hp * Np, vv = hp * npv, v3 = hp * Np3;
     const double* ah = alpha + (size_t)h * Np;
     const double* th = tV + vv;
     const double* xp = x + (size_t)p * D;
     const double* ls = hyp + (size_t)h * (3 + D) + 3;
     const double mean = htab[h * SPX_HT + 0], amp2 = htab[h * SPX_HT + 2], prior_v = htab[h * SPX_HT + 3];
-    double* o = out + ((size_t)h * P + p) * (1 + D);
+    double* o = out + hp * (1 + D);
 
-    double tt = 0.0;
-    for (int j = tid; j < Nv; j += 256) tt += th[j] * th[j];
-    tt = block_sum(tt, red);
+    const double tt = block_dot(th, th, nv, red);
+    const double func_s = sqrt(prior_v - tt);
     if (S == 0) {
-        const double* kh = kvec + vo;
-        double ka = 0.0;
-        for (int j = tid; j < N; j += 256) ka += kh[j] * ah[j];
-        ka = block_sum(ka, red);
-        if (tid == 0) {
-#pragma clang fp contract(off)
-            const double func_m = ka + mean;
-            const double func_v = prior_v - tt;
-            const double func_s = sqrt(func_v);
-            const double u = (best - func_m) / func_s;
-            const double cdf = ndtr_r(u);
-            const double pdf = exp(-(u * u) / 2.0) / 2.50662827463100050242;
-            sh_ei = func_s * (u * cdf + pdf);
-            sh_gm = -cdf;
-            sh_gs2 = 0.5 * pdf / func_s;
-        }
+        const double ka = block_dot(kvec + vo, ah, N, red);
+        if (tid == 0) ei_terms(best, ka + mean, func_s, sh_ei, sh_gm, sh_gs2);
         __syncthreads();
     } else {
-        // every fantasy against the one `best` (:645): func_m[s] = t . Gamma_s + mean; one wavefront per s
-        double* gmS = dyn;                 // [S]  -Phi_s
-        double* eiS = dyn + S;             // [S]
-        double* gsS = dyn + 2 * S;         // [S]  0.5 phi_s / func_s
-        const double func_v = prior_v - tt;
-        const double func_s = sqrt(func_v);
-        for (int sidx = wave; sidx < S; sidx += 4) {
-            const double* gs = gammaS + ((size_t)h * S + sidx) * Np;
-            double m = 0.0;
-            for (int j = lane; j < N; j += 64) m += th[j] * gs[j];
-#pragma unroll
-            for (int off = 32; off > 0; off >>= 1) m += __shfl_xor(m, off);
-            if (lane == 0) {
-#pragma clang fp contract(off)
-                const double func_m = m + mean;
-                const double u = (best - func_m) / func_s;
-                const double cdf = ndtr_r(u);
-                const double pdf = exp(-(u * u) / 2.0) / 2.50662827463100050242;
-                eiS[sidx] = func_s * (u * cdf + pdf);
-                gmS[sidx] = -cdf;
-                gsS[sidx] = 0.5 * pdf / func_s;
-            }
-        }
-        __syncthreads();
-        if (tid == 0) {
-            double e = 0.0, g2 = 0.0;
-            for (int sidx = 0; sidx < S; ++sidx) { e += eiS[sidx]; g2 += gsS[sidx]; }
-            sh_ei = e;
-            sh_gs2 = g2;
-            sh_gm = 1.0;
-        }
-        // u[j] = sum_s( -Phi_s alpha_s[j] )
         double* uh = uvec + vo;
-        for (int j = tid; j < Np; j += 256) {
-            double a = 0.0;
-            if (j < N)
-                for (int sidx = 0; sidx < S; ++sidx) a += gmS[sidx] * alphaS[((size_t)h * S + sidx) * Np + j];
-            uh[j] = a;
-        }
-        __syncthreads();
+        fantasy_terms(dyn, S, CON ? 1.0 : (double)S, th, gammaS + (size_t)h * S * Np, alphaS + (size_t)h * S * Np,
+                      CON ? nullptr : bests + (size_t)h * S, best, mean, func_s, N, Np, uh, sh_ei, sh_gm, sh_gs2);
         ah = uh;     // the mean-gradient weights of the fantasy branch (g_m folded in)
     }
-    if (Nc > 0) {
-        const double* kc = kC + vc;
-        const double* ac = alphaC + (size_t)h * Npc;
-        double mc = 0.0;
-        for (int j = tid; j < Nc; j += 256) mc += kc[j] * ac[j];
-        mc = block_sum(mc, red);
-        if (tid == 0) {
+    // third side: m3 = k3 . alpha3, then the constraint's P, phi and scale, or the time model's predicted duration
+    const double* a3h = alpha3 + (size_t)h * Np3;
+    double time_m = 1.0, amp23 = 0.0, pc = 1.0, pdfc = 0.0, c1 = 0.0;
+    if (N3 > 0) {
+        const double m3 = block_dot(k3 + v3, a3h, N3, red);
+        if (CON) {
+            if (tid == 0) {
 #pragma clang fp contract(off)
-            const double gain = conTab[h * SPX_HT + 0], camp2 = conTab[h * SPX_HT + 2];
-            const double a = gain * mc;
-            sh_pc = ndtr_r(a);
-            sh_pdfc = exp(-(a * a) / 2.0) / 2.50662827463100050242;
-            sh_c1 = 0.5 * camp2 * gain;
+                const double gain = tab3[h * SPX_HT + 0], camp2 = tab3[h * SPX_HT + 2];
+                const double g = gain * m3;
+                sh_pc = ndtr_r(g);
+                sh_pdfc = exp(-(g * g) / 2.0) / 2.50662827463100050242;
+                sh_c1 = 0.5 * camp2 * gain;
+            }
+            __syncthreads();
+            pc = sh_pc; pdfc = sh_pdfc; c1 = sh_c1;
+        } else {
+            amp23 = tab3[h * SPX_HT + 2];
+            time_m = exp(m3 + tab3[h * SPX_HT + 0]);
         }
-        __syncthreads();
     }
     const double g_m = sh_gm, g_s2 = sh_gs2, ei = sh_ei;
-    const double* lsC = Nc > 0 ? hypC + (size_t)h * (3 + D) + 3 : ls;
+    const double* ls3 = N3 > 0 ? hyp3 + (size_t)h * (3 + D) + 3 : ls;
 
     for (int d0 = 0; d0 < D; d0 += GD) {
         const int nd = min(GD, D - d0);
         double a1[GD], a2[GD], a3[GD];
-        grad_pass(Xs + (size_t)h * Np * Dp, Dp, ls, xp, dkdr2 + vo, ah, N, d0, nd, a1);
-        grad_pass(XsV + (size_t)h * Npv * Dp, Dp, ls, xp, dkV + vv, zV + vv, Nv, d0, nd, a2);
-        if (Nc > 0) {
-            grad_pass(XsC + (size_t)h * Npc * Dp, Dp, lsC, xp, dkC + vc, alphaC + (size_t)h * Npc, Nc, d0, nd, a3);
+        if (own_v) {
+            grad_pass<false>(Xs + (size_t)h * Np * Dp, Dp, ls, xp, dkdr2 + vo, ah, nullptr, N, d0, nd, a1, nullptr);
+            grad_pass<false>(XsV + (size_t)h * npv * Dp, Dp, ls, xp, dkV + vv, zV + vv, nullptr, nv, d0, nd, a2, nullptr);
+        } else {
+            grad_pass<true>(Xs + (size_t)h * Np * Dp, Dp, ls, xp, dkdr2 + vo, ah, zV + vv, N, d0, nd, a1, a2);
+        }
+        if (N3 > 0) {
+            grad_pass<false>(Xs3 + (size_t)h * Np3 * Dp, Dp, ls3, xp, dk3 + v3, a3h, nullptr, N3, d0, nd, a3, nullptr);
         } else {
 #pragma unroll
             for (int q = 0; q < GD; ++q) a3[q] = 0.0;
         }
-        __syncthreads();
-        if (lane == 0) {
-#pragma unroll
-            for (int q = 0; q < GD; ++q) {
-                redv[wave][q] = a1[q];
-                redv[wave][GD + q] = a2[q];
-                redv[wave][2 * GD + q] = a3[q];
-            }
-        }
-        __syncthreads();
+        redv_store(redv, a1, a2, a3);
         if (tid < nd) {
-#pragma clang fp contract(off)
-            const int q = tid;
-            const double s1v = ((redv[0][q] + redv[1][q]) + redv[2][q]) + redv[3][q];
-            const double s2v = ((redv[0][GD + q] + redv[1][GD + q]) + redv[2][GD + q]) + redv[3][GD + q];
-            double gd = 0.5 * amp2 * (s1v * g_m + (-2.0 * s2v) * g_s2);
-            if (Nc > 0) {
-                const double s3v = ((redv[0][2 * GD + q] + redv[1][2 * GD + q]) + redv[2][2 * GD + q]) + redv[3][2 * GD + q];
-                const double gcm = sh_c1 * s3v * sh_pdfc;
-                gd = sh_pc * gd + ei * gcm;
-            }
-            o[1 + d0 + q] = gd;
+            const double s1v = redv_sum(redv, tid), s2v = redv_sum(redv, GD + tid);
+            const double s3v = N3 > 0 ? redv_sum(redv, 2 * GD + tid) : 0.0;
+            o[1 + d0 + tid] = CON ? combine_con(amp2, s1v, s2v, g_m, g_s2, N3 > 0, c1, s3v, pdfc, pc, ei)
+                                  : combine_plain(amp2, s1v, s2v, g_m, g_s2, N3 > 0, amp23, s3v, time_m, ei);
         }
     }
-    if (tid == 0) o[0] = Nc > 0 ? ei * sh_pc : ei;
+    if (tid == 0) o[0] = N3 == 0 ? ei : CON ? ei * pc : ei / time_m;
 }
 
-void launch_point_finish_con(hipStream_t s, const double* Xs, const double* hyp, const double* htab, const double* alpha,
-                             const double* kvec, const double* dkdr2, int N, int Np, const double* XsV, const double* dkV,
-                             const double* tV, const double* zV, int Nv, int Npv, const double* XsC, const double* hypC,
-                             const double* conTab, const double* alphaC, const double* kC, const double* dkC, int Nc,
-                             int Npc, const double* x, double best, double* out, int D, int Dp, int nh, int P, int S,
-                             const double* gammaS, const double* alphaS, double* uvec)
+// the one place that knows the kernel's parameter order
+template <bool CON>
+static void launch_finish(hipStream_t s, const FinishArgs& a)
 {
-    const size_t lds = (size_t)3 * S * sizeof(double);   // up to 96 KB at S = 4096: above the 64 KB default limit
+    const size_t lds = (size_t)3 * a.S * sizeof(double);   // up to 96 KB at S = 4096: above the 64 KB default limit
     if (lds > 48 * 1024)
-        SPX_LDS_ATTR(k_point_finish_con, lds);
-    hipLaunchKernelGGL(k_point_finish_con, dim3(nh, P), dim3(256), lds, s, Xs, hyp, htab, alpha, kvec, dkdr2, N, Np, XsV,
-                       dkV, tV, zV, Nv, Npv, XsC, hypC, conTab, alphaC, kC, dkC, Nc, Npc, x, best, out, D, Dp, P, S, gammaS,
-                       alphaS, uvec);
+        SPX_LDS_ATTR(k_point_finish<CON>, lds);
+    hipLaunchKernelGGL(k_point_finish<CON>, dim3(a.nh, a.P), dim3(256), lds, s, a.m.Xs, a.m.hyp, a.htab, a.m.w, a.k, a.m.dk,
+                       a.m.n, a.m.Np, a.v.Xs, a.v.dk, a.t, a.v.w, a.v.n, a.v.Np, a.c.Xs, a.c.hyp, a.tab3, a.c.w, a.k3, a.c.dk,
+                       a.c.n, a.c.Np, a.x, a.best, a.out, a.D, a.Dp, a.P, a.S, a.gammaS, a.alphaS, a.bests, a.uvec);
+}
+
+void launch_point_finish(hipStream_t s, const FinishArgs& a, bool constrained)
+{
+    if (constrained) launch_finish<true>(s, a);
+    else launch_finish<false>(s, a);
 }

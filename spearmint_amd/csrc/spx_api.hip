@@ -1572,59 +1572,99 @@ int spx_sobol_grid(spx_handle* h, const uint32_t* dirs, int32_t dim_max, int32_t
     return SPX_OK;
 }
 
-int spx_ei_grad_batch(spx_handle* h, const double* points, int32_t P, double* neg_ei, double* grad)
+// ---- the refinement objective: both entry points are these helpers plus their own checks and choice of sides --------
+
+// One set of rows a call solves against: model `model` of r's tables (1: the time model's rows H..2H-1, into pt_kt /
+// pt_dkt), and with `solve` t = W k, z = W^T t = K^-1 k in r's pt_t / pt_z.  r is the calling handle itself, its internal
+// full handle or its constraint handle.
+struct RefineRows { spx_handle* r; int model; bool solve; };
+
+static int refine_rows_reserve(const spx_handle* h, const RefineRows& rr, int P)
 {
-    if (!h || !points || !neg_ei || !grad || P < 1) return fail(SPX_ERR_ARG, "spx_ei_grad_batch: bad argument");
-    if (h->multi) return spx_multi_ei_grad_batch(h->multi, points, P, neg_ei, grad);
-    if (!h->factored) return fail(SPX_ERR_ARG, "spx_ei_grad_batch: call spx_factor (or spx_ei_grid) first");
-    const int S = h->S;
-    const bool per_sec = (h->nmodels == 2);   // a time model was factored: EI per second (GPEIperSecChooser.py:349-434)
-    if (S > 0 && per_sec)
-        return fail(SPX_ERR_ARG, "spx_ei_grad_batch: fantasies with a time model are not defined "
-                    "(the reference's per-second refinement ignores pending jobs)");
-    int rc = ensure_init(h);
-    if (rc) return rc;
-    const int H = h->H, D = h->D, Dp = h->Dp, Np = h->Np;
-    const int64_t N = h->N;
-    const size_t vec = (size_t)H * P * Np * 8;
-    if ((rc = h->pt_x.reserve((size_t)P * D * 8))) return rc;
-    if ((rc = h->pt_k.reserve(vec))) return rc;
-    if ((rc = h->pt_dk.reserve(vec))) return rc;
-    if ((rc = h->pt_t.reserve(vec))) return rc;
-    if ((rc = h->pt_z.reserve(vec))) return rc;
-    if ((rc = h->pt_out.reserve((size_t)H * P * (1 + D) * 8))) return rc;
-    if (per_sec) {
-        if ((rc = h->pt_kt.reserve(vec))) return rc;
-        if ((rc = h->pt_dkt.reserve(vec))) return rc;
+    int rc;
+    spx_handle* r = rr.r;
+    const size_t vec = (size_t)h->H * P * r->Np * 8;
+    if ((rc = (rr.model ? r->pt_kt : r->pt_k).reserve(vec))) return rc;
+    if ((rc = (rr.model ? r->pt_dkt : r->pt_dk).reserve(vec))) return rc;
+    if (rr.solve) {
+        if ((rc = r->pt_t.reserve(vec))) return rc;
+        if ((rc = r->pt_z.reserve(vec))) return rc;
     }
+    return SPX_OK;
+}
+
+// k and dk/dr2 at the staged points, then the two solves; every launch goes on the calling handle's stream
+static void refine_rows_launch(spx_handle* h, const RefineRows& rr, int P)
+{
+    spx_handle* r = rr.r;
+    const int H = h->H, D = h->D, Dp = h->Dp, Np = r->Np;
+    double* k = (rr.model ? r->pt_kt : r->pt_k).d();
+    double* dk = (rr.model ? r->pt_dkt : r->pt_dk).d();
     hipStream_t s = h->stream;
+    const size_t m = (size_t)rr.model * H;
+    launch_point_cov(s, r->Xs.d() + m * Np * Dp, r->s1.d() + m * Np, r->hyp.d() + m * (3 + D), r->htab.d() + m * SPX_HT,
+                     h->pt_x.d(), k, dk, (int)r->N, Np, D, Dp, H, P, dev_kind(h));
+    if (rr.solve) {
+        launch_trimv_multi(s, r->WT.d(), k, r->pt_t.d(), Np, H, P);                // t = W k
+        launch_trimvT_multi(s, r->WT.d(), r->pt_t.d(), r->pt_z.d(), Np, H, P);     // z = W^T t = K^-1 k
+    }
+}
+
+// model `model` of r's tables as one side of the finish, with gradient weights w
+static FinishSide refine_side(const spx_handle* h, const spx_handle* r, int model, const double* w)
+{
+    const size_t m = (size_t)model * h->H;
+    return FinishSide{r->Xs.d() + m * r->Np * h->Dp, r->hyp.d() + m * (3 + h->D), model ? r->pt_dkt.d() : r->pt_dk.d(), w,
+                      (int)r->N, r->Np};
+}
+
+// Reserve everything the call needs before anything is queued, build alpha_s = W^T Gamma_s = K^-1 (fant_s - mean) for
+// every fantasy column once per set of fantasies (:501-502), stage the points and solve against every set of rows.
+static int refine_solve(spx_handle* h, const double* points, int P, const RefineRows* rows, int n_rows)
+{
+    int rc;
+    const int H = h->H, D = h->D, Np = h->Np, S = h->S;
+    if ((rc = h->pt_x.reserve((size_t)P * D * 8))) return rc;
+    if ((rc = h->pt_out.reserve((size_t)H * P * (1 + D) * 8))) return rc;
+    for (int i = 0; i < n_rows; ++i)
+        if ((rc = refine_rows_reserve(h, rows[i], P))) return rc;
     if (S > 0) {
-        if ((rc = h->pt_u.reserve(vec))) return rc;
-        if (!h->alphaS_valid) {   // alpha_s = W^T Gamma_s = K^-1 (fant_s - mean) for every fantasy column (:501-502)
+        if ((rc = h->pt_u.reserve((size_t)H * P * Np * 8))) return rc;
+        if (!h->alphaS_valid) {
             if ((rc = h->alphaS.reserve((size_t)H * S * Np * 8))) return rc;
-            launch_trimvT_multi(s, h->WT.d(), h->gammaS.d(), h->alphaS.d(), Np, H, S);
+            launch_trimvT_multi(h->stream, h->WT.d(), h->gammaS.d(), h->alphaS.d(), Np, H, S);
             h->alphaS_valid = true;
         }
     }
     stage_begin(h);
-    if ((rc = stage_h2d(h, h->pt_x.p, points, (size_t)P * D * 8, s))) return rc;
-    launch_point_cov(s, h->Xs.d(), h->s1.d(), h->hyp.d(), h->htab.d(), h->pt_x.d(), h->pt_k.d(), h->pt_dk.d(),
-                     (int)N, Np, D, Dp, H, P, dev_kind(h));
-    launch_trimv_multi(s, h->WT.d(), h->pt_k.d(), h->pt_t.d(), Np, H, P);        // t = W k
-    launch_trimvT_multi(s, h->WT.d(), h->pt_t.d(), h->pt_z.d(), Np, H, P);       // z = W^T t = K^-1 k
-    if (per_sec)   // k and dk/dr2 of the log-duration GP (table rows H..2H-1)
-        launch_point_cov(s, h->Xs.d() + (size_t)H * Np * Dp, h->s1.d() + (size_t)H * Np,
-                         h->hyp.d() + (size_t)H * (3 + D), h->htab.d() + (size_t)H * SPX_HT, h->pt_x.d(),
-                         h->pt_kt.d(), h->pt_dkt.d(), (int)N, Np, D, Dp, H, P, dev_kind(h));
-    launch_point_finish(s, h->Xs.d(), h->hyp.d(), h->htab.d(), h->alpha.d(), h->pt_k.d(), h->pt_dk.d(),
-                        h->pt_t.d(), h->pt_z.d(), h->pt_x.d(), h->best, h->pt_out.d(), (int)N, Np, D, Dp, H, P,
-                        per_sec ? h->pt_kt.d() : nullptr, per_sec ? h->pt_dkt.d() : nullptr, S,
-                        S > 0 ? h->gammaS.d() : nullptr, S > 0 ? h->alphaS.d() : nullptr,
-                        S > 0 ? h->bests.d() : nullptr, S > 0 ? h->pt_u.d() : nullptr);
+    if ((rc = stage_h2d(h, h->pt_x.p, points, (size_t)P * D * 8, h->stream))) return rc;
+    for (int i = 0; i < n_rows; ++i) refine_rows_launch(h, rows[i], P);
+    return SPX_OK;
+}
+
+// the finish over the mean side (the handle's own rows), the variance side v and the third side c3 (n = 0: none), then the
+// read-back and the sum over draws in draw order, as grad_optimize_ei_over_hypers does (GPEIOptChooser.py:368-380,
+// GPConstrainedEIChooser.py:471-501)
+static int refine_finish(spx_handle* h, const spx_handle* v, const FinishSide& c3, const double* k3, const double* tab3,
+                         bool constrained, double best, int P, double* neg, double* grad)
+{
+    int rc;
+    const int H = h->H, D = h->D, S = h->S;
+    FinishArgs a{};
+    a.m = refine_side(h, h, 0, h->alpha.d());
+    a.v = refine_side(h, v, 0, v->pt_z.d());
+    a.c = c3;
+    a.htab = h->htab.d(); a.k = h->pt_k.d(); a.t = v->pt_t.d(); a.k3 = k3; a.tab3 = tab3;
+    a.x = h->pt_x.d(); a.best = best; a.out = h->pt_out.d();
+    a.D = D; a.Dp = h->Dp; a.nh = H; a.P = P; a.S = S;
+    if (S > 0) {
+        a.gammaS = h->gammaS.d(); a.alphaS = h->alphaS.d(); a.uvec = h->pt_u.d();
+        if (!constrained) a.bests = h->bests.d();
+    }
+    launch_point_finish(h->stream, a, constrained);
     std::vector<double> out((size_t)H * P * (1 + D));
-    if ((rc = stage_d2h(h, out.data(), h->pt_out.p, out.size() * 8, s))) return rc;
+    if ((rc = stage_d2h(h, out.data(), h->pt_out.p, out.size() * 8, h->stream))) return rc;
     LAUNCHCHK();
-    // sum over draws in draw order, as grad_optimize_ei_over_hypers does (:368-380)
     for (int p = 0; p < P; ++p) {
         double f = 0.0;
         double* g = grad + (size_t)p * D;
@@ -1634,9 +1674,29 @@ int spx_ei_grad_batch(spx_handle* h, const double* points, int32_t P, double* ne
             f += -o[0];
             for (int d = 0; d < D; ++d) g[d] = g[d] + o[1 + d];
         }
-        neg_ei[p] = f;
+        neg[p] = f;
     }
     return SPX_OK;
+}
+
+int spx_ei_grad_batch(spx_handle* h, const double* points, int32_t P, double* neg_ei, double* grad)
+{
+    if (!h || !points || !neg_ei || !grad || P < 1) return fail(SPX_ERR_ARG, "spx_ei_grad_batch: bad argument");
+    if (h->multi) return spx_multi_ei_grad_batch(h->multi, points, P, neg_ei, grad);
+    if (!h->factored) return fail(SPX_ERR_ARG, "spx_ei_grad_batch: call spx_factor (or spx_ei_grid) first");
+    const bool per_sec = (h->nmodels == 2);   // a time model was factored: EI per second (GPEIperSecChooser.py:349-434)
+    if (h->S > 0 && per_sec)
+        return fail(SPX_ERR_ARG, "spx_ei_grad_batch: fantasies with a time model are not defined "
+                    "(the reference's per-second refinement ignores pending jobs)");
+    int rc = ensure_init(h);
+    if (rc) return rc;
+    // the handle's own rows, and k and dk/dr2 of the log-duration GP (table rows H..2H-1)
+    const RefineRows rows[2] = {{h, 0, true}, {h, 1, false}};
+    if ((rc = refine_solve(h, points, P, rows, per_sec ? 2 : 1))) return rc;
+    FinishSide tm{};
+    if (per_sec) tm = refine_side(h, h, 1, h->alpha.d() + (size_t)h->H * h->Np);
+    return refine_finish(h, h, tm, per_sec ? h->pt_kt.d() : nullptr,
+                         per_sec ? h->htab.d() + (size_t)h->H * SPX_HT : nullptr, false, h->best, P, neg_ei, grad);
 }
 
 int spx_ei_grad(spx_handle* h, const double* point, double* neg_ei_sum, double* grad)
@@ -1691,89 +1751,20 @@ int spx_constrained_ei_grad_batch(spx_handle* h, const double* points, int32_t P
                                  "spx_set_constraint_model)");
     int rc = ensure_init(h);
     if (rc) return rc;
-    const int S = h->S;
-    const bool two_factor = (S == 0 && Nc > 0);      // variance over X_c (the quirk of :692-803)
+    const bool two_factor = (h->S == 0 && c);        // variance over X_c (the quirk of :692-803)
     if (two_factor && (rc = ensure_full_factor(h))) return rc;
-    spx_handle* f = two_factor ? h->full : nullptr;
-    const int H = h->H, D = h->D, Dp = h->Dp, Np = h->Np;
-    const int64_t N = h->N;
-    const int Npc = c ? c->Np : 0;
-    const size_t vec = (size_t)H * P * Np * 8, vecc = (size_t)H * P * Npc * 8;
-    if ((rc = h->pt_x.reserve((size_t)P * D * 8))) return rc;
-    if ((rc = h->pt_k.reserve(vec))) return rc;
-    if ((rc = h->pt_dk.reserve(vec))) return rc;
-    if ((rc = h->pt_out.reserve((size_t)H * P * (1 + D) * 8))) return rc;
-    if (!two_factor) {
-        if ((rc = h->pt_t.reserve(vec))) return rc;
-        if ((rc = h->pt_z.reserve(vec))) return rc;
-    } else {
-        if ((rc = f->pt_k.reserve(vecc))) return rc;
-        if ((rc = f->pt_dk.reserve(vecc))) return rc;
-        if ((rc = f->pt_t.reserve(vecc))) return rc;
-        if ((rc = f->pt_z.reserve(vecc))) return rc;
-    }
-    if (c) {
-        if ((rc = c->pt_k.reserve(vecc))) return rc;
-        if ((rc = c->pt_dk.reserve(vecc))) return rc;
-    }
-    hipStream_t s = h->stream;
-    if (S > 0) {
-        if ((rc = h->pt_u.reserve(vec))) return rc;
-        if (!h->alphaS_valid) {   // alpha_s = W^T Gamma_s = K^-1 (fant_s - mean) for every fantasy column
-            if ((rc = h->alphaS.reserve((size_t)H * S * Np * 8))) return rc;
-            launch_trimvT_multi(s, h->WT.d(), h->gammaS.d(), h->alphaS.d(), Np, H, S);
-            h->alphaS_valid = true;
-        }
-    }
-    stage_begin(h);
-    if ((rc = stage_h2d(h, h->pt_x.p, points, (size_t)P * D * 8, s))) return rc;
-    const int kind = dev_kind(h);
-    launch_point_cov(s, h->Xs.d(), h->s1.d(), h->hyp.d(), h->htab.d(), h->pt_x.d(), h->pt_k.d(), h->pt_dk.d(),
-                     (int)N, Np, D, Dp, H, P, kind);
-    if (!two_factor) {
-        launch_trimv_multi(s, h->WT.d(), h->pt_k.d(), h->pt_t.d(), Np, H, P);        // t = W k
-        launch_trimvT_multi(s, h->WT.d(), h->pt_t.d(), h->pt_z.d(), Np, H, P);       // z = W^T t = K^-1 k
-    } else {
-        // k_f, dk_f: the objective's length scales against X_c; t_f = W_f k_f, z_f = W_f^T t_f
-        launch_point_cov(s, f->Xs.d(), f->s1.d(), f->hyp.d(), f->htab.d(), h->pt_x.d(), f->pt_k.d(), f->pt_dk.d(),
-                         (int)Nc, Npc, D, Dp, H, P, kind);
-        launch_trimv_multi(s, f->WT.d(), f->pt_k.d(), f->pt_t.d(), Npc, H, P);
-        launch_trimvT_multi(s, f->WT.d(), f->pt_t.d(), f->pt_z.d(), Npc, H, P);
-    }
-    if (c)   // k_c, dk_c: the constraint GP's own length scales and amplitude
-        launch_point_cov(s, c->Xs.d(), c->s1.d(), c->hyp.d(), c->htab.d(), h->pt_x.d(), c->pt_k.d(), c->pt_dk.d(),
-                         (int)Nc, Npc, D, Dp, H, P, kind);
-    if (S == 0 && !c) {
-        // no violation seen, no pending job: comp == compfull and P = 1 -- spx_ei_grad_batch's own launch
-        launch_point_finish(s, h->Xs.d(), h->hyp.d(), h->htab.d(), h->alpha.d(), h->pt_k.d(), h->pt_dk.d(),
-                            h->pt_t.d(), h->pt_z.d(), h->pt_x.d(), best, h->pt_out.d(), (int)N, Np, D, Dp, H, P,
-                            nullptr, nullptr, 0, nullptr, nullptr, nullptr, nullptr);
-    } else {
-        const spx_handle* v = two_factor ? f : h;     // whose rows the variance runs over
-        launch_point_finish_con(s, h->Xs.d(), h->hyp.d(), h->htab.d(), h->alpha.d(), h->pt_k.d(), h->pt_dk.d(), (int)N, Np,
-                                v->Xs.d(), v->pt_dk.d(), v->pt_t.d(), v->pt_z.d(), (int)v->N, v->Np,
-                                c ? c->Xs.d() : nullptr, c ? c->hyp.d() : nullptr, h->con_tab.d(),
-                                c ? c->alpha.d() : nullptr, c ? c->pt_k.d() : nullptr, c ? c->pt_dk.d() : nullptr,
-                                (int)Nc, Npc, h->pt_x.d(), best, h->pt_out.d(), D, Dp, H, P, S,
-                                S > 0 ? h->gammaS.d() : nullptr, S > 0 ? h->alphaS.d() : nullptr,
-                                S > 0 ? h->pt_u.d() : nullptr);
-    }
-    std::vector<double> out((size_t)H * P * (1 + D));
-    if ((rc = stage_d2h(h, out.data(), h->pt_out.p, out.size() * 8, s))) return rc;
-    LAUNCHCHK();
-    // sum over draws in draw order, as grad_optimize_ei_over_hypers does (:471-501)
-    for (int p = 0; p < P; ++p) {
-        double fsum = 0.0;
-        double* g = grad + (size_t)p * D;
-        for (int d = 0; d < D; ++d) g[d] = 0.0;
-        for (int i = 0; i < H; ++i) {
-            const double* o = &out[((size_t)i * P + p) * (1 + D)];
-            fsum += -o[0];
-            for (int d = 0; d < D; ++d) g[d] = g[d] + o[1 + d];
-        }
-        neg_cei[p] = fsum;
-    }
-    return SPX_OK;
+    RefineRows rows[3] = {{h, 0, !two_factor}};
+    int n_rows = 1;
+    // k_f, dk_f: the objective's length scales against X_c; t_f = W_f k_f, z_f = W_f^T t_f
+    if (two_factor) rows[n_rows++] = {h->full, 0, true};
+    // k_c, dk_c: the constraint GP's own length scales and amplitude
+    if (c) rows[n_rows++] = {c, 0, false};
+    if ((rc = refine_solve(h, points, P, rows, n_rows))) return rc;
+    FinishSide cm{};
+    if (c) cm = refine_side(h, c, 0, c->alpha.d());
+    // no violation seen, no pending job: comp == compfull and P = 1 -- spx_ei_grad_batch's own arithmetic
+    return refine_finish(h, two_factor ? h->full : h, cm, c ? c->pt_k.d() : nullptr, h->con_tab.d(), h->S > 0 || c, best, P,
+                         neg_cei, grad);
 }
 
 int spx_get_stat(spx_handle* h, const char* name, int64_t* value)

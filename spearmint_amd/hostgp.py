@@ -293,6 +293,20 @@ def fantasize_from_factor_rows(vals, hyper_row, l_rows, gamma, randn_ps):
     return fant_vals, np.min(fant_vals, axis=0)
 
 
+def fantasies_from_engine(eng, vals, hyper_rows, n, n_pend, S, randn, per_draw):
+    """fant[H, n + n_pend, S] and bests[H, S] for every resident draw of a factored engine: the bottom n_pend rows of
+    draw h's factor and its gamma (spx_get_factor_rows) are all the posterior of the pending points needs -- not the
+    N x N sub-Cholesky and two O(N^2 P) host solves against it.  per_draw: `randn[h]` is the (n_pend, S) standard-normal
+    array of draw h; otherwise `randn` is the one array every draw uses."""
+    H = hyper_rows.shape[0]
+    fant = np.empty((H, n + n_pend, S))
+    bests = np.empty((H, S))
+    for h in range(H):
+        l_rows, gam = eng.get_factor_rows(h, n, n_pend)
+        fant[h], bests[h] = fantasize_from_factor_rows(vals, hyper_rows[h], l_rows, gam, randn[h] if per_draw else randn)
+    return fant, bests
+
+
 class PendingPointModel(object):
     """EI (averaged over fantasies) and its gradient at a few points, with
     pending experiments -- the host-side refinement of GPEIOptChooser.py:441-525."""

@@ -277,6 +277,25 @@ def test_draw_additivity(eng, covar, branch):
     assert np.array_equal(f, fs) and np.array_equal(g, gs)
 
 
+def test_constrained_sum_over_fantasies_is_s_times_the_plain_mean(eng):
+    """The two objectives share one fantasy block: with every bests[h][s] equal to one value b and no violation seen, the
+    constrained entry (EI against b, SUMMED over the S = 4 fantasies, P = 1) returns exactly 4 times what the plain entry
+    (EI against bests[h][s], AVERAGED) returns -- dividing by 4 and by 1 are both exact.  The gradients are not compared:
+    their last combines round differently by design (refine_kernels.hip: combine_plain / combine_con)."""
+    p = rh.make_problem(7200, "Matern52", "fant", N=70, D=3, H=2, S=4)
+    b = float(np.min(p.vals))
+    p.bests = np.full((p.H, p.S), b)
+    pts = rh.points(p, 9, 9)
+    rh.setup(eng, p)
+    f_plain, _ = eng.ei_grad_batch(pts)
+    crows = np.column_stack((np.full(p.H, 1.5), np.full(p.H, 1e-3), np.ones(p.H), np.ones((p.H, p.D))))
+    eng.set_constraint_model(np.zeros((0, p.D)), np.zeros(0), crows)      # no violation seen
+    eng.factor()
+    eng.set_fantasies(p.fant, p.bests)
+    f_con, _ = eng.constrained_ei_grad_batch(pts, b)
+    assert np.array_equal(f_con, 4.0 * f_plain)
+
+
 # ---- 3. it is a gradient ---------------------------------------------------------------------------------------------------
 @pytest.mark.parametrize("D", [1, 4])
 @pytest.mark.parametrize("branch", BRANCHES)
