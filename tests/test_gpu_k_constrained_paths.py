@@ -614,22 +614,31 @@ def test_draw_count_mismatch_is_refused_and_the_handle_survives(eng):
 @pytest.mark.parametrize("entry", ["step", "factor", "step_timed"])
 @pytest.mark.parametrize("n_valid", [100, 243])
 def test_not_pd_constraint_model_is_draw_2H_plus_d(eng, entry, n_valid):
-    """A negative amp2_c in draw d: LinAlgError, spx_not_pd_info = (2H + d, pivot) as include/spx.h documents; the handle
-    is usable once a valid model is set, and its results are a fresh engine's."""
-    H, d = 4, 2
+    """Draw d of the constraint model stops being positive definite at pivot 200 (tests/factor_helpers.py's construction on
+    comp_c: row 63 copied into row 200, noise_c = -1.5e-6 amp2_c, length scale 0.25; dpotrf agrees and the leading block
+    keeps its distance): LinAlgError, spx_not_pd_info = (2H + d, 200) as include/spx.h documents; the handle is usable
+    once a valid model is set, and its results are a fresh engine's."""
+    from oracle import gp_ei_oracle as orc
+    from tests import factor_helpers as fh
+    H, d, i, j = 4, 2, 63, 200
     prob = _problem(360 + n_valid, 300, 300 - n_valid, 3000, 3, H)
     comp, vals, labels, cand, rows, crows, ff = prob
     good = labels > 0
     load(eng, "Matern52", prob)
     first = step(eng)
     bad = crows.copy()
-    bad[d, 2] = -1.0
-    eng.set_constraint_model(comp, ff, bad)
+    bad[d, 1] = fh.BAD_NOISE * bad[d, 2]
+    bad[d, 3:] = 0.25
+    comp_dup = comp.copy()
+    comp_dup[j] = comp_dup[i]
+    K = orc.cov(bad[d, 2], bad[d, 3:], comp_dup) + bad[d, 1] * np.eye(300)
+    assert fh.lapack_info(K) == j + 1 and fh.leading_min_eig(K, j) >= fh.MIN_LEADING_EIG * bad[d, 2]
+    eng.set_constraint_model(comp_dup, ff, bad)
     with options(eng, **({"timing": 1} if entry == "step_timed" else {})):
-        with pytest.raises(LinAlgError, match="constraint"):
+        with pytest.raises(LinAlgError, match="constraint") as raised:
             eng.factor() if entry == "factor" else eng.ei_step(KEEP)
     draw, pivot = eng.not_pd_info()
-    assert draw == 2 * H + d and 0 <= pivot < 300
+    assert draw == 2 * H + d and pivot == j and fh.minor_in(raised.value) == j + 1
     with pytest.raises(ValueError):
         eng.ei_draws()                           # no results of a pass that did not run
     # the objective's own model is untouched: without the constraint model the plain pass is a fresh engine's
