@@ -375,6 +375,9 @@ int spx_get_timings(spx_handle* h, double* ms, int64_t* launches, int n);
  *   "last_step_fused"  1 if the last EI pass ran as a one-kernel form (no K* / beta in memory; no fantasies);
  *   "last_step_skipped_padding"  1 if the last EI pass left the padding of N (to the GEMM's 128-row tiles) uncomputed
  *                      (option "gemm_partial", default on: same bits, up to -31 % per pass just above a multiple of 128);
+ *   "last_kstar_ring"  staging slots of the K(X*,X) ring the last EI pass ran with (option "streams" = 3; 0: it ran another way);
+ *   "last_corun_launches"  K(X*,X) launches of that pass in the form that fits beside two GEMM workgroups (k_cov_corun);
+ *   "gemm_lds_bytes"   dynamic LDS of one predict-GEMM workgroup (two are resident per CU; the co-resident K(X*,X) form uses none);
  *   "obs_dims"         D of the resident observations (0: none set);   "hip_runtime_version", "hip_driver_version", "clock_khz",
  *                      "mem_clock_khz", "wall_clock_khz", "l2_bytes", "mem_bus_bits": what the process runs on (bench.py: platform);
  *   "ranks_seen"       size of the communicator the last exchange ran on (one record per rank in its table): the ranks of the attached communicator
@@ -390,7 +393,7 @@ const char* spx_timing_name(int i);
 #define SPX_COVAR_ARDSE    2   /* gp.ARDSE    (gp.py:95-100)                                    */
 #define SPX_COVAR_SE       3   /* gp.SE       (gp.py:87-93): ARDSE with the length scales ignored */
 /* options: "covar" (SPX_COVAR_*); tuning knobs "kstar_budget_bytes" (K(X*,X) staging buffer;
- * 0 = default), "streams" (1|2), "timing" (0|1), "gemm_waves" (predict-GEMM variant of THIS
+ * 0 = default), "streams" (1|2|3, below), "timing" (0|1), "gemm_waves" (predict-GEMM variant of THIS
  * handle; values the build does not contain are rejected with SPX_ERR_ARG), and the forms of the
  * factorisation, all bit-identical, -1 = the default / chosen from the sizes:
  *   "lean_flow"     1 (default): the whole factorisation of spx_gp_logprob is ONE data-flow launch
@@ -408,6 +411,17 @@ const char* spx_timing_name(int i);
  * If an in-launch hand-off ever times out (its polls are bounded; never observed), the call is
  * repeated with one launch per block column, a warning is left in spx_last_error(), and the handle
  * stays in that form for "flow_rearm_after" clean factorisations (see spx_get_stat).
+ *   "streams"           how K(X*,X) of an EI pass is scheduled against the predict GEMM that reads it; the same bits in all:
+ *                       1 (default) one stream, each K(X*,X) launch in front of its GEMM; 2 a second stream and two staging
+ *                       buffers (the next item is produced while this one is consumed); 3 a stream of the device's lowest
+ *                       priority and a ring of staging slots: K(X*,X) runs up to a ring ahead, beside the GEMMs (and, in
+ *                       spx_ei_step, beside the factorisation), in a kernel form that fits into what two resident GEMM
+ *                       workgroups leave of a CU.  With "timing" = 1 a streams = 3 pass runs as streams = 1, so that every
+ *                       stage's events bracket its own kernels; the fused N <= 128 path never uses more than one stream;
+ *   "kstar_ring"        streams = 3: staging slots of the ring; 0 (default) as many as a sixteenth of the free device memory
+ *                       holds, at most 10 GiB, never more than the pass has work items (spx_get_stat "last_kstar_ring");
+ *   "kstar_corun"       streams = 3: K(X*,X) launches behind a pass's first use the co-resident kernel form (1, default) or
+ *                       the stand-alone one (0);
  *   "gemm_partial"      N not a multiple of 128: the last 128-row block of the predict GEMM computes only the 16-row tiles
  *                       that hold observations (k_predict_gemm_tail) and K(X*,X) does not write the pad rows (1, default,
  *                       where it saves at least 12 % of the pass), or everything is computed on the padded size (0);

@@ -58,7 +58,8 @@ void launch_cov_self(hipStream_t s, const double* Xs, const double* s1, const do
 void launch_cov_cross(hipStream_t s, const double* Xs, const double* s1, const double* Cs,
                       const double* s2, const double* htab, double* Kst, int N, int Np, int Mc,
                       int Dp, int nh, int kind = SPX_COV_MATERN52, int live_rows = 0 /*> 0: rows from here on are NOT written*/,
-                      bool allow_flat = true /*false: always the 3-D grid (option cov_flat)*/);
+                      bool allow_flat = true /*false: always the 3-D grid (option cov_flat)*/,
+                      bool corun = false /*true: the form that fits beside two predict-GEMM workgroups (k_cov_corun)*/);
 void launch_cross_mean(hipStream_t s, const double* Xs, const double* s1, const double* Cs,
                        const double* s2, const double* htab, const double* alpha, double* out,
                        int N, int Np, int Mc, int Dp, int nh, int kind = SPX_COV_MATERN52);
@@ -155,6 +156,7 @@ void launch_predict_gemm(hipStream_t s, int variant, const double* WT, const dou
                          double* part_ss, double* part_bg, int Np, int Mc, int nh, int part_nh, int part_h0,
                          const double* gammaS = nullptr, int S = 0, double* part_bgS = nullptr, int nlive = 0);
 bool predict_gemm_variant_ok(int v);
+size_t predict_gemm_lds_bytes();        // dynamic LDS of one predict-GEMM workgroup
 int predict_gemm_padding_plan(int variant, int N, int Np);
 void launch_ei_finalize_fant(hipStream_t s, const double* part_ss, const double* part_bgS,
                              const double* htab, const double* bests, const double* time_m, const double* cprob,

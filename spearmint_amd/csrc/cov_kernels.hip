@@ -334,18 +334,19 @@ __global__ __launch_bounds__(256, 2) void k_cov(
 // block next, row chunk fastest -- is dealt out in equal contiguous shares to a number of workgroups that is a whole multiple
 // of what the chip holds (2 per CU), so every residency round is full.  k_cov's grid at C3 was 1 792 workgroups on 512 places:
 // 3.5 rounds, the fourth half empty (13 % of the launch), 1 120 times per step.  Same arithmetic per element, same bits.
+// (share `blk` of `nblk` equal contiguous shares of the launch's units: the body of k_cov_flat and k_cov_corun)
 template <int QC, int KIND>
-__global__ __launch_bounds__(256, 2) void k_cov_flat(
+__device__ __forceinline__ void cov_flat_share(
     const double* __restrict__ Xs, const double* __restrict__ s1,
     const double* __restrict__ Cs, const double* __restrict__ s2,
     const double* __restrict__ htab, double* __restrict__ out, int N, int Np, int Mc, int Dp, int nchunks, int64_t ldo, int nh,
-    int live_rows)
+    int live_rows, unsigned blk, unsigned nblk)
 {
     const int jtop = live_rows > 0 ? live_rows : Np;        // (as in k_cov)
     const int nrc = (jtop + 127) >> 7, ncb = Mc >> 6;       // row chunks that hold live rows
     const int64_t per_h = (int64_t)ncb * nrc, U = per_h * nh;
-    int64_t u = U * blockIdx.x / gridDim.x;
-    const int64_t u1 = U * (blockIdx.x + 1) / gridDim.x;
+    int64_t u = U * blk / nblk;
+    const int64_t u1 = U * (blk + 1) / nblk;
     while (u < u1) {
         const int h = (int)(u / per_h);
         const int rem = (int)(u - (int64_t)h * per_h);
@@ -355,6 +356,37 @@ __global__ __launch_bounds__(256, 2) void k_cov_flat(
                              min(jtop, (rc + run) * 128));
         u += run;
     }
+}
+
+template <int QC, int KIND>
+__global__ __launch_bounds__(256, 2) void k_cov_flat(
+    const double* __restrict__ Xs, const double* __restrict__ s1,
+    const double* __restrict__ Cs, const double* __restrict__ s2,
+    const double* __restrict__ htab, double* __restrict__ out, int N, int Np, int Mc, int Dp, int nchunks, int64_t ldo, int nh,
+    int live_rows)
+{
+    cov_flat_share<QC, KIND>(Xs, s1, Cs, s2, htab, out, N, Np, Mc, Dp, nchunks, ldo, nh, live_rows, blockIdx.x, gridDim.x);
+}
+
+// K(X*,X) beside the predict GEMM (option streams = 3).  This is k_cov_flat's code, not another algorithm: what makes it fit
+// into what two resident GEMM workgroups leave of a CU -- 512 - 2 x 176 = 160 VGPRs per SIMD, so at most 152 here
+// (allocation granule 8), and no LDS (MODE 0 uses none; the GEMM's two workgroups hold 144 of the 160 KB) -- is how it is
+// launched: the contraction in chunks of at most four feature quads (QC <= 4, nchunks = Q / QC: at C3 k_cov_flat runs <8>
+// with 184 VGPRs, this runs <4> twice with 152), the column-side fragments re-read per chunk instead of hoisted, and a grid
+// of whole rounds of ONE workgroup per CU, all that fits there.  Same MFMAs on the same operands in the same order, so the
+// same bits; about a seventh slower when it runs alone, which it never does.  It has a symbol of its own so that the
+// budget test (tests/test_corun_budget.py) and a kernel trace can tell the co-resident launches from the stand-alone
+// ones, and so that its register bound is stated where the compiler must keep it (above 152 it would have to spill, and the
+// test reads the notes for scratch) instead of being a property k_cov_flat<4, .> happens to have today.
+template <int QC, int KIND>
+__global__ __launch_bounds__(256, 2) __attribute__((amdgpu_num_vgpr(152))) void k_cov_corun(
+    const double* __restrict__ Xs, const double* __restrict__ s1,
+    const double* __restrict__ Cs, const double* __restrict__ s2,
+    const double* __restrict__ htab, double* __restrict__ out, int N, int Np, int Mc, int Dp, int nchunks, int64_t ldo, int nh,
+    int live_rows)
+{
+    static_assert(QC <= 4, "the co-run form keeps at most four column-side quads in registers");
+    cov_flat_share<QC, KIND>(Xs, s1, Cs, s2, htab, out, N, Np, Mc, Dp, nchunks, ldo, nh, live_rows, blockIdx.x, gridDim.x);
 }
 
 template <int MODE, int KIND>
@@ -413,10 +445,38 @@ static void launch_cov_mode(hipStream_t s, int kind, const double* Xs, const dou
         launch_cov_kind<MODE, SPX_COV_MATERN52>(s, Xs, s1, Cs, s2, htab, alpha, out, N, Np, Mc, Dp, nh, ldo, live_rows, allow_flat);
 }
 
+template <int KIND>
+static void launch_cov_corun_kind(hipStream_t s, const double* Xs, const double* s1, const double* Cs, const double* s2,
+                                  const double* htab, double* out, int N, int Np, int Mc, int Dp, int nh, int64_t ldo,
+                                  int live_rows)
+{
+    const int Q = Dp / 4;
+    const int64_t places = spx_cov_cus();          // one workgroup per CU beside the GEMM's two
+    const int64_t units = (int64_t)nh * (Mc / 64) * (((live_rows > 0 ? live_rows : Np) + 127) / 128);
+    const int64_t rounds = (units + 16 * places - 1) / (16 * places);     // shares of at most 16 units, as k_cov_flat's
+    const dim3 grid((unsigned)(places * rounds));
+#define SPX_COVC_LAUNCH(QC_)                                                                                   \
+    hipLaunchKernelGGL((k_cov_corun<QC_, KIND>), grid, dim3(256), 0, s, Xs, s1, Cs, s2, htab, out, N, Np, Mc, Dp, Q / QC_, ldo, nh, live_rows)
+    if (Q == 1) SPX_COVC_LAUNCH(1);
+    else if (Q == 2) SPX_COVC_LAUNCH(2);
+    else SPX_COVC_LAUNCH(4);
+#undef SPX_COVC_LAUNCH
+}
+
+// corun: this launch runs beside a predict GEMM (option streams = 3, every item but a pass's first): k_cov_corun
 void launch_cov_cross(hipStream_t s, const double* Xs, const double* s1, const double* Cs,
                       const double* s2, const double* htab, double* Kst, int N, int Np, int Mc,
-                      int Dp, int nh, int kind, int live_rows, bool allow_flat)
+                      int Dp, int nh, int kind, int live_rows, bool allow_flat, bool corun)
 {
+    if (corun && allow_flat) {     // (option cov_flat = 0, always the 3-D grid, holds here too)
+        if (kind == SPX_COV_MATERN32)
+            launch_cov_corun_kind<SPX_COV_MATERN32>(s, Xs, s1, Cs, s2, htab, Kst, N, Np, Mc, Dp, nh, Mc, live_rows);
+        else if (kind == SPX_COV_ARDSE)
+            launch_cov_corun_kind<SPX_COV_ARDSE>(s, Xs, s1, Cs, s2, htab, Kst, N, Np, Mc, Dp, nh, Mc, live_rows);
+        else
+            launch_cov_corun_kind<SPX_COV_MATERN52>(s, Xs, s1, Cs, s2, htab, Kst, N, Np, Mc, Dp, nh, Mc, live_rows);
+        return;
+    }
     launch_cov_mode<0>(s, kind, Xs, s1, Cs, s2, htab, nullptr, Kst, N, Np, Mc, Dp, nh, Mc, live_rows, allow_flat);
 }
 

@@ -293,6 +293,19 @@ __global__ __launch_bounds__(64 * NW, NW / 2) void k_predict_gemm(
     }
 }
 
+// Static wave priority of the production GEMM kernels (k_predict_gemm_tri, k_predict_gemm_tail): raised once, at the top,
+// for the whole life of the wave -- no flips round the MFMA groups.  Issue is arbitrated by priority, then age: with
+// option streams = 3 a K(X*,X) producer workgroup (priority 0) shares the SIMD with two GEMM waves and then issues only
+// when both of them are stalled.  Alone on the chip the priority orders nothing.  (make GEMM_PRIO=0: a development build
+// without it, for attribution runs.)
+#ifndef SPX_GEMM_PRIO
+#define SPX_GEMM_PRIO 3
+#endif
+#define SPX_GEMM_SETPRIO()                                                \
+    do {                                                                  \
+        if (SPX_GEMM_PRIO > 0) __builtin_amdgcn_s_setprio(SPX_GEMM_PRIO); \
+    } while (0)
+
 // ---------------------------------------------------------------------------
 // k_predict_gemm_tri: the production tiling (128 x 128, 2 x 2 waves, LDS-DMA staging) that also skips the
 // structurally zero part of W's diagonal block.  In the K step that covers columns 16 d .. 16 d + 15 of the
@@ -304,7 +317,7 @@ __global__ __launch_bounds__(64 * NW, NW / 2) void k_predict_gemm(
 //     (that, and not the branches, is why skipping never paid with the contiguous layout);
 //   * the code of a full step is untouched: a diagonal step takes a second copy of the step body.
 // Full steps run the same code as k_predict_gemm; a diagonal step takes a second copy of the step body whose
-// MFMA groups are entered at the first live tile (wave-uniform jump).  The K order is unchanged; the row
+// MFMA groups sit behind wave-uniform guards (first live tile on).  The K order is unchanged; the row
 // ownership changes the order of the epilogue's floating-point sums, nothing else.  What did NOT work on the
 // way here (C3, ms per launch, 1.85-1.87 for k_predict_gemm on the same box): the same skip with the four waves
 // side by side (128 x 32 each, every wave the same triangular profile) 1.89 even before skipping; one
@@ -316,6 +329,7 @@ __global__ __launch_bounds__(256, 2) void k_predict_gemm_tri(
     double* __restrict__ part_bg, int Np, int Mc, int nh, int ncb, int nrb,
     int part_nh, int part_h0, const double* __restrict__ gammaS, int S, double* __restrict__ part_bgS)
 {
+    SPX_GEMM_SETPRIO();
     extern __shared__ __attribute__((aligned(16))) double smem[];
     double* As = smem;                      // [2][BK][LDT]
     double* Bs = smem + 2 * BK * LDT;       // [2][BK][LDT]
@@ -395,24 +409,29 @@ __global__ __launch_bounds__(256, 2) void k_predict_gemm_tri(
             // k_predict_gemm, sink the last MFMA group of a full step below them)
             asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
             __syncthreads();
-        } else {
-#define SPX_TRI_G4(MT_)                                                      \
-    _Pragma("unroll") for (int nt = 0; nt < 4; ++nt) acc[MT_][nt] = MFMA_F64(a[MT_], b[nt], acc[MT_][nt]);
+        }
+        // The diagonal step is an `if` of its own behind the full step's, not its `else`, and its condition is a copy of m0
+        // that the compiler cannot see through: as the two arms of one if / else the accumulators of this arm got registers
+        // of their own (a second copy of twelve tiles: 250 VGPRs, 48 v_mov_b64 into it and 48 back per diagonal step per
+        // wave).  Behind a plain `if` every MFMA accumulates into the tile it reads, as in the full step: 176 VGPRs, no
+        // accumulator move in the loop.  One copy of the MFMAs, each row tile behind its own wave-uniform guard (the form
+        // of k_predict_gemm_tail), in the K order of the full step.
+        int md = m0;
+        asm volatile("" : "+s"(md));
+        if (md != 0) {
 #pragma unroll
             for (int k0 = 0; k0 < BK; k0 += 4) {
-                double a[4], b[4];
+                double b[4];
 #pragma unroll
                 for (int t = 0; t < 4; ++t) b[t] = Bc[(k0 + g) * LDT + 16 * t];
 #pragma unroll
-                for (int t = 0; t < 4; ++t) a[t] = Ac[(k0 + g) * LDT + 32 * t];
-                switch (m0) {            // one copy of the MFMAs, entered at the first live tile
-                    case 1: SPX_TRI_G4(1)
-                    case 2: SPX_TRI_G4(2)
-                    case 3: SPX_TRI_G4(3)
-                    default: break;
-                }
+                for (int mt = 1; mt < 4; ++mt)
+                    if (mt >= m0) {
+                        const double a = Ac[(k0 + g) * LDT + 32 * mt];
+#pragma unroll
+                        for (int nt = 0; nt < 4; ++nt) acc[mt][nt] = MFMA_F64(a, b[nt], acc[mt][nt]);
+                    }
             }
-#undef SPX_TRI_G4
             asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
             __syncthreads();
         }
@@ -500,6 +519,7 @@ __global__ __launch_bounds__(256, 2) void k_predict_gemm_tail(
     double* __restrict__ part_bg, int Np, int Mc, int nh, int ncb, int ib, int nlive,
     int part_nh, int part_h0, const double* __restrict__ gammaS, int S, double* __restrict__ part_bgS)
 {
+    SPX_GEMM_SETPRIO();
     extern __shared__ __attribute__((aligned(16))) double smem[];
     double* As = smem;                      // [2][BK][LDT]
     double* Bs = smem + 2 * BK * LDT;       // [2][BK][LDT]
@@ -689,12 +709,14 @@ static void launch_gemm_variant(hipStream_t s, int grid, size_t lds, const doubl
 }
 
 // nlive: predict_gemm_padding_plan()'s figure when the caller wants the padding of N skipped (and has told K(X*,X) so), else 0
+size_t predict_gemm_lds_bytes() { return (size_t)(4 * BK * LDT) * sizeof(double); }
+
 void launch_predict_gemm(hipStream_t s, int variant, const double* WT, const double* Kst, const double* gamma,
                          double* part_ss, double* part_bg, int Np, int Mc, int nh, int part_nh, int part_h0,
                          const double* gammaS, int S, double* part_bgS, int nlive)
 {
     const int ncb = Mc / BN, nrb = Np / BM;
-    const size_t lds = (size_t)(4 * BK * LDT) * sizeof(double);
+    const size_t lds = predict_gemm_lds_bytes();
     const int grid = 8 * ((ncb + 7) / 8) * nrb * nh;
 #define SPX_GO(NW_, STG_, ABL_)                                                                               \
     launch_gemm_variant<NW_, STG_, ABL_>(s, grid, lds, WT, Kst, gamma, part_ss, part_bg, Np, Mc, nh, ncb, nrb, \

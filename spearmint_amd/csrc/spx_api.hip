@@ -63,7 +63,11 @@ static int ensure_init(spx_handle* h)
 {
     HIPCHK(hipSetDevice(h->device));
     if (!h->inited) {
-        HIPCHK(hipStreamCreateWithFlags(&h->stream, hipStreamNonBlocking));
+        // the main stream (factorisation, predict GEMM, EI) at the device's highest priority, the K(X*,X) producer of option
+        // streams = 3 (ensure_ring) at its lowest: a place that comes free on a CU goes to a waiting GEMM workgroup first
+        int prio_least = 0, prio_greatest = 0;
+        if (hipDeviceGetStreamPriorityRange(&prio_least, &prio_greatest) != hipSuccess) { (void)hipGetLastError(); prio_least = prio_greatest = 0; }
+        HIPCHK(hipStreamCreateWithPriority(&h->stream, hipStreamNonBlocking, prio_greatest));
         HIPCHK(hipStreamCreateWithFlags(&h->stream2, hipStreamNonBlocking));
         for (int i = 0; i < 6; ++i) HIPCHK(hipEventCreateWithFlags(&h->ev_sync[i], hipEventDisableTiming));
         HIPCHK(hipEventCreate(&h->ev_t0));
@@ -76,6 +80,33 @@ static int ensure_init(spx_handle* h)
         h->inited = true;
     }
     return SPX_OK;
+}
+
+// option streams = 3: the producer stream and `R` ring slots (events only: the buffers are reserved by the pass)
+static int ensure_ring(spx_handle* h, int R)
+{
+    if (!h->stream3) {
+        int prio_least = 0, prio_greatest = 0;
+        if (hipDeviceGetStreamPriorityRange(&prio_least, &prio_greatest) != hipSuccess) { (void)hipGetLastError(); prio_least = prio_greatest = 0; }
+        HIPCHK(hipStreamCreateWithPriority(&h->stream3, hipStreamNonBlocking, prio_least));
+    }
+    while ((int)h->ring.size() < R) {
+        spx_handle::RingSlot sl;
+        HIPCHK(hipEventCreateWithFlags(&sl.ready, hipEventDisableTiming));
+        hipError_t e = hipEventCreateWithFlags(&sl.consumed, hipEventDisableTiming);
+        if (e != hipSuccess) {
+            (void)hipEventDestroy(sl.ready);
+            (void)hipGetLastError();
+            return fail(SPX_ERR_HIP, "hipEventCreateWithFlags failed: %s", hipGetErrorString(e));
+        }
+        h->ring.push_back(sl);
+    }
+    return SPX_OK;
+}
+// the ring's buffers beyond the first `keep` slots go back to the device (a pass that needs fewer, or another mode)
+static void ring_trim(spx_handle* h, int keep)
+{
+    for (size_t i = (size_t)std::max(keep, 0); i < h->ring.size(); ++i) { h->ring[i].Kst.release(); h->ring[i].part_bgS.release(); }
 }
 
 static int ev_begin(spx_handle* h, int stage, hipStream_t strm)
@@ -160,6 +191,15 @@ void spx_destroy(spx_handle* h)
         (void)hipSetDevice(h->device);
         (void)hipStreamSynchronize(h->stream);
         (void)hipStreamSynchronize(h->stream2);
+        if (h->stream3) (void)hipStreamSynchronize(h->stream3);
+        for (auto& sl : h->ring) {
+            sl.Kst.release();
+            sl.part_bgS.release();
+            (void)hipEventDestroy(sl.ready);
+            (void)hipEventDestroy(sl.consumed);
+        }
+        h->ring.clear();
+        if (h->stream3) (void)hipStreamDestroy(h->stream3);
         DevBuf* bufs[] = {&h->comp, &h->vals, &h->ldur, &h->cand, &h->hyp, &h->htab, &h->Xs, &h->X2s,
                           &h->s1, &h->Lm, &h->WT, &h->Dinv, &h->gamma, &h->alpha, &h->info, &h->lp,
                           &h->Cs[0], &h->s2[0], &h->Kst[0], &h->part_ss[0], &h->part_bg[0], &h->time_m[0],
@@ -277,8 +317,16 @@ int spx_set_option(spx_handle* h, const char* name, int64_t value)
         h->gemm_partial = value < 0 ? -1 : (value != 0);
         return SPX_OK;
     }
-    if (!strcmp(name, "streams")) {  // 1 = everything on one stream (default), 2 = alternate EI work items
-        h->nstreams = value == 2 ? 2 : 1;
+    if (!strcmp(name, "streams")) {  // 1 = everything on one stream (default), 2 = alternate EI work items, 3 = K(X*,X) ahead of the GEMM through a ring
+        h->nstreams = (value == 2 || value == 3) ? (int)value : 1;
+        return SPX_OK;
+    }
+    if (!strcmp(name, "kstar_ring")) {   // streams = 3: staging slots of the ring (0, default: as many as the byte budget holds)
+        h->ring_opt = value <= 0 ? 0 : (int)std::min<int64_t>(value, 4096);
+        return SPX_OK;
+    }
+    if (!strcmp(name, "kstar_corun")) {  // streams = 3: K(X*,X) launches beside a GEMM in the form that fits there (1, default) or as k_cov_flat (0); same bits
+        h->corun_opt = value < 0 ? -1 : (value != 0);
         return SPX_OK;
     }
     if (!strcmp(name, "timing")) {  // per-launch HIP events on the handle's stream; (re)starts the accumulators
@@ -927,6 +975,7 @@ int spx_ei_step(spx_handle* h, int32_t flags)
         // upload staging relies on it) and without a factor it did not check
         (void)hipStreamSynchronize(h->stream);
         (void)hipStreamSynchronize(h->stream2);
+        if (h->stream3) (void)hipStreamSynchronize(h->stream3);
         (void)hipGetLastError();
         if (rc != SPX_ERR_NOT_PD) h->factored = false;
     }
@@ -988,7 +1037,45 @@ static int ei_run_impl(spx_handle* h, int32_t flags, bool factor_pending)
     // with K* and beta in registers (fused_kernels.hip; option ei_fused); same bits as the three-stage path below
     const bool fused = Np == SPX_PADN && S == 0 && h->ei_fused != 0;
     h->last_fused = fused;
-    const int ns = fused ? 1 : h->nstreams;
+    // streams = 3 with per-launch timing: the pass runs in order on one stream, so that every stage's events bracket that
+    // stage's kernels alone (the stage table, bench.py --full's roofline)
+    const bool timing_on = h->timing || (flags & SPX_FLAG_TIMING);
+    const int ns = fused ? 1 : ((h->nstreams == 3 && timing_on) ? 1 : h->nstreams);
+    // streams = 3: K(X*,X) of work item i goes to slot i % R of a ring of staging buffers (each with its own fantasy
+    // partials), so the producer stream runs up to R items ahead of the GEMM.  R comes from a byte budget -- a sixteenth of
+    // what the device has free, at most 10 GiB (C3: one chunk's twenty draws, 9.4 GB of 288), found when the size of a slot
+    // changes and not per pass (as fant_budget) -- or from option "kstar_ring"; never more slots than the pass has items.
+    const bool ringed = ns == 3 && !time_only;
+    int R = 0;
+    if (ringed) {
+        const int64_t slot = (int64_t)Hb * Np * Mc * 8 + (S > 0 ? (int64_t)nrb * 2 * Hb * S * Mc * 8 : 0);
+        if (h->ring_budget_slot != slot) {
+            size_t mem_free = 0, mem_total = 0;
+            int64_t b = 10ll << 30;
+            if (hipMemGetInfo(&mem_free, &mem_total) == hipSuccess) {
+                int64_t held = 0;
+                for (auto& sl : h->ring) held += (int64_t)(sl.Kst.cap + sl.part_bgS.cap);
+                b = std::min<int64_t>(b, (int64_t)(mem_free / 16) + held);
+            } else (void)hipGetLastError();
+            h->ring_budget = b;
+            h->ring_budget_slot = slot;
+        }
+        const int64_t nitems = ((Mp + Mc - 1) / Mc) * ((H + Hb - 1) / Hb);
+        int64_t r = h->ring_opt > 0 ? h->ring_opt : h->ring_budget / slot;
+        r = std::max<int64_t>(1, std::min<int64_t>(std::min<int64_t>(r, nitems), 4096));
+        R = (int)r;
+        if ((rc = ensure_ring(h, R))) return rc;
+        for (int k = 0; k < R; ++k) {
+            if ((rc = h->ring[k].Kst.reserve((size_t)Hb * Np * Mc * 8))) return rc;
+            if (S > 0 && (rc = h->ring[k].part_bgS.reserve((size_t)nrb * 2 * Hb * S * Mc * 8))) return rc;
+        }
+    }
+    if (ns == 3 && !ringed && (rc = ensure_ring(h, 0))) return rc;   // (a time-only pass: the producer stream alone)
+    // slots the pass does not use go back to the device -- but a streams = 3 handle that runs ONE pass another way (per-launch
+    // timing, the fused path, time only) keeps its ring: the next pass would only allocate the same gigabytes again
+    if (ringed || h->nstreams != 3) ring_trim(h, R);
+    h->ring_used = R;
+    h->corun_launches = 0;
     for (int b = 0; b < 2; ++b) {
         // scaled candidates (all draws) and predicted durations are double-buffered by chunk parity,
         // the K(X*,X) staging buffer and the partial sums by stream
@@ -998,7 +1085,7 @@ static int ei_run_impl(spx_handle* h, int32_t flags, bool factor_pending)
         if (constrained && (rc = h->con_p[b].reserve((size_t)H * Mc * 8))) return rc;
         if (constrained && h->con_n > 0 && (rc = h->con_Cs[b].reserve((size_t)H * Mc * Dp * 8))) return rc;
         if (constrained && h->con_n > 0 && (rc = h->con_s2[b].reserve((size_t)H * Mc * 8))) return rc;
-        if (b < ns && !fused && !time_only) {
+        if (b < ns && ns <= 2 && !fused && !time_only) {
             if ((rc = h->Kst[b].reserve((size_t)Hb * Np * Mc * 8))) return rc;
             if (S > 0 && (rc = h->part_bgS[b].reserve((size_t)nrb * 2 * Hb * S * Mc * 8))) return rc;
         }
@@ -1039,10 +1126,14 @@ static int ei_run_impl(spx_handle* h, int32_t flags, bool factor_pending)
     // Streams: G (consumer: predict GEMM + EI finalize) and P (producer: candidate scaling and
     // K(X*,X)).  With one stream P == G and everything is in order.  With two, the K(X*,X)
     // staging buffer is double-buffered per work item and item i+1 is produced while item i is
-    // consumed: the producer kernels are VALU/store-bound, the GEMM is MFMA-bound, and at 152 /
-    // 178 VGPRs one producer wave fits next to the two GEMM waves of a SIMD.
+    // consumed (whether the two share a SIMD depends on the kernels' registers: two GEMM waves of 176 VGPRs leave room for
+    // a producer wave of at most 152 -- k_cov_corun, used by streams = 3 only; k_cov_flat at D = 32 takes 184).
     // events: [0..1] K* of buffer b ready, [2..3] buffer b consumed, [4..5] chunk parity consumed
-    hipStream_t G = h->stream, P = (ns == 2) ? h->stream2 : h->stream;
+    // With three (option streams = 3) P is a stream of the device's lowest priority and the hand-off is the ring: item i
+    // waits for slot i % R to be consumed (item i - R's GEMM), so K(X*,X) runs beside the GEMMs -- and, in a step, beside
+    // the factorisation -- instead of in front of each.  events per slot: K* ready (P -> G), consumed (G -> P).
+    hipStream_t G = h->stream, P = (ns == 3) ? h->stream3 : (ns == 2) ? h->stream2 : h->stream;
+    const int64_t ring_items = ringed ? ((Mp + Mc - 1) / Mc) * ((H + Hb - 1) / Hb) : 0;
     // A step (factor_pending): the factorisation is still running on G -- a chain of small launches that leaves most of the
     // chip idle -- and the first producer work of the pass (candidate scaling, K(X*,X) of the first group of draws) depends
     // only on what the factorisation's FIRST kernel wrote.  It goes to the second stream, beside the factorisation
@@ -1055,7 +1146,7 @@ static int ei_run_impl(spx_handle* h, int32_t flags, bool factor_pending)
     // still queued on G.  Its scaling and K(X*,X) launches read x / ls, the row norms and the hyper table (written by the
     // factorisation's first kernel: ev_obs); a time model's predicted durations read alpha of the duration GP -- the END of
     // the factorisation (ev_fac).
-    if (factor_pending && ns == 2) HIPCHK(hipStreamWaitEvent(P, per_sec ? h->ev_fac : h->ev_obs, 0));
+    if (factor_pending && ns >= 2) HIPCHK(hipStreamWaitEvent(P, per_sec ? h->ev_fac : h->ev_obs, 0));
     int item = 0, chunk = 0;
     for (int64_t c0 = 0; c0 < Mp; c0 += Mc, ++chunk) {
         const int mc = (int)std::min<int64_t>(Mc, Mp - c0);       // multiple of 128
@@ -1066,7 +1157,7 @@ static int ei_run_impl(spx_handle* h, int32_t flags, bool factor_pending)
         double* s2 = h->s2[par].d();
         double* tm = per_sec ? h->time_m[par].d() : nullptr;
         // the chunk-level buffers of this parity were last read (by EI finalize on G) two chunks ago
-        if (ns == 2 && chunk >= 2) HIPCHK(hipStreamWaitEvent(P, h->ev_sync[4 + par], 0));
+        if (ns >= 2 && chunk >= 2) HIPCHK(hipStreamWaitEvent(P, h->ev_sync[4 + par], 0));
         if (per_sec) {
             // log-duration GP: predicted duration of every candidate of the chunk, all draws in one launch
             const bool side = overlap && chunk == 0;         // (a step's first chunk: the objective's scaling runs on P0 meanwhile)
@@ -1114,14 +1205,24 @@ static int ei_run_impl(spx_handle* h, int32_t flags, bool factor_pending)
                                                            keep_mom ? h->mom_v.d() : nullptr, (int)N, mc, Dp, H, c0, M, Mp, h->n_cu));
         for (int h0 = 0; h0 < (fused ? 0 : H); h0 += Hb, ++item) {
             const int nhb = std::min(Hb, H - h0);
-            const int k = (ns == 2) ? (item & 1) : 0;
+            const int k = (ns == 3) ? item % R : (ns == 2) ? (item & 1) : 0;
             if (ns == 2 && item >= 2) HIPCHK(hipStreamWaitEvent(P, h->ev_sync[2 + k], 0));   // buffer k consumed
+            if (ns == 3 && item >= R) HIPCHK(hipStreamWaitEvent(P, h->ring[k].consumed, 0)); // slot k consumed (item - R)
             hipStream_t Pi = (item == 0) ? Pc : P;
+            double* Kst_k = (ns == 3) ? h->ring[k].Kst.d() : h->Kst[k].d();
+            double* bgS_k = S > 0 ? ((ns == 3) ? h->ring[k].part_bgS.d() : h->part_bgS[k].d()) : nullptr;
+            // (the pass's first K(X*,X) has the chip to itself -- or shares it with the factorisation's small launches: today's
+            // kernel; every later one runs beside a GEMM: the form that fits there)
+            const bool corun = ns == 3 && item > 0 && h->corun_opt != 0 && h->cov_flat != 0;
+            h->corun_launches += corun ? 1 : 0;
             TIMED_S(ST_COV_CROSS, Pi, launch_cov_cross(Pi, h->Xs.d() + (size_t)h0 * Np * Dp, h->s1.d() + (size_t)h0 * Np,
                                                       Cs + (size_t)h0 * mc * Dp, s2 + (size_t)h0 * mc,
-                                                      h->htab.d() + (size_t)h0 * SPX_HT, h->Kst[k].d(), (int)N, Np, mc, Dp, nhb, dev_kind(h),
-                                                      cov_live_rows, h->cov_flat != 0));
-            if (ns == 2) {
+                                                      h->htab.d() + (size_t)h0 * SPX_HT, Kst_k, (int)N, Np, mc, Dp, nhb, dev_kind(h),
+                                                      cov_live_rows, h->cov_flat != 0, corun));
+            if (ns == 3) {
+                HIPCHK(hipEventRecord(h->ring[k].ready, P));
+                HIPCHK(hipStreamWaitEvent(G, h->ring[k].ready, 0));
+            } else if (ns == 2) {
                 HIPCHK(hipEventRecord(h->ev_sync[k], P));
                 HIPCHK(hipStreamWaitEvent(G, h->ev_sync[k], 0));
             } else if (Pi != G) {
@@ -1129,13 +1230,13 @@ static int ei_run_impl(spx_handle* h, int32_t flags, bool factor_pending)
                 HIPCHK(hipStreamWaitEvent(G, h->ev_p0, 0));
             }
             // with fantasies the launch's partial sums are consumed right away and sit at draws 0 .. nhb-1
-            TIMED_S(ST_PREDICT_GEMM, G, launch_predict_gemm(G, h->gemm_variant, h->WT.d() + (size_t)h0 * nn, h->Kst[k].d(),
+            TIMED_S(ST_PREDICT_GEMM, G, launch_predict_gemm(G, h->gemm_variant, h->WT.d() + (size_t)h0 * nn, Kst_k,
                                                             h->gamma.d() + (size_t)h0 * Np, h->part_ss[0].d(),
                                                             h->part_bg[0].d(), Np, mc, nhb, S > 0 ? nhb : H, S > 0 ? 0 : h0,
                                                             S > 0 ? h->gammaS.d() + (size_t)h0 * S * Np : nullptr, S,
-                                                            S > 0 ? h->part_bgS[k].d() : nullptr, gemm_nlive));
+                                                            bgS_k, gemm_nlive));
             if (S > 0)
-                TIMED_S(ST_EI_FINALIZE, G, launch_ei_finalize_fant(G, h->part_ss[0].d(), h->part_bgS[k].d(),
+                TIMED_S(ST_EI_FINALIZE, G, launch_ei_finalize_fant(G, h->part_ss[0].d(), bgS_k,
                                                                    h->htab.d() + (size_t)h0 * SPX_HT,
                                                                    h->bests.d() + (size_t)h0 * S,
                                                                    per_sec ? tm + (size_t)h0 * mc : nullptr,
@@ -1143,14 +1244,15 @@ static int ei_run_impl(spx_handle* h, int32_t flags, bool factor_pending)
                                                                    h->ei_draw.d(), nrb, mc, nhb, S, c0, M, Mp, h0,
                                                                    h->scratch.d()));
             if (ns == 2) HIPCHK(hipEventRecord(h->ev_sync[2 + k], G));
+            if (ns == 3 && (int64_t)item + R < ring_items) HIPCHK(hipEventRecord(h->ring[k].consumed, G));   // (only where an item waits for it)
         }
         if (S == 0 && !fused)   // every draw of the chunk in one launch
             TIMED_S(ST_EI_FINALIZE, G, launch_ei_finalize(G, h->part_ss[0].d(), h->part_bg[0].d(), h->htab.d(), tm, cp, h->best,
                                                           h->ei_draw.d(), keep_mom ? h->mom_m.d() : nullptr,
                                                           keep_mom ? h->mom_v.d() : nullptr, nrb, mc, H, c0, M, Mp, 0));
-        if (ns == 2) HIPCHK(hipEventRecord(h->ev_sync[4 + par], G));
+        if (ns >= 2) HIPCHK(hipEventRecord(h->ev_sync[4 + par], G));
     }
-    if (ns == 2 && (per_sec || constrained) && keep_mom) {   // the duration / probability copies ran on P
+    if (ns >= 2 && (per_sec || constrained) && keep_mom) {   // the duration / probability copies ran on P
         HIPCHK(hipEventRecord(h->ev_sync[0], P));
         HIPCHK(hipStreamWaitEvent(G, h->ev_sync[0], 0));
     }
@@ -1783,6 +1885,9 @@ int spx_get_stat(spx_handle* h, const char* name, int64_t* value)
     else if (!strcmp(name, "obs_dims")) *value = h->have_obs ? h->D : 0;   // D of the resident observations (0: none)
     else if (!strcmp(name, "last_step_fused")) *value = h->last_fused ? 1 : 0; // the last EI pass ran k_ei_fused128
     else if (!strcmp(name, "last_step_skipped_padding")) *value = h->last_skip_pad ? 1 : 0;   // ... skipped the padding of N (k_predict_gemm_tail)
+    else if (!strcmp(name, "last_corun_launches")) *value = h->corun_launches;   // K(X*,X) launches of the last EI pass in the co-resident form (k_cov_corun)
+    else if (!strcmp(name, "last_kstar_ring")) *value = h->ring_used;   // slots of the K(X*,X) ring the last EI pass ran with (0: not a streams = 3 pass)
+    else if (!strcmp(name, "gemm_lds_bytes")) *value = (int64_t)predict_gemm_lds_bytes();   // dynamic LDS of a predict-GEMM workgroup (two are resident per CU)
     else if (!strcmp(name, "hip_runtime_version") || !strcmp(name, "hip_driver_version")) {
         // what the process runs on: a measurement names it (bench.py's line), two boxes of one pool differed in round 5
         int v = 0;

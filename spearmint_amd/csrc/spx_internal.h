@@ -86,6 +86,10 @@ struct PinBuf {
     void release() { if (p) (void)hipHostFree(p); p = nullptr; cap = 0; }
 };
 
+#ifndef SPX_DEFAULT_CORUN
+#define SPX_DEFAULT_CORUN -1          // option "kstar_corun" of a new handle (make DEFAULT_CORUN=0: the attribution build, for
+#endif                                // callers such as bench.py that set "streams" but not this option)
+
 enum Stage {
     ST_SCALE = 0, ST_COV_SELF, ST_CHOL_DIAG, ST_CHOL_PANEL, ST_TRINV, ST_GAMMA_ALPHA,
     ST_COV_CROSS, ST_CROSS_MEAN, ST_PREDICT_GEMM, ST_EI_FINALIZE, ST_MEAN_ARGMAX,
@@ -98,6 +102,17 @@ struct spx_handle {
     hipStream_t stream2 = nullptr;   // optional producer stream (option "streams" = 2): K(X*,X) of the next
                                      // work item is generated (VALU) while the GEMM of the current one runs (MFMA)
     hipEvent_t ev_sync[6] = {nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};
+    // option "streams" = 3: K(X*,X) runs AHEAD of the predict GEMM on a low-priority stream of its own, through a ring of
+    // staging slots (ei_run_impl); the stream, the slots and their events are made on the first such pass
+    hipStream_t stream3 = nullptr;
+    struct RingSlot { DevBuf Kst, part_bgS; hipEvent_t ready = nullptr, consumed = nullptr; };
+    std::vector<RingSlot> ring;
+    int ring_opt = 0;                   // option "kstar_ring": slots of the ring (0 = from ring_budget)
+    int corun_opt = SPX_DEFAULT_CORUN;                 // option "kstar_corun": the producer's launches beside a GEMM use k_cov_corun 1 / 0 / -1 = default (on)
+    int64_t ring_budget = 0;            // bytes the ring may take (a share of free device memory) ...
+    int64_t ring_budget_slot = -1;      // ... as found when the size of a slot last changed
+    int ring_used = 0;                  // slots of the last streams = 3 pass (spx_get_stat "last_kstar_ring")
+    int corun_launches = 0;             // K(X*,X) launches of the last pass that took k_cov_corun (spx_get_stat "last_corun_launches")
     hipEvent_t ev_t0 = nullptr, ev_t1 = nullptr;   // whole-stage timers (factor / ei_run)
     hipEvent_t ev_fac = nullptr;                   // spx_ei_step: the whole factorisation (alpha included) is done (stream)
     hipEvent_t ev_obs = nullptr, ev_p0 = nullptr;  // spx_ei_step: observations scaled (stream) / first K(X*,X) ready (stream2)
