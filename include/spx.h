@@ -373,6 +373,9 @@ int spx_get_timings(spx_handle* h, double* ms, int64_t* launches, int n);
  *   "flow_rearms"      times the handle went back to the one-launch form after a fallback;
  *   "flow_enabled"     1 while the one-launch factorisation is in use;   "n_cu"  compute units of the device;
  *   "last_step_fused"  1 if the last EI pass ran as a one-kernel form (no K* / beta in memory; no fantasies);
+ *   "last_factor_flow" 1 if the last factorisation (spx_factor, spx_ei_step, spx_gp_logprob) was the one data-flow launch;
+ *   "last_factor_cov_in_flow"  1 if that launch built the tiles of K(X,X) itself (option "lean_flow_cov"), 0 if k_cov wrote them;
+ *   "last_logprob_one_launch"  1 if the last spx_gp_logprob ran as ONE launch (option "lean_one");
  *   "last_step_skipped_padding"  1 if the last EI pass left the padding of N (to the GEMM's 128-row tiles) uncomputed
  *                      (option "gemm_partial", default on: same bits, up to -31 % per pass just above a multiple of 128);
  *   "last_kstar_ring"  staging slots of the K(X*,X) ring the last EI pass ran with (option "streams" = 3; 0: it ran another way);
@@ -425,6 +428,9 @@ const char* spx_timing_name(int i);
  *   "gemm_partial"      N not a multiple of 128: the last 128-row block of the predict GEMM computes only the 16-row tiles
  *                       that hold observations (k_predict_gemm_tail) and K(X*,X) does not write the pad rows (1, default,
  *                       where it saves at least 12 % of the pass), or everything is computed on the padded size (0);
+ *   "cov_flat"          K(X*,X) launches of several residency rounds deal their work out in equal contiguous shares
+ *                       (k_cov_flat; 1, default) or run as the 3-D grid (0); the same bits.  Holds for the launches of an EI
+ *                       pass and for spx_get_cross_cov, so that the two forms can be compared element by element;
  *   "flow_rearm_after"  clean factorisations before the one-launch form is tried again (default 16, 0 = never);
  *   "flow_spin_limit"   polls a waiting workgroup makes before it gives up (0 = default, 2^20); tests set 1.
  * A kernel that is refused the dynamic LDS it asks for (hipFuncSetAttribute) makes the call fail with

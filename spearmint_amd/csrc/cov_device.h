@@ -17,6 +17,13 @@
 // no special-case selects: matern52_corr clamps r^2 into a range where they need none and
 // restores NaN / inf inputs with one fma at the end.  They work on W independent values in
 // lock step (every stage is a loop over W) so that consecutive instructions are independent.
+//
+// The "~1 ulp" of sqrt_pos and exp_neg and the "either way" of every clamp below are held by tests/test_gpu_q_cov_yardstick.py
+// against a 50-digit reference on inputs whose r^2 is exact (tests/cov_mp.py), through every kernel that includes this file:
+// with u = (1 + s) 2^-52 k + poly 2^-1074 (s = sqrt5 r, sqrt3 r or 0) the budget of the roundings listed here is 3 u for the
+// Matern kinds and 2 u for ARDSE; measured on an MI355X, the worst element of K(X*,X) against the reference rounded to float64
+// is 1.00 u (Matern52), 0.99 u (Matern32), 0.97 u (ARDSE) -- numpy's own on the same data: 1.03 / 0.92 / 0.52 u -- denormal
+// results and both sides of each clamp included (the test's docstring has K, the factor's first column and func_m).
 
 // sqrt(x) for x in [1e-300, 1e300], ~1 ulp: v_rsq_f64 seed + two coupled Newton steps.
 template <int W>

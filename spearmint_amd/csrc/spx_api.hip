@@ -682,6 +682,7 @@ static int do_factor(spx_handle* h, bool tolerate_not_pd, bool lean = false, boo
     // k_lean_flow builds the tiles of K(X,X) itself, where they are consumed: -1 ... -8 % per call at every size (no k_cov
     // launch, no round trip of the matrix through memory; option lean_flow_cov, scripts/dev/lean_option_ab.py)
     const bool cov_in_flow = flow && h->lean_flow_cov != 0;
+    h->cov_in_flow_ran = cov_in_flow;
     if (!cov_in_flow)
         TIMED(ST_COV_SELF, launch_cov_self(s, h->Xs.d(), h->s1.d(), h->X2s.d(), h->htab.d(), h->Lm.d(), (int)N, Np, Dp, nh, tiled, dev_kind(h)));
     // Trailing updates two block columns at a time (k_lean_step2) halve the traffic of the trailing matrices but
@@ -1488,7 +1489,8 @@ int spx_get_cross_cov(spx_handle* h, int32_t draw, int64_t c0, int64_t nc, doubl
     launch_scale_rows(s, h->cand.d() + (size_t)c0 * D, nc, mc, D, Dp, h->hyp.d() + 3 + (size_t)draw * hs, hs, 1, 2.0,
                       cs.d(), s2.d());
     launch_cov_cross(s, h->Xs.d() + (size_t)draw * Np * Dp, h->s1.d() + (size_t)draw * Np, cs.d(), s2.d(),
-                     h->htab.d() + (size_t)draw * SPX_HT, kst.d(), (int)h->N, Np, mc, Dp, 1, dev_kind(h));
+                     h->htab.d() + (size_t)draw * SPX_HT, kst.d(), (int)h->N, Np, mc, Dp, 1, dev_kind(h), 0,
+                     h->cov_flat != 0);   // (option cov_flat holds here as in the EI pass: the two forms can be compared element by element)
     hipError_t e = hipStreamSynchronize(s);
     if (e == hipSuccess)
         e = hipMemcpy2D(out, (size_t)nc * 8, kst.p, (size_t)mc * 8, (size_t)nc * 8, (size_t)h->N, hipMemcpyDeviceToHost);
@@ -1884,6 +1886,9 @@ int spx_get_stat(spx_handle* h, const char* name, int64_t* value)
     else if (!strcmp(name, "n_cu")) *value = h->n_cu;
     else if (!strcmp(name, "obs_dims")) *value = h->have_obs ? h->D : 0;   // D of the resident observations (0: none)
     else if (!strcmp(name, "last_step_fused")) *value = h->last_fused ? 1 : 0; // the last EI pass ran k_ei_fused128
+    else if (!strcmp(name, "last_factor_flow")) *value = h->flow_used ? 1 : 0;             // the last factorisation ran k_lean_flow
+    else if (!strcmp(name, "last_factor_cov_in_flow")) *value = h->cov_in_flow_ran ? 1 : 0;   // ... which built K(X,X) tile by tile itself
+    else if (!strcmp(name, "last_logprob_one_launch")) *value = h->fused_ran ? 1 : 0;      // the last do_factor was the one-launch log-likelihood
     else if (!strcmp(name, "last_step_skipped_padding")) *value = h->last_skip_pad ? 1 : 0;   // ... skipped the padding of N (k_predict_gemm_tail)
     else if (!strcmp(name, "last_corun_launches")) *value = h->corun_launches;   // K(X*,X) launches of the last EI pass in the co-resident form (k_cov_corun)
     else if (!strcmp(name, "last_kstar_ring")) *value = h->ring_used;   // slots of the K(X*,X) ring the last EI pass ran with (0: not a streams = 3 pass)

@@ -142,6 +142,7 @@ struct spx_handle {
     double* fused_lp = nullptr;         // (spx_gp_logprob -> do_factor: pinned destinations of the fused form's results)
     int* fused_info = nullptr;
     bool fused_ran = false;             // the last do_factor took the fused form
+    bool cov_in_flow_ran = false;       // the last do_factor's k_lean_flow built the tiles of K(X,X) itself
     const void* info_clean_ptr = nullptr;   // the not-PD flags at this address ...
     size_t info_clean_bytes = 0;            // ... in a buffer of this size are all zero (left so by the fused launch)
     int cov_flat = -1;                  // option "cov_flat": k_cov_flat for multi-round K(X*,X) launches 1 / 0 / -1 = default (on)

@@ -598,7 +598,8 @@ class Engine(object):
         return msg if msg.startswith("warning:") else "warning: the data-flow factorisation fell back (%d so far)" % n
 
     def stat(self, name):
-        """A counter of the handle: "flow_fallbacks", "flow_rearms", "flow_enabled", "n_cu", "last_step_fused", "ranks_seen" (include/spx.h: spx_get_stat)."""
+        """A counter of the handle: "flow_fallbacks", "flow_rearms", "flow_enabled", "n_cu", "last_step_fused", "last_factor_flow", "last_factor_cov_in_flow",
+        "last_logprob_one_launch", "ranks_seen" (include/spx.h: spx_get_stat)."""
         v = ctypes.c_int64(0)
         self._check(self._lib.spx_get_stat(self._h, name.encode("ascii"), ctypes.byref(v)))
         return int(v.value)

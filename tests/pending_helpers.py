@@ -16,7 +16,8 @@ from tests import refine_mp as rm
 
 FLAG_PER_SEC, FLAG_KEEP_MOMENTS, FLAG_TIME_ONLY = 1, 2, 8
 OPTION_DEFAULTS = {"kstar_budget_bytes": 0, "streams": 1, "step_overlap": -1, "ei_fused": -1, "gemm_partial": -1,
-                   "timing": 0, "cov_flat": -1, "ei_flow": -1, "stage_copies": -1, "gemm_waves": 0}
+                   "timing": 0, "cov_flat": -1, "ei_flow": -1, "stage_copies": -1, "gemm_waves": 0,
+                   "kstar_corun": -1, "lean_flow_cov": -1, "lean_one": -1}
 
 
 @contextlib.contextmanager
