@@ -12,23 +12,13 @@ typedef double d2 __attribute__((ext_vector_type(2)));
 //   C/D: reg r of lane l is element [row = (l >> 4) + 4 r][col = l & 15]
 #define MFMA_F64(a, b, c) __builtin_amdgcn_mfma_f64_16x16x4f64((a), (b), (c), 0, 0, 0)
 
-// geometry shared by host and device code
-#define SPX_NB 64        // Cholesky / inverse block size
-#define SPX_BM 128       // predict GEMM: rows (observations) per workgroup tile
-#define SPX_BN 128       // predict GEMM: candidates per workgroup tile
-#define SPX_BK 16        // predict GEMM: contraction depth per LDS stage
-#define SPX_PADN 128     // observations are padded to a multiple of this
+#include "spx_geom.h"   // SPX_NB, SPX_BM, SPX_BN, SPX_BK, SPX_PADN, SPX_HT, round_up, padded_dim
 
 // correlation function of the GP (gp.py:87-132; spx.h SPX_COVAR_*).  SE is ARDSE with unit length scales
 // (gp.py:88): the API layer substitutes the length scales, the kernels see ARDSE.
 #define SPX_COV_MATERN52 0
 #define SPX_COV_MATERN32 1
 #define SPX_COV_ARDSE 2
-
-// device hyper table row: [mean, noise, amp2, amp2*(1+1e-6)]
-#define SPX_HT 4
-
-static inline int64_t round_up(int64_t x, int64_t m) { return (x + m - 1) / m * m; }
 
 // The launchers below return nothing: a kernel that needs more dynamic LDS than the default asks for it right before its
 // launch, and a refusal is NOTED (per host thread, spx_api.hip) and reported by the API's next launch check (LAUNCHCHK) as
@@ -157,7 +147,6 @@ void launch_predict_gemm(hipStream_t s, int variant, const double* WT, const dou
                          const double* gammaS = nullptr, int S = 0, double* part_bgS = nullptr, int nlive = 0);
 bool predict_gemm_variant_ok(int v);
 size_t predict_gemm_lds_bytes();        // dynamic LDS of one predict-GEMM workgroup
-int predict_gemm_padding_plan(int variant, int N, int Np);
 void launch_ei_finalize_fant(hipStream_t s, const double* part_ss, const double* part_bgS,
                              const double* htab, const double* bests, const double* time_m, const double* cprob,
                              double* ei_draw, int nrb, int Mc, int nh, int S, int64_t c0, int64_t M,

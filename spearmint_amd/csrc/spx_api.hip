@@ -111,7 +111,7 @@ static void ring_trim(spx_handle* h, int keep)
 
 static int ev_begin(spx_handle* h, int stage, hipStream_t strm)
 {
-    if (!h->timing) return -1;
+    if (!h->opt.timing) return -1;
     if (h->ev_used == h->ev_pool.size()) {
         spx_handle::Ev e;
         if (hipEventCreate(&e.a) != hipSuccess || hipEventCreate(&e.b) != hipSuccess) return -1;
@@ -147,16 +147,88 @@ static void ev_collect(spx_handle* h)
 
 int spx_ensure_init(spx_handle* h) { return ensure_init(h); }
 
-static int padded_dim(int D)
+// kernel-level correlation kind of a handle: SE runs as ARDSE on unit length scales (do_factor substitutes them)
+static inline int dev_kind(const spx_handle* h) { return h->opt.cov_kind == SPX_COVAR_SE ? SPX_COV_ARDSE : h->opt.cov_kind; }
+// the EI path's factor is tile-major (k_lean_flow made it) -- false again once a log-likelihood call has overwritten it
+static inline bool factor_tiled(const spx_handle* h) { return !h->last_factor->lean && h->last_factor->flow; }
+
+// ---- options: one table.  The tri-state and clamped-integer kinds are served by it, the others by the handlers above it ----
+static int opt_kstar_budget(spx_handle* h, int64_t value)
 {
-    if (D <= 4) return 4;
-    if (D <= 8) return 8;
-    if (D <= 16) return 16;
-    return (int)round_up(D, 32);
+    h->opt.kst_budget = value > 0 ? value : (512ll << 20);
+    return SPX_OK;
+}
+static int opt_gemm_waves(spx_handle* h, int64_t value)
+{
+    if (!predict_gemm_variant_ok((int)value))
+        return fail(SPX_ERR_ARG, "spx_set_option: gemm_waves=%lld is not a variant of this build", (long long)value);
+    h->opt.gemm_variant = (int)value;
+    return SPX_OK;
+}
+static int opt_covar(spx_handle* h, int64_t value)
+{
+    if (value < SPX_COVAR_MATERN52 || value > SPX_COVAR_SE)
+        return fail(SPX_ERR_ARG, "spx_set_option: covar=%lld is not one of SPX_COVAR_*", (long long)value);
+    if (h->opt.cov_kind != (int)value) { h->factored = false; h->ran = false; h->ran_time = false; h->S = 0; h->full_valid = false; }
+    h->opt.cov_kind = (int)value;
+    return SPX_OK;
+}
+static int opt_lean_flow(spx_handle* h, int64_t value)
+{
+    h->opt.lean_flow = value < 0 ? -1 : (value != 0);
+    h->flow_demoted = false;        // asking again re-arms a handle that a hand-off time-out had sent to the launches
+    h->flow_clean = 0;
+    return SPX_OK;
+}
+static int opt_streams(spx_handle* h, int64_t value)
+{
+    h->opt.nstreams = (value == 2 || value == 3) ? (int)value : 1;
+    return SPX_OK;
+}
+static int opt_timing(spx_handle* h, int64_t value)
+{
+    h->opt.timing = value != 0;
+    memset(h->st_ms, 0, sizeof h->st_ms);
+    memset(h->st_n, 0, sizeof h->st_n);
+    return SPX_OK;
 }
 
-// kernel-level correlation kind of a handle: SE runs as ARDSE on unit length scales (do_factor substitutes them)
-static inline int dev_kind(const spx_handle* h) { return h->cov_kind == SPX_COVAR_SE ? SPX_COV_ARDSE : h->cov_kind; }
+struct OptRow {
+    const char* name;
+    int Options::* member;                  // tri-state: value < 0 ? -1 : (value != 0) ...
+    int neg, max;                           // ... or, max > 0, a clamped integer: value < 0 ? neg : min(value, max)
+    int (*call)(spx_handle*, int64_t);      // ... or a handler
+};
+#define OPT_TRI(name, member) {name, &Options::member, 0, 0, nullptr}
+#define OPT_CLAMP(name, member, neg, max) {name, &Options::member, neg, max, nullptr}
+#define OPT_CALL(name, fn) {name, nullptr, 0, 0, fn}
+static const OptRow kOptions[] = {
+    OPT_CALL("kstar_budget_bytes", opt_kstar_budget),   // K(X*,X) staging buffer per stream (0 = default, 512 MiB)
+    OPT_CALL("gemm_waves", opt_gemm_waves),             // predict-GEMM variant of this handle (predict_kernels.hip)
+    OPT_CALL("covar", opt_covar),                       // SPX_COVAR_*: the reference's covar= (gp.py:87-132)
+    OPT_TRI("lean_lazy", lean_lazy),                    // log-likelihood path: trailing updates two steps at a time (1), one (0), by size (-1, default)
+    OPT_TRI("step_overlap", step_overlap),              // spx_ei_step: candidate scaling + first K(X*,X) on the second stream beside the factorisation (1, default) or behind it (0)
+    OPT_TRI("ei_fused", ei_fused),                      // N <= 128, no fantasies: K* -> beta -> EI of a chunk in one kernel (1, default) or the general three-stage path (0)
+    OPT_TRI("ei_flow", ei_flow),                        // spx_factor through k_lean_flow (1, default), the left-looking launches (0)
+    OPT_TRI("lean_flow_cov", lean_flow_cov),            // k_lean_flow builds K(X,X) tile by tile itself (1, default) or reads k_cov's (0)
+    OPT_TRI("lean_flow_yield", lean_flow_yield),        // k_lean_flow, two workgroups per CU: yield to a neighbour's diagonal block (1, default) or not (0)
+    OPT_TRI("lean_flow_cu", lean_flow_cu),              // k_lean_flow: one workgroup per CU (1), two (0), by size (-1, default)
+    OPT_CALL("lean_flow", opt_lean_flow),               // log-likelihood path: the whole factorisation as ONE data-flow launch (1, default), one launch per block column (0)
+    OPT_CLAMP("flow_rearm_after", flow_rearm_after, 16, 1 << 30),   // clean factorisations after a hand-off time-out before k_lean_flow is tried again (default 16; 0 = never)
+    OPT_CLAMP("flow_spin_limit", flow_spin_limit, 0, 1 << 30),      // polls a k_lean_flow workgroup waits for a hand-off before it gives up (0 = default, 2^20); tests set 1 to see a time-out
+    OPT_TRI("lean_ps", lean_ps),                        // log-likelihood path: panel solve pipelined inside the step launch (1, default), separate launch (0)
+    OPT_TRI("lean_merge", lean_merge),                  // log-likelihood path: observation scaling and the right-hand-side rows in one launch (1, default) or two (0)
+    OPT_TRI("lean_one", lean_one),                      // spx_gp_logprob as one launch (1, default) or prologue + k_lean_flow + reduction (0): same bits
+    OPT_TRI("lean_poll", lean_poll),                    // the one-launch call's results are awaited by polling their pinned flags (1, default) instead of hipStreamSynchronize (0)
+    OPT_TRI("lean_zc", lean_zc),                        // the one-launch call reads the hyper rows from the pinned staging buffer itself (1, default) instead of behind a host-to-device copy (0)
+    OPT_TRI("stage_copies", stage_copies),              // callers' small host buffers through the handle's page-locked staging buffer (1, default) or handed to the runtime as they are (0)
+    OPT_TRI("cov_flat", cov_flat),                      // K(X*,X) launches of several residency rounds: equal contiguous shares (k_cov_flat; 1, default) or the 3-D grid (0)
+    OPT_TRI("gemm_partial", gemm_partial),              // N not a multiple of 128: skip the padding's K steps / row tiles / K* rows (1, default) or compute them (0)
+    OPT_CALL("streams", opt_streams),                   // 1 = everything on one stream (default), 2 = alternate EI work items, 3 = K(X*,X) ahead of the GEMM through a ring
+    OPT_CLAMP("kstar_ring", ring_opt, 0, 4096),         // streams = 3: staging slots of the ring (0, default: as many as the byte budget holds)
+    OPT_TRI("kstar_corun", corun_opt),                  // streams = 3: K(X*,X) launches beside a GEMM in the form that fits there (1, default) or as k_cov_flat (0); same bits
+    OPT_CALL("timing", opt_timing),                     // per-launch HIP events on the handle's stream; (re)starts the accumulators
+};
 
 extern "C" {
 
@@ -232,107 +304,10 @@ int spx_set_option(spx_handle* h, const char* name, int64_t value)
 {
     if (!h || !name) return fail(SPX_ERR_ARG, "spx_set_option: null");
     if (h->multi) return spx_multi_set_option(h->multi, name, value);
-    if (!strcmp(name, "kstar_budget_bytes")) {
-        h->kst_budget = value > 0 ? value : (512ll << 20);
-        return SPX_OK;
-    }
-    if (!strcmp(name, "gemm_waves")) {   // predict-GEMM variant of this handle (predict_kernels.hip)
-        if (!predict_gemm_variant_ok((int)value))
-            return fail(SPX_ERR_ARG, "spx_set_option: gemm_waves=%lld is not a variant of this build", (long long)value);
-        h->gemm_variant = (int)value;
-        return SPX_OK;
-    }
-    if (!strcmp(name, "covar")) {   // SPX_COVAR_*: the reference's covar= (gp.py:87-132)
-        if (value < SPX_COVAR_MATERN52 || value > SPX_COVAR_SE)
-            return fail(SPX_ERR_ARG, "spx_set_option: covar=%lld is not one of SPX_COVAR_*", (long long)value);
-        if (h->cov_kind != (int)value) { h->factored = false; h->ran = false; h->ran_time = false; h->S = 0; h->full_valid = false; }
-        h->cov_kind = (int)value;
-        return SPX_OK;
-    }
-    if (!strcmp(name, "lean_lazy")) {   // log-likelihood path: trailing updates two steps at a time (1), one (0), by size (-1, default)
-        h->lean_lazy = value < 0 ? -1 : (value != 0);
-        return SPX_OK;
-    }
-    if (!strcmp(name, "step_overlap")) {   // spx_ei_step: candidate scaling + first K(X*,X) on the second stream beside the factorisation (1, default) or behind it (0)
-        h->step_overlap = value < 0 ? -1 : (value != 0);
-        return SPX_OK;
-    }
-    if (!strcmp(name, "ei_fused")) {       // N <= 128, no fantasies: K* -> beta -> EI of a chunk in one kernel (1, default) or the general three-stage path (0)
-        h->ei_fused = value < 0 ? -1 : (value != 0);
-        return SPX_OK;
-    }
-    if (!strcmp(name, "ei_flow")) {        // spx_factor through k_lean_flow (1, default), the left-looking launches (0)
-        h->ei_flow = value < 0 ? -1 : (value != 0);
-        return SPX_OK;
-    }
-    if (!strcmp(name, "lean_flow_cov")) {  // k_lean_flow builds K(X,X) tile by tile itself (1, default) or reads k_cov's (0)
-        h->lean_flow_cov = value < 0 ? -1 : (value != 0);
-        return SPX_OK;
-    }
-    if (!strcmp(name, "lean_flow_yield")) {   // k_lean_flow, two workgroups per CU: yield to a neighbour's diagonal block (1, default) or not (0)
-        h->lean_flow_yield = value < 0 ? -1 : (value != 0);
-        return SPX_OK;
-    }
-    if (!strcmp(name, "lean_flow_cu")) {   // k_lean_flow: one workgroup per CU (1), two (0), by size (-1, default)
-        h->lean_flow_cu = value < 0 ? -1 : (value != 0);
-        return SPX_OK;
-    }
-    if (!strcmp(name, "lean_flow")) {   // log-likelihood path: the whole factorisation as ONE data-flow launch (1, default), one launch per block column (0)
-        h->lean_flow = value < 0 ? -1 : (value != 0);
-        h->flow_demoted = false;        // asking again re-arms a handle that a hand-off time-out had sent to the launches
-        h->flow_clean = 0;
-        return SPX_OK;
-    }
-    if (!strcmp(name, "flow_rearm_after")) {   // clean factorisations after a hand-off time-out before k_lean_flow is tried again (default 16; 0 = never)
-        h->flow_rearm_after = value < 0 ? 16 : (int)std::min<int64_t>(value, 1 << 30);
-        return SPX_OK;
-    }
-    if (!strcmp(name, "flow_spin_limit")) {    // polls a k_lean_flow workgroup waits for a hand-off before it gives up (0 = default, 2^20); tests set 1 to see a time-out
-        h->flow_spin_limit = value <= 0 ? 0 : (int)std::min<int64_t>(value, 1 << 30);
-        return SPX_OK;
-    }
-    if (!strcmp(name, "lean_ps")) {     // log-likelihood path: panel solve pipelined inside the step launch (1, default), separate launch (0)
-        h->lean_ps = value < 0 ? -1 : (value != 0);
-        return SPX_OK;
-    }
-    if (!strcmp(name, "lean_merge")) {     // log-likelihood path: observation scaling and the right-hand-side rows in one launch (1, default) or two (0)
-        h->lean_merge = value < 0 ? -1 : (value != 0);
-        return SPX_OK;
-    }
-    if (!strcmp(name, "lean_one")) {       // spx_gp_logprob as one launch (1, default) or prologue + k_lean_flow + reduction (0): same bits
-        h->lean_one = value < 0 ? -1 : (value != 0);
-        return SPX_OK;
-    }
-    if (!strcmp(name, "lean_poll")) { h->lean_poll = value < 0 ? -1 : (value != 0); return SPX_OK; }   // (spx_internal.h)
-    if (!strcmp(name, "lean_zc")) { h->lean_zc = value < 0 ? -1 : (value != 0); return SPX_OK; }
-    if (!strcmp(name, "stage_copies")) {   // callers' small host buffers through the handle's page-locked staging buffer (1, default) or handed to the runtime as they are (0)
-        h->stage_copies = value < 0 ? -1 : (value != 0);
-        return SPX_OK;
-    }
-    if (!strcmp(name, "cov_flat")) {       // K(X*,X) launches of several residency rounds: equal contiguous shares (k_cov_flat; 1, default) or the 3-D grid (0)
-        h->cov_flat = value < 0 ? -1 : (value != 0);
-        return SPX_OK;
-    }
-    if (!strcmp(name, "gemm_partial")) {   // N not a multiple of 128: skip the padding's K steps / row tiles / K* rows (1, default) or compute them (0)
-        h->gemm_partial = value < 0 ? -1 : (value != 0);
-        return SPX_OK;
-    }
-    if (!strcmp(name, "streams")) {  // 1 = everything on one stream (default), 2 = alternate EI work items, 3 = K(X*,X) ahead of the GEMM through a ring
-        h->nstreams = (value == 2 || value == 3) ? (int)value : 1;
-        return SPX_OK;
-    }
-    if (!strcmp(name, "kstar_ring")) {   // streams = 3: staging slots of the ring (0, default: as many as the byte budget holds)
-        h->ring_opt = value <= 0 ? 0 : (int)std::min<int64_t>(value, 4096);
-        return SPX_OK;
-    }
-    if (!strcmp(name, "kstar_corun")) {  // streams = 3: K(X*,X) launches beside a GEMM in the form that fits there (1, default) or as k_cov_flat (0); same bits
-        h->corun_opt = value < 0 ? -1 : (value != 0);
-        return SPX_OK;
-    }
-    if (!strcmp(name, "timing")) {  // per-launch HIP events on the handle's stream; (re)starts the accumulators
-        h->timing = value != 0;
-        memset(h->st_ms, 0, sizeof h->st_ms);
-        memset(h->st_n, 0, sizeof h->st_n);
+    for (const OptRow& r : kOptions) {
+        if (strcmp(name, r.name)) continue;
+        if (r.call) return r.call(h, value);
+        h->opt.*r.member = r.max ? (value < 0 ? r.neg : (int)std::min<int64_t>(value, r.max)) : (value < 0 ? -1 : (value != 0));
         return SPX_OK;
     }
     return fail(SPX_ERR_ARG, "spx_set_option: unknown option '%s'", name);
@@ -348,7 +323,7 @@ int spx_set_option(spx_handle* h, const char* name, int64_t value)
 static void stage_begin(spx_handle* h) { h->stage_off = 0; }
 static int stage_h2d(spx_handle* h, void* dst, const void* src, size_t bytes, hipStream_t s)
 {
-    if (h->stage_copies == 0 || bytes > SPX_STAGE_MAX || h->stage_off + bytes > 4 * (size_t)SPX_STAGE_MAX) {
+    if (h->opt.stage_copies == 0 || bytes > SPX_STAGE_MAX || h->stage_off + bytes > 4 * (size_t)SPX_STAGE_MAX) {
         HIPCHK(hipMemcpyAsync(dst, src, bytes, hipMemcpyHostToDevice, s));
         return SPX_OK;
     }
@@ -369,7 +344,7 @@ static int stage_h2d(spx_handle* h, void* dst, const void* src, size_t bytes, hi
 // device -> caller's buffer, complete on return (the stream is synchronised)
 static int stage_d2h(spx_handle* h, void* dst, const void* src, size_t bytes, hipStream_t s)
 {
-    if (h->stage_copies == 0 || bytes > SPX_STAGE_MAX) {
+    if (h->opt.stage_copies == 0 || bytes > SPX_STAGE_MAX) {
         HIPCHK(hipMemcpyAsync(dst, src, bytes, hipMemcpyDeviceToHost, s));
         HIPCHK(hipStreamSynchronize(s));
         return SPX_OK;
@@ -481,9 +456,9 @@ int spx_set_constraint_model(spx_handle* h, const double* comp_c, const double* 
     if (Nc > 0) {
         if (!h->con) {
             if ((rc = spx_create(h->device, &h->con))) return rc;
-            h->con->stage_copies = h->stage_copies;
+            h->con->opt.stage_copies = h->opt.stage_copies;
         }
-        h->con->cov_kind = h->cov_kind;
+        h->con->opt.cov_kind = h->opt.cov_kind;
         // the factor's rows: [0, noise_c, amp2_c, ls_c...] -- alpha_c = K_c^-1 (ff - 0): no mean term (:819-842)
         std::vector<double> rows(c_hypers, c_hypers + (size_t)H * hs);
         for (int i = 0; i < H; ++i) rows[(size_t)i * hs] = 0.0;
@@ -515,7 +490,7 @@ static int factor_constraint(spx_handle* h)
     spx_handle* c = h->con;
     // option "covar" changed since the last factorisation: alpha_c, the scaled rows and (SE) the unit length scales of the
     // internal handle belong to the old kernel
-    if (c->cov_kind != h->cov_kind) { c->cov_kind = h->cov_kind; c->factored = false; h->con_factored = false; }
+    if (c->opt.cov_kind != h->opt.cov_kind) { c->opt.cov_kind = h->opt.cov_kind; c->factored = false; h->con_factored = false; }
     if (h->con_factored) return SPX_OK;
     if (c->H != h->H || c->D != h->D)
         return fail(SPX_ERR_ARG, "spx_factor: the constraint model has H=%d, D=%d but the objective H=%d, D=%d "
@@ -551,10 +526,11 @@ static void warn_flow_fallback(spx_handle* h)
     char buf[320];
     snprintf(buf, sizeof buf, "warning: a hand-off inside the data-flow factorisation timed out (%lld so far on this handle); "
              "this call was repeated with one launch per block column (same results) and the handle stays there for %d "
-             "clean factorisations", (long long)h->flow_fallbacks, h->flow_rearm_after);
+             "clean factorisations", (long long)h->flow_fallbacks, h->opt.flow_rearm_after);
     spx_err_slot() = buf;
 }
 
+#define SPX_POLL_SENTINEL 0x7fffffff   // no not-PD flag has this value (pivots <= 2^20, time-outs < 0)
 // defer_sync (log-likelihood path): return with the work queued -- the caller adds its own kernel, copies `info` back
 // together with its result, synchronises ONCE and calls finish_factor (one host round trip per call instead of two)
 static int do_factor(spx_handle* h, bool tolerate_not_pd, bool lean = false, bool defer_sync = false)
@@ -563,19 +539,16 @@ static int do_factor(spx_handle* h, bool tolerate_not_pd, bool lean = false, boo
         return fail(SPX_ERR_ARG, "spx_factor: observations and hypers must be set first");
     int rc = ensure_init(h);
     if (rc) return rc;
-    // lean: objective GP only, Cholesky + forward solve, no W = L^-1 (log-likelihood path)
-    const int nm = (h->have_time && !lean) ? 2 : 1;
-    if (!lean) h->nmodels = nm;
-    const int H = h->H, nh = nm * H, D = h->D, Dp = h->Dp;
+    FactorShape sh;
+    sh.N = h->N; sh.D = h->D; sh.H = h->H; sh.Np = h->Np;
+    sh.have_time = h->have_time; sh.lean = lean; sh.defer_sync = defer_sync; sh.have_dest = h->fused_lp != nullptr;
+    sh.flow_demoted = h->flow_demoted; sh.rhs_rows_on = h->rhs_rows_on;
+    FactorPlan& p = lean ? h->lean_plan : h->factor_plan;
+    p = plan_factor(h->opt, sh);              // every decision of this call (spx_plan.h); below: reserve, upload, launch
+    h->last_factor = &p;
+    if (!lean) h->nmodels = p.nm;
+    const int nm = p.nm, H = h->H, nh = p.nh, D = h->D, Dp = p.Dp, Np = p.Np, nblk = p.nblk, hs = p.hs;
     const int64_t N = h->N;
-    // The EI path pads the observations to the predict GEMM's 128-row tiles.  The log-likelihood path (tile-major, up to
-    // 32 draws) only needs whole 64 x 64 blocks: N <= 64 is ONE diagonal block instead of two, N = 129 .. 192 three
-    // instead of four -- the padding block is an identity that costs a full link of the chain of diagonal blocks
-    // (~17 us of a 64 us call at N <= 64).  Same bits: padding rows never touch the others.
-    const int Np = (lean && nh <= 32) ? (int)round_up(N, SPX_NB) : h->Np;
-    if (lean) h->lean_np = Np;
-    const int nblk = Np / SPX_NB;
-    const int hs = 3 + D;
 
     // host-side hyper tables: raw rows (for ls) and [mean, noise, amp2, amp2*(1+1e-6)]
     // (members, not locals: the log-likelihood path returns before it synchronises, and the upload must not outlive its source)
@@ -588,7 +561,7 @@ static int do_factor(spx_handle* h, bool tolerate_not_pd, bool lean = false, boo
         for (int i = 0; i < H; ++i) {
             const double* r = &src[(size_t)i * hs];
             memcpy(&raw[((size_t)m * H + i) * hs], r, sizeof(double) * hs);
-            if (h->cov_kind == SPX_COVAR_SE)   // gp.SE ignores its length scales (gp.py:88)
+            if (h->opt.cov_kind == SPX_COVAR_SE)   // gp.SE ignores its length scales (gp.py:88)
                 for (int d = 0; d < D; ++d) raw[((size_t)m * H + i) * hs + 3 + d] = 1.0;
             double* t = &tab[((size_t)m * H + i) * SPX_HT];
             t[0] = r[0]; t[1] = r[1]; t[2] = r[2];
@@ -597,113 +570,53 @@ static int do_factor(spx_handle* h, bool tolerate_not_pd, bool lean = false, boo
     }
     // raw rows and the table travel in ONE upload: htab is a view of the tail of the hyp buffer
     raw.insert(raw.end(), tab.begin(), tab.end());
-    if ((rc = h->hyp.reserve(raw.size() * 8))) return rc;
+    if ((rc = h->hyp.reserve(p.hyp_doubles * 8))) return rc;
     h->htab.alias_of(h->hyp.d() + (size_t)nh * hs);
-    const size_t nn = (size_t)nh * Np * Np;
-    if ((rc = h->Xs.reserve((size_t)nh * Np * Dp * 8))) return rc;
-    if ((rc = h->X2s.reserve((size_t)nh * Np * Dp * 8))) return rc;
-    if ((rc = h->s1.reserve((size_t)nh * Np * 8))) return rc;
-    if ((rc = h->Lm.reserve(nn * 8))) return rc;
-    if (!lean && (rc = h->WT.reserve(nn * 8))) return rc;
-    if ((rc = h->Dinv.reserve((size_t)nh * nblk * SPX_NB * SPX_NB * 8))) return rc;
-    if ((rc = h->gamma.reserve((size_t)nh * Np * 8))) return rc;
-    if ((rc = h->alpha.reserve((size_t)nh * Np * 8))) return rc;
-    if ((rc = h->info.reserve((size_t)nh * sizeof(int)))) return rc;
+    if ((rc = h->Xs.reserve(p.xs_bytes))) return rc;
+    if ((rc = h->X2s.reserve(p.xs_bytes))) return rc;
+    if ((rc = h->s1.reserve(p.vec_bytes))) return rc;
+    if ((rc = h->Lm.reserve(p.nn_bytes))) return rc;
+    if (!lean && (rc = h->WT.reserve(p.nn_bytes))) return rc;
+    if ((rc = h->Dinv.reserve(p.dinv_bytes))) return rc;
+    if ((rc = h->gamma.reserve(p.vec_bytes))) return rc;
+    if ((rc = h->alpha.reserve(p.vec_bytes))) return rc;
+    if ((rc = h->info.reserve(p.info_bytes))) return rc;
 
     hipStream_t s = h->stream;
     h->ev_used = 0;
     hipEvent_t t0 = h->ev_t0, t1 = h->ev_t1;
     // through pinned memory: a pageable source makes the runtime stage the copy and wait for it (the stream is idle here:
     // every entry point that queues work on it synchronises before it returns, so the staging buffer is free)
-    if ((rc = h->pin_up.reserve(raw.size() * 8))) return rc;
-    memcpy(h->pin_up.p, raw.data(), raw.size() * 8);
-    // (the fused log-likelihood launch reads the rows out of the pinned buffer itself -- option lean_zc: one stream operation
-    // fewer in front of it; decided below, where `fused` is known: the copy is queued unless that form runs)
-    // (measured, profiles/r06_lean_one_ab.log: one launch instead of three is -11 us of 46 at N <= 64 with the polled
-    // completion and the zero-copy rows, -12 of 91 at N = 256, -2 ... -4 % up to N = 1024; at N = 2048 with several draws the
-    // items' own scaling costs more than the two launches did (+3 %), and with hundreds of items the reads of host memory do)
-    const bool fused_early = lean && nh <= 32 && h->lean_merge != 0 && h->lean_flow != 0 && !h->flow_demoted && h->lean_flow_cov != 0
-                             && h->lean_one != 0 && h->fused_lp != nullptr && Dp <= 64
-                             && (h->lean_one > 0 || nblk <= 16 || nh <= 2);
-    int fused_items = (nblk + 1) / 2;
-    for (int i = 0; i < nblk; ++i) fused_items += (i + 2) / 2;
-    const bool zero_copy = fused_early && h->lean_zc != 0 && !h->timing && (h->lean_zc > 0 || (int64_t)nh * fused_items <= 256);
-    if (!zero_copy) HIPCHK(hipMemcpyAsync(h->hyp.p, h->pin_up.p, raw.size() * 8, hipMemcpyHostToDevice, s));
-    if (h->timing || !lean) HIPCHK(hipEventRecord(t0, s));
-    // the log-likelihood path zeroes info (and the hand-off flags) in its right-hand-side kernel: two stream operations
-    // fewer per call
-    const bool zero_in_kernel = lean && nh <= 32;
-    // (otherwise k_scale_rows, the first kernel below, clears them)
+    if ((rc = h->pin_up.reserve(p.hyp_doubles * 8))) return rc;
+    memcpy(h->pin_up.p, raw.data(), p.hyp_doubles * 8);
+    if (p.poll) for (int k = 0; k < H; ++k) h->fused_info[k] = SPX_POLL_SENTINEL;   // (coherent pinned memory: in place before the launch is queued)
+    if (!p.zero_copy) HIPCHK(hipMemcpyAsync(h->hyp.p, h->pin_up.p, p.hyp_doubles * 8, hipMemcpyHostToDevice, s));
+    if (p.bracket) HIPCHK(hipEventRecord(t0, s));
     // (W^T's zeros above the diagonal blocks are written by k_trinv itself)
 
     const double* ls = h->hyp.d() + 3;
-    // The log-likelihood call is a chain of small dependent launches (~4 us each whatever they do): when nothing between
-    // them needs x / ls (k_lean_flow builds K(X,X) itself: the default), the scaling of the observations and the
-    // right-hand-side rows are ONE launch, further down where the right-hand side used to be written (option lean_merge).
-    const bool merged_prologue = lean && nh <= 32 && h->lean_merge != 0 && h->lean_flow != 0 && !h->flow_demoted && h->lean_flow_cov != 0;
-    // ... and since round 6 NO launch of their own (option lean_one): k_lean_flow's items scale the rows they need into LDS,
-    // generate the right-hand-side rows, and the last item of a draw reduces the log-likelihood into pinned host memory --
-    // the call is the upload of the hyper rows and ONE launch.  (Dp <= 64: a block's scaled rows fit the kernel's LDS tile.)
-    const bool fused = fused_early;
-    h->fused_ran = fused;
     // the not-PD flags: zeroed once per allocation; the fused launch leaves them zero.  (Address AND size: a buffer that grew may
     // come back at the address the smaller one had -- its new words are not the zeros the old ones were.)
-    if (fused && (h->info_clean_ptr != h->info.p || h->info_clean_bytes != h->info.cap)) {
+    if (p.fused && (h->info_clean_ptr != h->info.p || h->info_clean_bytes != h->info.cap)) {
         HIPCHK(hipMemsetAsync(h->info.p, 0, h->info.cap, s));
         h->info_clean_ptr = h->info.p;
         h->info_clean_bytes = h->info.cap;
     }
-    if (!fused) h->info_clean_ptr = nullptr;
+    if (!p.fused) h->info_clean_ptr = nullptr;
     // x / ls and, in the same launch, the second operand pre-multiplied by 2 (gp.py:50; exact)
-    if (!merged_prologue)
+    if (!p.merged_prologue)
         TIMED(ST_SCALE, launch_scale_rows(s, h->comp.d(), N, Np, D, Dp, ls, hs, nh, 1.0, h->Xs.d(), h->s1.d(), h->X2s.d(),
-                                          zero_in_kernel ? nullptr : (int*)h->info.p, nh));
+                                          p.zero_in_kernel ? nullptr : (int*)h->info.p, nh));
     // (spx_ei_step: the candidate side of the EI pass needs x / ls and the hyper table, not the factor -- it starts here,
     // on the second stream, beside the factorisation)
-    if (defer_sync && !lean) HIPCHK(hipEventRecord(h->ev_obs, s));
-    // The factorisation, blocked with 64x64 tiles; three generations, the same factor bit for bit (every tile receives its
-    // update steps in the order 0, 1, 2, ..., through the same MFMA chains, and the diagonal blocks share diag_block):
-    //   flow  k_lean_flow: ONE data-flow launch for all block columns of all draws, tile-major storage (the default);
-    //   rl    the log-likelihood path's one-step-deep launches per block column, tile-major (k_lean_step_ps, or
-    //         k_lean_step [+ k_lean_step2] + k_lean_trsm), up to 32 draws -- the fallback of `flow` there;
-    //   else  the batched left-looking launches of the EI path, row-major (k_chol_diag + k_chol_panel) -- the fallback of
-    //         `flow` for spx_factor, and the log-likelihood path beyond 32 draws.
-    const int rl = (lean && nh <= 32) ? 1 : 0;   // beyond ~40 draws the one-step launches are work-bound and lose
-    // The EI path (spx_factor) takes the data-flow launch too (option ei_flow, default on; measured against the left-looking
-    // launches: factor stage 0.28 -> 0.19 ms at N = 256 x 10 draws, 6.3 -> 3.8 ms at 2048 x 20, 2.3 -> 1.5 ms at
-    // 1024 x 40, 0.85 -> 0.61 ms at 512 x 60): no right-hand-side rows, the diagonal blocks of L kept for spx_get_factor,
-    // W = L^-1 from the tile-major factor (k_trinv<true>); every EI result stays what it was.
-    const int eflow = (!lean && h->ei_flow != 0) ? 1 : 0;
-    const int flow = ((rl || eflow) && h->lean_flow != 0 && !h->flow_demoted) ? 1 : 0;
-    const bool tiled = rl || flow;
-    // (how busy the launch will be: draws x block columns^1.5 -- the residency rule below was read off scripts/dev/flow_modes.py)
-    const double flow_load = (double)nh * nblk * sqrt((double)nblk);
-    const bool flow_alone = h->lean_flow_cu >= 0 ? h->lean_flow_cu != 0 : flow_load <= 800.0;
-    // k_lean_flow builds the tiles of K(X,X) itself, where they are consumed: -1 ... -8 % per call at every size (no k_cov
-    // launch, no round trip of the matrix through memory; option lean_flow_cov, scripts/dev/lean_option_ab.py)
-    const bool cov_in_flow = flow && h->lean_flow_cov != 0;
-    h->cov_in_flow_ran = cov_in_flow;
-    if (!cov_in_flow)
-        TIMED(ST_COV_SELF, launch_cov_self(s, h->Xs.d(), h->s1.d(), h->X2s.d(), h->htab.d(), h->Lm.d(), (int)N, Np, Dp, nh, tiled, dev_kind(h)));
-    // Trailing updates two block columns at a time (k_lean_step2) halve the traffic of the trailing matrices but
-    // put a second MFMA step in front of every other diagonal block; that pays once the lower triangles of the
-    // batch no longer fit the 256 MB Infinity Cache (measured: N=2048 from ~20 draws, N=4096 from 6; -3 ... -16 %),
-    // and costs 5-10 % below that.  Same factor either way, bit for bit.
-    const int lazy = h->lean_lazy >= 0 ? h->lean_lazy : ((double)nh * Np * Np * 4.0 > 300e6 ? 1 : 0);
-    // Panel solve inside the step launch, pipelined behind the diagonal block's pivots (k_lean_step_ps): option lean_ps
-    // (measured against a launch of its own per panel solve, scripts/dev/lean_option_ab.py: -1 ... -8 % per call from N = 256
-    // up -- 2048: -6.5 % at 4-12 draws, -1 % at one; 1000: -3 ... -13 %; 4096: -4 ... -5 %)
-    const int want_ps = h->lean_ps >= 0 ? h->lean_ps : 1;
-    const int ps = (rl && !lazy && want_ps && !flow) ? 1 : 0;   // (only without the data-flow launch, below)
-    if (ps && (rc = h->ps_flags.reserve((size_t)nh * nblk * sizeof(int)))) return rc;   // zeroed by k_lean_rhs_init
-    // The whole factorisation as ONE data-flow launch (k_lean_flow; option lean_flow, default on): against one launch per
-    // block column -27 ... -36 % per call at N = 2048 (1-32 draws), -25 ... -34 % at N = 1000, -20 % at N = 256, -6 ... -10 %
-    // at N = 64 (profiles/r03_flow_ab.log); the same factor bit for bit
+    if (p.step) HIPCHK(hipEventRecord(h->ev_obs, s));
+    if (!p.cov_in_flow)
+        TIMED(ST_COV_SELF, launch_cov_self(s, h->Xs.d(), h->s1.d(), h->X2s.d(), h->htab.d(), h->Lm.d(), (int)N, Np, Dp, nh, p.tiled, dev_kind(h)));
+    if (p.ps && (rc = h->ps_flags.reserve(p.ps_bytes))) return rc;   // zeroed by k_lean_rhs_init
     int* lflags = nullptr; int* dflags = nullptr; int* cu_busy = nullptr; unsigned* tickets = nullptr;
-    if (flow) {
-        const size_t nfl = (size_t)nh * (nblk + 1) * nblk + (size_t)nh * nblk + 2 + 4096;   // (+ one word per CU: cu_busy)
-        if (nfl > h->flow_flags_n || h->flow_gen >= (1 << 27)) {
-            if ((rc = h->flow_flags.reserve(nfl * sizeof(int)))) return rc;
+    if (p.flow) {
+        if (p.nfl > h->flow_flags_n || h->flow_gen >= (1 << 27)) {
+            if ((rc = h->flow_flags.reserve(p.nfl * sizeof(int)))) return rc;
             HIPCHK(hipMemsetAsync(h->flow_flags.p, 0, h->flow_flags.cap, h->stream));
             h->flow_flags_n = h->flow_flags.cap / sizeof(int);
             h->flow_gen = 0;
@@ -714,51 +627,40 @@ static int do_factor(spx_handle* h, bool tolerate_not_pd, bool lean = false, boo
         lflags = cu_busy + 4096;
         dflags = lflags + (size_t)nh * (nblk + 1) * nblk;
     }
-    h->flow_used = flow != 0;
-    // Residency (option lean_flow_cu: 1 / 0 / -1 = by size; scripts/dev/flow_modes.py).  A diagonal block's dependent MFMA
-    // chain runs a third slower beside a neighbour whose products keep the matrix pipes busy, and the whole call follows
-    // that chain.  Small launches (draws x block columns^1.5 <= 800: N = 2048 up to 4 draws, N = 1000 up to 12) get ONE
-    // workgroup per CU (the launch asks for 96 KB of LDS).  Larger ones need the places: two per CU, and a workgroup yields
-    // while its neighbour is the next link of a draw's chain -- from the end of its history through its diagonal block
-    // (option lean_flow_yield; a word per CU, found by XCC_ID / HW_ID).  Against two per CU without yielding: N = 2048:
-    // -11 % at 4 draws, -13 % at 6, -10 % at 8, -2 % at 12; N = 4096: -16 % at 2 draws; N = 1000: -7 % at 20 draws.
     // lean: the right-hand side vals - mean rides through the factorisation as an extra row block,
     // so y = L^-1 (vals - mean) is ready when the last column is
     double* rhs = nullptr;
     // (spx_gp_logprob_rhs: draw h's right-hand side is row h of rhs_rows instead of the shared values)
     const double* vsrc = h->rhs_rows_on ? h->rhs_rows.d() : h->vals.d();
-    const int64_t vstride = h->rhs_rows_on ? N : 0;
     if (lean) {
-        if ((rc = h->rhs.reserve((size_t)nh * SPX_NB * Np * 8))) return rc;
+        if ((rc = h->rhs.reserve(p.rhs_bytes))) return rc;
         rhs = h->rhs.d();
-        if (rl) {
-            if ((rc = h->diagL.reserve((size_t)nh * Np * 8))) return rc;
-            if (fused) {}            // (nothing to launch)
-            else if (merged_prologue)     // (implies flow and cov_in_flow: nothing before this point read x / ls)
+        if (p.rl) {
+            if ((rc = h->diagL.reserve(p.diagL_bytes))) return rc;
+            if (p.fused) {}            // (nothing to launch)
+            else if (p.merged_prologue)     // (implies flow and cov_in_flow: nothing before this point read x / ls)
                 TIMED(ST_SCALE, launch_lean_prologue(s, h->comp.d(), N, Np, D, Dp, ls, hs, nh, h->Xs.d(), h->s1.d(), h->X2s.d(),
-                                                     vsrc, h->htab.d(), rhs, (int*)h->info.p, ps ? (int*)h->ps_flags.p : nullptr,
-                                                     vstride));
+                                                     vsrc, h->htab.d(), rhs, (int*)h->info.p, p.ps ? (int*)h->ps_flags.p : nullptr,
+                                                     p.vstride));
             else
                 TIMED(ST_GAMMA_ALPHA, launch_lean_rhs_init(s, vsrc, h->htab.d(), rhs, (int)N, Np, nh, (int*)h->info.p,
-                                                           ps ? (int*)h->ps_flags.p : nullptr, vstride));
+                                                           p.ps ? (int*)h->ps_flags.p : nullptr, p.vstride));
         } else {
-            TIMED(ST_GAMMA_ALPHA, launch_rhs_init(s, vsrc, h->htab.d(), rhs, (int)N, Np, nh, vstride));
+            TIMED(ST_GAMMA_ALPHA, launch_rhs_init(s, vsrc, h->htab.d(), rhs, (int)N, Np, nh, p.vstride));
         }
-        h->lean_tiled = rl != 0;
     }
-    h->factor_tiled = !lean && flow;
-    FlowFused ff{h->comp.d(), zero_copy ? (const double*)h->pin_up.p : h->hyp.d(), vsrc, D, hs, h->fused_lp, h->fused_info,
-                 lean ? vstride : 0};
-    const double* htab_dev = zero_copy ? (const double*)h->pin_up.p + (size_t)nh * hs : h->htab.d();
-    if (flow)
-        TIMED(ST_CHOL_DIAG, launch_lean_flow(s, h->Lm.d(), h->Dinv.d(), (int*)h->info.p, rhs, lean ? h->diagL.d() : nullptr, lflags, dflags, tickets, Np, nh, h->flow_gen, flow_alone,
-                                             cov_in_flow ? h->Xs.d() : nullptr, h->X2s.d(), h->s1.d(), htab_dev, (int)N, Dp, dev_kind(h),
-                                             h->lean_flow_yield != 0 ? cu_busy : nullptr, h->flow_spin_limit, fused ? &ff : nullptr));
-    for (int k = 0; k < (flow ? 0 : nblk); ++k) {
-        if (ps) {
+    FlowFused ff{h->comp.d(), p.zero_copy ? (const double*)h->pin_up.p : h->hyp.d(), vsrc, D, hs, h->fused_lp, h->fused_info,
+                 lean ? p.vstride : 0};
+    const double* htab_dev = p.zero_copy ? (const double*)h->pin_up.p + (size_t)nh * hs : h->htab.d();
+    if (p.flow)
+        TIMED(ST_CHOL_DIAG, launch_lean_flow(s, h->Lm.d(), h->Dinv.d(), (int*)h->info.p, rhs, lean ? h->diagL.d() : nullptr, lflags, dflags, tickets, Np, nh, h->flow_gen, p.flow_alone,
+                                             p.cov_in_flow ? h->Xs.d() : nullptr, h->X2s.d(), h->s1.d(), htab_dev, (int)N, Dp, dev_kind(h),
+                                             p.yield ? cu_busy : nullptr, h->opt.flow_spin_limit, p.fused ? &ff : nullptr));
+    for (int k = 0; k < (p.flow ? 0 : nblk); ++k) {
+        if (p.ps) {
             TIMED(ST_CHOL_DIAG, launch_lean_step_ps(s, h->Lm.d(), h->Dinv.d(), (int*)h->info.p, rhs, h->diagL.d(), (int*)h->ps_flags.p, Np, k, nh));
-        } else if (rl) {
-            TIMED(ST_CHOL_DIAG, launch_lean_step(s, h->Lm.d(), h->Dinv.d(), (int*)h->info.p, rhs, h->diagL.d(), Np, k, nh, lazy));
+        } else if (p.rl) {
+            TIMED(ST_CHOL_DIAG, launch_lean_step(s, h->Lm.d(), h->Dinv.d(), (int*)h->info.p, rhs, h->diagL.d(), Np, k, nh, p.lazy));
             TIMED(ST_CHOL_PANEL, launch_lean_trsm(s, h->Lm.d(), h->Dinv.d(), rhs, Np, k, nh));
         } else {
             TIMED(ST_CHOL_DIAG, launch_chol_diag(s, h->Lm.d(), h->Dinv.d(), (int*)h->info.p, Np, k, nh, 0));
@@ -766,7 +668,7 @@ static int do_factor(spx_handle* h, bool tolerate_not_pd, bool lean = false, boo
         }
     }
     if (!lean) {
-        TIMED(ST_TRINV, launch_trinv(s, h->Lm.d(), h->Dinv.d(), h->WT.d(), Np, nh, flow != 0));
+        TIMED(ST_TRINV, launch_trinv(s, h->Lm.d(), h->Dinv.d(), h->WT.d(), Np, nh, p.flow));
         TIMED(ST_GAMMA_ALPHA, launch_gamma(s, h->WT.d(), h->vals.d(), h->htab.d(), h->gamma.d(), (int)N, Np, H));
         if (nm == 2)
             TIMED(ST_GAMMA_ALPHA, launch_gamma(s, h->WT.d() + (size_t)H * Np * Np, h->ldur.d(),
@@ -774,8 +676,8 @@ static int do_factor(spx_handle* h, bool tolerate_not_pd, bool lean = false, boo
                                                 h->gamma.d() + (size_t)H * Np, (int)N, Np, H));
         TIMED(ST_GAMMA_ALPHA, launch_alpha(s, h->WT.d(), h->gamma.d(), h->alpha.d(), Np, nh));
     }
-    if (h->timing || !lean) HIPCHK(hipEventRecord(t1, s));
-    if (defer_sync && !lean) HIPCHK(hipEventRecord(h->ev_fac, s));   // (spx_ei_step with two streams: alpha is ready)
+    if (p.bracket) HIPCHK(hipEventRecord(t1, s));
+    if (p.step) HIPCHK(hipEventRecord(h->ev_fac, s));   // (spx_ei_step with two streams: alpha is ready)
     if (defer_sync) return SPX_OK;
     std::vector<int> info(nh);
     if ((rc = stage_d2h(h, info.data(), h->info.p, (size_t)nh * sizeof(int), s))) return rc;
@@ -787,7 +689,7 @@ static int finish_factor(spx_handle* h, const std::vector<int>& info, bool toler
     const int nh = (int)info.size(), H = h->H;
     LAUNCHCHK();
     float ms = 0.f;
-    if (h->timing) {
+    if (h->opt.timing) {
         (void)hipEventElapsedTime(&ms, h->ev_t0, h->ev_t1);
         ev_collect(h);
         h->st_ms[ST_FACTOR_TOTAL] += ms; h->st_n[ST_FACTOR_TOTAL] += 1;
@@ -798,7 +700,7 @@ static int finish_factor(spx_handle* h, const std::vector<int>& info, bool toler
             h->handoff_timeout = true;
             return fail(SPX_ERR_HIP, "log-likelihood factorisation: in-launch hand-off timed out (draw %d)", i);
         }
-    if (h->flow_demoted && h->flow_rearm_after > 0 && ++h->flow_clean >= h->flow_rearm_after) {
+    if (h->flow_demoted && h->opt.flow_rearm_after > 0 && ++h->flow_clean >= h->opt.flow_rearm_after) {
         h->flow_demoted = false;     // the next factorisation is the data-flow launch again
         h->flow_clean = 0;
         h->flow_rearms += 1;
@@ -824,7 +726,7 @@ int spx_factor(spx_handle* h)
     if (rc) return rc;
     h->handoff_timeout = false;
     rc = do_factor(h, false);
-    if (rc == SPX_ERR_HIP && h->handoff_timeout && h->flow_used) {   // as in spx_gp_logprob: never seen; bounded, then the launches
+    if (rc == SPX_ERR_HIP && h->handoff_timeout && h->last_factor->flow) {   // as in spx_gp_logprob: never seen; bounded, then the launches
         note_flow_timeout(h);
         rc = do_factor(h, false);
         if (!rc) warn_flow_fallback(h);
@@ -876,30 +778,6 @@ int spx_set_fantasies(spx_handle* h, const double* fant, const double* bests, in
     return SPX_OK;
 }
 
-// candidate-chunk / draw-group plan for the K(X*,X) staging buffer
-static void plan_chunks(const spx_handle* h, int64_t* Mc, int* Hb)
-{
-    const int64_t Mp = round_up(h->M, SPX_BN);
-    int64_t mc_budget = h->kst_budget / (8ll * h->Np) / SPX_BN * SPX_BN;   // what the staging buffer holds of one draw
-    if (mc_budget < SPX_BN) mc_budget = SPX_BN;
-    int64_t mc = mc_budget < Mp ? mc_budget : Mp;
-    // equal-sized chunks (no tiny, inefficient last launch) ...
-    const int64_t nchunks = (Mp + mc - 1) / mc;
-    mc = round_up((Mp + nchunks - 1) / nchunks, SPX_BN);
-    // ... of a whole number of candidate tiles per XCD when there are several: the predict GEMM deals the
-    // 128-candidate tiles of a launch round-robin to the 8 XCDs, and a launch with 245 tiles runs as long as one
-    // with 248 (measured at C3: 7 chunks of 224 tiles 268 ms per step, 6 of 261 or 5 of 313 tiles 273 ms)
-    if (nchunks > 1) {
-        const int64_t up = round_up(mc, 8 * SPX_BN);
-        if (up <= mc_budget) mc = up;
-        else if (mc >= 16 * SPX_BN) mc = mc / (8 * SPX_BN) * (8 * SPX_BN);
-    }
-    int64_t hb = h->kst_budget / (8ll * h->Np * mc);
-    if (hb < 1) hb = 1;
-    if (hb > h->H) hb = h->H;
-    *Mc = mc;
-    *Hb = (int)hb;
-}
 
 // factor_pending (spx_ei_step): the factorisation is queued on the stream but not yet checked -- its not-PD flags travel
 // home with the winner, and ONE synchronisation ends the step
@@ -950,7 +828,7 @@ int spx_ei_step(spx_handle* h, int32_t flags)
         int rc = spx_multi_factor(h->multi);
         return rc ? rc : spx_multi_ei_run(h->multi, flags & ~SPX_FLAG_TIME_ONLY);
     }
-    if (h->timing || (flags & SPX_FLAG_TIMING) || !h->have_cand) {   // stage timers bracket each call: keep the two-call form
+    if (h->opt.timing || (flags & SPX_FLAG_TIMING) || !h->have_cand) {   // stage timers bracket each call: keep the two-call form
         int rc = spx_factor(h);
         return rc ? rc : ei_run_impl(h, flags, false);
     }
@@ -963,7 +841,7 @@ int spx_ei_step(spx_handle* h, int32_t flags)
     if (rc) return rc;
     h->S = 0;                      // a new factorisation drops the fantasies (finish_factor), here before the run
     rc = ei_run_impl(h, flags, true);
-    if (rc == SPX_ERR_HIP && h->handoff_timeout && h->flow_used) {   // as in spx_factor: bounded, then the launches
+    if (rc == SPX_ERR_HIP && h->handoff_timeout && h->last_factor->flow) {   // as in spx_factor: bounded, then the launches
         note_flow_timeout(h);
         rc = do_factor(h, false);
         if (!rc) rc = ei_run_impl(h, flags, false);
@@ -987,122 +865,86 @@ static int ei_run_impl(spx_handle* h, int32_t flags, bool factor_pending)
 {
     if (!h->factored && !factor_pending) return fail(SPX_ERR_ARG, "spx_ei_run: call spx_factor first");
     if (!h->have_cand) return fail(SPX_ERR_ARG, "spx_ei_run: no candidates set");
-    const bool per_sec = (flags & SPX_FLAG_PER_SEC) != 0;
-    const bool keep_mom = (flags & SPX_FLAG_KEEP_MOMENTS) != 0;
-    const bool time_only = (flags & SPX_FLAG_TIME_ONLY) != 0;
-    const bool constrained = (flags & SPX_FLAG_CONSTRAINED) != 0;
     int rc = check_run_flags(h, flags, h->nmodels);
     if (rc) return rc;
     if ((rc = ensure_init(h))) return rc;
-    if (constrained && h->con_n > 0 && (!h->con_factored || h->con->cov_kind != h->cov_kind))
+    if ((flags & SPX_FLAG_CONSTRAINED) && h->con_n > 0 && (!h->con_factored || h->con->opt.cov_kind != h->opt.cov_kind))
         return fail(SPX_ERR_ARG, "spx_ei_run: the constraint model is not factored (spx_factor after spx_set_constraint_model)");
-    const int H = h->H, D = h->D, Dp = h->Dp, Np = h->Np, hs = 3 + D;
-    const int64_t N = h->N, M = h->M, Mp = round_up(M, SPX_BN);
-    const int nrb = Np / SPX_BM;
-    int64_t Mc; int Hb;
-    plan_chunks(h, &Mc, &Hb);
-    const int S = h->S;
-    if (S > 0) {
-        // the per-fantasy partial means are [nrb][2][S][Mc]: keep them under 2 GB (of 288: at C3 size with 100 fantasies the
-        // plan's own 28 672-candidate chunks fit; the 256 MB of earlier rounds cut them to 9 856 -- 420 launch pairs of a
-        // few dozen workgroups instead of 140)
-        // (... of what the device has free: a smaller or fuller GPU takes smaller chunks instead of an allocation failure)
-        // (queried when the number of fantasies changes, not per pass: the chunk plan -- buffer sizes, launch counts -- then
-        // stays what it was from pass to pass and across ranks that share a device)
-        if (h->fant_budget_S != S) {
-            size_t mem_free = 0, mem_total = 0;
-            int64_t b = 2048ll << 20;
-            if (hipMemGetInfo(&mem_free, &mem_total) == hipSuccess) {
-                const int64_t have = (int64_t)(mem_free / 8) + (int64_t)(h->part_bgS[0].cap + h->part_bgS[1].cap + h->scratch.cap) / 2;
-                b = std::max<int64_t>(64ll << 20, std::min<int64_t>(b, have));
-            } else (void)hipGetLastError();
-            h->fant_budget = b;
-            h->fant_budget_S = S;
-        }
-        const int64_t fant_budget = h->fant_budget;
-        int64_t cap = fant_budget / ((int64_t)nrb * 2 * S * 8) / SPX_BN * SPX_BN;
-        if (cap < SPX_BN) cap = SPX_BN;
-        if (Mc > cap) {
-            const int64_t nchunks = (Mp + cap - 1) / cap;
-            Mc = round_up((Mp + nchunks - 1) / nchunks, SPX_BN);
-        }
-        // ... and as many draws per launch as that leaves room for (small problems: all of them -- ten launch pairs of a
-        // 20 000-candidate pass become one)
-        int64_t hb = fant_budget / ((int64_t)nrb * 2 * S * 8 * Mc);
-        if (hb > 65535 / S) hb = 65535 / S;       // (grid.y of the per-fantasy EI kernel)
-        if (hb < 1) hb = 1;
-        if (hb < Hb) Hb = (int)hb;
+    EiShape sh;
+    sh.N = h->N; sh.M = h->M; sh.Np = h->Np; sh.D = h->D; sh.H = h->H; sh.S = h->S; sh.nmodels = h->nmodels;
+    sh.flags = flags; sh.factor_pending = factor_pending; sh.kst_budget = h->opt.kst_budget;
+    // The byte budgets of the plan are shares of what the device has free (a smaller or fuller GPU takes smaller chunks
+    // instead of an allocation failure).  They are queried when the number of fantasies / the size of a ring slot changes, not
+    // per pass: the plan -- buffer sizes, launch counts -- then stays what it was from pass to pass and across ranks that
+    // share a device.  Fantasies: an eighth of free memory, at most 2 GB.
+    if (sh.S > 0 && h->fant_budget_S != sh.S) {
+        size_t mem_free = 0, mem_total = 0;
+        int64_t b = 2048ll << 20;
+        if (hipMemGetInfo(&mem_free, &mem_total) == hipSuccess) {
+            const int64_t have = (int64_t)(mem_free / 8) + (int64_t)(h->part_bgS[0].cap + h->part_bgS[1].cap + h->scratch.cap) / 2;
+            b = std::max<int64_t>(64ll << 20, std::min<int64_t>(b, have));
+        } else (void)hipGetLastError();
+        h->fant_budget = b;
+        h->fant_budget_S = sh.S;
     }
-
-    // N <= 128 without fantasies: the whole EI pass of a chunk -- K(X,X*), beta = W K*, the moments, EI -- is one kernel
-    // with K* and beta in registers (fused_kernels.hip; option ei_fused); same bits as the three-stage path below
-    const bool fused = Np == SPX_PADN && S == 0 && h->ei_fused != 0;
-    h->last_fused = fused;
-    // streams = 3 with per-launch timing: the pass runs in order on one stream, so that every stage's events bracket that
-    // stage's kernels alone (the stage table, bench.py --full's roofline)
-    const bool timing_on = h->timing || (flags & SPX_FLAG_TIMING);
-    const int ns = fused ? 1 : ((h->nstreams == 3 && timing_on) ? 1 : h->nstreams);
-    // streams = 3: K(X*,X) of work item i goes to slot i % R of a ring of staging buffers (each with its own fantasy
-    // partials), so the producer stream runs up to R items ahead of the GEMM.  R comes from a byte budget -- a sixteenth of
-    // what the device has free, at most 10 GiB (C3: one chunk's twenty draws, 9.4 GB of 288), found when the size of a slot
-    // changes and not per pass (as fant_budget) -- or from option "kstar_ring"; never more slots than the pass has items.
-    const bool ringed = ns == 3 && !time_only;
-    int R = 0;
-    if (ringed) {
-        const int64_t slot = (int64_t)Hb * Np * Mc * 8 + (S > 0 ? (int64_t)nrb * 2 * Hb * S * Mc * 8 : 0);
-        if (h->ring_budget_slot != slot) {
-            size_t mem_free = 0, mem_total = 0;
-            int64_t b = 10ll << 30;
-            if (hipMemGetInfo(&mem_free, &mem_total) == hipSuccess) {
-                int64_t held = 0;
-                for (auto& sl : h->ring) held += (int64_t)(sl.Kst.cap + sl.part_bgS.cap);
-                b = std::min<int64_t>(b, (int64_t)(mem_free / 16) + held);
-            } else (void)hipGetLastError();
-            h->ring_budget = b;
-            h->ring_budget_slot = slot;
-        }
-        const int64_t nitems = ((Mp + Mc - 1) / Mc) * ((H + Hb - 1) / Hb);
-        int64_t r = h->ring_opt > 0 ? h->ring_opt : h->ring_budget / slot;
-        r = std::max<int64_t>(1, std::min<int64_t>(std::min<int64_t>(r, nitems), 4096));
-        R = (int)r;
+    sh.fant_budget = h->fant_budget;
+    sh.ring_budget = h->ring_budget;
+    EiPlan& p = h->ei_plan;
+    p = plan_ei(h->opt, sh);                  // every decision of this pass (spx_plan.h); below: reserve and launch
+    // The ring: a sixteenth of free memory, at most 10 GiB.  Its slot size comes out of the plan, so a new size means a new
+    // budget and the plan again.
+    if (p.ringed && h->ring_budget_slot != p.slot_bytes) {
+        size_t mem_free = 0, mem_total = 0;
+        int64_t b = 10ll << 30;
+        if (hipMemGetInfo(&mem_free, &mem_total) == hipSuccess) {
+            int64_t held = 0;
+            for (auto& sl : h->ring) held += (int64_t)(sl.Kst.cap + sl.part_bgS.cap);
+            b = std::min<int64_t>(b, (int64_t)(mem_free / 16) + held);
+        } else (void)hipGetLastError();
+        h->ring_budget = b;
+        h->ring_budget_slot = p.slot_bytes;
+        sh.ring_budget = b;
+        p = plan_ei(h->opt, sh);
+    }
+    const bool per_sec = p.per_sec, keep_mom = p.keep_mom, time_only = p.time_only, constrained = p.constrained, fused = p.fused;
+    const int H = h->H, D = h->D, Dp = p.Dp, Np = h->Np, hs = 3 + D, nrb = p.nrb, Hb = p.Hb, S = h->S, ns = p.ns, R = p.R;
+    const int64_t N = h->N, M = h->M, Mp = p.Mp, Mc = p.Mc;
+    if (p.ringed) {
         if ((rc = ensure_ring(h, R))) return rc;
         for (int k = 0; k < R; ++k) {
-            if ((rc = h->ring[k].Kst.reserve((size_t)Hb * Np * Mc * 8))) return rc;
-            if (S > 0 && (rc = h->ring[k].part_bgS.reserve((size_t)nrb * 2 * Hb * S * Mc * 8))) return rc;
+            if ((rc = h->ring[k].Kst.reserve(p.kst_bytes))) return rc;
+            if (S > 0 && (rc = h->ring[k].part_bgS.reserve(p.bgS_bytes))) return rc;
         }
     }
-    if (ns == 3 && !ringed && (rc = ensure_ring(h, 0))) return rc;   // (a time-only pass: the producer stream alone)
-    // slots the pass does not use go back to the device -- but a streams = 3 handle that runs ONE pass another way (per-launch
-    // timing, the fused path, time only) keeps its ring: the next pass would only allocate the same gigabytes again
-    if (ringed || h->nstreams != 3) ring_trim(h, R);
-    h->ring_used = R;
+    if (ns == 3 && !p.ringed && (rc = ensure_ring(h, 0))) return rc;   // (a time-only pass: the producer stream alone)
+    if (p.trim_ring) ring_trim(h, R);
     h->corun_launches = 0;
     for (int b = 0; b < 2; ++b) {
         // scaled candidates (all draws) and predicted durations are double-buffered by chunk parity,
         // the K(X*,X) staging buffer and the partial sums by stream
-        if ((rc = h->Cs[b].reserve((size_t)H * Mc * Dp * 8))) return rc;
-        if ((rc = h->s2[b].reserve((size_t)H * Mc * 8))) return rc;
-        if (per_sec && (rc = h->time_m[b].reserve((size_t)H * Mc * 8))) return rc;
-        if (constrained && (rc = h->con_p[b].reserve((size_t)H * Mc * 8))) return rc;
-        if (constrained && h->con_n > 0 && (rc = h->con_Cs[b].reserve((size_t)H * Mc * Dp * 8))) return rc;
-        if (constrained && h->con_n > 0 && (rc = h->con_s2[b].reserve((size_t)H * Mc * 8))) return rc;
-        if (b < ns && ns <= 2 && !fused && !time_only) {
-            if ((rc = h->Kst[b].reserve((size_t)Hb * Np * Mc * 8))) return rc;
-            if (S > 0 && (rc = h->part_bgS[b].reserve((size_t)nrb * 2 * Hb * S * Mc * 8))) return rc;
+        if ((rc = h->Cs[b].reserve(p.cs_bytes))) return rc;
+        if ((rc = h->s2[b].reserve(p.s2_bytes))) return rc;
+        if (per_sec && (rc = h->time_m[b].reserve(p.s2_bytes))) return rc;
+        if (constrained && (rc = h->con_p[b].reserve(p.s2_bytes))) return rc;
+        if (constrained && h->con_n > 0 && (rc = h->con_Cs[b].reserve(p.cs_bytes))) return rc;
+        if (constrained && h->con_n > 0 && (rc = h->con_s2[b].reserve(p.s2_bytes))) return rc;
+        if (b < p.kst_bufs) {
+            if ((rc = h->Kst[b].reserve(p.kst_bytes))) return rc;
+            if (S > 0 && (rc = h->part_bgS[b].reserve(p.bgS_bytes))) return rc;
         }
     }
     // column sums of beta^2 and beta*gamma per row block for ALL draws of a chunk: written by the
     // GEMM launches and read by one EI-finalize launch per chunk, all on the consumer stream
-    if (!fused && !time_only && (rc = h->part_ss[0].reserve((size_t)nrb * H * Mc * 8))) return rc;
-    if (!fused && !time_only && (rc = h->part_bg[0].reserve((size_t)nrb * H * Mc * 8))) return rc;
-    if (S > 0 && (rc = h->scratch.reserve((size_t)Hb * S * Mc * 8))) return rc;   // EI per (draw of the group, fantasy, candidate)
-    if ((rc = h->ei_draw.reserve((size_t)H * Mp * 8))) return rc;
-    if ((rc = h->ei_mean.reserve((size_t)Mp * 8))) return rc;
+    if (p.gemm_path && (rc = h->part_ss[0].reserve(p.part_bytes))) return rc;
+    if (p.gemm_path && (rc = h->part_bg[0].reserve(p.part_bytes))) return rc;
+    if (S > 0 && (rc = h->scratch.reserve(p.scratch_bytes))) return rc;   // EI per (draw of the group, fantasy, candidate)
+    if ((rc = h->ei_draw.reserve(p.draw_bytes))) return rc;
+    if ((rc = h->ei_mean.reserve(p.mean_bytes))) return rc;
     if (keep_mom) {
-        if ((rc = h->mom_m.reserve((size_t)H * Mp * 8))) return rc;
-        if ((rc = h->mom_v.reserve((size_t)H * Mp * 8))) return rc;
-        if (per_sec && (rc = h->mom_t.reserve((size_t)H * Mp * 8))) return rc;
-        if (constrained && (rc = h->mom_c.reserve((size_t)H * Mp * 8))) return rc;
+        if ((rc = h->mom_m.reserve(p.draw_bytes))) return rc;
+        if ((rc = h->mom_v.reserve(p.draw_bytes))) return rc;
+        if (per_sec && (rc = h->mom_t.reserve(p.draw_bytes))) return rc;
+        if (constrained && (rc = h->mom_c.reserve(p.draw_bytes))) return rc;
     }
     const int nab = argmax_blocks(M);
     if ((rc = h->am_val.reserve((size_t)nab * 8))) return rc;
@@ -1111,17 +953,11 @@ static int ei_run_impl(spx_handle* h, int32_t flags, bool factor_pending)
     if ((rc = h->am_out_idx.reserve(8))) return rc;
 
     hipStream_t s = h->stream;
-    if (flags & SPX_FLAG_TIMING) h->timing = true;
+    if (flags & SPX_FLAG_TIMING) h->opt.timing = true;
     h->ev_used = 0;
     hipEvent_t t0 = h->ev_t0, t1 = h->ev_t1;
     HIPCHK(hipEventRecord(t0, s));
-    // N is padded to the predict GEMM's 128-row tiles with an identity: the production GEMM skips what the padding would
-    // multiply (K steps and row tiles from tile ceil(N / 16) on) and K(X*,X) then leaves those rows unwritten.  Same bits.
-    const int gemm_nlive = (!fused && h->gemm_partial != 0) ? predict_gemm_padding_plan(h->gemm_variant, (int)N, Np) : 0;
-    const bool skip_pad = gemm_nlive > 0;
-    const int cov_live_rows = 16 * gemm_nlive;
-    h->last_skip_pad = skip_pad;
-
+    const int gemm_nlive = p.gemm_nlive;
     const double* ls = h->hyp.d() + 3;
     const size_t nn = (size_t)Np * Np;
     // Streams: G (consumer: predict GEMM + EI finalize) and P (producer: candidate scaling and
@@ -1134,13 +970,12 @@ static int ei_run_impl(spx_handle* h, int32_t flags, bool factor_pending)
     // waits for slot i % R to be consumed (item i - R's GEMM), so K(X*,X) runs beside the GEMMs -- and, in a step, beside
     // the factorisation -- instead of in front of each.  events per slot: K* ready (P -> G), consumed (G -> P).
     hipStream_t G = h->stream, P = (ns == 3) ? h->stream3 : (ns == 2) ? h->stream2 : h->stream;
-    const int64_t ring_items = ringed ? ((Mp + Mc - 1) / Mc) * ((H + Hb - 1) / Hb) : 0;
     // A step (factor_pending): the factorisation is still running on G -- a chain of small launches that leaves most of the
     // chip idle -- and the first producer work of the pass (candidate scaling, K(X*,X) of the first group of draws) depends
     // only on what the factorisation's FIRST kernel wrote.  It goes to the second stream, beside the factorisation
     // (C2: K(X*,X) of all ten draws, 0.10 ms, hidden behind a 0.17 ms factorisation).  A time model's predicted durations
     // need alpha: they stay behind the factorisation on G, with the chunk's other-parity scaling buffers to themselves.
-    const bool overlap = factor_pending && ns == 1 && h->step_overlap != 0;
+    const bool overlap = p.overlap;
     hipStream_t P0 = overlap ? h->stream2 : P;
     if (overlap) HIPCHK(hipStreamWaitEvent(P0, h->ev_obs, 0));
     // Two streams (option streams = 2) in a step: the producer stream has no other order against the factorisation that is
@@ -1212,14 +1047,12 @@ static int ei_run_impl(spx_handle* h, int32_t flags, bool factor_pending)
             hipStream_t Pi = (item == 0) ? Pc : P;
             double* Kst_k = (ns == 3) ? h->ring[k].Kst.d() : h->Kst[k].d();
             double* bgS_k = S > 0 ? ((ns == 3) ? h->ring[k].part_bgS.d() : h->part_bgS[k].d()) : nullptr;
-            // (the pass's first K(X*,X) has the chip to itself -- or shares it with the factorisation's small launches: today's
-            // kernel; every later one runs beside a GEMM: the form that fits there)
-            const bool corun = ns == 3 && item > 0 && h->corun_opt != 0 && h->cov_flat != 0;
+            const bool corun = p.corun && item > 0;
             h->corun_launches += corun ? 1 : 0;
             TIMED_S(ST_COV_CROSS, Pi, launch_cov_cross(Pi, h->Xs.d() + (size_t)h0 * Np * Dp, h->s1.d() + (size_t)h0 * Np,
                                                       Cs + (size_t)h0 * mc * Dp, s2 + (size_t)h0 * mc,
                                                       h->htab.d() + (size_t)h0 * SPX_HT, Kst_k, (int)N, Np, mc, Dp, nhb, dev_kind(h),
-                                                      cov_live_rows, h->cov_flat != 0, corun));
+                                                      p.cov_live_rows, p.cov_flat, corun));
             if (ns == 3) {
                 HIPCHK(hipEventRecord(h->ring[k].ready, P));
                 HIPCHK(hipStreamWaitEvent(G, h->ring[k].ready, 0));
@@ -1231,7 +1064,7 @@ static int ei_run_impl(spx_handle* h, int32_t flags, bool factor_pending)
                 HIPCHK(hipStreamWaitEvent(G, h->ev_p0, 0));
             }
             // with fantasies the launch's partial sums are consumed right away and sit at draws 0 .. nhb-1
-            TIMED_S(ST_PREDICT_GEMM, G, launch_predict_gemm(G, h->gemm_variant, h->WT.d() + (size_t)h0 * nn, Kst_k,
+            TIMED_S(ST_PREDICT_GEMM, G, launch_predict_gemm(G, h->opt.gemm_variant, h->WT.d() + (size_t)h0 * nn, Kst_k,
                                                             h->gamma.d() + (size_t)h0 * Np, h->part_ss[0].d(),
                                                             h->part_bg[0].d(), Np, mc, nhb, S > 0 ? nhb : H, S > 0 ? 0 : h0,
                                                             S > 0 ? h->gammaS.d() + (size_t)h0 * S * Np : nullptr, S,
@@ -1245,7 +1078,7 @@ static int ei_run_impl(spx_handle* h, int32_t flags, bool factor_pending)
                                                                    h->ei_draw.d(), nrb, mc, nhb, S, c0, M, Mp, h0,
                                                                    h->scratch.d()));
             if (ns == 2) HIPCHK(hipEventRecord(h->ev_sync[2 + k], G));
-            if (ns == 3 && (int64_t)item + R < ring_items) HIPCHK(hipEventRecord(h->ring[k].consumed, G));   // (only where an item waits for it)
+            if (ns == 3 && (int64_t)item + R < p.ring_items) HIPCHK(hipEventRecord(h->ring[k].consumed, G));   // (only where an item waits for it)
         }
         if (S == 0 && !fused)   // every draw of the chunk in one launch
             TIMED_S(ST_EI_FINALIZE, G, launch_ei_finalize(G, h->part_ss[0].d(), h->part_bg[0].d(), h->htab.d(), tm, cp, h->best,
@@ -1258,7 +1091,7 @@ static int ei_run_impl(spx_handle* h, int32_t flags, bool factor_pending)
         HIPCHK(hipStreamWaitEvent(G, h->ev_sync[0], 0));
     }
     // the winner (and, in a step, the factorisation's flags) go home through pinned memory with the last kernel's own stores
-    const int n_info = factor_pending ? h->nmodels * H : 0;
+    const int n_info = p.n_info;
     if ((rc = h->pin_res.reserve(16 + (size_t)n_info * sizeof(int)))) return rc;
     double* mirror = (double*)h->pin_res.p;
     TIMED(ST_MEAN_ARGMAX, {
@@ -1276,7 +1109,7 @@ static int ei_run_impl(spx_handle* h, int32_t flags, bool factor_pending)
     }
     float ms = 0.f;
     (void)hipEventElapsedTime(&ms, t0, t1);
-    if (h->timing) {
+    if (h->opt.timing) {
         ev_collect(h);
         h->st_ms[ST_EI_RUN_TOTAL] += ms; h->st_n[ST_EI_RUN_TOTAL] += 1;
     }
@@ -1325,18 +1158,25 @@ int spx_get_ei_draws(spx_handle* h, double* out)
     return SPX_OK;
 }
 
+// one [Mp]-strided row per draw of up to two results of the last pass, into the caller's M doubles each
+static int get_draw_rows(spx_handle* h, const char* who, int32_t draw, const DevBuf& a, double* out_a,
+                         const DevBuf* b = nullptr, double* out_b = nullptr)
+{
+    if (draw < 0 || draw >= h->H) return fail(SPX_ERR_ARG, "%s: draw out of range", who);
+    int rc = ensure_init(h);
+    if (rc) return rc;
+    const int64_t Mp = round_up(h->M, SPX_BN);
+    if (out_a) HIPCHK(hipMemcpy(out_a, a.d() + (size_t)draw * Mp, (size_t)h->M * 8, hipMemcpyDeviceToHost));
+    if (b && out_b) HIPCHK(hipMemcpy(out_b, b->d() + (size_t)draw * Mp, (size_t)h->M * 8, hipMemcpyDeviceToHost));
+    return SPX_OK;
+}
+
 int spx_get_moments(spx_handle* h, int32_t draw, double* func_m, double* func_v)
 {
     if (h && h->multi) return spx_multi_get_moments(h->multi, draw, func_m, func_v);
     if (!h || !h->ran || !h->ran_moments)
         return fail(SPX_ERR_ARG, "spx_get_moments: run spx_ei_run with SPX_FLAG_KEEP_MOMENTS first");
-    if (draw < 0 || draw >= h->H) return fail(SPX_ERR_ARG, "spx_get_moments: draw out of range");
-    int rc = ensure_init(h);
-    if (rc) return rc;
-    const int64_t Mp = round_up(h->M, SPX_BN);
-    if (func_m) HIPCHK(hipMemcpy(func_m, h->mom_m.d() + (size_t)draw * Mp, (size_t)h->M * 8, hipMemcpyDeviceToHost));
-    if (func_v) HIPCHK(hipMemcpy(func_v, h->mom_v.d() + (size_t)draw * Mp, (size_t)h->M * 8, hipMemcpyDeviceToHost));
-    return SPX_OK;
+    return get_draw_rows(h, "spx_get_moments", draw, h->mom_m, func_m, &h->mom_v, func_v);
 }
 
 int spx_get_time_mean(spx_handle* h, int32_t draw, double* out)
@@ -1344,12 +1184,7 @@ int spx_get_time_mean(spx_handle* h, int32_t draw, double* out)
     if (h && h->multi) return spx_multi_get_time_mean(h->multi, draw, out);
     if (!h || !out || !((h->ran && (h->ran_moments || h->ran_tmean)) || h->ran_time) || h->nmodels != 2)
         return fail(SPX_ERR_ARG, "spx_get_time_mean: run spx_ei_run with SPX_FLAG_PER_SEC | SPX_FLAG_KEEP_MOMENTS first");
-    if (draw < 0 || draw >= h->H) return fail(SPX_ERR_ARG, "spx_get_time_mean: draw out of range");
-    int rc = ensure_init(h);
-    if (rc) return rc;
-    const int64_t Mp = round_up(h->M, SPX_BN);
-    HIPCHK(hipMemcpy(out, h->mom_t.d() + (size_t)draw * Mp, (size_t)h->M * 8, hipMemcpyDeviceToHost));
-    return SPX_OK;
+    return get_draw_rows(h, "spx_get_time_mean", draw, h->mom_t, out);
 }
 
 int spx_get_constraint_prob(spx_handle* h, int32_t draw, double* out)
@@ -1357,12 +1192,17 @@ int spx_get_constraint_prob(spx_handle* h, int32_t draw, double* out)
     if (h && h->multi) return fail(SPX_ERR_ARG, "spx_get_constraint_prob: the constraint model is single-device only");
     if (!h || !out || !h->ran || !h->ran_con)
         return fail(SPX_ERR_ARG, "spx_get_constraint_prob: run spx_ei_run with SPX_FLAG_CONSTRAINED | SPX_FLAG_KEEP_MOMENTS first");
-    if (draw < 0 || draw >= h->H) return fail(SPX_ERR_ARG, "spx_get_constraint_prob: draw out of range");
-    int rc = ensure_init(h);
-    if (rc) return rc;
-    const int64_t Mp = round_up(h->M, SPX_BN);
-    HIPCHK(hipMemcpy(out, h->mom_c.d() + (size_t)draw * Mp, (size_t)h->M * 8, hipMemcpyDeviceToHost));
-    return SPX_OK;
+    return get_draw_rows(h, "spx_get_constraint_prob", draw, h->mom_c, out);
+}
+
+// Element (ri, cj) of a 64 x 64 tile of the tile-major factor (k_lean_flow): tile (I, J) at (I nblk + J) * 4096 doubles; below
+// the diagonal in accumulator order -- value q = 4 nt + r of thread t at ((q >> 1) * 256 + t) * 2 + (q & 1) is the element
+// (16 (t >> 6) + ((t & 63) >> 4) + 4 r, 16 nt + (t & 15)) -- the diagonal tiles row-major (diag_block's Lkk)
+static inline double tile_elem(const double* tile, bool diagonal, int ri, int cj)
+{
+    if (diagonal) return tile[ri * 64 + cj];
+    const int t = (ri >> 4) * 64 + (ri & 3) * 16 + (cj & 15), q = (cj >> 4) * 4 + ((ri & 15) >> 2);
+    return tile[((q >> 1) * 256 + t) * 2 + (q & 1)];
 }
 
 int spx_get_factor(spx_handle* h, int32_t draw, double* K, double* L, double* alpha)
@@ -1384,26 +1224,14 @@ int spx_get_factor(spx_handle* h, int32_t draw, double* K, double* L, double* al
         HIPCHK(hipStreamSynchronize(h->stream));
         HIPCHK(hipMemcpy2D(K, (size_t)N * 8, h->scratch.p, (size_t)Np * 8, (size_t)N * 8, (size_t)N, hipMemcpyDeviceToHost));
     }
-    if (L && h->factor_tiled) {
-        // tile-major factor (k_lean_flow): tile (I, J) at (I nblk + J) * 4096 doubles; below the diagonal in accumulator
-        // order -- value q = 4 nt + r of thread t at ((q >> 1) * 256 + t) * 2 + (q & 1) is the element
-        // (16 (t >> 6) + ((t & 63) >> 4) + 4 r, 16 nt + (t & 15)) -- the diagonal tiles row-major (diag_block's Lkk)
+    if (L && factor_tiled(h)) {
         std::vector<double> T(nn);
         HIPCHK(hipMemcpy(T.data(), h->Lm.d() + (size_t)draw * nn, nn * 8, hipMemcpyDeviceToHost));
         const int nblk = Np / SPX_NB;
         for (int64_t i = 0; i < N; ++i)
             for (int64_t j = 0; j < N; ++j) {
-                double v = 0.0;
-                if (j <= i) {
-                    const int I = (int)(i >> 6), J = (int)(j >> 6), ri = (int)(i & 63), cj = (int)(j & 63);
-                    const double* tile = T.data() + ((size_t)I * nblk + J) * 4096;
-                    if (I == J) v = tile[ri * 64 + cj];
-                    else {
-                        const int t = (ri >> 4) * 64 + (ri & 3) * 16 + (cj & 15), q = (cj >> 4) * 4 + ((ri & 15) >> 2);
-                        v = tile[((q >> 1) * 256 + t) * 2 + (q & 1)];
-                    }
-                }
-                L[i * N + j] = v;
+                const int I = (int)(i >> 6), J = (int)(j >> 6);
+                L[i * N + j] = j <= i ? tile_elem(T.data() + ((size_t)I * nblk + J) * 4096, I == J, (int)(i & 63), (int)(j & 63)) : 0.0;
             }
     } else if (L) {
         HIPCHK(hipMemcpy2D(L, (size_t)N * 8, h->Lm.d() + (size_t)draw * nn, (size_t)Np * 8, (size_t)N * 8, (size_t)N,
@@ -1432,8 +1260,8 @@ int spx_get_factor_rows(spx_handle* h, int32_t draw, int64_t row0, int64_t nrows
     if (rc) return rc;
     const int Np = h->Np;
     const size_t nn = (size_t)Np * Np;
-    if (L_rows && nrows > 0 && h->factor_tiled) {
-        // (tile-major factor: the tiles (I, 0 .. I) of a block row are contiguous; same element map as spx_get_factor)
+    if (L_rows && nrows > 0 && factor_tiled(h)) {
+        // (tile-major factor: the tiles (I, 0 .. I) of a block row are contiguous)
         const int nblk = Np / SPX_NB;
         std::vector<double> T;
         for (int I = (int)(row0 >> 6); I <= (int)((row0 + nrows - 1) >> 6); ++I) {
@@ -1442,19 +1270,8 @@ int spx_get_factor_rows(spx_handle* h, int32_t draw, int64_t row0, int64_t nrows
             for (int64_t i = std::max<int64_t>(row0, (int64_t)I * 64); i < std::min<int64_t>(row0 + nrows, (int64_t)(I + 1) * 64); ++i) {
                 double* out = L_rows + (size_t)(i - row0) * N;
                 const int ri = (int)(i & 63);
-                for (int64_t j = 0; j < N; ++j) {
-                    double v = 0.0;
-                    if (j <= i) {
-                        const int J = (int)(j >> 6), cj = (int)(j & 63);
-                        const double* tile = T.data() + (size_t)J * 4096;
-                        if (I == J) v = tile[ri * 64 + cj];
-                        else {
-                            const int t = (ri >> 4) * 64 + (ri & 3) * 16 + (cj & 15), q = (cj >> 4) * 4 + ((ri & 15) >> 2);
-                            v = tile[((q >> 1) * 256 + t) * 2 + (q & 1)];
-                        }
-                    }
-                    out[j] = v;
-                }
+                for (int64_t j = 0; j < N; ++j)
+                    out[j] = j <= i ? tile_elem(T.data() + (size_t)(j >> 6) * 4096, I == (int)(j >> 6), ri, (int)(j & 63)) : 0.0;
             }
         }
     } else if (L_rows && nrows > 0) {
@@ -1490,7 +1307,7 @@ int spx_get_cross_cov(spx_handle* h, int32_t draw, int64_t c0, int64_t nc, doubl
                       cs.d(), s2.d());
     launch_cov_cross(s, h->Xs.d() + (size_t)draw * Np * Dp, h->s1.d() + (size_t)draw * Np, cs.d(), s2.d(),
                      h->htab.d() + (size_t)draw * SPX_HT, kst.d(), (int)h->N, Np, mc, Dp, 1, dev_kind(h), 0,
-                     h->cov_flat != 0);   // (option cov_flat holds here as in the EI pass: the two forms can be compared element by element)
+                     h->opt.cov_flat != 0);   // (option cov_flat holds here as in the EI pass: the two forms can be compared element by element)
     hipError_t e = hipStreamSynchronize(s);
     if (e == hipSuccess)
         e = hipMemcpy2D(out, (size_t)nc * 8, kst.p, (size_t)mc * 8, (size_t)nc * 8, (size_t)h->N, hipMemcpyDeviceToHost);
@@ -1507,7 +1324,7 @@ int spx_gp_logprob(spx_handle* h, double* out)
     if (h->multi) return spx_multi_gp_logprob(h->multi, out);
     h->handoff_timeout = false;
     int rc = gp_logprob_once(h, out);
-    if (rc == SPX_ERR_HIP && h->handoff_timeout && h->flow_used) {
+    if (rc == SPX_ERR_HIP && h->handoff_timeout && h->last_factor->flow) {
         // never seen on a healthy device; if the one-launch data flow ever stalls (its spins are bounded), the call is
         // repeated with one launch per block column -- same kernels' arithmetic, same bits -- and the handle stays there
         note_flow_timeout(h);
@@ -1538,7 +1355,6 @@ int spx_gp_logprob_rhs(spx_handle* h, const double* rows, const double* rhs, int
     return rc;
 }
 
-#define SPX_POLL_SENTINEL 0x7fffffff   // no not-PD flag has this value (pivots <= 2^20, time-outs < 0)
 static int gp_logprob_once(spx_handle* h, double* out)
 {
     // the kernels write the H values and the H not-PD flags straight into pinned host memory: no device-to-host copies
@@ -1549,26 +1365,24 @@ static int gp_logprob_once(spx_handle* h, double* out)
     double* lp_host = (double*)h->pin_res.p;
     int* info_host = (int*)(lp_host + h->H);
     h->fused_lp = lp_host; h->fused_info = info_host;
-    const bool polled = h->lean_poll != 0 && !h->timing;
-    if (polled) for (int k = 0; k < h->H; ++k) info_host[k] = SPX_POLL_SENTINEL;   // (coherent pinned memory: in place before the launch is queued)
     rc = do_factor(h, true, true, true);   // K(X,X), Cholesky, forward solve -- no inverse; queued, not yet synchronised
     h->fused_lp = nullptr; h->fused_info = nullptr;
     if (rc) { h->info_clean_ptr = nullptr; return rc; }
     if ((rc = h->lp.reserve((size_t)h->H * 8))) return rc;
     std::vector<int> info(h->H);
-    if (h->lean_tiled) {
-        if (!h->fused_ran)   // (the fused launch has reduced the log-likelihood itself)
-            launch_lean_logprob(h->stream, h->diagL.d(), h->rhs.d(), (const int*)h->info.p, lp_host, info_host, (int)h->N, h->lean_np, h->H);
-        // The fused launch stores every draw's value, then -- released at system scope -- its flag into the pinned buffer: the
-        // host watches the flags instead of waiting for the stream to drain (the end-of-kernel release and the completion
-        // signal are ~7 us of a 42 us call).  What is still running then -- other workgroups' last instructions, the ticket
-        // reset -- is ordered in front of whatever this stream is given next.  Bounded: after 20 ms (a long call at N = 8192
-        // takes 10) the stream is synchronised the ordinary way.
+    const FactorPlan& lp = h->lean_plan;    // (what do_factor just ran)
+    const bool polled = lp.poll;
+    if (lp.rl) {
+        if (!lp.fused)   // (the fused launch has reduced the log-likelihood itself)
+            launch_lean_logprob(h->stream, h->diagL.d(), h->rhs.d(), (const int*)h->info.p, lp_host, info_host, (int)h->N, lp.Np, h->H);
+        // polled: the host watches the pinned flags of the fused launch.  What is still running when they have all arrived --
+        // other workgroups' last instructions, the ticket reset -- is ordered in front of whatever this stream is given next.
+        // Bounded: after 20 ms (a long call at N = 8192 takes 10) the stream is synchronised the ordinary way.
         // (the device-side flags count as clean again only once this call is known to have ended well)
         const void* const clean_ptr = h->info_clean_ptr;
-        if (h->fused_ran) h->info_clean_ptr = nullptr;
+        if (lp.fused) h->info_clean_ptr = nullptr;
         bool seen = false;
-        if (h->fused_ran && polled) {
+        if (polled) {
             volatile int* fl = (volatile int*)info_host;
             const auto t0 = std::chrono::steady_clock::now();
             for (unsigned spin = 0;; ++spin) {
@@ -1580,13 +1394,13 @@ static int gp_logprob_once(spx_handle* h, double* out)
         }
         if (!seen) HIPCHK(hipStreamSynchronize(h->stream));
         LAUNCHCHK();
-        if (h->fused_ran && polled)      // (a launch that never ran -- refused, or a device error -- leaves its flags untouched)
+        if (polled)      // (a launch that never ran -- refused, or a device error -- leaves its flags untouched)
             for (int k = 0; k < h->H; ++k)
                 if (info_host[k] == SPX_POLL_SENTINEL)
                     return fail(SPX_ERR_HIP, "spx_gp_logprob: the launch finished without delivering draw %d", k);
         // a hand-off that timed out: a workgroup that gives up later than the draw's reducing item leaves -1 behind it -- the
         // device-side flags are then zeroed again before the next one-launch call
-        if (h->fused_ran) {
+        if (lp.fused) {
             bool timed_out = false;
             for (int k = 0; k < h->H; ++k) timed_out |= info_host[k] < 0;
             if (!timed_out) h->info_clean_ptr = clean_ptr;
@@ -1594,7 +1408,7 @@ static int gp_logprob_once(spx_handle* h, double* out)
         memcpy(out, lp_host, (size_t)h->H * 8);
         memcpy(info.data(), info_host, (size_t)h->H * sizeof(int));
     } else {
-        launch_logprob(h->stream, h->Lm.d(), h->rhs.d(), (size_t)SPX_NB * h->lean_np, (const int*)h->info.p, h->lp.d(), h->lean_np, h->H);
+        launch_logprob(h->stream, h->Lm.d(), h->rhs.d(), (size_t)SPX_NB * lp.Np, (const int*)h->info.p, h->lp.d(), lp.Np, h->H);
         HIPCHK(hipMemcpyAsync(out, h->lp.p, (size_t)h->H * 8, hipMemcpyDeviceToHost, h->stream));
         HIPCHK(hipMemcpyAsync(info.data(), h->info.p, (size_t)h->H * sizeof(int), hipMemcpyDeviceToHost, h->stream));
         HIPCHK(hipStreamSynchronize(h->stream));
@@ -1812,15 +1626,15 @@ int spx_ei_grad(spx_handle* h, const double* point, double* neg_ei_sum, double* 
 // points, through the ordinary factorisation path on an internal handle.  Not positive definite: draw 3H + d.
 static int ensure_full_factor(spx_handle* h)
 {
-    if (h->full_valid && h->full && h->full->factored && h->full->cov_kind == h->cov_kind) return SPX_OK;
+    if (h->full_valid && h->full && h->full->factored && h->full->opt.cov_kind == h->opt.cov_kind) return SPX_OK;
     h->full_valid = false;
     int rc;
     if (!h->full) {
         if ((rc = spx_create(h->device, &h->full))) return rc;
-        h->full->stage_copies = h->stage_copies;
+        h->full->opt.stage_copies = h->opt.stage_copies;
     }
     spx_handle* f = h->full;
-    f->cov_kind = h->cov_kind;
+    f->opt.cov_kind = h->opt.cov_kind;
     const std::vector<double> zeros((size_t)h->con_n, 0.0);   // (the values are not read: only W_f and the scaled rows are)
     if ((rc = spx_set_observations(f, h->con_comp_host.data(), zeros.data(), h->con_n, h->D))) return rc;
     if ((rc = spx_set_hypers(f, h->hyp_host.data(), h->H))) return rc;
@@ -1850,7 +1664,7 @@ int spx_constrained_ei_grad_batch(spx_handle* h, const double* points, int32_t P
     spx_handle* c = Nc > 0 ? h->con : nullptr;
     if (c && (c->H != h->H || c->D != h->D))
         return fail(SPX_ERR_ARG, "spx_constrained_ei_grad_batch: the constraint model does not match the objective's H / D");
-    if (c && (!h->con_factored || !c->factored || c->cov_kind != h->cov_kind))
+    if (c && (!h->con_factored || !c->factored || c->opt.cov_kind != h->opt.cov_kind))
         return fail(SPX_ERR_ARG, "spx_constrained_ei_grad_batch: the constraint model is not factored (spx_factor after "
                                  "spx_set_constraint_model)");
     int rc = ensure_init(h);
@@ -1880,18 +1694,18 @@ int spx_get_stat(spx_handle* h, const char* name, int64_t* value)
         return fail(SPX_ERR_ARG, "spx_get_stat: ask the per-device handles (single-GPU handles only)");
     }
     if (!strcmp(name, "flow_fallbacks")) *value = h->flow_fallbacks;          // hand-off time-outs of k_lean_flow so far
-    else if (!strcmp(name, "flow_enabled")) *value = (h->lean_flow != 0 && !h->flow_demoted);   // 0 while a time-out keeps the handle on one launch per block column
+    else if (!strcmp(name, "flow_enabled")) *value = (h->opt.lean_flow != 0 && !h->flow_demoted);   // 0 while a time-out keeps the handle on one launch per block column
     else if (!strcmp(name, "flow_rearms")) *value = h->flow_rearms;           // times the handle went back to k_lean_flow after a fallback
     else if (!strcmp(name, "ranks_seen")) *value = h->comm ? h->ranks_seen : 1;   // size of the communicator the last exchange ran on (its table has one record per rank)
     else if (!strcmp(name, "n_cu")) *value = h->n_cu;
     else if (!strcmp(name, "obs_dims")) *value = h->have_obs ? h->D : 0;   // D of the resident observations (0: none)
-    else if (!strcmp(name, "last_step_fused")) *value = h->last_fused ? 1 : 0; // the last EI pass ran k_ei_fused128
-    else if (!strcmp(name, "last_factor_flow")) *value = h->flow_used ? 1 : 0;             // the last factorisation ran k_lean_flow
-    else if (!strcmp(name, "last_factor_cov_in_flow")) *value = h->cov_in_flow_ran ? 1 : 0;   // ... which built K(X,X) tile by tile itself
-    else if (!strcmp(name, "last_logprob_one_launch")) *value = h->fused_ran ? 1 : 0;      // the last do_factor was the one-launch log-likelihood
-    else if (!strcmp(name, "last_step_skipped_padding")) *value = h->last_skip_pad ? 1 : 0;   // ... skipped the padding of N (k_predict_gemm_tail)
+    else if (!strcmp(name, "last_step_fused")) *value = h->ei_plan.fused ? 1 : 0; // the last EI pass ran k_ei_fused128
+    else if (!strcmp(name, "last_factor_flow")) *value = h->last_factor->flow ? 1 : 0;             // the last factorisation ran k_lean_flow
+    else if (!strcmp(name, "last_factor_cov_in_flow")) *value = h->last_factor->cov_in_flow ? 1 : 0;   // ... which built K(X,X) tile by tile itself
+    else if (!strcmp(name, "last_logprob_one_launch")) *value = h->last_factor->fused ? 1 : 0;      // the last do_factor was the one-launch log-likelihood
+    else if (!strcmp(name, "last_step_skipped_padding")) *value = h->ei_plan.gemm_nlive > 0 ? 1 : 0;   // ... skipped the padding of N (k_predict_gemm_tail)
     else if (!strcmp(name, "last_corun_launches")) *value = h->corun_launches;   // K(X*,X) launches of the last EI pass in the co-resident form (k_cov_corun)
-    else if (!strcmp(name, "last_kstar_ring")) *value = h->ring_used;   // slots of the K(X*,X) ring the last EI pass ran with (0: not a streams = 3 pass)
+    else if (!strcmp(name, "last_kstar_ring")) *value = h->ei_plan.R;   // slots of the K(X*,X) ring the last EI pass ran with (0: not a streams = 3 pass)
     else if (!strcmp(name, "gemm_lds_bytes")) *value = (int64_t)predict_gemm_lds_bytes();   // dynamic LDS of a predict-GEMM workgroup (two are resident per CU)
     else if (!strcmp(name, "hip_runtime_version") || !strcmp(name, "hip_driver_version")) {
         // what the process runs on: a measurement names it (bench.py's line), two boxes of one pool differed in round 5

@@ -10,6 +10,7 @@
 
 #include "../../include/spx.h"
 #include "common.h"
+#include "spx_plan.h"
 
 std::string& spx_err_slot();            // thread-local last-error text
 int spx_fail(int code, const char* fmt, ...);
@@ -86,9 +87,6 @@ struct PinBuf {
     void release() { if (p) (void)hipHostFree(p); p = nullptr; cap = 0; }
 };
 
-#ifndef SPX_DEFAULT_CORUN
-#define SPX_DEFAULT_CORUN -1          // option "kstar_corun" of a new handle (make DEFAULT_CORUN=0: the attribution build, for
-#endif                                // callers such as bench.py that set "streams" but not this option)
 
 enum Stage {
     ST_SCALE = 0, ST_COV_SELF, ST_CHOL_DIAG, ST_CHOL_PANEL, ST_TRINV, ST_GAMMA_ALPHA,
@@ -97,6 +95,14 @@ enum Stage {
 };
 struct spx_handle {
     int device = 0;
+    Options opt;                     // everything spx_set_option writes (spx_plan.h)
+    // What the last calls ran (spx_plan.h): decided by plan_factor / plan_ei before anything was queued, read back by
+    // gp_logprob_once, spx_get_factor*, the time-out recovery and spx_get_stat.  A call that fails in a reservation or a
+    // launch leaves the plan it failed with.
+    FactorPlan lean_plan;            // the last log-likelihood factorisation (spx_gp_logprob)
+    FactorPlan factor_plan;          // the last EI-path factorisation (spx_factor, spx_ei_step)
+    const FactorPlan* last_factor = &factor_plan;   // ... and whichever of the two ran last
+    EiPlan ei_plan;                  // the last EI pass
     bool inited = false;
     hipStream_t stream = nullptr;    // main stream (also the only one the factorization uses)
     hipStream_t stream2 = nullptr;   // optional producer stream (option "streams" = 2): K(X*,X) of the next
@@ -107,11 +113,8 @@ struct spx_handle {
     hipStream_t stream3 = nullptr;
     struct RingSlot { DevBuf Kst, part_bgS; hipEvent_t ready = nullptr, consumed = nullptr; };
     std::vector<RingSlot> ring;
-    int ring_opt = 0;                   // option "kstar_ring": slots of the ring (0 = from ring_budget)
-    int corun_opt = SPX_DEFAULT_CORUN;                 // option "kstar_corun": the producer's launches beside a GEMM use k_cov_corun 1 / 0 / -1 = default (on)
     int64_t ring_budget = 0;            // bytes the ring may take (a share of free device memory) ...
     int64_t ring_budget_slot = -1;      // ... as found when the size of a slot last changed
-    int ring_used = 0;                  // slots of the last streams = 3 pass (spx_get_stat "last_kstar_ring")
     int corun_launches = 0;             // K(X*,X) launches of the last pass that took k_cov_corun (spx_get_stat "last_corun_launches")
     hipEvent_t ev_t0 = nullptr, ev_t1 = nullptr;   // whole-stage timers (factor / ei_run)
     hipEvent_t ev_fac = nullptr;                   // spx_ei_step: the whole factorisation (alpha included) is done (stream)
@@ -126,28 +129,12 @@ struct spx_handle {
     int nmodels = 1;  // 1 = objective GP only, 2 = + log-duration GP
     double best = 0.0;
     int not_pd_draw = -1, not_pd_pivot = -1;
-    int64_t kst_budget = 512ll << 20;   // K(X*,X) staging buffer per stream (bytes)
-    int nstreams = 1;
-    int cov_kind = 0;                   // SPX_COVAR_* (option "covar"); SE = ARDSE kernels on unit length scales
-    int lean_lazy = -1;                 // option "lean_lazy": 0 / 1 / -1 = by batch size
-    int gemm_variant = 0;               // predict-GEMM variant of THIS handle (option "gemm_waves"); 0 = production
     int64_t fant_budget = 0;            // bytes the per-fantasy partial means may take (an eighth of free memory, <= 2 GB) ...
     int fant_budget_S = -1;             // ... as found when the number of fantasies last changed
-    int lean_one = -1;                  // option "lean_one": the log-likelihood call as ONE launch (scaling, right-hand side and the
-                                        // reduction inside k_lean_flow) 1 / 0 / -1 = default (on)
-    int lean_poll = -1;                 // option "lean_poll": the fused call's results are awaited by polling their pinned flags
-                                        // (1, default) instead of hipStreamSynchronize (0)
-    int lean_zc = -1;                   // option "lean_zc": the fused launch reads the hyper rows from the pinned staging buffer
-                                        // itself (1, default) instead of behind a host-to-device copy (0)
     double* fused_lp = nullptr;         // (spx_gp_logprob -> do_factor: pinned destinations of the fused form's results)
     int* fused_info = nullptr;
-    bool fused_ran = false;             // the last do_factor took the fused form
-    bool cov_in_flow_ran = false;       // the last do_factor's k_lean_flow built the tiles of K(X,X) itself
     const void* info_clean_ptr = nullptr;   // the not-PD flags at this address ...
     size_t info_clean_bytes = 0;            // ... in a buffer of this size are all zero (left so by the fused launch)
-    int cov_flat = -1;                  // option "cov_flat": k_cov_flat for multi-round K(X*,X) launches 1 / 0 / -1 = default (on)
-    int gemm_partial = -1;              // option "gemm_partial": skip the padding of N in the EI pass 1 / 0 / -1 = default (on)
-    bool last_skip_pad = false;         // the last EI pass did
     struct spx_multi* multi = nullptr;  // non-null: this handle fronts several per-GPU handles (spx_multi.hip)
     struct spx_comm* comm = nullptr;    // non-null: one-process-per-GPU communicator attached (spx_comm_attach)
 
@@ -190,43 +177,24 @@ struct spx_handle {
     bool rhs_rows_on = false;
     DevBuf rhs;                                                     // spx_gp_logprob: [H][64][Np] right-hand-side rows
     DevBuf diagL;                                                   // spx_gp_logprob (tile-major path): diag(L), [H][Np]
-    int lean_np = 0;                                                // padded size of the last lean factorisation (a multiple of 64, not of 128)
-    bool lean_tiled = false;                                        // the last lean factorisation used tile-major storage
-    int lean_ps = -1;                                               // option "lean_ps": 0 / 1 / -1 = default (on)
-    int lean_merge = -1;                                            // option "lean_merge": scaling + right-hand side as one launch (k_lean_prologue) 1 / 0 / -1 = default (on)
     DevBuf ps_flags;                                                // k_lean_step_ps: progress of every diagonal block, [H][nblk]
-    int lean_flow = -1;                                             // option "lean_flow": whole factorisation in one launch (k_lean_flow)
-    int ei_fused = -1;                                              // option "ei_fused": N <= 128 without fantasies: the EI pass of a chunk as ONE kernel (k_ei_fused128) 1 / 0 / -1 = default (on)
     int64_t flow_fallbacks = 0;                                     // k_lean_flow hand-off time-outs that sent this handle back to one launch per block column
     bool flow_demoted = false;                                      // ... and it is there now (until flow_rearm_after clean factorisations, or option lean_flow)
     int flow_clean = 0;                                             // clean factorisations since the last time-out
-    int flow_rearm_after = 16;                                      // option "flow_rearm_after" (0 = never)
     int64_t flow_rearms = 0;                                        // times the handle went back to k_lean_flow
-    int flow_spin_limit = 0;                                        // option "flow_spin_limit": polls before a hand-off gives up (0 = the kernel's default)
     int ranks_seen = 1;                                             // records in the last all-gather's table (spx_comm_exchange)
-    bool last_fused = false;                                        // the last EI pass used k_ei_fused128
-    int step_overlap = -1;                                          // option "step_overlap": spx_ei_step starts the candidate side beside the factorisation 1 / 0 / -1 = default (on)
     int n_cu = 256;                                                 // compute units of the device (ensure_init)
-    int ei_flow = -1;                                               // option "ei_flow": spx_factor through k_lean_flow 1 / 0 / -1 = default (on)
-    bool factor_tiled = false;                                      // the EI path's factor is tile-major (k_lean_flow made it)
-    int lean_flow_cov = -1;                                         // option "lean_flow_cov": K(X,X) built inside k_lean_flow 1 / 0 / -1 = default (on)
-    int lean_flow_yield = -1;                                       // option "lean_flow_yield": 1 / 0 / -1 = default (on)
-    int lean_flow_cu = -1;                                          // option "lean_flow_cu": one workgroup per CU 1 / 0 / -1 = by size
     DevBuf flow_flags;                                              // k_lean_flow: [H][nblk + 1][nblk] tile flags + [H][nblk] diagonal progress + the ticket and done counters
     size_t flow_flags_n = 0;                                        // ints the flags were zeroed for
     int flow_gen = 0;                                               // generation of the last call (flags are compared, not cleared)
     PinBuf pin_stage;                                               // staging of the callers' small host buffers (stage_h2d / stage_d2h in spx_api.hip)
     size_t stage_off = 0;
-    int stage_copies = -1;              // option "stage_copies"
     PinBuf pin_up, pin_res;                                         // hyper-parameter upload staging; log-likelihood results
     bool handoff_timeout = false;                                   // finish_factor saw info < 0
-    bool flow_used = false;                                         // the last factorisation ran k_lean_flow
 
     double best_val = 0.0;
     int64_t best_idx = -1;
 
-    // timing
-    bool timing = false;
     struct Ev { hipEvent_t a, b; int stage; };
     std::vector<Ev> ev_pool;
     size_t ev_used = 0;
