@@ -178,6 +178,29 @@ int spx_factor(spx_handle* h);
  * the predicted durations (spx_get_time_mean) but no func_m / func_v: spx_get_moments refuses. */
 int spx_set_fantasies(spx_handle* h, const double* fant, const double* bests, int32_t S);
 
+#define SPX_MAX_PENDING 64
+/* Pending-experiment fantasies formed by the library (GPEIChooser.py:219-249).  Call after spx_set_observations was
+ * given [comp; pend] (n = N + P rows; vals[N..n) placeholders, not read) and spx_factor / spx_ei_step has run.
+ *   P        trailing resident rows that are pending, 1 <= P <= min(SPX_MAX_PENDING, n - 1)
+ *   z        standard normals, drawn by the caller where the reference consumes its RNG:
+ *            per_draw != 0: H x P x S (draw d uses z[d]);  per_draw == 0: P x S, shared by all draws
+ *   S        1 .. 4096.   z == NULL or S == 0 clears, as spx_set_fantasies(NULL) does.
+ * Per draw: pend_m = L21 gamma[:N] + mean;  pend_K = L_S L_S^T - noise I (the product rounded, then the subtraction:
+ * no contraction);  C = lower Cholesky of pend_K;  pend_fant = C z + pend_m;
+ * bests[s] = min(np.min(vals[:N]), min_p pend_fant[p][s]) with np.min's NaN rule.
+ * Leaves the handle in the state spx_set_fantasies(fant = [tile(vals[:N]); pend_fant], bests, S) leaves it in; every
+ * later call (spx_ei_run with any flag, spx_ei_grad_batch, spx_constrained_ei_grad_batch, what drops or keeps the
+ * fantasies) behaves as after that call.  Gamma is written in its factored form: rows < N of every column are gamma[:N],
+ * rows N..n are L_S^-1 C z_s, pad rows are zero.  Nothing of the factor travels to the host,
+ * and no H x n x S array is formed anywhere.
+ * SPX_ERR_NOT_PD when a pivot of some draw's pend_K is not > 0 (spla.cholesky raising at :239); spx_not_pd_info then
+ * reports draw 4H + d and the 0-based pivot inside the P x P block; the handle then holds no fantasies.
+ * SPX_ERR_ARG: not factored, P or S out of range, the 2-D partition.  (A time model over other rows than these n cannot
+ * be resident: spx_set_time_model takes the durations of the resident rows, and new observations drop it.) */
+int spx_draw_fantasies(spx_handle* h, int32_t P, const double* z, int32_t per_draw, int32_t S);
+/* pend_fant (P x S, row-major) and bests (S) of draw `draw`, as the last spx_draw_fantasies formed them; either may be NULL */
+int spx_get_pending_fantasies(spx_handle* h, int32_t draw, double* pend_fant, double* bests);
+
 /* Hot path, stage 2: K(X*,X) (:187), triangular solve (:195), predictive
  * mean/variance (:198-199), EI (:202-206) for every (candidate, draw); then the
  * MCMC mean and the argmax (:153).  Results stay on the device.               */
@@ -378,6 +401,9 @@ int spx_get_timings(spx_handle* h, double* ms, int64_t* launches, int n);
  *   "last_logprob_one_launch"  1 if the last spx_gp_logprob ran as ONE launch (option "lean_one");
  *   "last_step_skipped_padding"  1 if the last EI pass left the padding of N (to the GEMM's 128-row tiles) uncomputed
  *                      (option "gemm_partial", default on: same bits, up to -31 % per pass just above a multiple of 128);
+ *   "last_fantasies_device"  1 while the resident fantasies came from spx_draw_fantasies; 0 after spx_set_fantasies or when there are none
+ *                      (on a multi-device handle: device slot 0's);   "fantasies_pending_rows", "fantasies_count": P and S of those
+ *                      fantasies (the sizes spx_get_pending_fantasies writes), 0 while last_fantasies_device is 0;
  *   "last_kstar_ring"  staging slots of the K(X*,X) ring the last EI pass ran with (option "streams" = 3; 0: it ran another way);
  *   "last_corun_launches"  K(X*,X) launches of that pass in the form that fits beside two GEMM workgroups (k_cov_corun);
  *   "gemm_lds_bytes"   dynamic LDS of one predict-GEMM workgroup (two are resident per CU; the co-resident K(X*,X) form uses none);

@@ -205,9 +205,7 @@ class GPConstrainedEIChooser(GPEIBase):
             eng.set_constraint_model(comp, self.cst.ff, crows)     # quirk 2: self.ff, the same for every draw
         if pend.shape[0] > 0:
             eng.factor()
-            fant, bests = hostgp.fantasies_from_engine(eng, valsv, rows, compv.shape[0], pend.shape[0],
-                                                       self.pending_samples, randn, per_draw=True)
-            eng.set_fantasies(fant, bests)
+            self._set_fantasies(eng, valsv, rows, compv.shape[0], pend.shape[0], self.pending_samples, randn, per_draw=True)
             eng.ei_run(FLAG_CONSTRAINED)
         else:
             eng.ei_step(FLAG_CONSTRAINED)
@@ -233,9 +231,7 @@ class GPConstrainedEIChooser(GPEIBase):
             rs = npr.RandomState()
             rs.set_state(self.randomstate)
             randn = rs.randn(pend.shape[0], self.pending_samples)
-            fant, bests = hostgp.fantasies_from_engine(eng, valsv, rows, valsv.shape[0], pend.shape[0],
-                                                       self.pending_samples, randn, per_draw=False)
-            eng.set_fantasies(fant, bests)
+            self._set_fantasies(eng, valsv, rows, valsv.shape[0], pend.shape[0], self.pending_samples, randn, per_draw=False)
         best = np.min(valsv)
         return refine.lbfgs_many(lambda X: eng.constrained_ei_grad_batch(X, best), points, [(0, 1)] * comp.shape[1],
                                  log=log)

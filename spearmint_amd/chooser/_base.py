@@ -48,7 +48,7 @@ class GPEIBase(object):
 
     def __init__(self, expt_dir, covar="Matern52", mcmc_iters=10, pending_samples=100,
                  noiseless=False, device=0, ndev=1, lib=None, gpu_logprob="auto", gpu_refine="auto",
-                 lookahead="auto", follow="auto", sampler="native", gpu_sobol=0, **unused):
+                 lookahead="auto", follow="auto", sampler="native", gpu_sobol=0, gpu_fantasies="auto", **unused):
         if covar not in hostgp.COVARS:
             # the reference does getattr(gp, covar) here (GPEIChooser.py:52)
             raise AttributeError("no covariance function %r (gp.py has %s)" % (covar, ", ".join(hostgp.COVARS)))
@@ -78,6 +78,10 @@ class GPEIBase(object):
         # every size (scripts/dev/refine_threshold.py, 10 draws: one call for all 20 refinement points 0.06 ms from N = 8 to
         # N = 128; the host's per-draw models 0.74 ms per POINT at N = 8, 0.96 at 128): "auto" = GPU.
         self.gpu_refine = str(gpu_refine)
+        # who forms the posterior of the pending points and the fantasies: "1" / "auto" the library (spx_draw_fantasies:
+        # only the standard normals travel), "0" the host from the factor's bottom rows (hostgp.fantasies_from_engine,
+        # the oracle of the device form).  The normals are drawn in the same place and order either way.
+        self.gpu_fantasies = str(gpu_fantasies)
         # Depth of the slice sampler's speculation (util.slice_sample_batched): `lookahead` = step-out points per side and
         # shrink proposals evaluated per GPU call; `follow` = "P:H": cross-move speculation -- the next coordinate move's
         # edges, ladder and first P proposals under the hypotheses "this move accepts its 1st ... H-th proposal" ride in
@@ -182,6 +186,23 @@ class GPEIBase(object):
         if self.gpu_refine == "auto":    # the GPU wins from N = 8 on; SPX_REFINE_MIN_N keeps the first proposals on the host
             return n >= int(os.environ.get("SPX_REFINE_MIN_N", "0"))
         return _as_bool(self.gpu_refine)
+
+    def _use_gpu_fantasies(self, eng, n_pend):
+        if self.gpu_fantasies != "auto" and not _as_bool(self.gpu_fantasies):
+            return False
+        if not hasattr(eng, "draw_fantasies"):
+            return False
+        from ..engine import MAX_PENDING
+        return n_pend <= MAX_PENDING
+
+    def _set_fantasies(self, eng, vals, hyper_rows, n_comp, n_pend, S, randn, per_draw):
+        """The engine, factored over [comp; pend], gets its fantasies from the normals `randn` (per_draw: randn[h] is
+        draw h's (P, S) array): on the device, or through the host posterior (GPEIChooser.py:219-249)."""
+        if self._use_gpu_fantasies(eng, n_pend):
+            eng.draw_fantasies(randn, n_pend)      # (per_draw: the list of H (P, S) arrays becomes one (H, P, S) array there)
+            return
+        fant, bests = hostgp.fantasies_from_engine(eng, vals, hyper_rows, n_comp, n_pend, S, randn, per_draw=per_draw)
+        eng.set_fantasies(fant, bests)
 
     def _speculation_depth(self, comp, vals):
         """(lookahead, (follow proposals, follow hypotheses)) for this problem size.
@@ -525,10 +546,10 @@ class GPEIBase(object):
     def _ei_with_pending_gpu(self, comp, pend, cand, vals, hyper_rows, randn, want_draws):
         """Pending experiments: fantasise their outcomes (GPEIChooser.py:209-266).
         GPU: factorisation of cov([comp; pend]) for every draw, K(X*,X), the solve,
-        Sigma beta^2 and the S fantasy means, EI averaged over fantasies.  Host: the
-        O(N^2 P) posterior of the P pending points and the S joint fantasy draws
-        (`randn[h]` is the (P, S) standard-normal matrix of draw h, drawn by the
-        caller at the point where the reference consumes the RNG)."""
+        Sigma beta^2 and the S fantasy means, EI averaged over fantasies -- and, unless
+        gpu_fantasies=0, the posterior of the P pending points and the S joint fantasy
+        draws (_set_fantasies).  Host: `randn[h]`, the (P, S) standard-normal matrix of
+        draw h, drawn by the caller at the point where the reference consumes the RNG."""
         hyper_rows = np.ascontiguousarray(np.atleast_2d(hyper_rows), dtype=np.float64)
         n_comp, n_pend = comp.shape[0], pend.shape[0]
         eng = self.engine()
@@ -538,9 +559,7 @@ class GPEIBase(object):
         eng.set_candidates(cand)
         eng.set_hypers(hyper_rows)
         eng.factor()
-        fant, bests = hostgp.fantasies_from_engine(eng, vals, hyper_rows, n_comp, n_pend, randn[0].shape[1], randn,
-                                                   per_draw=True)
-        eng.set_fantasies(fant, bests)
+        self._set_fantasies(eng, vals, hyper_rows, n_comp, n_pend, randn[0].shape[1], randn, per_draw=True)
         eng.ei_run()
         idx, _ = eng.best()
         mean = eng.ei_mean()

@@ -138,6 +138,13 @@ void launch_ei_fused128(hipStream_t s, int kind, const double* WT, const double*
                         double* ei_draw, double* mom_m, double* mom_v, int N, int Mc, int Dp, int nh, int64_t c0,
                         int64_t M, int64_t Mp, int n_cu);
 
+// fantasy_kernels.hip: the pending posterior and the fantasies of spx_draw_fantasies
+size_t fant_post_stride(int P);   // doubles per draw of `post`: C [P][P] | T = L_S^-1 C [P][P] | pend_m [P] | np.min(vals[:N])
+void launch_fant_posterior(hipStream_t s, const double* Lm, bool tiled, const double* gamma, const double* htab,
+                           const double* vals, double* post, int* info, int N, int P, int Np, int H);
+void launch_fant_fill(hipStream_t s, const double* post, const double* z, size_t z_stride, const double* gamma,
+                      double* gammaS, double* bests, double* pend_fant, int N, int P, int Np, int S, int H);
+
 // sobol_kernels.hip
 void launch_sobol_grid(hipStream_t s, const uint32_t* dirs, int dim, int64_t n, int64_t skip, double* out);
 

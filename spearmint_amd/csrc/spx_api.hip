@@ -276,7 +276,7 @@ void spx_destroy(spx_handle* h)
                           &h->s1, &h->Lm, &h->WT, &h->Dinv, &h->gamma, &h->alpha, &h->info, &h->lp,
                           &h->Cs[0], &h->s2[0], &h->Kst[0], &h->part_ss[0], &h->part_bg[0], &h->time_m[0],
                           &h->Cs[1], &h->s2[1], &h->Kst[1], &h->part_ss[1], &h->part_bg[1], &h->time_m[1],
-                          &h->fantT, &h->gammaS, &h->bests, &h->part_bgS[0], &h->part_bgS[1],
+                          &h->fantT, &h->gammaS, &h->bests, &h->part_bgS[0], &h->part_bgS[1], &h->fant_z, &h->fant_post, &h->fant_pend, &h->fant_info,
                           &h->pt_x, &h->pt_k, &h->pt_dk, &h->pt_t, &h->pt_z, &h->pt_out, &h->pt_kt, &h->pt_dkt,
                           &h->ei_draw, &h->ei_mean, &h->mom_m, &h->mom_v, &h->mom_t, &h->am_val, &h->am_idx,
                           &h->am_out_val, &h->am_out_idx, &h->scratch, &h->sobol_dirs, &h->sobol_out, &h->rhs, &h->diagL, &h->ps_flags, &h->flow_flags,
@@ -747,6 +747,7 @@ int spx_set_fantasies(spx_handle* h, const double* fant, const double* bests, in
 {
     if (!h) return fail(SPX_ERR_ARG, "spx_set_fantasies: null handle");
     if (h->multi) return spx_multi_set_fantasies(h->multi, fant, bests, S);
+    h->fant_device = false;
     if (!fant || !bests || S <= 0) { h->S = 0; return SPX_OK; }   // clear
     if (!h->factored) return fail(SPX_ERR_ARG, "spx_set_fantasies: call spx_factor first");
     if (S > 4096) return fail(SPX_ERR_ARG, "spx_set_fantasies: at most 4096 fantasies (got %d)", S);
@@ -775,6 +776,67 @@ int spx_set_fantasies(spx_handle* h, const double* fant, const double* bests, in
     h->S = S;
     h->alphaS_valid = false;
     h->ran = false; h->ran_time = false;
+    return SPX_OK;
+}
+
+// The pending branch without the host (GPEIChooser.py:219-249): the posterior of the P trailing rows from the resident
+// factor, the fantasies from the caller's normals, bests and Gamma -- two launches and one wait for the device; P S (or H P S)
+// doubles go up, H flags come back.  Gamma's first N rows do not depend on the fantasy (L is lower triangular): they are
+// copied from gamma, only the last P are solved for (fantasy_kernels.hip).
+int spx_draw_fantasies(spx_handle* h, int32_t P, const double* z, int32_t per_draw, int32_t S)
+{
+    if (!h) return fail(SPX_ERR_ARG, "spx_draw_fantasies: null handle");
+    if (h->multi) return spx_multi_draw_fantasies(h->multi, P, z, per_draw, S);
+    if (!z || S <= 0) { h->S = 0; h->fant_device = false; return SPX_OK; }   // clear
+    if (!h->factored) return fail(SPX_ERR_ARG, "spx_draw_fantasies: call spx_factor first");
+    if (S > 4096) return fail(SPX_ERR_ARG, "spx_draw_fantasies: at most 4096 fantasies (got %d)", S);
+    if (P < 1 || P > SPX_MAX_PENDING || P > h->N - 1)
+        return fail(SPX_ERR_ARG, "spx_draw_fantasies: P = %d pending rows, need 1 .. min(%d, n - 1) with n = %lld", P,
+                    SPX_MAX_PENDING, (long long)h->N);
+    int rc = ensure_init(h);
+    if (rc) return rc;
+    const int H = h->H, Np = h->Np, Nc = (int)(h->N - P);
+    const size_t zcount = (size_t)(per_draw ? H : 1) * P * S;
+    if ((rc = h->fant_z.reserve(zcount * 8))) return rc;
+    if ((rc = h->fant_post.reserve((size_t)H * fant_post_stride(P) * 8))) return rc;
+    if ((rc = h->fant_pend.reserve((size_t)H * P * S * 8))) return rc;
+    if ((rc = h->fant_info.reserve((size_t)H * sizeof(int)))) return rc;
+    if ((rc = h->gammaS.reserve((size_t)H * S * Np * 8))) return rc;
+    if ((rc = h->bests.reserve((size_t)H * S * 8))) return rc;
+    hipStream_t s = h->stream;
+    stage_begin(h);
+    if ((rc = stage_h2d(h, h->fant_z.p, z, zcount * 8, s))) return rc;
+    launch_fant_posterior(s, h->Lm.d(), factor_tiled(h), h->gamma.d(), h->htab.d(), h->vals.d(), h->fant_post.d(),
+                          (int*)h->fant_info.p, Nc, P, Np, H);
+    launch_fant_fill(s, h->fant_post.d(), h->fant_z.d(), per_draw ? (size_t)P * S : 0, h->gamma.d(), h->gammaS.d(),
+                     h->bests.d(), h->fant_pend.d(), Nc, P, Np, S, H);
+    std::vector<int> info(H);
+    h->S = 0; h->fant_device = false;      // (until the flags are home)
+    if ((rc = stage_d2h(h, info.data(), h->fant_info.p, (size_t)H * sizeof(int), s))) return rc;
+    LAUNCHCHK();
+    h->alphaS_valid = false;
+    h->ran = false; h->ran_time = false;
+    for (int d = 0; d < H; ++d)     // (a clean call leaves spx_not_pd_info what the factorisation made it, as spx_set_fantasies does)
+        if (info[d]) {
+            h->not_pd_draw = 4 * H + d; h->not_pd_pivot = info[d] - 1;
+            return fail(SPX_ERR_NOT_PD, "%d-th leading minor of the array is not positive definite (draw %d, posterior of "
+                                        "the pending points)", info[d], d);
+        }
+    h->S = S; h->fant_P = P; h->fant_device = true;
+    return SPX_OK;
+}
+
+int spx_get_pending_fantasies(spx_handle* h, int32_t draw, double* pend_fant, double* bests)
+{
+    if (h && h->multi) return spx_multi_get_pending_fantasies(h->multi, draw, pend_fant, bests);
+    if (!h || !h->factored || h->S <= 0 || !h->fant_device)
+        return fail(SPX_ERR_ARG, "spx_get_pending_fantasies: call spx_draw_fantasies first");
+    if (draw < 0 || draw >= h->H) return fail(SPX_ERR_ARG, "spx_get_pending_fantasies: draw out of range");
+    int rc = ensure_init(h);
+    if (rc) return rc;
+    const size_t ps = (size_t)h->fant_P * h->S;
+    if (pend_fant && (rc = stage_d2h(h, pend_fant, h->fant_pend.d() + (size_t)draw * ps, ps * 8, h->stream))) return rc;
+    if (bests && (rc = stage_d2h(h, bests, h->bests.d() + (size_t)draw * h->S, (size_t)h->S * 8, h->stream))) return rc;
     return SPX_OK;
 }
 
@@ -1689,7 +1751,8 @@ int spx_get_stat(spx_handle* h, const char* name, int64_t* value)
 {
     if (!h || !name || !value) return fail(SPX_ERR_ARG, "spx_get_stat: null");
     if (h->multi) {
-        if (!strcmp(name, "ranks_seen") || !strcmp(name, "flow_fallbacks") || !strcmp(name, "flow_rearms") || !strcmp(name, "obs_dims"))
+        if (!strcmp(name, "ranks_seen") || !strcmp(name, "flow_fallbacks") || !strcmp(name, "flow_rearms") || !strcmp(name, "obs_dims")
+            || !strcmp(name, "last_fantasies_device") || !strcmp(name, "fantasies_pending_rows") || !strcmp(name, "fantasies_count"))
             return spx_multi_stat(h->multi, name, value);
         return fail(SPX_ERR_ARG, "spx_get_stat: ask the per-device handles (single-GPU handles only)");
     }
@@ -1705,6 +1768,9 @@ int spx_get_stat(spx_handle* h, const char* name, int64_t* value)
     else if (!strcmp(name, "last_logprob_one_launch")) *value = h->last_factor->fused ? 1 : 0;      // the last do_factor was the one-launch log-likelihood
     else if (!strcmp(name, "last_step_skipped_padding")) *value = h->ei_plan.gemm_nlive > 0 ? 1 : 0;   // ... skipped the padding of N (k_predict_gemm_tail)
     else if (!strcmp(name, "last_corun_launches")) *value = h->corun_launches;   // K(X*,X) launches of the last EI pass in the co-resident form (k_cov_corun)
+    else if (!strcmp(name, "last_fantasies_device")) *value = (h->S > 0 && h->fant_device) ? 1 : 0;   // the resident fantasies came from spx_draw_fantasies
+    else if (!strcmp(name, "fantasies_pending_rows")) *value = (h->S > 0 && h->fant_device) ? h->fant_P : 0;   // ... P and
+    else if (!strcmp(name, "fantasies_count")) *value = (h->S > 0 && h->fant_device) ? h->S : 0;               // ... S of them
     else if (!strcmp(name, "last_kstar_ring")) *value = h->ei_plan.R;   // slots of the K(X*,X) ring the last EI pass ran with (0: not a streams = 3 pass)
     else if (!strcmp(name, "gemm_lds_bytes")) *value = (int64_t)predict_gemm_lds_bytes();   // dynamic LDS of a predict-GEMM workgroup (two are resident per CU)
     else if (!strcmp(name, "hip_runtime_version") || !strcmp(name, "hip_driver_version")) {

@@ -150,6 +150,10 @@ struct spx_handle {
     DevBuf fantT, gammaS, bests, part_bgS[2];
     DevBuf alphaS;                 // [H][S][Np] = W^T Gamma_s, built on the first spx_ei_grad_batch after spx_set_fantasies
     bool alphaS_valid = false;
+    // spx_draw_fantasies: the resident fantasies were formed on the device from P trailing pending rows
+    bool fant_device = false;
+    int fant_P = 0;
+    DevBuf fant_z, fant_post, fant_pend, fant_info;   // z as uploaded; C | T | pend_m | min per draw; pend_fant [H][P][S]; pivot flags [H]
     DevBuf pt_x, pt_k, pt_dk, pt_t, pt_z, pt_out, pt_kt, pt_dkt, pt_u;   // spx_ei_grad_batch work vectors
     DevBuf rec_send, rec_recv, rec_out;   // {best mean EI, global index} records of the multi-GPU all-gather
     // 2-D partition with a communicator attached (spx_set_partition): the M_total-vector of EI sums / means
@@ -213,6 +217,8 @@ int spx_multi_set_hypers(spx_multi* m, const double* hypers, int32_t H);
 int spx_multi_set_time_model(spx_multi* m, const double* log_durs, const double* time_hypers);
 int spx_multi_factor(spx_multi* m);
 int spx_multi_set_fantasies(spx_multi* m, const double* fant, const double* bests, int32_t S);
+int spx_multi_draw_fantasies(spx_multi* m, int32_t P, const double* z, int32_t per_draw, int32_t S);
+int spx_multi_get_pending_fantasies(spx_multi* m, int32_t draw, double* pend_fant, double* bests);
 int spx_multi_ei_run(spx_multi* m, int32_t flags);
 int spx_multi_get_best(spx_multi* m, int64_t* best_idx, double* best_val);
 int spx_multi_get_ei_mean(spx_multi* m, double* out);

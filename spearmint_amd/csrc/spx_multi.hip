@@ -679,6 +679,7 @@ int spx_multi_info(spx_multi* m, int32_t* n_dev, int32_t* transport, int32_t* de
 int spx_multi_stat(spx_multi* m, const char* name, int64_t* value)
 {
     if (!strcmp(name, "ranks_seen")) { *value = m->n; return SPX_OK; }   // the device slots of the handle (= the size of its communicator)
+    if (!strcmp(name, "last_fantasies_device") || !strcmp(name, "fantasies_pending_rows") || !strcmp(name, "fantasies_count")) return spx_get_stat(m->kids[0], name, value);   // replicated: every slot holds the same
     if (!strcmp(name, "obs_dims")) { *value = m->N > 0 ? m->D : 0; return SPX_OK; }   // D of the resident observations (0: none)
     if (!strcmp(name, "flow_fallbacks") || !strcmp(name, "flow_rearms")) {   // summed over the devices' handles
         int64_t sum = 0;
@@ -814,6 +815,19 @@ int spx_multi_set_fantasies(spx_multi* m, const double* fant, const double* best
     if (m->ph > 1 && fant && bests && S > 0)
         return fail(SPX_ERR_ARG, "spx_set_fantasies: not available in the 2-D partition (spx_set_partition)");
     return m->pool->run([=](int i) { return spx_set_fantasies(m->kids[i], fant, bests, S); });
+}
+
+int spx_multi_draw_fantasies(spx_multi* m, int32_t P, const double* z, int32_t per_draw, int32_t S)
+{
+    m->ran = false;
+    if (m->ph > 1 && z && S > 0)
+        return fail(SPX_ERR_ARG, "spx_draw_fantasies: not available in the 2-D partition (spx_set_partition)");
+    return m->pool->run([=](int i) { return spx_draw_fantasies(m->kids[i], P, z, per_draw, S); });   // replicated, as the factor is
+}
+
+int spx_multi_get_pending_fantasies(spx_multi* m, int32_t draw, double* pend_fant, double* bests)
+{
+    return spx_get_pending_fantasies(m->kids[0], draw, pend_fant, bests);
 }
 
 int spx_multi_ei_run(spx_multi* m, int32_t flags)

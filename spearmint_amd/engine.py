@@ -31,6 +31,7 @@ FLAG_KEEP_MOMENTS = 2
 FLAG_TIMING = 4
 FLAG_TIME_ONLY = 8
 FLAG_CONSTRAINED = 16
+MAX_PENDING = 64      # include/spx.h SPX_MAX_PENDING: pending rows spx_draw_fantasies takes
 
 _c_double_p = ctypes.POINTER(ctypes.c_double)
 _c_int64_p = ctypes.POINTER(ctypes.c_int64)
@@ -92,6 +93,8 @@ ABI = {
     "spx_set_constraint_model": (ctypes.c_int, [_vp, _c_double_p, _c_double_p, ctypes.c_int64, _c_double_p]),
     "spx_factor": (ctypes.c_int, [_vp]),
     "spx_set_fantasies": (ctypes.c_int, [_vp, _c_double_p, _c_double_p, ctypes.c_int32]),
+    "spx_draw_fantasies": (ctypes.c_int, [_vp, ctypes.c_int32, _c_double_p, ctypes.c_int32, ctypes.c_int32]),
+    "spx_get_pending_fantasies": (ctypes.c_int, [_vp, ctypes.c_int32, _c_double_p, _c_double_p]),
     "spx_ei_run": (ctypes.c_int, [_vp, ctypes.c_int32]),
     "spx_ei_step": (ctypes.c_int, [_vp, ctypes.c_int32]),
     "spx_get_best": (ctypes.c_int, [_vp, _c_int64_p, _c_double_p]),
@@ -375,6 +378,34 @@ class Engine(object):
         if fant.ndim != 3 or fant.shape[0] != self.H or fant.shape[1] != self.N or bests.shape != (self.H, fant.shape[2]):
             raise ValueError("fant must be (H, n, S) and bests (H, S)")
         self._check(self._lib.spx_set_fantasies(self._h, _dp(fant), _dp(bests), fant.shape[2]))
+
+    def draw_fantasies(self, z, n_pend):
+        """The pending posterior, the fantasies, bests and Gamma formed on the device (include/spx.h: spx_draw_fantasies)
+        from standard normals z: (P, S) shared by every draw, or (H, P, S) with draw d using z[d].  The last P = n_pend
+        resident rows are the pending points.  None clears.  LinAlgError where spla.cholesky of a draw's posterior
+        covariance would raise."""
+        if z is None:
+            self._check(self._lib.spx_draw_fantasies(self._h, 0, None, 0, 0))
+            return
+        z = _f64(z)
+        P = int(n_pend)
+        if z.ndim == 2 and z.shape[0] == P:
+            per_draw = 0
+        elif z.ndim == 3 and z.shape[0] == self.H and z.shape[1] == P:
+            per_draw = 1
+        else:
+            raise ValueError("z must be (P, S) or (H, P, S) with P = n_pend")
+        self._check(self._lib.spx_draw_fantasies(self._h, P, _dp(z), per_draw, z.shape[-1]))
+
+    def get_pending_fantasies(self, draw):
+        """(pend_fant (P, S), bests (S,)) of one draw as the last draw_fantasies formed them."""
+        P, S = self.stat("fantasies_pending_rows"), self.stat("fantasies_count")     # the handle's own sizes
+        if P < 1 or S < 1:
+            raise ValueError("get_pending_fantasies: call draw_fantasies first")
+        pf = np.empty((P, S))
+        b = np.empty(S)
+        self._check(self._lib.spx_get_pending_fantasies(self._h, int(draw), _dp(pf), _dp(b)))
+        return pf, b
 
     def ei_run(self, flags=0):
         self._check(self._lib.spx_ei_run(self._h, int(flags)))
