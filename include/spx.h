@@ -147,7 +147,8 @@ int spx_set_candidates(spx_handle* h, const double* cand, int64_t M, int32_t D,
 /* H hyper-parameter draws, rows [mean, noise, amp2, ls...] */
 int spx_set_hypers(spx_handle* h, const double* hypers, int32_t H);
 /* second GP on log durations (GPEIperSecChooser.py:176, :437-458):
- * log_durs (N), time_hypers H x (3+D).  Pass NULLs to clear.                  */
+ * log_durs (N), time_hypers H x (3+D).  Pass NULLs to clear.  Either form
+ * drops the factorisation and everything made from it (fantasies, results).    */
 int spx_set_time_model(spx_handle* h, const double* log_durs,
                        const double* time_hypers);
 /* Probit constraint GP (GPConstrainedEIChooser.py:816-842): Nc points comp_c (Nc x D, all completed jobs, Nc independent
@@ -156,7 +157,8 @@ int spx_set_time_model(spx_handle* h, const double* log_durs,
  * by the next spx_factor / spx_ei_step, before the objective draws, on an internal handle of the same device (same
  * factorisation path, SPX_ERR_NOT_PD as for the objective; spx_not_pd_info reports draw 2H + d; 3H + d is the objective's
  * draw d over these Nc points, factored by spx_constrained_ei_grad_batch).  Nc = 0 is the
- * all-valid case (comp_c / ff may be NULL): P_d = Phi(gain_d).  All three pointers NULL clears the model.
+ * all-valid case (comp_c / ff may be NULL): P_d = Phi(gain_d).  All three pointers NULL clears the model.  Either form
+ * drops the results of the last pass and the two factorisations over X_c; the objective's own factor stays.
  * SPX_ERR_ARG on a multi-device handle.                                                                            */
 int spx_set_constraint_model(spx_handle* h, const double* comp_c, const double* ff, int64_t Nc,
                              const double* c_hypers);

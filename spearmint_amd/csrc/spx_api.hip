@@ -169,8 +169,12 @@ static int opt_covar(spx_handle* h, int64_t value)
 {
     if (value < SPX_COVAR_MATERN52 || value > SPX_COVAR_SE)
         return fail(SPX_ERR_ARG, "spx_set_option: covar=%lld is not one of SPX_COVAR_*", (long long)value);
-    if (h->opt.cov_kind != (int)value) { h->factored = false; h->ran = false; h->ran_time = false; h->S = 0; h->full_valid = false; }
+    if (h->opt.cov_kind == (int)value) return SPX_OK;
     h->opt.cov_kind = (int)value;
+    spx_drop(h, Held::COVAR);         // the three factorisations and what was made from them
+    // the internal handles follow at once: their factors, scaled rows and (SE) unit length scales belong to the old kernel
+    if (h->con) opt_covar(h->con, value);
+    if (h->full) opt_covar(h->full, value);
     return SPX_OK;
 }
 static int opt_lean_flow(spx_handle* h, int64_t value)
@@ -366,8 +370,8 @@ int spx_set_observations(spx_handle* h, const double* comp, const double* vals, 
         return fail(SPX_ERR_ARG, "spx_set_observations: bad arguments (N=%lld, D=%d)", (long long)N, D);
     int rc = ensure_init(h);
     if (rc) return rc;
-    if (h->have_cand && D != h->D) h->have_cand = false;
-    if (h->have_hyp && D != h->D) { h->have_hyp = false; h->have_time = false; }
+    spx_drop(h, Held::OBS);
+    if (D != h->D) { spx_drop(h, Held::CAND); spx_drop(h, Held::HYP); }   // (candidates and hypers of another dimension)
     h->N = N; h->D = D; h->Dp = padded_dim(D); h->Np = (int)round_up(N, SPX_PADN);
     if ((rc = h->comp.reserve((size_t)N * D * 8))) return rc;
     if ((rc = h->vals.reserve((size_t)N * 8))) return rc;
@@ -381,9 +385,7 @@ int spx_set_observations(spx_handle* h, const double* comp, const double* vals, 
     }
     h->best = b;
     HIPCHK(hipStreamSynchronize(h->stream));
-    h->have_obs = true; h->have_time = false; h->factored = false; h->ran = false; h->ran_time = false; h->S = 0;
-    h->full_valid = false;
-    return SPX_OK;
+    return spx_hold(h, Held::OBS);
 }
 
 int spx_set_candidates(spx_handle* h, const double* cand, int64_t M, int32_t D, int64_t index_base)
@@ -391,18 +393,18 @@ int spx_set_candidates(spx_handle* h, const double* cand, int64_t M, int32_t D, 
     if (h && h->multi) return spx_multi_set_candidates(h->multi, cand, M, D, index_base);
     if (!h || !cand || M < 1 || D < 1)
         return fail(SPX_ERR_ARG, "spx_set_candidates: bad arguments (M=%lld, D=%d)", (long long)M, D);
-    if (h->have_obs && D != h->D)
+    if (h->held.has(Held::OBS) && D != h->D)
         return fail(SPX_ERR_ARG, "spx_set_candidates: D=%d but observations have D=%d", D, h->D);
     int rc = ensure_init(h);
     if (rc) return rc;
-    if (!h->have_obs) { h->D = D; h->Dp = padded_dim(D); }
+    spx_drop(h, Held::CAND);
+    if (!h->held.has(Held::OBS)) { h->D = D; h->Dp = padded_dim(D); }
     h->M = M; h->index_base = index_base;
     if ((rc = h->cand.reserve((size_t)M * D * 8))) return rc;
     stage_begin(h);
     if ((rc = stage_h2d(h, h->cand.p, cand, (size_t)M * D * 8, h->stream))) return rc;
     HIPCHK(hipStreamSynchronize(h->stream));
-    h->have_cand = true; h->ran = false; h->ran_time = false;
-    return SPX_OK;
+    return spx_hold(h, Held::CAND);
 }
 
 int spx_set_hypers(spx_handle* h, const double* hypers, int32_t H)
@@ -411,30 +413,29 @@ int spx_set_hypers(spx_handle* h, const double* hypers, int32_t H)
     if (!h || !hypers || H < 1) return fail(SPX_ERR_ARG, "spx_set_hypers: bad arguments (H=%d)", H);
     if (H > NP_PAIRWISE_MAX_N)   // the mean over draws walks numpy's pairwise tree with fixed-depth stacks (np_sum.h)
         return fail(SPX_ERR_ARG, "spx_set_hypers: at most %d hyper-parameter draws (got %d)", NP_PAIRWISE_MAX_N, H);
-    if (!h->have_obs) return fail(SPX_ERR_ARG, "spx_set_hypers: call spx_set_observations first");
+    if (!h->held.has(Held::OBS)) return fail(SPX_ERR_ARG, "spx_set_hypers: call spx_set_observations first");
+    spx_drop(h, Held::HYP);
     h->H = H;
     h->hyp_host.assign(hypers, hypers + (size_t)H * (3 + h->D));
-    h->have_hyp = true; h->have_time = false; h->factored = false; h->ran = false; h->ran_time = false; h->S = 0;
-    h->full_valid = false;
-    return SPX_OK;
+    return spx_hold(h, Held::HYP);
 }
 
 int spx_set_time_model(spx_handle* h, const double* log_durs, const double* time_hypers)
 {
     if (!h) return fail(SPX_ERR_ARG, "spx_set_time_model: null handle");
     if (h->multi) return spx_multi_set_time_model(h->multi, log_durs, time_hypers);
-    if (!log_durs || !time_hypers) { h->have_time = false; h->factored = false; return SPX_OK; }
-    if (!h->have_obs || !h->have_hyp)
+    if (!log_durs || !time_hypers) { spx_drop(h, Held::TIME); return SPX_OK; }
+    if (!h->held.has(Held::OBS) || !h->held.has(Held::HYP))
         return fail(SPX_ERR_ARG, "spx_set_time_model: set observations and hypers first");
     int rc = ensure_init(h);
     if (rc) return rc;
+    spx_drop(h, Held::TIME);
     if ((rc = h->ldur.reserve((size_t)h->N * 8))) return rc;
     stage_begin(h);
     if ((rc = stage_h2d(h, h->ldur.p, log_durs, (size_t)h->N * 8, h->stream))) return rc;
     HIPCHK(hipStreamSynchronize(h->stream));
     h->thyp_host.assign(time_hypers, time_hypers + (size_t)h->H * (3 + h->D));
-    h->have_time = true; h->factored = false; h->ran = false; h->ran_time = false;
-    return SPX_OK;
+    return spx_hold(h, Held::TIME);
 }
 
 // ---------------------------------------------------------------------------
@@ -445,20 +446,21 @@ int spx_set_constraint_model(spx_handle* h, const double* comp_c, const double* 
     if (!h) return fail(SPX_ERR_ARG, "spx_set_constraint_model: null handle");
     if (h->multi) return fail(SPX_ERR_ARG, "spx_set_constraint_model: the constraint model is single-device only "
                                            "(multi-device handles and hyper_shards > 1 are not supported)");
-    if (!comp_c && !ff && !c_hypers) { h->have_con = false; h->con_factored = false; h->ran_con = false; h->full_valid = false; return SPX_OK; }
-    if (!h->have_obs || !h->have_hyp)
+    if (!comp_c && !ff && !c_hypers) { spx_drop(h, Held::CON); return SPX_OK; }
+    if (!h->held.has(Held::OBS) || !h->held.has(Held::HYP))
         return fail(SPX_ERR_ARG, "spx_set_constraint_model: set observations and hypers first");
     if (!c_hypers || Nc < 0 || Nc > (1 << 20) || (Nc > 0 && (!comp_c || !ff)))
         return fail(SPX_ERR_ARG, "spx_set_constraint_model: bad arguments (Nc=%lld)", (long long)Nc);
     int rc = ensure_init(h);
     if (rc) return rc;
     const int H = h->H, D = h->D, hs = 3 + D;
+    spx_drop(h, Held::CON);
     if (Nc > 0) {
         if (!h->con) {
             if ((rc = spx_create(h->device, &h->con))) return rc;
             h->con->opt.stage_copies = h->opt.stage_copies;
+            h->con->opt.cov_kind = h->opt.cov_kind;     // (from here on option "covar" reaches it: opt_covar)
         }
-        h->con->opt.cov_kind = h->opt.cov_kind;
         // the factor's rows: [0, noise_c, amp2_c, ls_c...] -- alpha_c = K_c^-1 (ff - 0): no mean term (:819-842)
         std::vector<double> rows(c_hypers, c_hypers + (size_t)H * hs);
         for (int i = 0; i < H; ++i) rows[(size_t)i * hs] = 0.0;
@@ -466,7 +468,6 @@ int spx_set_constraint_model(spx_handle* h, const double* comp_c, const double* 
         if ((rc = spx_set_hypers(h->con, rows.data(), H))) return rc;
         h->con_comp_host.assign(comp_c, comp_c + (size_t)Nc * D);
     }
-    h->full_valid = false;
     h->con_tab_host.assign((size_t)H * SPX_HT, 0.0);
     for (int i = 0; i < H; ++i) {
         const double* r = c_hypers + (size_t)i * hs;
@@ -478,20 +479,15 @@ int spx_set_constraint_model(spx_handle* h, const double* comp_c, const double* 
     if ((rc = stage_h2d(h, h->con_tab.p, h->con_tab_host.data(), h->con_tab_host.size() * 8, h->stream))) return rc;
     HIPCHK(hipStreamSynchronize(h->stream));
     h->con_n = Nc;
-    h->have_con = true; h->con_factored = false; h->ran_con = false; h->ran = false;
-    return SPX_OK;
+    return spx_hold(h, Held::CON);
 }
 
 // The constraint model's alpha_c, before the objective's factorisation (spx_factor / spx_ei_step).  Its own handle, its own
 // synchronisation: a not-PD constraint covariance is reported as draw 2H + d.
 static int factor_constraint(spx_handle* h)
 {
-    if (!h->have_con || h->con_n == 0) return SPX_OK;
+    if (!h->held.has(Held::CON) || h->con_n == 0 || h->held.has(Held::CON_FACTOR)) return SPX_OK;
     spx_handle* c = h->con;
-    // option "covar" changed since the last factorisation: alpha_c, the scaled rows and (SE) the unit length scales of the
-    // internal handle belong to the old kernel
-    if (c->opt.cov_kind != h->opt.cov_kind) { c->opt.cov_kind = h->opt.cov_kind; c->factored = false; h->con_factored = false; }
-    if (h->con_factored) return SPX_OK;
     if (c->H != h->H || c->D != h->D)
         return fail(SPX_ERR_ARG, "spx_factor: the constraint model has H=%d, D=%d but the objective H=%d, D=%d "
                                  "(call spx_set_constraint_model again)", c->H, c->D, h->H, h->D);
@@ -503,8 +499,7 @@ static int factor_constraint(spx_handle* h)
                     c->not_pd_pivot + 1, c->not_pd_draw);
     }
     if (rc) return rc;
-    h->con_factored = true;
-    return SPX_OK;
+    return spx_hold(h, Held::CON_FACTOR);
 }
 
 // A hand-off of k_lean_flow timed out (its polls are bounded: an error, never a hang; not seen on a healthy device -- a
@@ -535,13 +530,14 @@ static void warn_flow_fallback(spx_handle* h)
 // together with its result, synchronises ONCE and calls finish_factor (one host round trip per call instead of two)
 static int do_factor(spx_handle* h, bool tolerate_not_pd, bool lean = false, bool defer_sync = false)
 {
-    if (!h->have_obs || !h->have_hyp)
+    if (!h->held.has(Held::OBS) || !h->held.has(Held::HYP))
         return fail(SPX_ERR_ARG, "spx_factor: observations and hypers must be set first");
     int rc = ensure_init(h);
     if (rc) return rc;
+    spx_drop(h, Held::FACTOR);      // both paths overwrite Xs, the hyper tables and L; finish_factor sets it again (not the lean path)
     FactorShape sh;
     sh.N = h->N; sh.D = h->D; sh.H = h->H; sh.Np = h->Np;
-    sh.have_time = h->have_time; sh.lean = lean; sh.defer_sync = defer_sync; sh.have_dest = h->fused_lp != nullptr;
+    sh.have_time = h->held.has(Held::TIME); sh.lean = lean; sh.defer_sync = defer_sync; sh.have_dest = h->fused_lp != nullptr;
     sh.flow_demoted = h->flow_demoted; sh.rhs_rows_on = h->rhs_rows_on;
     FactorPlan& p = lean ? h->lean_plan : h->factor_plan;
     p = plan_factor(h->opt, sh);              // every decision of this call (spx_plan.h); below: reserve, upload, launch
@@ -707,15 +703,10 @@ static int finish_factor(spx_handle* h, const std::vector<int>& info, bool toler
     }
     for (int i = 0; i < nh; ++i)
         if (info[i]) { h->not_pd_draw = i; h->not_pd_pivot = info[i] - 1; break; }
-    h->factored = !lean;
-    h->ran = false; h->ran_time = false;
-    h->S = 0;
-    if (h->not_pd_draw >= 0 && !tolerate_not_pd) {
-        h->factored = false;
+    if (h->not_pd_draw >= 0 && !tolerate_not_pd)
         return fail(SPX_ERR_NOT_PD, "%d-th leading minor of the array is not positive definite (draw %d%s)",
                     h->not_pd_pivot + 1, h->not_pd_draw % H, h->not_pd_draw >= H ? ", time model" : "");
-    }
-    return SPX_OK;
+    return lean ? SPX_OK : spx_hold(h, Held::FACTOR);
 }
 
 int spx_factor(spx_handle* h)
@@ -743,16 +734,26 @@ int spx_not_pd_info(spx_handle* h, int32_t* draw, int32_t* pivot)
     return SPX_OK;
 }
 
+// The clear forms of spx_set_fantasies / spx_draw_fantasies: the fantasies go; the results of the last pass, a record of what
+// it computed with them, stay readable (as they always did -- the next pass runs without them)
+static int clear_fantasies(spx_handle* h)
+{
+    const bool had = h->held.has(Held::RESULTS);
+    const Held::Results r = h->held.results;
+    spx_drop(h, Held::FANT);
+    return had ? spx_hold(h, Held::RESULTS, r) : (int)SPX_OK;
+}
+
 int spx_set_fantasies(spx_handle* h, const double* fant, const double* bests, int32_t S)
 {
     if (!h) return fail(SPX_ERR_ARG, "spx_set_fantasies: null handle");
     if (h->multi) return spx_multi_set_fantasies(h->multi, fant, bests, S);
-    h->fant_device = false;
-    if (!fant || !bests || S <= 0) { h->S = 0; return SPX_OK; }   // clear
-    if (!h->factored) return fail(SPX_ERR_ARG, "spx_set_fantasies: call spx_factor first");
+    if (!fant || !bests || S <= 0) return clear_fantasies(h);
+    if (!h->held.has(Held::FACTOR)) return fail(SPX_ERR_ARG, "spx_set_fantasies: call spx_factor first");
     if (S > 4096) return fail(SPX_ERR_ARG, "spx_set_fantasies: at most 4096 fantasies (got %d)", S);
     int rc = ensure_init(h);
     if (rc) return rc;
+    spx_drop(h, Held::FANT);
     const int H = h->H, Np = h->Np;
     const int64_t n = h->N;
     // host transpose to [H][S][n] so that every fantasy column is a contiguous right-hand side
@@ -774,9 +775,7 @@ int spx_set_fantasies(spx_handle* h, const double* fant, const double* bests, in
     HIPCHK(hipStreamSynchronize(s));
     LAUNCHCHK();
     h->S = S;
-    h->alphaS_valid = false;
-    h->ran = false; h->ran_time = false;
-    return SPX_OK;
+    return spx_hold(h, Held::FANT);
 }
 
 // The pending branch without the host (GPEIChooser.py:219-249): the posterior of the P trailing rows from the resident
@@ -787,14 +786,15 @@ int spx_draw_fantasies(spx_handle* h, int32_t P, const double* z, int32_t per_dr
 {
     if (!h) return fail(SPX_ERR_ARG, "spx_draw_fantasies: null handle");
     if (h->multi) return spx_multi_draw_fantasies(h->multi, P, z, per_draw, S);
-    if (!z || S <= 0) { h->S = 0; h->fant_device = false; return SPX_OK; }   // clear
-    if (!h->factored) return fail(SPX_ERR_ARG, "spx_draw_fantasies: call spx_factor first");
+    if (!z || S <= 0) return clear_fantasies(h);
+    if (!h->held.has(Held::FACTOR)) return fail(SPX_ERR_ARG, "spx_draw_fantasies: call spx_factor first");
     if (S > 4096) return fail(SPX_ERR_ARG, "spx_draw_fantasies: at most 4096 fantasies (got %d)", S);
     if (P < 1 || P > SPX_MAX_PENDING || P > h->N - 1)
         return fail(SPX_ERR_ARG, "spx_draw_fantasies: P = %d pending rows, need 1 .. min(%d, n - 1) with n = %lld", P,
                     SPX_MAX_PENDING, (long long)h->N);
     int rc = ensure_init(h);
     if (rc) return rc;
+    spx_drop(h, Held::FANT);
     const int H = h->H, Np = h->Np, Nc = (int)(h->N - P);
     const size_t zcount = (size_t)(per_draw ? H : 1) * P * S;
     if ((rc = h->fant_z.reserve(zcount * 8))) return rc;
@@ -811,11 +811,8 @@ int spx_draw_fantasies(spx_handle* h, int32_t P, const double* z, int32_t per_dr
     launch_fant_fill(s, h->fant_post.d(), h->fant_z.d(), per_draw ? (size_t)P * S : 0, h->gamma.d(), h->gammaS.d(),
                      h->bests.d(), h->fant_pend.d(), Nc, P, Np, S, H);
     std::vector<int> info(H);
-    h->S = 0; h->fant_device = false;      // (until the flags are home)
     if ((rc = stage_d2h(h, info.data(), h->fant_info.p, (size_t)H * sizeof(int), s))) return rc;
     LAUNCHCHK();
-    h->alphaS_valid = false;
-    h->ran = false; h->ran_time = false;
     for (int d = 0; d < H; ++d)     // (a clean call leaves spx_not_pd_info what the factorisation made it, as spx_set_fantasies does)
         if (info[d]) {
             h->not_pd_draw = 4 * H + d; h->not_pd_pivot = info[d] - 1;
@@ -823,13 +820,13 @@ int spx_draw_fantasies(spx_handle* h, int32_t P, const double* z, int32_t per_dr
                                         "the pending points)", info[d], d);
         }
     h->S = S; h->fant_P = P; h->fant_device = true;
-    return SPX_OK;
+    return spx_hold(h, Held::FANT);
 }
 
 int spx_get_pending_fantasies(spx_handle* h, int32_t draw, double* pend_fant, double* bests)
 {
     if (h && h->multi) return spx_multi_get_pending_fantasies(h->multi, draw, pend_fant, bests);
-    if (!h || !h->factored || h->S <= 0 || !h->fant_device)
+    if (!h || !h->held.has(Held::FANT) || !h->fant_device)
         return fail(SPX_ERR_ARG, "spx_get_pending_fantasies: call spx_draw_fantasies first");
     if (draw < 0 || draw >= h->H) return fail(SPX_ERR_ARG, "spx_get_pending_fantasies: draw out of range");
     int rc = ensure_init(h);
@@ -858,7 +855,7 @@ static int check_run_flags(const spx_handle* h, int32_t flags, int nmodels)
         return fail(SPX_ERR_ARG, "spx_ei_run: SPX_FLAG_PER_SEC needs spx_set_time_model before spx_factor");
     if (flags & SPX_FLAG_CONSTRAINED) {
         if (per_sec) return fail(SPX_ERR_ARG, "spx_ei_run: SPX_FLAG_CONSTRAINED cannot be combined with SPX_FLAG_PER_SEC");
-        if (!h->have_con) return fail(SPX_ERR_ARG, "spx_ei_run: SPX_FLAG_CONSTRAINED needs spx_set_constraint_model");
+        if (!h->held.has(Held::CON)) return fail(SPX_ERR_ARG, "spx_ei_run: SPX_FLAG_CONSTRAINED needs spx_set_constraint_model");
         if (h->comm) return fail(SPX_ERR_ARG, "spx_ei_run: SPX_FLAG_CONSTRAINED is single-device only (communicator attached)");
         if (h->con_n > 0 && (h->con->H != h->H || h->con->D != h->D))
             return fail(SPX_ERR_ARG, "spx_ei_run: the constraint model does not match the objective's H / D");
@@ -890,18 +887,17 @@ int spx_ei_step(spx_handle* h, int32_t flags)
         int rc = spx_multi_factor(h->multi);
         return rc ? rc : spx_multi_ei_run(h->multi, flags & ~SPX_FLAG_TIME_ONLY);
     }
-    if (h->opt.timing || (flags & SPX_FLAG_TIMING) || !h->have_cand) {   // stage timers bracket each call: keep the two-call form
+    if (h->opt.timing || (flags & SPX_FLAG_TIMING) || !h->held.has(Held::CAND)) {   // stage timers bracket each call: keep the two-call form
         int rc = spx_factor(h);
         return rc ? rc : ei_run_impl(h, flags, false);
     }
     // the pass's argument checks BEFORE anything is queued (ei_run_impl repeats them for spx_ei_run)
-    int rc = check_run_flags(h, flags, h->have_time ? 2 : 1);
+    int rc = check_run_flags(h, flags, h->held.has(Held::TIME) ? 2 : 1);
     if (rc) return rc;
     if ((rc = factor_constraint(h))) return rc;
     h->handoff_timeout = false;
     rc = do_factor(h, false, false, true);
     if (rc) return rc;
-    h->S = 0;                      // a new factorisation drops the fantasies (finish_factor), here before the run
     rc = ei_run_impl(h, flags, true);
     if (rc == SPX_ERR_HIP && h->handoff_timeout && h->last_factor->flow) {   // as in spx_factor: bounded, then the launches
         note_flow_timeout(h);
@@ -913,25 +909,25 @@ int spx_ei_step(spx_handle* h, int32_t flags)
     if (rc) {
         // any other error exit of a pending step (argument checks that depend on the plan, a failed reservation, a launch
         // error): the factorisation may still be queued -- every entry point returns with the streams idle (the pinned
-        // upload staging relies on it) and without a factor it did not check
+        // upload staging relies on it); the factor it did not check is not held (do_factor dropped it)
         (void)hipStreamSynchronize(h->stream);
         (void)hipStreamSynchronize(h->stream2);
         if (h->stream3) (void)hipStreamSynchronize(h->stream3);
         (void)hipGetLastError();
-        if (rc != SPX_ERR_NOT_PD) h->factored = false;
     }
     return rc;
 }
 
 static int ei_run_impl(spx_handle* h, int32_t flags, bool factor_pending)
 {
-    if (!h->factored && !factor_pending) return fail(SPX_ERR_ARG, "spx_ei_run: call spx_factor first");
-    if (!h->have_cand) return fail(SPX_ERR_ARG, "spx_ei_run: no candidates set");
+    if (!h->held.has(Held::FACTOR) && !factor_pending) return fail(SPX_ERR_ARG, "spx_ei_run: call spx_factor first");
+    if (!h->held.has(Held::CAND)) return fail(SPX_ERR_ARG, "spx_ei_run: no candidates set");
     int rc = check_run_flags(h, flags, h->nmodels);
     if (rc) return rc;
     if ((rc = ensure_init(h))) return rc;
-    if ((flags & SPX_FLAG_CONSTRAINED) && h->con_n > 0 && (!h->con_factored || h->con->opt.cov_kind != h->opt.cov_kind))
+    if ((flags & SPX_FLAG_CONSTRAINED) && h->con_n > 0 && !h->held.has(Held::CON_FACTOR))
         return fail(SPX_ERR_ARG, "spx_ei_run: the constraint model is not factored (spx_factor after spx_set_constraint_model)");
+    spx_drop(h, Held::RESULTS);     // the pass overwrites them; a failed one keeps the factor and the fantasies
     EiShape sh;
     sh.N = h->N; sh.M = h->M; sh.Np = h->Np; sh.D = h->D; sh.H = h->H; sh.S = h->S; sh.nmodels = h->nmodels;
     sh.flags = flags; sh.factor_pending = factor_pending; sh.kst_budget = h->opt.kst_budget;
@@ -1167,7 +1163,7 @@ static int ei_run_impl(spx_handle* h, int32_t flags, bool factor_pending)
     h->best_idx = ((const int64_t*)mirror)[1];
     if (factor_pending) {
         std::vector<int> info((const int*)(mirror + 2), (const int*)(mirror + 2) + n_info);
-        if ((rc = finish_factor(h, info, false, false))) { h->ran = false; h->ran_time = false; return rc; }
+        if ((rc = finish_factor(h, info, false, false))) return rc;
     }
     float ms = 0.f;
     (void)hipEventElapsedTime(&ms, t0, t1);
@@ -1175,20 +1171,19 @@ static int ei_run_impl(spx_handle* h, int32_t flags, bool factor_pending)
         ev_collect(h);
         h->st_ms[ST_EI_RUN_TOTAL] += ms; h->st_n[ST_EI_RUN_TOTAL] += 1;
     }
-    h->ran = !time_only;             // (a time-only pass has no EI results: spx_get_best & co. refuse)
-    h->ran_time = time_only;
-    h->ran_2d = false;
-    h->ran_moments = keep_mom && S == 0 && !time_only;
-    h->ran_tmean = keep_mom && per_sec;       // (with fantasies the pass keeps no func_m / func_v, but mom_t is written all the same)
-    h->ran_con = constrained && keep_mom && !time_only;
-    if (h->comm) return spx_comm_exchange(h);   // one process per GPU: the winner over all ranks
-    return SPX_OK;
+    Held::Results r;
+    r.time_only = time_only;         // (a time-only pass has no EI results: spx_get_best & co. refuse)
+    r.moments = keep_mom && S == 0 && !time_only;
+    r.tmean = keep_mom && per_sec;   // (with fantasies the pass keeps no func_m / func_v, but mom_t is written all the same)
+    r.con = constrained && keep_mom && !time_only;
+    if (h->comm && (rc = spx_comm_exchange(h, &r.global2d))) return rc;   // one process per GPU: the winner over all ranks
+    return spx_hold(h, Held::RESULTS, r);
 }
 
 int spx_get_best(spx_handle* h, int64_t* best_idx, double* best_val)
 {
     if (h && h->multi) return spx_multi_get_best(h->multi, best_idx, best_val);
-    if (!h || !h->ran) return fail(SPX_ERR_ARG, "spx_get_best: no results (call spx_ei_run)");
+    if (!h || !h->held.ei()) return fail(SPX_ERR_ARG, "spx_get_best: no results (call spx_ei_run)");
     if (best_idx) *best_idx = h->best_idx + h->index_base;
     if (best_val) *best_val = h->best_val;
     return SPX_OK;
@@ -1197,18 +1192,18 @@ int spx_get_best(spx_handle* h, int64_t* best_idx, double* best_val)
 int spx_get_ei_mean(spx_handle* h, double* out)
 {
     if (h && h->multi) return spx_multi_get_ei_mean(h->multi, out);
-    if (!h || !out || !h->ran) return fail(SPX_ERR_ARG, "spx_get_ei_mean: no results / null output");
+    if (!h || !out || !h->held.ei()) return fail(SPX_ERR_ARG, "spx_get_ei_mean: no results / null output");
     int rc = ensure_init(h);
     if (rc) return rc;
     // after the all-reduce of a partitioned run: the GLOBAL mean (all draws of all ranks) of this handle's candidates
-    const double* src = h->ran_2d ? h->ei_sum_full.d() + h->index_base : h->ei_mean.d();
+    const double* src = h->held.results.global2d ? h->ei_sum_full.d() + h->index_base : h->ei_mean.d();
     return stage_d2h(h, out, src, (size_t)h->M * 8, h->stream);
 }
 
 int spx_get_ei_draws(spx_handle* h, double* out)
 {
     if (h && h->multi) return spx_multi_get_ei_draws(h->multi, out);
-    if (!h || !out || !h->ran) return fail(SPX_ERR_ARG, "spx_get_ei_draws: no results / null output");
+    if (!h || !out || !h->held.ei()) return fail(SPX_ERR_ARG, "spx_get_ei_draws: no results / null output");
     int rc = ensure_init(h);
     if (rc) return rc;
     const int64_t M = h->M, Mp = round_up(M, SPX_BN);
@@ -1236,7 +1231,7 @@ static int get_draw_rows(spx_handle* h, const char* who, int32_t draw, const Dev
 int spx_get_moments(spx_handle* h, int32_t draw, double* func_m, double* func_v)
 {
     if (h && h->multi) return spx_multi_get_moments(h->multi, draw, func_m, func_v);
-    if (!h || !h->ran || !h->ran_moments)
+    if (!h || !h->held.results.moments)
         return fail(SPX_ERR_ARG, "spx_get_moments: run spx_ei_run with SPX_FLAG_KEEP_MOMENTS first");
     return get_draw_rows(h, "spx_get_moments", draw, h->mom_m, func_m, &h->mom_v, func_v);
 }
@@ -1244,7 +1239,7 @@ int spx_get_moments(spx_handle* h, int32_t draw, double* func_m, double* func_v)
 int spx_get_time_mean(spx_handle* h, int32_t draw, double* out)
 {
     if (h && h->multi) return spx_multi_get_time_mean(h->multi, draw, out);
-    if (!h || !out || !((h->ran && (h->ran_moments || h->ran_tmean)) || h->ran_time) || h->nmodels != 2)
+    if (!h || !out || !(h->held.results.moments || h->held.results.tmean) || h->nmodels != 2)
         return fail(SPX_ERR_ARG, "spx_get_time_mean: run spx_ei_run with SPX_FLAG_PER_SEC | SPX_FLAG_KEEP_MOMENTS first");
     return get_draw_rows(h, "spx_get_time_mean", draw, h->mom_t, out);
 }
@@ -1252,7 +1247,7 @@ int spx_get_time_mean(spx_handle* h, int32_t draw, double* out)
 int spx_get_constraint_prob(spx_handle* h, int32_t draw, double* out)
 {
     if (h && h->multi) return fail(SPX_ERR_ARG, "spx_get_constraint_prob: the constraint model is single-device only");
-    if (!h || !out || !h->ran || !h->ran_con)
+    if (!h || !out || !h->held.results.con)
         return fail(SPX_ERR_ARG, "spx_get_constraint_prob: run spx_ei_run with SPX_FLAG_CONSTRAINED | SPX_FLAG_KEEP_MOMENTS first");
     return get_draw_rows(h, "spx_get_constraint_prob", draw, h->mom_c, out);
 }
@@ -1270,7 +1265,7 @@ static inline double tile_elem(const double* tile, bool diagonal, int ri, int cj
 int spx_get_factor(spx_handle* h, int32_t draw, double* K, double* L, double* alpha)
 {
     if (h && h->multi) return spx_multi_get_factor(h->multi, draw, K, L, alpha);
-    if (!h || !h->factored) return fail(SPX_ERR_ARG, "spx_get_factor: call spx_factor first");
+    if (!h || !h->held.has(Held::FACTOR)) return fail(SPX_ERR_ARG, "spx_get_factor: call spx_factor first");
     const int nh = h->nmodels * h->H;
     if (draw < 0 || draw >= nh) return fail(SPX_ERR_ARG, "spx_get_factor: draw out of range");
     int rc = ensure_init(h);
@@ -1313,7 +1308,7 @@ int spx_get_factor(spx_handle* h, int32_t draw, double* K, double* L, double* al
 int spx_get_factor_rows(spx_handle* h, int32_t draw, int64_t row0, int64_t nrows, double* L_rows, double* gamma)
 {
     if (h && h->multi) return spx_multi_get_factor_rows(h->multi, draw, row0, nrows, L_rows, gamma);
-    if (!h || !h->factored) return fail(SPX_ERR_ARG, "spx_get_factor_rows: call spx_factor first");
+    if (!h || !h->held.has(Held::FACTOR)) return fail(SPX_ERR_ARG, "spx_get_factor_rows: call spx_factor first");
     const int nh = h->nmodels * h->H;
     const int64_t N = h->N;
     if (draw < 0 || draw >= nh) return fail(SPX_ERR_ARG, "spx_get_factor_rows: draw out of range");
@@ -1349,7 +1344,7 @@ int spx_get_factor_rows(spx_handle* h, int32_t draw, int64_t row0, int64_t nrows
 int spx_get_cross_cov(spx_handle* h, int32_t draw, int64_t c0, int64_t nc, double* out)
 {
     if (h && h->multi) return spx_multi_get_cross_cov(h->multi, draw, c0, nc, out);
-    if (!h || !out || !h->factored || !h->have_cand)
+    if (!h || !out || !h->held.has(Held::FACTOR) || !h->held.has(Held::CAND))
         return fail(SPX_ERR_ARG, "spx_get_cross_cov: need spx_factor and candidates");
     const int nh = h->nmodels * h->H;
     if (draw < 0 || draw >= nh || c0 < 0 || nc < 1 || c0 + nc > h->M)
@@ -1401,7 +1396,7 @@ int spx_gp_logprob_rhs(spx_handle* h, const double* rows, const double* rhs, int
     if (!h || !rows || !rhs || !lp_out) return fail(SPX_ERR_ARG, "spx_gp_logprob_rhs: null argument");
     if (h->multi) return fail(SPX_ERR_ARG, "spx_gp_logprob_rhs: single-device only (multi-device handle)");
     if (n_rows < 1 || n_rows > 32) return fail(SPX_ERR_ARG, "spx_gp_logprob_rhs: 1 .. 32 rows per call (got %d)", n_rows);
-    if (!h->have_obs) return fail(SPX_ERR_ARG, "spx_gp_logprob_rhs: call spx_set_observations first (the points)");
+    if (!h->held.has(Held::OBS)) return fail(SPX_ERR_ARG, "spx_gp_logprob_rhs: call spx_set_observations first (the points)");
     int rc = spx_set_hypers(h, rows, n_rows);
     if (rc) return rc;
     const size_t bytes = (size_t)n_rows * h->N * 8;
@@ -1523,13 +1518,14 @@ int spx_sobol_grid(spx_handle* h, const uint32_t* dirs, int32_t dim_max, int32_t
     if (skip + n - 2 >= (1ll << 30) || skip < -(1ll << 40))
         return fail(SPX_ERR_ARG, "spx_sobol_grid: skip + n - 2 = %lld does not fit 30 direction columns "
                     "(the reference stops with 'Too many calls')", (long long)(skip + n - 2));
-    if (as_candidates && h->have_obs && dim != h->D)
+    if (as_candidates && h->held.has(Held::OBS) && dim != h->D)
         return fail(SPX_ERR_ARG, "spx_sobol_grid: dim=%d but observations have D=%d", dim, h->D);
     int rc = ensure_init(h);
     if (rc) return rc;
     hipStream_t s = h->stream;
     const size_t tbytes = (size_t)dim * 30 * sizeof(uint32_t);
     if ((rc = h->sobol_dirs.reserve(tbytes))) return rc;
+    if (as_candidates) spx_drop(h, Held::CAND);
     DevBuf& dst = as_candidates ? h->cand : h->sobol_out;
     if ((rc = dst.reserve((size_t)n * dim * 8))) return rc;
     HIPCHK(hipMemcpyAsync(h->sobol_dirs.p, dirs, tbytes, hipMemcpyHostToDevice, s));
@@ -1545,9 +1541,9 @@ int spx_sobol_grid(spx_handle* h, const uint32_t* dirs, int32_t dim_max, int32_t
         *kernel_ms = ms;
     }
     if (as_candidates) {
-        if (!h->have_obs) { h->D = dim; h->Dp = padded_dim(dim); }
+        if (!h->held.has(Held::OBS)) { h->D = dim; h->Dp = padded_dim(dim); }
         h->M = n; h->index_base = 0;
-        h->have_cand = true; h->ran = false; h->ran_time = false;
+        return spx_hold(h, Held::CAND);
     }
     return SPX_OK;
 }
@@ -1610,10 +1606,10 @@ static int refine_solve(spx_handle* h, const double* points, int P, const Refine
         if ((rc = refine_rows_reserve(h, rows[i], P))) return rc;
     if (S > 0) {
         if ((rc = h->pt_u.reserve((size_t)H * P * Np * 8))) return rc;
-        if (!h->alphaS_valid) {
+        if (!h->held.has(Held::ALPHA_S)) {
             if ((rc = h->alphaS.reserve((size_t)H * S * Np * 8))) return rc;
             launch_trimvT_multi(h->stream, h->WT.d(), h->gammaS.d(), h->alphaS.d(), Np, H, S);
-            h->alphaS_valid = true;
+            if ((rc = spx_hold(h, Held::ALPHA_S))) return rc;
         }
     }
     stage_begin(h);
@@ -1663,7 +1659,7 @@ int spx_ei_grad_batch(spx_handle* h, const double* points, int32_t P, double* ne
 {
     if (!h || !points || !neg_ei || !grad || P < 1) return fail(SPX_ERR_ARG, "spx_ei_grad_batch: bad argument");
     if (h->multi) return spx_multi_ei_grad_batch(h->multi, points, P, neg_ei, grad);
-    if (!h->factored) return fail(SPX_ERR_ARG, "spx_ei_grad_batch: call spx_factor (or spx_ei_grid) first");
+    if (!h->held.has(Held::FACTOR)) return fail(SPX_ERR_ARG, "spx_ei_grad_batch: call spx_factor (or spx_ei_grid) first");
     const bool per_sec = (h->nmodels == 2);   // a time model was factored: EI per second (GPEIperSecChooser.py:349-434)
     if (h->S > 0 && per_sec)
         return fail(SPX_ERR_ARG, "spx_ei_grad_batch: fantasies with a time model are not defined "
@@ -1688,15 +1684,14 @@ int spx_ei_grad(spx_handle* h, const double* point, double* neg_ei_sum, double* 
 // points, through the ordinary factorisation path on an internal handle.  Not positive definite: draw 3H + d.
 static int ensure_full_factor(spx_handle* h)
 {
-    if (h->full_valid && h->full && h->full->factored && h->full->opt.cov_kind == h->opt.cov_kind) return SPX_OK;
-    h->full_valid = false;
+    if (h->held.has(Held::FULL_FACTOR)) return SPX_OK;
     int rc;
     if (!h->full) {
         if ((rc = spx_create(h->device, &h->full))) return rc;
         h->full->opt.stage_copies = h->opt.stage_copies;
+        h->full->opt.cov_kind = h->opt.cov_kind;     // (from here on option "covar" reaches it: opt_covar)
     }
     spx_handle* f = h->full;
-    f->opt.cov_kind = h->opt.cov_kind;
     const std::vector<double> zeros((size_t)h->con_n, 0.0);   // (the values are not read: only W_f and the scaled rows are)
     if ((rc = spx_set_observations(f, h->con_comp_host.data(), zeros.data(), h->con_n, h->D))) return rc;
     if ((rc = spx_set_hypers(f, h->hyp_host.data(), h->H))) return rc;
@@ -1708,8 +1703,7 @@ static int ensure_full_factor(spx_handle* h)
                                     "constraint model's points)", f->not_pd_pivot + 1, f->not_pd_draw);
     }
     if (rc) return rc;
-    h->full_valid = true;
-    return SPX_OK;
+    return spx_hold(h, Held::FULL_FACTOR);
 }
 
 int spx_constrained_ei_grad_batch(spx_handle* h, const double* points, int32_t P, double best, double* neg_cei, double* grad)
@@ -1717,8 +1711,8 @@ int spx_constrained_ei_grad_batch(spx_handle* h, const double* points, int32_t P
     if (!h || !points || !neg_cei || !grad || P < 1) return fail(SPX_ERR_ARG, "spx_constrained_ei_grad_batch: bad argument");
     if (h->multi) return fail(SPX_ERR_ARG, "spx_constrained_ei_grad_batch: the constraint model is single-device only "
                                            "(multi-device handle)");
-    if (!h->factored) return fail(SPX_ERR_ARG, "spx_constrained_ei_grad_batch: call spx_factor (or spx_ei_step) first");
-    if (!h->have_con) return fail(SPX_ERR_ARG, "spx_constrained_ei_grad_batch: needs spx_set_constraint_model");
+    if (!h->held.has(Held::FACTOR)) return fail(SPX_ERR_ARG, "spx_constrained_ei_grad_batch: call spx_factor (or spx_ei_step) first");
+    if (!h->held.has(Held::CON)) return fail(SPX_ERR_ARG, "spx_constrained_ei_grad_batch: needs spx_set_constraint_model");
     if (h->nmodels == 2) return fail(SPX_ERR_ARG, "spx_constrained_ei_grad_batch: not defined with a time model");
     if ((int64_t)h->con_tab_host.size() != (int64_t)h->H * SPX_HT)
         return fail(SPX_ERR_ARG, "spx_constrained_ei_grad_batch: the constraint model has a different number of draws");
@@ -1726,7 +1720,7 @@ int spx_constrained_ei_grad_batch(spx_handle* h, const double* points, int32_t P
     spx_handle* c = Nc > 0 ? h->con : nullptr;
     if (c && (c->H != h->H || c->D != h->D))
         return fail(SPX_ERR_ARG, "spx_constrained_ei_grad_batch: the constraint model does not match the objective's H / D");
-    if (c && (!h->con_factored || !c->factored || c->opt.cov_kind != h->opt.cov_kind))
+    if (c && !h->held.has(Held::CON_FACTOR))
         return fail(SPX_ERR_ARG, "spx_constrained_ei_grad_batch: the constraint model is not factored (spx_factor after "
                                  "spx_set_constraint_model)");
     int rc = ensure_init(h);
@@ -1761,7 +1755,7 @@ int spx_get_stat(spx_handle* h, const char* name, int64_t* value)
     else if (!strcmp(name, "flow_rearms")) *value = h->flow_rearms;           // times the handle went back to k_lean_flow after a fallback
     else if (!strcmp(name, "ranks_seen")) *value = h->comm ? h->ranks_seen : 1;   // size of the communicator the last exchange ran on (its table has one record per rank)
     else if (!strcmp(name, "n_cu")) *value = h->n_cu;
-    else if (!strcmp(name, "obs_dims")) *value = h->have_obs ? h->D : 0;   // D of the resident observations (0: none)
+    else if (!strcmp(name, "obs_dims")) *value = h->held.has(Held::OBS) ? h->D : 0;   // D of the resident observations (0: none)
     else if (!strcmp(name, "last_step_fused")) *value = h->ei_plan.fused ? 1 : 0; // the last EI pass ran k_ei_fused128
     else if (!strcmp(name, "last_factor_flow")) *value = h->last_factor->flow ? 1 : 0;             // the last factorisation ran k_lean_flow
     else if (!strcmp(name, "last_factor_cov_in_flow")) *value = h->last_factor->cov_in_flow ? 1 : 0;   // ... which built K(X,X) tile by tile itself

@@ -11,6 +11,7 @@
 #include "../../include/spx.h"
 #include "common.h"
 #include "spx_plan.h"
+#include "spx_held.h"
 
 std::string& spx_err_slot();            // thread-local last-error text
 int spx_fail(int code, const char* fmt, ...);
@@ -122,11 +123,8 @@ struct spx_handle {
 
     int64_t N = 0, M = 0, index_base = 0;
     int D = 0, Dp = 0, Np = 0, H = 0;
-    bool have_obs = false, have_cand = false, have_hyp = false, have_time = false;
-    bool factored = false, ran = false, ran_moments = false;
-    bool ran_time = false;           // the last pass was SPX_FLAG_TIME_ONLY: predicted durations are valid, EI results are not
-    bool ran_tmean = false;          // the last pass kept its predicted durations (PER_SEC | KEEP_MOMENTS), with or without fantasies
-    int nmodels = 1;  // 1 = objective GP only, 2 = + log-duration GP
+    Held held;        // what of all this is resident and valid (spx_held.h); taken away by spx_drop below alone
+    int nmodels = 1;  // what FACTOR was built with: 1 = objective GP only, 2 = + log-duration GP
     double best = 0.0;
     int not_pd_draw = -1, not_pd_pivot = -1;
     int64_t fant_budget = 0;            // bytes the per-fantasy partial means may take (an eighth of free memory, <= 2 GB) ...
@@ -145,11 +143,10 @@ struct spx_handle {
     DevBuf Xs, X2s, s1, Lm, WT, Dinv, gamma, alpha, info, lp;
     DevBuf Cs[2], s2[2], Kst[2], part_ss[2], part_bg[2], time_m[2], ei_draw, ei_mean, mom_m, mom_v, mom_t;
     DevBuf am_val, am_idx, am_out_val, am_out_idx, scratch;
-    // pending-experiment fantasies (spx_set_fantasies): S right-hand sides per draw
+    // pending-experiment fantasies (spx_set_fantasies): S right-hand sides per draw; S > 0 exactly when FANT is held
     int S = 0;
     DevBuf fantT, gammaS, bests, part_bgS[2];
-    DevBuf alphaS;                 // [H][S][Np] = W^T Gamma_s, built on the first spx_ei_grad_batch after spx_set_fantasies
-    bool alphaS_valid = false;
+    DevBuf alphaS;                 // [H][S][Np] = W^T Gamma_s, built on the first spx_ei_grad_batch after spx_set_fantasies (ALPHA_S)
     // spx_draw_fantasies: the resident fantasies were formed on the device from P trailing pending rows
     bool fant_device = false;
     int fant_P = 0;
@@ -160,13 +157,11 @@ struct spx_handle {
     int part_ph = 1;
     int64_t part_M = 0;            // > 0: the collective is the all-reduce(SUM) of EI sums
     int part_H = 0;
-    bool ran_2d = false;
     DevBuf ei_sum_full;
     DevBuf sobol_dirs, sobol_out;                                   // spx_sobol_grid
     // probit constraint model (spx_set_constraint_model): an internal handle on the same device factors
     // (amp2_c (K_c + 1e-6 I) + noise_c I) alpha_c = ff over its own Nc points; the EI pass reads its scaled rows and alpha_c
     spx_handle* con = nullptr;
-    bool have_con = false, con_factored = false, ran_con = false;
     int64_t con_n = 0;                                              // Nc (0: all valid, P_d = Phi(gain_d))
     std::vector<double> con_tab_host;                               // [H][SPX_HT]: gain, noise_c, amp2_c, amp2_c
     DevBuf con_tab, con_Cs[2], con_s2[2], con_p[2], mom_c;
@@ -174,7 +169,6 @@ struct spx_handle {
     // reference's no-pending refinement objective, GPConstrainedEIChooser.py:692-803) -- a third internal handle, factored
     // on the first call and kept until observations, hypers, the constraint points or option "covar" change
     spx_handle* full = nullptr;
-    bool full_valid = false;
     std::vector<double> con_comp_host;                              // X_c as spx_set_constraint_model received it
     // spx_gp_logprob_rhs: a right-hand side per hyper row, [H][N], read in place of the resident values while set
     DevBuf rhs_rows;
@@ -206,6 +200,20 @@ struct spx_handle {
     int64_t st_n[ST_COUNT] = {0};
 };
 
+// Take x, and everything made from it, away from the handle: the bits, and the data that means nothing without them.  Every
+// entry point calls this for what it is about to overwrite BEFORE its first mutation and sets it again after its last check.
+inline void spx_drop(spx_handle* h, Held::Thing x)
+{
+    const Held was = h->held;
+    h->held.drop(x);
+    if (was.has(Held::FANT) && !h->held.has(Held::FANT)) { h->S = 0; h->fant_P = 0; h->fant_device = false; }
+    if (was.has(Held::FACTOR) && !h->held.has(Held::FACTOR)) h->nmodels = 1;
+}
+// ... and give it back; a refusal means that an entry point set a product without what it is made from
+inline int spx_hold(spx_handle* h, Held::Thing x, Held::Results r = Held::Results())
+{
+    return h->held.set(x, r) ? SPX_OK : spx_fail(SPX_ERR_ARG, "internal error: thing %d set without what it is made from", (int)x);
+}
 
 // ---- several GPUs behind one handle (spx_multi.hip) --------------------------------------------
 struct spx_multi;
@@ -237,7 +245,7 @@ int spx_multi_get_timings(spx_multi* m, double* ms, int64_t* launches, int n);
 int spx_multi_stat(spx_multi* m, const char* name, int64_t* value);
 int spx_multi_info(spx_multi* m, int32_t* n_dev, int32_t* transport, int32_t* device_ids, int32_t cap);
 // one process per GPU (spx_comm_attach): exchange this handle's record with the other ranks / drop the communicator
-int spx_comm_exchange(spx_handle* h);
+int spx_comm_exchange(spx_handle* h, bool* global_2d);
 void spx_comm_release(spx_handle* h);
 // single-GPU pieces the multi layer needs
 int spx_ensure_init(spx_handle* h);

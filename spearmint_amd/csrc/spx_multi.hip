@@ -467,7 +467,7 @@ struct spx_comm {
     int nranks = 1, rank = 0;
 };
 
-static int comm_exchange_sums(spx_handle* k)
+static int comm_exchange_sums(spx_handle* k, bool* global_2d)
 {
     spx_comm* c = k->comm;
     const int64_t Mt = k->part_M;
@@ -491,17 +491,17 @@ static int comm_exchange_sums(spx_handle* k)
     HIPCHK(hipStreamSynchronize(k->stream));
     LAUNCHCHK();
     k->best_idx -= k->index_base;   // spx_get_best adds the base back: the index is global
-    k->ran_2d = true;
+    *global_2d = true;              // (the pass's results: spx_get_ei_mean serves the all-reduced vector)
     return SPX_OK;
 }
 
-int spx_comm_exchange(spx_handle* k)
+int spx_comm_exchange(spx_handle* k, bool* global_2d)
 {
     spx_comm* c = k->comm;
     int rc = spx_ensure_init(k);
     if (rc) return rc;
-    if (k->part_M > 0) return comm_exchange_sums(k);
-    k->ran_2d = false;
+    if (k->part_M > 0) return comm_exchange_sums(k, global_2d);
+    *global_2d = false;
     if ((rc = k->rec_send.reserve(sizeof(SpxRecord)))) return rc;
     if ((rc = k->rec_recv.reserve(sizeof(SpxRecord) * c->nranks))) return rc;
     if ((rc = k->rec_out.reserve(sizeof(SpxRecord)))) return rc;
@@ -631,6 +631,7 @@ int spx_comm_attach(spx_handle* h, const char* id, int32_t nranks, int32_t rank)
     if (h->multi) return fail(SPX_ERR_ARG, "spx_comm_attach: a multi-device handle has its own communicator");
     int rc = spx_ensure_init(h);   // hipSetDevice(h->device): the communicator binds to the current device
     if (rc) return rc;
+    spx_drop(h, Held::PARTITION);
     spx_comm_release(h);
     spx_comm* c = new spx_comm();
     if ((rc = load_rccl(&c->rccl))) { delete c; return rc; }
@@ -645,7 +646,6 @@ int spx_comm_attach(spx_handle* h, const char* id, int32_t nranks, int32_t rank)
     c->nranks = nranks;
     c->rank = rank;
     h->comm = c;
-    h->ran = false;
     return SPX_OK;
 }
 
@@ -658,11 +658,10 @@ int spx_set_partition(spx_handle* h, int32_t hyper_shards, int64_t M_total, int3
         return fail(SPX_ERR_ARG, "spx_set_partition: bad totals (M_total=%lld, H_total=%d)", (long long)M_total, H_total);
     if (h->comm && M_total > 0 && h->comm->nranks % hyper_shards)
         return fail(SPX_ERR_ARG, "spx_set_partition: %d hyper shards do not divide %d ranks", hyper_shards, h->comm->nranks);
+    spx_drop(h, Held::PARTITION);
     h->part_ph = hyper_shards;
     h->part_M = M_total;
     h->part_H = H_total;
-    h->ran = false;
-    h->ran_2d = false;
     return SPX_OK;
 }
 
@@ -717,8 +716,7 @@ static int multi_set_partition(spx_multi* m, int32_t hyper_shards)
         m->M = 0; m->active = 0; m->on.assign(m->n, 0);
         m->ran = false; m->ran2d = false; m->last_was_logprob = false;
         // the devices' own state must not survive either (a stale factorisation of the full draw set)
-        return m->pool->run([m](int i) { m->kids[i]->have_hyp = false; m->kids[i]->have_cand = false;
-                                         m->kids[i]->factored = false; m->kids[i]->ran = false; return (int)SPX_OK; });
+        return m->pool->run([m](int i) { spx_drop(m->kids[i], Held::HYP); spx_drop(m->kids[i], Held::CAND); return (int)SPX_OK; });
     }
     return SPX_OK;
 }
