@@ -203,6 +203,33 @@ int spx_draw_fantasies(spx_handle* h, int32_t P, const double* z, int32_t per_dr
 /* pend_fant (P x S, row-major) and bests (S) of draw `draw`, as the last spx_draw_fantasies formed them; either may be NULL */
 int spx_get_pending_fantasies(spx_handle* h, int32_t draw, double* pend_fant, double* bests);
 
+/* ---- the acquisition function ------------------------------------------------------------------------------------
+ * What an EI pass scores candidates with, from the same predictive moments func_m / func_v of every (candidate, draw)
+ * (func_s = sqrt(func_v): NaN for func_v < 0, as np.sqrt gives, and then so is every acquisition):
+ *   SPX_ACQ_EI   expected improvement, the reference's and the default; par must be 0
+ *   SPX_ACQ_PI   probability of improvement  Phi((best - par - func_m) / func_s),  par = xi >= 0
+ *   SPX_ACQ_LCB  the negated lower confidence bound  par * func_s - func_m,        par = kappa >= 0
+ *                (larger is better, as for EI and PI; kappa = 0: minus the posterior mean -- its argmax is where the
+ *                model's mean is lowest)
+ * `best` is what EI uses: the minimum of the resident values, or bests[s] per fantasy.  With fantasies the value of
+ * every fantasy is averaged over S in numpy's order exactly as EI's is (LCB: par * func_s - func_m_s).  Over the draws:
+ * the numpy-order mean, then the argmax with numpy's rule -- everything but the formula is the EI pass.
+ * The setting belongs to the handle (a multi-device handle replicates it to every device; with a communicator attached
+ * every rank sets it on its own handle).  spx_ei_run, spx_ei_step, spx_ei_grid, spx_ei_grad_batch and spx_ei_grad follow
+ * it; spx_get_best, spx_get_ei_mean and spx_get_ei_draws keep their names and return the chosen acquisition's values.
+ * spx_ei_grad_batch returns MINUS the acquisition summed over the draws, and the gradient of that in the scaling it has
+ * for EI (the reference's factor one half included), so the same L-BFGS-B driver minimises it.
+ * spx_set_acquisition takes away the results of the last pass (the result getters refuse until the next one) and nothing
+ * else: the factorisation, the fantasies and what the refinement built from them stay.
+ * OUT OF SCOPE, refused with SPX_ERR_ARG: an unknown kind; par negative or not finite, or non-zero for SPX_ACQ_EI; any
+ * acquisition but SPX_ACQ_EI in a pass with SPX_FLAG_PER_SEC, SPX_FLAG_CONSTRAINED or SPX_FLAG_TIME_ONLY, in
+ * spx_ei_grad_batch while a time model is factored, and in spx_constrained_ei_grad_batch.  The handle stays usable. */
+#define SPX_ACQ_EI  0
+#define SPX_ACQ_PI  1
+#define SPX_ACQ_LCB 2
+int spx_set_acquisition(spx_handle* h, int32_t kind, double par);
+int spx_get_acquisition(spx_handle* h, int32_t* kind, double* par);   /* either may be NULL */
+
 /* Hot path, stage 2: K(X*,X) (:187), triangular solve (:195), predictive
  * mean/variance (:198-199), EI (:202-206) for every (candidate, draw); then the
  * MCMC mean and the argmax (:153).  Results stay on the device.               */

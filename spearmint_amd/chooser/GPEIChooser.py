@@ -54,6 +54,8 @@ class GPEIChooser(GPEIBase):
             randn = [npr.randn(pend.shape[0], self.pending_samples)] if pend.shape[0] > 0 else []
             best, _, _ = self.ei_over_hypers_gpu(comp, pend, cand, vals, self.current_hyper_row()[None, :],
                                                  randn=randn)
+            if self.recommend:     # (the proposal is fixed; no random numbers from here on)
+                self._recommend(grid, comp, vals, self.current_hyper_row()[None, :])
             return int(candidates[best])
         # The reference alternates "sample hypers" and "compute_ei" (:145-151).
         # Without pending experiments compute_ei consumes no random numbers, so
@@ -75,4 +77,6 @@ class GPEIChooser(GPEIBase):
             self._lp_key = None
             self.sample_hypers_many(comp, vals, self.mcmc_iters, after)
         best, _, _ = self.ei_over_hypers_gpu(comp, pend, cand, vals, np.array(rows), randn=randn)
+        if self.recommend:         # (the proposal is fixed; no random numbers from here on)
+            self._recommend(grid, comp, vals, np.array(rows))
         return int(candidates[best])

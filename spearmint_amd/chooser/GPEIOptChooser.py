@@ -43,6 +43,10 @@ class GPEIOptChooser(GPEIBase):
         # (a fork-based Pool cannot share a HIP context)
         self.use_multiprocessing = _as_bool(use_multiprocessing)
         self.rescore_grid = _as_bool(rescore_grid)   # 1: score [grid; refined] again in the second pass, as the reference does
+        # the host refinement (gpu_refine=0, or SPX_REFINE_MIN_N keeping the first proposals on the host) knows EI alone
+        if self.acq != "EI" and not self._use_gpu_refine(0):
+            raise ValueError("acq=%s needs the refinement on the GPU at every size (allowed with gpu_refine=0 or "
+                             "SPX_REFINE_MIN_N > 0: acq=EI)" % self.acq)
         self.hyper_samples = []
 
     # -- state -----------------------------------------------------------------
@@ -202,6 +206,7 @@ class GPEIOptChooser(GPEIBase):
         else:
             _, mean_ref, _ = self.ei_over_hypers_gpu(comp, pend, refined, vals, rows, want_draws=False, randn=randn)
             best = int(np.argmax(np.concatenate((mean1[10:], mean_ref))))
-        if best >= numcand:
-            return (int(numcand), refined[best - numcand, :])
-        return int(candidates[best])
+        job = (int(numcand), refined[best - numcand, :]) if best >= numcand else int(candidates[best])
+        if self.recommend:         # (the proposal is fixed; no random numbers from here on)
+            self._recommend(grid, comp, vals, rows, refine_count=self.grid_subset)
+        return job

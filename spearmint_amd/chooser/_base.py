@@ -45,14 +45,23 @@ class GPEIBase(object):
     noiseless_checks_mean = True   # mean in [min, max] also in noiseless mode
     state_keys = ("dims", "ls", "amp2", "noise", "mean")
     max_rows_per_call = 32         # spx_gp_logprob: one data-flow launch up to 32 hyper rows (spx_api.hip: do_factor, `rl`)
+    acq_allowed = ("EI", "PI", "LCB")   # acq=: what the engine scores candidates with (include/spx.h SPX_ACQ_*)
+    recommend_allowed = True       # recommend=1: the model-mean recommendation after every proposal (_recommend)
 
     def __init__(self, expt_dir, covar="Matern52", mcmc_iters=10, pending_samples=100,
                  noiseless=False, device=0, ndev=1, lib=None, gpu_logprob="auto", gpu_refine="auto",
-                 lookahead="auto", follow="auto", sampler="native", gpu_sobol=0, gpu_fantasies="auto", **unused):
+                 lookahead="auto", follow="auto", sampler="native", gpu_sobol=0, gpu_fantasies="auto", acq="EI", acq_par=0,
+                 recommend=0, **unused):
         if covar not in hostgp.COVARS:
             # the reference does getattr(gp, covar) here (GPEIChooser.py:52)
             raise AttributeError("no covariance function %r (gp.py has %s)" % (covar, ", ".join(hostgp.COVARS)))
         self.covar = covar        # every kernel of gp.py runs on the GPU: option "covar" of the handle
+        self.acq, self.acq_par = self._parse_acquisition(acq, acq_par)
+        self.recommend = _as_bool(recommend)
+        if self.recommend and not self.recommend_allowed:
+            raise ValueError("recommend=1 is not available on %s (allowed: recommend=0)" % type(self).__name__)
+        self.last_recommendation = None
+        self.recommendation_file = os.path.join(expt_dir, "recommendation.txt")
         self.expt_dir = expt_dir
         self.locker = Locker()
         self.state_pkl = os.path.join(expt_dir, self.__module__ + ".pkl")
@@ -109,6 +118,90 @@ class GPEIBase(object):
         self.D = -1
         self._eng = None          # created lazily in next(): never before a fork, never pickled
         self.last_overall_ei = None
+
+    # -- acquisition -----------------------------------------------------------
+    @classmethod
+    def _parse_acquisition(cls, acq, acq_par):
+        """acq=EI|PI|LCB and acq_par=<xi or kappa>: finite, >= 0, and 0 for EI (include/spx.h: spx_set_acquisition)."""
+        name = str(acq).strip().upper()
+        if name not in cls.acq_allowed:
+            raise ValueError("acq=%s is not available on %s (allowed: %s)" % (acq, cls.__name__, ", ".join(cls.acq_allowed)))
+        try:
+            par = float(acq_par)
+        except (TypeError, ValueError):
+            raise ValueError("acq_par=%r is not a number (allowed: a finite value >= 0; 0 with acq=EI)" % (acq_par,))
+        if not (par >= 0.0) or par == float("inf"):
+            raise ValueError("acq_par=%r is out of range (allowed: a finite value >= 0 -- xi of acq=PI, kappa of acq=LCB; 0 with "
+                             "acq=EI)" % (acq_par,))
+        if name == "EI" and par != 0.0:
+            raise ValueError("acq=EI takes no parameter (allowed: acq_par=0; got %r)" % (acq_par,))
+        return name, par
+
+    def _apply_acquisition(self, eng):
+        """Before a pass: the handle scores with this chooser's acquisition.  EI is the handle's default and is left
+        untouched, so an engine that knows nothing else is never asked."""
+        if self.acq != "EI":
+            from ..engine import ACQ
+            eng.set_acquisition(ACQ[self.acq], self.acq_par)
+
+    # -- the model-mean recommendation (recommend=1) ---------------------------------
+    def _recommend(self, grid, comp, vals, hyper_rows, refine_count=0):
+        """Where the posterior mean, averaged over this call's hyper draws, is lowest: the negated lower confidence bound with
+        kappa = 0 through the same grid pass (and, refine_count > 0, the same lock-step L-BFGS-B over spx_ei_grad_batch)
+        that proposals take.  Completed points only: no pending rows, no fantasies.  Draws no random numbers.  Leaves
+        self.last_recommendation = {x, grid_index (-1: off the grid), mean, std} and appends a line to recommendation.txt
+        (under the chooser's Locker, as its other files are written): mean std grid_index x[0] ... x[D-1].
+        NaN: a proposal follows numpy's argmax (the first NaN wins, on purpose: the reference's rule).  A recommendation is
+        the opposite kind of answer -- a point to USE -- so a point whose mean is NaN is never refined and never recommended;
+        if no point has a mean, nothing is recommended: last_recommendation is None and no line is written."""
+        from .. import refine
+        from ..engine import ACQ_LCB, FLAG_KEEP_MOMENTS
+        eng = self.engine()
+        grid = np.ascontiguousarray(grid, dtype=np.float64)
+        rows = np.ascontiguousarray(np.atleast_2d(hyper_rows), dtype=np.float64)
+        prev = eng.get_acquisition()
+        self._lp_key = None
+        try:
+            eng.set_observations(comp, vals)
+            eng.set_candidates(grid)
+            eng.set_hypers(rows)
+            eng.set_acquisition(ACQ_LCB, 0.0)
+            eng.ei_step()
+            neg_mean = eng.ei_mean()                     # minus the mean over draws of func_m
+            finite = np.nonzero(~np.isnan(neg_mean))[0]
+            if finite.size == 0:
+                self.last_recommendation = None
+                return None
+            if refine_count > 0:
+                keep = finite[np.argsort(neg_mean[finite])[-refine_count:]]
+                refined = refine.lbfgs_many(eng.ei_grad_batch, grid[keep, :], [(0, 1)] * grid.shape[1], log=log)
+                pts, index = np.vstack((refined, grid[keep, :])), np.concatenate((np.full(keep.shape[0], -1), keep))
+            else:
+                keep = finite[[int(np.argmax(neg_mean[finite]))]]
+                pts, index = grid[keep, :], keep
+            eng.set_candidates(pts)
+            eng.ei_run(FLAG_KEEP_MOMENTS)
+            mom = [eng.get_moments(d) for d in range(rows.shape[0])]
+        finally:
+            eng.set_acquisition(*prev)
+        func_m = np.array([m[0] for m in mom])           # (H, points)
+        func_v = np.array([m[1] for m in mom])
+        mean = np.mean(func_m, axis=0)
+        if np.all(np.isnan(mean)):                       # (a refinement that walked every point into a NaN)
+            self.last_recommendation = None
+            return None
+        k = int(np.nanargmin(mean))
+        rec = {"x": np.array(pts[k], dtype=float), "grid_index": int(index[k]), "mean": float(mean[k]),
+               "std": float(np.sqrt(np.mean(func_v[:, k]) + np.var(func_m[:, k])))}
+        self.last_recommendation = rec
+        self.locker.lock_wait(self.recommendation_file)
+        try:
+            with open(self.recommendation_file, "a") as fh:
+                fh.write("%.17g %.17g %d %s\n" % (rec["mean"], rec["std"], rec["grid_index"],
+                                                  " ".join("%.17g" % v for v in rec["x"])))
+        finally:
+            self.locker.unlock(self.recommendation_file)
+        return rec
 
     # -- GPU handle -----------------------------------------------------------
     def engine(self):
@@ -534,6 +627,7 @@ class GPEIBase(object):
             return self._ei_with_pending_gpu(comp, pend, cand, vals, hyper_rows, randn, want_draws)
         hyper_rows = np.ascontiguousarray(np.atleast_2d(hyper_rows), dtype=np.float64)
         self._lp_key = None     # the one-shot call below replaces the engine's resident observations
+        self._apply_acquisition(self.engine())
         idx, val, mean, draws = self.engine().ei_grid(comp, vals, cand, hyper_rows,
                                                       want_mean=True, want_draws=want_draws)
         warning = self.engine().last_warning()    # (a hand-off time-out of the one-launch factorisation: results are unaffected)
@@ -554,6 +648,7 @@ class GPEIBase(object):
         n_comp, n_pend = comp.shape[0], pend.shape[0]
         eng = self.engine()
         self._lp_key = None
+        self._apply_acquisition(eng)
         comp_pend = np.concatenate((comp, pend))
         eng.set_observations(comp_pend, np.concatenate((vals, np.zeros(n_pend))))
         eng.set_candidates(cand)

@@ -20,6 +20,12 @@ typedef double d2 __attribute__((ext_vector_type(2)));
 #define SPX_COV_MATERN32 1
 #define SPX_COV_ARDSE 2
 
+// acquisition function (spx.h SPX_ACQ_*, the same numbers: spx_api.hip asserts it): a template parameter of every kernel
+// that ends in an acquisition value (ei_device.h: acq_dev; refine_kernels.hip: acq_terms)
+#define SPX_ACQ_DEV_EI 0
+#define SPX_ACQ_DEV_PI 1
+#define SPX_ACQ_DEV_LCB 2
+
 // The launchers below return nothing: a kernel that needs more dynamic LDS than the default asks for it right before its
 // launch, and a refusal is NOTED (per host thread, spx_api.hip) and reported by the API's next launch check (LAUNCHCHK) as
 // SPX_ERR_HIP naming the kernel -- not left to surface as an opaque launch failure.
@@ -128,6 +134,8 @@ struct FinishArgs {
     const double* alphaS;  // [nh][S][Np]
     const double* bests;   // [nh][S], plain objective only
     double* uvec;          // [nh][P][Np] work vector
+    int acq;               // SPX_ACQ_* (plain objective only; 0 = EI) and its parameter: xi / kappa
+    double par;
 };
 // constrained = false: EI, averaged over the fantasies; true: EI x P(feasible), summed over them (refine_kernels.hip)
 void launch_point_finish(hipStream_t s, const FinishArgs& a, bool constrained);
@@ -136,7 +144,7 @@ void launch_point_finish(hipStream_t s, const FinishArgs& a, bool constrained);
 void launch_ei_fused128(hipStream_t s, int kind, const double* WT, const double* gamma, const double* Xs, const double* s1,
                         const double* Cs, const double* s2, const double* htab, const double* time_m, const double* cprob, double best,
                         double* ei_draw, double* mom_m, double* mom_v, int N, int Mc, int Dp, int nh, int64_t c0,
-                        int64_t M, int64_t Mp, int n_cu);
+                        int64_t M, int64_t Mp, int n_cu, int acq = 0 /*SPX_ACQ_*: ei_device.h*/, double par = 0.0);
 
 // fantasy_kernels.hip: the pending posterior and the fantasies of spx_draw_fantasies
 size_t fant_post_stride(int P);   // doubles per draw of `post`: C [P][P] | T = L_S^-1 C [P][P] | pend_m [P] | np.min(vals[:N])
@@ -157,11 +165,11 @@ size_t predict_gemm_lds_bytes();        // dynamic LDS of one predict-GEMM workg
 void launch_ei_finalize_fant(hipStream_t s, const double* part_ss, const double* part_bgS,
                              const double* htab, const double* bests, const double* time_m, const double* cprob,
                              double* ei_draw, int nrb, int Mc, int nh, int S, int64_t c0, int64_t M,
-                             int64_t Mp, int h0, double* ei_s);
+                             int64_t Mp, int h0, double* ei_s, int acq = 0, double par = 0.0);
 void launch_ei_finalize(hipStream_t s, const double* part_ss, const double* part_bg,
                         const double* htab, const double* time_m, const double* cprob, double best, double* ei_draw,
                         double* mom_m, double* mom_v, int nrb, int Mc, int nh, int64_t c0,
-                        int64_t M, int64_t Mp, int h0);
+                        int64_t M, int64_t Mp, int h0, int acq = 0, double par = 0.0);
 void launch_mean_over_draws(hipStream_t s, const double* ei_draw, double* ei_mean, int64_t M,
                             int64_t Mp, int H);
 void launch_sum_over_draws(hipStream_t s, const double* ei_draw, double* out, int64_t M, int64_t Mp, int H);

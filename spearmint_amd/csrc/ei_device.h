@@ -29,3 +29,19 @@ __device__ __forceinline__ double ei_dev(double func_m, double func_v, double be
     return func_s * (u * ncdf + npdf);
 }
 
+// The acquisition of the handle (spx.h SPX_ACQ_*, spx_set_acquisition) from the same moments: one source for the three
+// formulas, chosen at COMPILE time -- every kernel that ends in an acquisition value is a template over ACQ, and its EI
+// instantiation is ei_dev above, untouched.  par: xi (PI) / kappa (LCB); EI does not read it.
+//   PI   Phi((best - xi - func_m) / func_s)      Phi keeps its relative accuracy in the lower tail (ndtr_dev)
+//   LCB  kappa func_s - func_m                   (the negated lower confidence bound: larger is better, as EI and PI)
+// func_v < 0: func_s is NaN and so is every acquisition, kappa = 0 included (0 * NaN), as numpy has it.
+template <int ACQ>
+__device__ __forceinline__ double acq_dev(double func_m, double func_v, double best, double par)
+{
+#pragma clang fp contract(off)
+    if (ACQ == SPX_ACQ_DEV_EI) return ei_dev(func_m, func_v, best);
+    const double func_s = sqrt(func_v);
+    if (ACQ == SPX_ACQ_DEV_PI) return ndtr_dev((best - par - func_m) / func_s);
+    return par * func_s - func_m;
+}
+

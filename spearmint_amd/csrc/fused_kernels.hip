@@ -130,7 +130,7 @@ __device__ __forceinline__ void fused_pass(const double* __restrict__ Ws, const 
     bg_out += bgw[0] + bgw[1];
 }
 
-template <int QC, int KIND, bool ONECH>
+template <int QC, int KIND, bool ONECH, int ACQ>
 __global__ __launch_bounds__(FU_THREADS, 1) void k_ei_fused128(
     const double* __restrict__ WT /*[nh][128][128]*/, const double* __restrict__ gamma /*[nh][128]*/,
     const double* __restrict__ Xs /*[nh][128][Dp]*/, const double* __restrict__ s1 /*[nh][128]*/,
@@ -138,7 +138,7 @@ __global__ __launch_bounds__(FU_THREADS, 1) void k_ei_fused128(
     const double* __restrict__ htab, const double* __restrict__ time_m /*[nh][Mc] or null*/,
     const double* __restrict__ cprob /*[nh][Mc] or null*/, double best,
     double* __restrict__ ei_draw /*[H][Mp]*/, double* __restrict__ mom_m, double* __restrict__ mom_v,
-    int N, int Mc, int Dp, int nchunks, int wgs_per_draw, int64_t c0g, int64_t M, int64_t Mp)
+    int N, int Mc, int Dp, int nchunks, int wgs_per_draw, int64_t c0g, int64_t M, int64_t Mp, double par)
 {
 #pragma clang fp contract(off)
     extern __shared__ __attribute__((aligned(16))) double smem[];
@@ -205,7 +205,7 @@ __global__ __launch_bounds__(FU_THREADS, 1) void k_ei_fused128(
         if (tile < tile1 && c0g + c < M) {
             const double func_m = kbg[slot] + mean;
             const double func_v = prior_v - kss[slot];
-            double ei = ei_dev(func_m, func_v, best);
+            double ei = acq_dev<ACQ>(func_m, func_v, best, par);
             if (time_m) ei = ei / time_m[(size_t)h * Mc + c];
             if (cprob) ei = ei * cprob[(size_t)h * Mc + c];   // GPConstrainedEIChooser.py:878
             const size_t o = (size_t)h * Mp + c0g + c;
@@ -218,11 +218,11 @@ __global__ __launch_bounds__(FU_THREADS, 1) void k_ei_fused128(
     }
 }
 
-template <int KIND>
+template <int KIND, int ACQ>
 static void launch_fused_kind(hipStream_t s, const double* WT, const double* gamma, const double* Xs, const double* s1,
                               const double* Cs, const double* s2, const double* htab, const double* time_m, const double* cprob, double best,
                               double* ei_draw, double* mom_m, double* mom_v, int N, int Mc, int Dp, int nh, int64_t c0,
-                              int64_t M, int64_t Mp, int n_cu)
+                              int64_t M, int64_t Mp, int n_cu, double par)
 {
     const int Q = Dp / 4;
     const size_t lds = (size_t)(FU_NP * FU_LDW + 2 * FU_NP) * sizeof(double);   // 146 KB: one workgroup per CU
@@ -242,9 +242,9 @@ static void launch_fused_kind(hipStream_t s, const double* WT, const double* gam
     dim3 grid(per, nh);
 #define SPX_FU_LAUNCH(QC_, ONE_)                                                                                          \
     do {                                                                                                                  \
-        SPX_LDS_ATTR((k_ei_fused128<QC_, KIND, ONE_>), lds);                                  \
-        hipLaunchKernelGGL((k_ei_fused128<QC_, KIND, ONE_>), grid, dim3(FU_THREADS), lds, s, WT, gamma, Xs, s1, Cs, s2, htab,   \
-                           time_m, cprob, best, ei_draw, mom_m, mom_v, N, Mc, Dp, Q / QC_, per, c0, M, Mp);                      \
+        SPX_LDS_ATTR((k_ei_fused128<QC_, KIND, ONE_, ACQ>), lds);                                                         \
+        hipLaunchKernelGGL((k_ei_fused128<QC_, KIND, ONE_, ACQ>), grid, dim3(FU_THREADS), lds, s, WT, gamma, Xs, s1, Cs, s2,  \
+                           htab, time_m, cprob, best, ei_draw, mom_m, mom_v, N, Mc, Dp, Q / QC_, per, c0, M, Mp, par);        \
     } while (0)
     if (Q == 1) SPX_FU_LAUNCH(1, true);
     else if (Q == 2) SPX_FU_LAUNCH(2, true);
@@ -254,16 +254,30 @@ static void launch_fused_kind(hipStream_t s, const double* WT, const double* gam
 #undef SPX_FU_LAUNCH
 }
 
-// EI of every (candidate of the chunk, draw): N <= 128 (Np = 128), no fantasies.  ei_draw[h][c0 + c].
+template <int KIND>
+static void launch_fused_acq(hipStream_t s, int acq, const double* WT, const double* gamma, const double* Xs, const double* s1,
+                             const double* Cs, const double* s2, const double* htab, const double* time_m, const double* cprob, double best,
+                             double* ei_draw, double* mom_m, double* mom_v, int N, int Mc, int Dp, int nh, int64_t c0,
+                             int64_t M, int64_t Mp, int n_cu, double par)
+{
+    if (acq == SPX_ACQ_DEV_PI)
+        launch_fused_kind<KIND, SPX_ACQ_DEV_PI>(s, WT, gamma, Xs, s1, Cs, s2, htab, time_m, cprob, best, ei_draw, mom_m, mom_v, N, Mc, Dp, nh, c0, M, Mp, n_cu, par);
+    else if (acq == SPX_ACQ_DEV_LCB)
+        launch_fused_kind<KIND, SPX_ACQ_DEV_LCB>(s, WT, gamma, Xs, s1, Cs, s2, htab, time_m, cprob, best, ei_draw, mom_m, mom_v, N, Mc, Dp, nh, c0, M, Mp, n_cu, par);
+    else
+        launch_fused_kind<KIND, SPX_ACQ_DEV_EI>(s, WT, gamma, Xs, s1, Cs, s2, htab, time_m, cprob, best, ei_draw, mom_m, mom_v, N, Mc, Dp, nh, c0, M, Mp, n_cu, par);
+}
+
+// The acquisition (EI unless spx_set_acquisition chose another) of every (candidate of the chunk, draw): N <= 128 (Np = 128), no fantasies.  ei_draw[h][c0 + c].
 void launch_ei_fused128(hipStream_t s, int kind, const double* WT, const double* gamma, const double* Xs, const double* s1,
                         const double* Cs, const double* s2, const double* htab, const double* time_m, const double* cprob, double best,
                         double* ei_draw, double* mom_m, double* mom_v, int N, int Mc, int Dp, int nh, int64_t c0,
-                        int64_t M, int64_t Mp, int n_cu)
+                        int64_t M, int64_t Mp, int n_cu, int acq, double par)
 {
     if (kind == SPX_COV_MATERN32)
-        launch_fused_kind<SPX_COV_MATERN32>(s, WT, gamma, Xs, s1, Cs, s2, htab, time_m, cprob, best, ei_draw, mom_m, mom_v, N, Mc, Dp, nh, c0, M, Mp, n_cu);
+        launch_fused_acq<SPX_COV_MATERN32>(s, acq, WT, gamma, Xs, s1, Cs, s2, htab, time_m, cprob, best, ei_draw, mom_m, mom_v, N, Mc, Dp, nh, c0, M, Mp, n_cu, par);
     else if (kind == SPX_COV_ARDSE)
-        launch_fused_kind<SPX_COV_ARDSE>(s, WT, gamma, Xs, s1, Cs, s2, htab, time_m, cprob, best, ei_draw, mom_m, mom_v, N, Mc, Dp, nh, c0, M, Mp, n_cu);
+        launch_fused_acq<SPX_COV_ARDSE>(s, acq, WT, gamma, Xs, s1, Cs, s2, htab, time_m, cprob, best, ei_draw, mom_m, mom_v, N, Mc, Dp, nh, c0, M, Mp, n_cu, par);
     else
-        launch_fused_kind<SPX_COV_MATERN52>(s, WT, gamma, Xs, s1, Cs, s2, htab, time_m, cprob, best, ei_draw, mom_m, mom_v, N, Mc, Dp, nh, c0, M, Mp, n_cu);
+        launch_fused_acq<SPX_COV_MATERN52>(s, acq, WT, gamma, Xs, s1, Cs, s2, htab, time_m, cprob, best, ei_draw, mom_m, mom_v, N, Mc, Dp, nh, c0, M, Mp, n_cu, par);
 }

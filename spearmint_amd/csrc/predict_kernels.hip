@@ -749,13 +749,14 @@ void launch_predict_gemm(hipStream_t s, int variant, const double* WT, const dou
 #undef SPX_GO
 }
 
-// one thread per (candidate of the chunk, draw of the group)
+// one thread per (candidate of the chunk, draw of the group); ACQ: the acquisition (ei_device.h), par its parameter
+template <int ACQ>
 __global__ __launch_bounds__(256) void k_ei_finalize(
     const double* __restrict__ part_ss, const double* __restrict__ part_bg,
     const double* __restrict__ htab, const double* __restrict__ time_m /*[nh][Mc] or null*/,
     const double* __restrict__ cprob /*[nh][Mc] or null*/,
     double best, double* __restrict__ ei_draw /*[H][Mp]*/, double* __restrict__ mom_m,
-    double* __restrict__ mom_v, int nrb, int Mc, int nh, int64_t c0, int64_t M, int64_t Mp, int h0)
+    double* __restrict__ mom_v, int nrb, int Mc, int nh, int64_t c0, int64_t M, int64_t Mp, int h0, double par)
 {
 #pragma clang fp contract(off)
     const int c = blockIdx.x * 256 + threadIdx.x;
@@ -771,7 +772,7 @@ __global__ __launch_bounds__(256) void k_ei_finalize(
     const double prior_v = htab[h * SPX_HT + 3];  // amp2*(1+1e-6)
     const double func_m = bg + mean;
     const double func_v = prior_v - ss;
-    double ei = ei_dev(func_m, func_v, best);
+    double ei = acq_dev<ACQ>(func_m, func_v, best, par);
     if (time_m) ei = ei / time_m[(size_t)h * Mc + c];
     if (cprob) ei = ei * cprob[(size_t)h * Mc + c];   // constrained_ei = ei*func_constraint_m (GPConstrainedEIChooser.py:878)
     const size_t o = (size_t)(h0 + h) * Mp + c0 + c;
@@ -785,10 +786,15 @@ __global__ __launch_bounds__(256) void k_ei_finalize(
 void launch_ei_finalize(hipStream_t s, const double* part_ss, const double* part_bg,
                         const double* htab, const double* time_m, const double* cprob, double best, double* ei_draw,
                         double* mom_m, double* mom_v, int nrb, int Mc, int nh, int64_t c0,
-                        int64_t M, int64_t Mp, int h0)
+                        int64_t M, int64_t Mp, int h0, int acq, double par)
 {
-    hipLaunchKernelGGL(k_ei_finalize, dim3((Mc + 255) / 256, nh), dim3(256), 0, s, part_ss, part_bg,
-                       htab, time_m, cprob, best, ei_draw, mom_m, mom_v, nrb, Mc, nh, c0, M, Mp, h0);
+#define SPX_FIN(ACQ_)                                                                                         \
+    hipLaunchKernelGGL(k_ei_finalize<ACQ_>, dim3((Mc + 255) / 256, nh), dim3(256), 0, s, part_ss, part_bg, htab, time_m, \
+                       cprob, best, ei_draw, mom_m, mom_v, nrb, Mc, nh, c0, M, Mp, h0, par)
+    if (acq == SPX_ACQ_DEV_PI) SPX_FIN(SPX_ACQ_DEV_PI);
+    else if (acq == SPX_ACQ_DEV_LCB) SPX_FIN(SPX_ACQ_DEV_LCB);
+    else SPX_FIN(SPX_ACQ_DEV_EI);
+#undef SPX_FIN
 }
 
 
@@ -797,10 +803,11 @@ void launch_ei_finalize(hipStream_t s, const double* part_ss, const double* part
 // (k_ei_fant_values; the single-launch form walked the S fantasies of a candidate in ONE thread -- 39 workgroups per launch
 // at S = 100, 338 ms of an 807 ms pass at C3 size), then the ordered sum over S per candidate (k_ei_fant_mean: np_sum.h, the
 // same additions in the same order as the streaming form it replaces: eight accumulators, the tree, the tail).
+template <int ACQ>
 __global__ __launch_bounds__(256) void k_ei_fant_values(
     const double* __restrict__ part_ss, const double* __restrict__ part_bgS,
     const double* __restrict__ htab, const double* __restrict__ bests /*[nh][S]*/, int nrb, int Mc, int nh,
-    int S, int64_t c0, int64_t M, double* __restrict__ ei_s /*[nh][S][Mc]*/)
+    int S, int64_t c0, int64_t M, double* __restrict__ ei_s /*[nh][S][Mc]*/, double par)
 {
 #pragma clang fp contract(off)
     const int c = blockIdx.x * 256 + threadIdx.x;
@@ -816,7 +823,7 @@ __global__ __launch_bounds__(256) void k_ei_fant_values(
         const size_t o1 = ((((size_t)ib * 2 + 1) * nh + h) * S + sidx) * Mc + c;
         bg += part_bgS[o0] + part_bgS[o1];
     }
-    ei_s[((size_t)h * S + sidx) * Mc + c] = ei_dev(bg + mean, func_v, bests[(size_t)h * S + sidx]);
+    ei_s[((size_t)h * S + sidx) * Mc + c] = acq_dev<ACQ>(bg + mean, func_v, bests[(size_t)h * S + sidx], par);
 }
 
 __global__ __launch_bounds__(256) void k_ei_fant_mean(const double* __restrict__ ei_s, const double* __restrict__ time_m,
@@ -838,10 +845,15 @@ __global__ __launch_bounds__(256) void k_ei_fant_mean(const double* __restrict__
 void launch_ei_finalize_fant(hipStream_t s, const double* part_ss, const double* part_bgS,
                              const double* htab, const double* bests, const double* time_m, const double* cprob,
                              double* ei_draw, int nrb, int Mc, int nh, int S, int64_t c0, int64_t M,
-                             int64_t Mp, int h0, double* ei_s)
+                             int64_t Mp, int h0, double* ei_s, int acq, double par)
 {
-    hipLaunchKernelGGL(k_ei_fant_values, dim3((Mc + 255) / 256, nh * S), dim3(256), 0, s, part_ss, part_bgS, htab, bests, nrb,
-                       Mc, nh, S, c0, M, ei_s);
+#define SPX_FANT(ACQ_)                                                                                                  \
+    hipLaunchKernelGGL(k_ei_fant_values<ACQ_>, dim3((Mc + 255) / 256, nh * S), dim3(256), 0, s, part_ss, part_bgS, htab, bests, \
+                       nrb, Mc, nh, S, c0, M, ei_s, par)
+    if (acq == SPX_ACQ_DEV_PI) SPX_FANT(SPX_ACQ_DEV_PI);
+    else if (acq == SPX_ACQ_DEV_LCB) SPX_FANT(SPX_ACQ_DEV_LCB);
+    else SPX_FANT(SPX_ACQ_DEV_EI);
+#undef SPX_FANT
     hipLaunchKernelGGL(k_ei_fant_mean, dim3((Mc + 255) / 256, nh), dim3(256), 0, s, ei_s, time_m, cprob, ei_draw, Mc, S, c0, M, Mp, h0);
 }
 

@@ -18,6 +18,8 @@
 // Gamma_s = W (fant_s - mean) (equal to k . alpha_s), EI_s against bests[s], and
 //   grad[d] = 0.5 amp2 ( sum_j G[j][d] u[j] + (-2 z . G[:,d]) mean_s(0.5 phi_s / s) ),
 //   u[j] = mean_s( -Phi_s alpha_s[j] ),  alpha_s = W^T Gamma_s                    (:505-523)
+// Another acquisition a in EI's place (spx_set_acquisition; plain objective only): -Phi and 0.5 phi / s above are
+// dEI/d func_m and dEI/d func_v, and acq_terms<ACQ> supplies a with da/d func_m and da/d func_v in their place.
 // The finish (k_point_finish, one workgroup per draw and point) exists once and serves two objectives as its cases.  It
 // meets up to three sets of rows, each with its own count and padding (FinishSide in common.h):
 //   mean side      the handle's own factor (N rows: the valid points, or [valid; pend]): func_m = k . alpha + mean, alpha . G
@@ -250,7 +252,8 @@ __device__ __forceinline__ double block_dot(const double* __restrict__ a, const 
     return block_sum(v, red);
 }
 
-// EI against `best` and the weights of its gradient: d(-EI)/d func_m = -Phi, d(-EI)/d func_v = 0.5 phi / func_s  (:420-430)
+// EI against `best` and the two weights of its gradient as the reference has them (g_ei_m, g_ei_s2 of :420-430):
+// dEI/d func_m = -Phi and dEI/d func_v = 0.5 phi / func_s; combine_plain's signs turn them into d(-EI)/dx
 __device__ __forceinline__ void ei_terms(double best, double func_m, double func_s, double& ei, double& g_m, double& g_s2)
 {
 #pragma clang fp contract(off)
@@ -262,20 +265,47 @@ __device__ __forceinline__ void ei_terms(double best, double func_m, double func
     g_s2 = 0.5 * pdf / func_s;
 }
 
-// the S fantasies of draw h: func_m[s] = t . Gamma_s + mean (one wavefront per s), EI_s against bests[s] (null: the one
-// `best`), then over the fantasies  ei = sum_s EI_s / div,  g_s2 = sum_s (0.5 phi_s / func_s) / div  and the mean-gradient
-// weights  u[j] = sum_s( -Phi_s alpha_s[j] ) / div  with -Phi_s folded in (so g_m = 1).  div = S averages, div = 1 sums.
+// The same for the handle's acquisition a (ei_device.h: acq_dev): its value and the two weights combine_plain consumes,
+// g_m = da/d func_m and g_s2 = da/d func_v -- EI's -Phi and 0.5 phi / func_s are exactly these -- so that the combine
+// yields d(-a)/dx in the scaling it has for EI.  With u = (best - xi - func_m) / func_s:
+//   PI   Phi(u)                    g_m = -phi(u) / func_s     g_s2 = -phi(u) u / (2 func_v)
+//   LCB  kappa func_s - func_m     g_m = -1                   g_s2 = kappa / (2 func_s)
+template <int ACQ>
+__device__ __forceinline__ void acq_terms(double best, double par, double func_m, double func_s, double& val, double& g_m,
+                                          double& g_s2)
+{
+#pragma clang fp contract(off)
+    if (ACQ == SPX_ACQ_DEV_EI) {
+        ei_terms(best, func_m, func_s, val, g_m, g_s2);
+    } else if (ACQ == SPX_ACQ_DEV_PI) {
+        const double u = (best - par - func_m) / func_s;
+        const double pdf = exp(-(u * u) / 2.0) / 2.50662827463100050242;
+        val = ndtr_r(u);
+        g_m = -(pdf / func_s);
+        g_s2 = -(pdf * u / (2.0 * (func_s * func_s)));
+    } else {
+        val = par * func_s - func_m;
+        g_m = -1.0;
+        g_s2 = par / (2.0 * func_s);
+    }
+}
+
+// the S fantasies of draw h: func_m[s] = t . Gamma_s + mean (one wavefront per s), the acquisition a_s (acq_terms<ACQ>; EI:
+// EI_s) against bests[s] (null: the one `best`) with its weights gm_s = da_s/d func_m and gs_s = da_s/d func_v (EI: -Phi_s
+// and 0.5 phi_s / func_s), then over the fantasies  ei = sum_s a_s / div,  g_s2 = sum_s gs_s / div  and the mean-gradient
+// weights  u[j] = sum_s( gm_s alpha_s[j] ) / div  with gm_s folded in (so g_m = 1).  div = S averages, div = 1 sums.
+template <int ACQ>
 __device__ __forceinline__ void fantasy_terms(double* dyn /*[3][S]*/, int S, double div, const double* __restrict__ th,
                                               const double* __restrict__ gammaS /*[S][Np]*/,
                                               const double* __restrict__ alphaS /*[S][Np]*/,
-                                              const double* __restrict__ bests /*[S] or null*/, double best, double mean,
+                                              const double* __restrict__ bests /*[S] or null*/, double best, double par, double mean,
                                               double func_s, int N, int Np, double* __restrict__ uh /*[Np]*/, double& ei,
                                               double& g_m, double& g_s2)
 {
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-    double* gmS = dyn;                 // [S]  -Phi_s
-    double* eiS = dyn + S;             // [S]
-    double* gsS = dyn + 2 * S;         // [S]  0.5 phi_s / func_s
+    double* gmS = dyn;                 // [S]  da_s/d func_m   (EI: -Phi_s)
+    double* eiS = dyn + S;             // [S]  a_s
+    double* gsS = dyn + 2 * S;         // [S]  da_s/d func_v   (EI: 0.5 phi_s / func_s)
     for (int sidx = wave; sidx < S; sidx += 4) {
         const double* gs = gammaS + (size_t)sidx * Np;
         double m = 0.0;
@@ -284,7 +314,7 @@ __device__ __forceinline__ void fantasy_terms(double* dyn /*[3][S]*/, int S, dou
         for (int off = 32; off > 0; off >>= 1) m += __shfl_xor(m, off);
         if (lane == 0) {
 #pragma clang fp contract(off)
-            ei_terms(bests ? bests[sidx] : best, m + mean, func_s, eiS[sidx], gmS[sidx], gsS[sidx]);
+            acq_terms<ACQ>(bests ? bests[sidx] : best, par, m + mean, func_s, eiS[sidx], gmS[sidx], gsS[sidx]);
         }
     }
     __syncthreads();
@@ -399,7 +429,8 @@ __device__ __forceinline__ double combine_con(double amp2, double s1v, double s2
 //   CON = true   EI x P(feasible) (sum over the fantasies against the one `best`); third side = constraint model
 // (positional __restrict__ parameters, not the FinishArgs struct itself: __restrict__ does not carry through struct members,
 // and with the struct as the kernel's argument the compiler spilled 23 / 16 SGPRs, none this way; launch_finish unpacks it.)
-template <bool CON>
+// ACQ: the acquisition in EI's place (plain objective only: acq_terms; the constrained objective is EI's alone), par its parameter
+template <bool CON, int ACQ>
 __global__ __launch_bounds__(256) void k_point_finish(
     // mean side
     const double* __restrict__ Xs, const double* __restrict__ hyp, const double* __restrict__ htab,
@@ -413,7 +444,7 @@ __global__ __launch_bounds__(256) void k_point_finish(
     const double* __restrict__ x, double best, double* __restrict__ out, int D, int Dp, int P,
     // fantasies (mean side == variance side then)
     int S, const double* __restrict__ gammaS /*[H][S][Np]*/, const double* __restrict__ alphaS /*[H][S][Np]*/,
-    const double* __restrict__ bests /*[H][S], plain only*/, double* __restrict__ uvec /*[H][P][Np] work vector*/)
+    const double* __restrict__ bests /*[H][S], plain only*/, double* __restrict__ uvec /*[H][P][Np] work vector*/, double par)
 {
     extern __shared__ double dyn[];        // S > 0: [3][S]
     __shared__ double red[4];
@@ -435,12 +466,12 @@ __global__ __launch_bounds__(256) void k_point_finish(
     const double func_s = sqrt(prior_v - tt);
     if (S == 0) {
         const double ka = block_dot(kvec + vo, ah, N, red);
-        if (tid == 0) ei_terms(best, ka + mean, func_s, sh_ei, sh_gm, sh_gs2);
+        if (tid == 0) acq_terms<ACQ>(best, par, ka + mean, func_s, sh_ei, sh_gm, sh_gs2);
         __syncthreads();
     } else {
         double* uh = uvec + vo;
-        fantasy_terms(dyn, S, CON ? 1.0 : (double)S, th, gammaS + (size_t)h * S * Np, alphaS + (size_t)h * S * Np,
-                      CON ? nullptr : bests + (size_t)h * S, best, mean, func_s, N, Np, uh, sh_ei, sh_gm, sh_gs2);
+        fantasy_terms<ACQ>(dyn, S, CON ? 1.0 : (double)S, th, gammaS + (size_t)h * S * Np, alphaS + (size_t)h * S * Np,
+                           CON ? nullptr : bests + (size_t)h * S, best, par, mean, func_s, N, Np, uh, sh_ei, sh_gm, sh_gs2);
         ah = uh;     // the mean-gradient weights of the fantasy branch (g_m folded in)
     }
     // third side: m3 = k3 . alpha3, then the constraint's P, phi and scale, or the time model's predicted duration
@@ -494,19 +525,22 @@ __global__ __launch_bounds__(256) void k_point_finish(
 }
 
 // the one place that knows the kernel's parameter order
-template <bool CON>
+template <bool CON, int ACQ>
 static void launch_finish(hipStream_t s, const FinishArgs& a)
 {
     const size_t lds = (size_t)3 * a.S * sizeof(double);   // up to 96 KB at S = 4096: above the 64 KB default limit
     if (lds > 48 * 1024)
-        SPX_LDS_ATTR(k_point_finish<CON>, lds);
-    hipLaunchKernelGGL(k_point_finish<CON>, dim3(a.nh, a.P), dim3(256), lds, s, a.m.Xs, a.m.hyp, a.htab, a.m.w, a.k, a.m.dk,
-                       a.m.n, a.m.Np, a.v.Xs, a.v.dk, a.t, a.v.w, a.v.n, a.v.Np, a.c.Xs, a.c.hyp, a.tab3, a.c.w, a.k3, a.c.dk,
-                       a.c.n, a.c.Np, a.x, a.best, a.out, a.D, a.Dp, a.P, a.S, a.gammaS, a.alphaS, a.bests, a.uvec);
+        SPX_LDS_ATTR((k_point_finish<CON, ACQ>), lds);
+    hipLaunchKernelGGL((k_point_finish<CON, ACQ>), dim3(a.nh, a.P), dim3(256), lds, s, a.m.Xs, a.m.hyp, a.htab, a.m.w, a.k,
+                       a.m.dk, a.m.n, a.m.Np, a.v.Xs, a.v.dk, a.t, a.v.w, a.v.n, a.v.Np, a.c.Xs, a.c.hyp, a.tab3, a.c.w, a.k3,
+                       a.c.dk, a.c.n, a.c.Np, a.x, a.best, a.out, a.D, a.Dp, a.P, a.S, a.gammaS, a.alphaS, a.bests, a.uvec,
+                       a.par);
 }
 
 void launch_point_finish(hipStream_t s, const FinishArgs& a, bool constrained)
 {
-    if (constrained) launch_finish<true>(s, a);
-    else launch_finish<false>(s, a);
+    if (constrained) launch_finish<true, SPX_ACQ_DEV_EI>(s, a);
+    else if (a.acq == SPX_ACQ_DEV_PI) launch_finish<false, SPX_ACQ_DEV_PI>(s, a);
+    else if (a.acq == SPX_ACQ_DEV_LCB) launch_finish<false, SPX_ACQ_DEV_LCB>(s, a);
+    else launch_finish<false, SPX_ACQ_DEV_EI>(s, a);
 }

@@ -317,6 +317,35 @@ int spx_set_option(spx_handle* h, const char* name, int64_t value)
     return fail(SPX_ERR_ARG, "spx_set_option: unknown option '%s'", name);
 }
 
+// The acquisition every later pass and refinement call computes in EI's place (spx.h).  Nothing but the results of the last
+// pass depends on it: the factor, the fantasies and alpha_s stay.
+static_assert(SPX_ACQ_EI == SPX_ACQ_DEV_EI && SPX_ACQ_PI == SPX_ACQ_DEV_PI && SPX_ACQ_LCB == SPX_ACQ_DEV_LCB,
+              "spx.h and common.h number the acquisitions alike");
+int spx_set_acquisition(spx_handle* h, int32_t kind, double par)
+{
+    if (!h) return fail(SPX_ERR_ARG, "spx_set_acquisition: null handle");
+    if (kind != SPX_ACQ_EI && kind != SPX_ACQ_PI && kind != SPX_ACQ_LCB)
+        return fail(SPX_ERR_ARG, "spx_set_acquisition: unknown acquisition %d (SPX_ACQ_EI, SPX_ACQ_PI, SPX_ACQ_LCB)", (int)kind);
+    if (!(par >= 0.0) || !std::isfinite(par))
+        return fail(SPX_ERR_ARG, "spx_set_acquisition: the parameter must be finite and >= 0 (got %g)", par);
+    if (kind == SPX_ACQ_EI && par != 0.0)
+        return fail(SPX_ERR_ARG, "spx_set_acquisition: SPX_ACQ_EI takes no parameter (par must be 0, got %g)", par);
+    if (h->multi) return spx_multi_set_acquisition(h->multi, kind, par);
+    spx_drop(h, Held::RESULTS);
+    h->acq = kind;
+    h->acq_par = par;
+    return SPX_OK;
+}
+
+int spx_get_acquisition(spx_handle* h, int32_t* kind, double* par)
+{
+    if (!h) return fail(SPX_ERR_ARG, "spx_get_acquisition: null handle");
+    if (h->multi) return spx_multi_get_acquisition(h->multi, kind, par);
+    if (kind) *kind = h->acq;
+    if (par) *par = h->acq_par;
+    return SPX_OK;
+}
+
 // Copies between a CALLER's host buffer and the device.  The runtime's own path for pageable host memory (a pool of staging
 // chunks) stalls for 13-28 ms every few dozen small copies on this stack (profiles/r06_set_obs_spikes.log: one
 // spx_set_observations in five, median 0.03 ms) -- at Spearmint's operating sizes that is a whole next().  Buffers up to
@@ -848,6 +877,9 @@ static int check_run_flags(const spx_handle* h, int32_t flags, int nmodels)
     const bool per_sec = (flags & SPX_FLAG_PER_SEC) != 0;
     const bool keep_mom = (flags & SPX_FLAG_KEEP_MOMENTS) != 0;
     const bool time_only = (flags & SPX_FLAG_TIME_ONLY) != 0;
+    if (h->acq != SPX_ACQ_EI && (flags & (SPX_FLAG_PER_SEC | SPX_FLAG_CONSTRAINED | SPX_FLAG_TIME_ONLY)))
+        return fail(SPX_ERR_ARG, "spx_ei_run: SPX_FLAG_PER_SEC / SPX_FLAG_CONSTRAINED / SPX_FLAG_TIME_ONLY are defined for "
+                                 "SPX_ACQ_EI only (spx_set_acquisition chose %s)", h->acq == SPX_ACQ_PI ? "PI" : "LCB");
     if (time_only && !(per_sec && keep_mom))
         return fail(SPX_ERR_ARG, "spx_ei_run: SPX_FLAG_TIME_ONLY needs SPX_FLAG_PER_SEC | SPX_FLAG_KEEP_MOMENTS");
     if (time_only && h->comm) return fail(SPX_ERR_ARG, "spx_ei_run: SPX_FLAG_TIME_ONLY has no winner to exchange (communicator attached)");
@@ -1096,7 +1128,8 @@ static int ei_run_impl(spx_handle* h, int32_t flags, bool factor_pending)
         if (fused)
             TIMED_S(ST_PREDICT_GEMM, G, launch_ei_fused128(G, dev_kind(h), h->WT.d(), h->gamma.d(), h->Xs.d(), h->s1.d(), Cs, s2,
                                                            h->htab.d(), tm, cp, h->best, h->ei_draw.d(), keep_mom ? h->mom_m.d() : nullptr,
-                                                           keep_mom ? h->mom_v.d() : nullptr, (int)N, mc, Dp, H, c0, M, Mp, h->n_cu));
+                                                           keep_mom ? h->mom_v.d() : nullptr, (int)N, mc, Dp, H, c0, M, Mp, h->n_cu,
+                                                           h->acq, h->acq_par));
         for (int h0 = 0; h0 < (fused ? 0 : H); h0 += Hb, ++item) {
             const int nhb = std::min(Hb, H - h0);
             const int k = (ns == 3) ? item % R : (ns == 2) ? (item & 1) : 0;
@@ -1134,14 +1167,15 @@ static int ei_run_impl(spx_handle* h, int32_t flags, bool factor_pending)
                                                                    per_sec ? tm + (size_t)h0 * mc : nullptr,
                                                                    constrained ? cp + (size_t)h0 * mc : nullptr,
                                                                    h->ei_draw.d(), nrb, mc, nhb, S, c0, M, Mp, h0,
-                                                                   h->scratch.d()));
+                                                                   h->scratch.d(), h->acq, h->acq_par));
             if (ns == 2) HIPCHK(hipEventRecord(h->ev_sync[2 + k], G));
             if (ns == 3 && (int64_t)item + R < p.ring_items) HIPCHK(hipEventRecord(h->ring[k].consumed, G));   // (only where an item waits for it)
         }
         if (S == 0 && !fused)   // every draw of the chunk in one launch
             TIMED_S(ST_EI_FINALIZE, G, launch_ei_finalize(G, h->part_ss[0].d(), h->part_bg[0].d(), h->htab.d(), tm, cp, h->best,
                                                           h->ei_draw.d(), keep_mom ? h->mom_m.d() : nullptr,
-                                                          keep_mom ? h->mom_v.d() : nullptr, nrb, mc, H, c0, M, Mp, 0));
+                                                          keep_mom ? h->mom_v.d() : nullptr, nrb, mc, H, c0, M, Mp, 0, h->acq,
+                                                          h->acq_par));
         if (ns >= 2) HIPCHK(hipEventRecord(h->ev_sync[4 + par], G));
     }
     if (ns >= 2 && (per_sec || constrained) && keep_mom) {   // the duration / probability copies ran on P
@@ -1633,6 +1667,7 @@ static int refine_finish(spx_handle* h, const spx_handle* v, const FinishSide& c
     a.htab = h->htab.d(); a.k = h->pt_k.d(); a.t = v->pt_t.d(); a.k3 = k3; a.tab3 = tab3;
     a.x = h->pt_x.d(); a.best = best; a.out = h->pt_out.d();
     a.D = D; a.Dp = h->Dp; a.nh = H; a.P = P; a.S = S;
+    a.acq = constrained ? SPX_ACQ_EI : h->acq; a.par = constrained ? 0.0 : h->acq_par;
     if (S > 0) {
         a.gammaS = h->gammaS.d(); a.alphaS = h->alphaS.d(); a.uvec = h->pt_u.d();
         if (!constrained) a.bests = h->bests.d();
@@ -1661,6 +1696,9 @@ int spx_ei_grad_batch(spx_handle* h, const double* points, int32_t P, double* ne
     if (h->multi) return spx_multi_ei_grad_batch(h->multi, points, P, neg_ei, grad);
     if (!h->held.has(Held::FACTOR)) return fail(SPX_ERR_ARG, "spx_ei_grad_batch: call spx_factor (or spx_ei_grid) first");
     const bool per_sec = (h->nmodels == 2);   // a time model was factored: EI per second (GPEIperSecChooser.py:349-434)
+    if (per_sec && h->acq != SPX_ACQ_EI)
+        return fail(SPX_ERR_ARG, "spx_ei_grad_batch: a time model is factored, and per second is defined for SPX_ACQ_EI only "
+                                 "(spx_set_acquisition)");
     if (h->S > 0 && per_sec)
         return fail(SPX_ERR_ARG, "spx_ei_grad_batch: fantasies with a time model are not defined "
                     "(the reference's per-second refinement ignores pending jobs)");
@@ -1711,6 +1749,9 @@ int spx_constrained_ei_grad_batch(spx_handle* h, const double* points, int32_t P
     if (!h || !points || !neg_cei || !grad || P < 1) return fail(SPX_ERR_ARG, "spx_constrained_ei_grad_batch: bad argument");
     if (h->multi) return fail(SPX_ERR_ARG, "spx_constrained_ei_grad_batch: the constraint model is single-device only "
                                            "(multi-device handle)");
+    if (h->acq != SPX_ACQ_EI)
+        return fail(SPX_ERR_ARG, "spx_constrained_ei_grad_batch: the constrained objective is defined for SPX_ACQ_EI only "
+                                 "(spx_set_acquisition)");
     if (!h->held.has(Held::FACTOR)) return fail(SPX_ERR_ARG, "spx_constrained_ei_grad_batch: call spx_factor (or spx_ei_step) first");
     if (!h->held.has(Held::CON)) return fail(SPX_ERR_ARG, "spx_constrained_ei_grad_batch: needs spx_set_constraint_model");
     if (h->nmodels == 2) return fail(SPX_ERR_ARG, "spx_constrained_ei_grad_batch: not defined with a time model");

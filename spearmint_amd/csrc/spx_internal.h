@@ -126,6 +126,8 @@ struct spx_handle {
     Held held;        // what of all this is resident and valid (spx_held.h); taken away by spx_drop below alone
     int nmodels = 1;  // what FACTOR was built with: 1 = objective GP only, 2 = + log-duration GP
     double best = 0.0;
+    int acq = 0;              // SPX_ACQ_*: what the EI pass and the refinement objective compute (spx_set_acquisition) ...
+    double acq_par = 0.0;     // ... and its parameter: xi (PI) / kappa (LCB)
     int not_pd_draw = -1, not_pd_pivot = -1;
     int64_t fant_budget = 0;            // bytes the per-fantasy partial means may take (an eighth of free memory, <= 2 GB) ...
     int fant_budget_S = -1;             // ... as found when the number of fantasies last changed
@@ -219,6 +221,8 @@ inline int spx_hold(spx_handle* h, Held::Thing x, Held::Results r = Held::Result
 struct spx_multi;
 void spx_multi_destroy(spx_multi* m);
 int spx_multi_set_option(spx_multi* m, const char* name, int64_t value);
+int spx_multi_set_acquisition(spx_multi* m, int32_t kind, double par);
+int spx_multi_get_acquisition(spx_multi* m, int32_t* kind, double* par);
 int spx_multi_set_observations(spx_multi* m, const double* comp, const double* vals, int64_t N, int32_t D);
 int spx_multi_set_candidates(spx_multi* m, const double* cand, int64_t M, int32_t D, int64_t index_base);
 int spx_multi_set_hypers(spx_multi* m, const double* hypers, int32_t H);

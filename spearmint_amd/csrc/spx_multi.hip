@@ -729,6 +729,18 @@ int spx_multi_set_option(spx_multi* m, const char* name, int64_t value)
     return rc;
 }
 
+// replicated to every device slot, as an option is; the devices drop their results, so the front does
+int spx_multi_set_acquisition(spx_multi* m, int32_t kind, double par)
+{
+    m->ran = false; m->ran2d = false;
+    return m->pool->run([=](int i) { return spx_set_acquisition(m->kids[i], kind, par); });
+}
+
+int spx_multi_get_acquisition(spx_multi* m, int32_t* kind, double* par)
+{
+    return spx_get_acquisition(m->kids[0], kind, par);
+}
+
 int spx_multi_set_observations(spx_multi* m, const double* comp, const double* vals, int64_t N, int32_t D)
 {
     int rc = m->pool->run([=](int i) { return spx_set_observations(m->kids[i], comp, vals, N, D); });

@@ -33,6 +33,12 @@ FLAG_TIME_ONLY = 8
 FLAG_CONSTRAINED = 16
 MAX_PENDING = 64      # include/spx.h SPX_MAX_PENDING: pending rows spx_draw_fantasies takes
 
+# include/spx.h SPX_ACQ_*: the acquisition an EI pass and the refinement objective compute (spx_set_acquisition)
+ACQ_EI = 0
+ACQ_PI = 1            # probability of improvement, parameter xi
+ACQ_LCB = 2           # negated lower confidence bound kappa * func_s - func_m, parameter kappa
+ACQ = {"EI": ACQ_EI, "PI": ACQ_PI, "LCB": ACQ_LCB}
+
 _c_double_p = ctypes.POINTER(ctypes.c_double)
 _c_int64_p = ctypes.POINTER(ctypes.c_int64)
 _c_int32_p = ctypes.POINTER(ctypes.c_int32)
@@ -95,6 +101,8 @@ ABI = {
     "spx_set_fantasies": (ctypes.c_int, [_vp, _c_double_p, _c_double_p, ctypes.c_int32]),
     "spx_draw_fantasies": (ctypes.c_int, [_vp, ctypes.c_int32, _c_double_p, ctypes.c_int32, ctypes.c_int32]),
     "spx_get_pending_fantasies": (ctypes.c_int, [_vp, ctypes.c_int32, _c_double_p, _c_double_p]),
+    "spx_set_acquisition": (ctypes.c_int, [_vp, ctypes.c_int32, ctypes.c_double]),
+    "spx_get_acquisition": (ctypes.c_int, [_vp, _c_int32_p, _c_double_p]),
     "spx_ei_run": (ctypes.c_int, [_vp, ctypes.c_int32]),
     "spx_ei_step": (ctypes.c_int, [_vp, ctypes.c_int32]),
     "spx_get_best": (ctypes.c_int, [_vp, _c_int64_p, _c_double_p]),
@@ -363,6 +371,23 @@ class Engine(object):
         if name not in COVAR:
             raise AttributeError("no covariance function %r (gp.py has %s)" % (name, ", ".join(sorted(COVAR))))
         self.set_option("covar", COVAR[name])
+
+    def set_acquisition(self, kind, par=0.0):
+        """What the next passes and refinement calls score with (include/spx.h: spx_set_acquisition): ACQ_EI (par 0),
+        ACQ_PI (par = xi >= 0) or ACQ_LCB (par = kappa >= 0); a name of ACQ ("EI", "PI", "LCB") is taken too.  Drops the
+        results of the last pass, keeps the factor and the fantasies."""
+        if not isinstance(kind, int):
+            if kind not in ACQ:
+                raise ValueError("no acquisition %r (allowed: %s)" % (kind, ", ".join(sorted(ACQ))))
+            kind = ACQ[kind]
+        self._check(self._lib.spx_set_acquisition(self._h, int(kind), float(par)))
+
+    def get_acquisition(self):
+        """(kind, par) as the handle holds them."""
+        kind = ctypes.c_int32(-1)
+        par = ctypes.c_double(0.0)
+        self._check(self._lib.spx_get_acquisition(self._h, ctypes.byref(kind), ctypes.byref(par)))
+        return int(kind.value), float(par.value)
 
     # -- hot path ---------------------------------------------------------
     def factor(self):
