@@ -250,6 +250,37 @@ int spx_get_ei_mean(spx_handle* h, double* out /* M */);
 /* overall_ei exactly as the reference lays it out: M x H, row-major           */
 int spx_get_ei_draws(spx_handle* h, double* out /* M*H */);
 
+/* ---- parameter sensitivity: main effects of the posterior mean ---------------------------------------------------
+ * The functional-ANOVA main effect of every input dimension under every resident hyper draw, from ONE structured grid of
+ * (D T + 1) Q rows that is formed, scored and reduced on the device.  D = dimension of the resident observations, H = resident
+ * draws; base = Q points of the unit cube (Q x D, row-major), levels = T values substituted into one coordinate at a time.
+ *   rows     r = (j T + k) Q + q  is base[q] with coordinate j replaced by levels[k]   (j < D, k < T, q < Q);
+ *            the last Q rows, r = D T Q + q, are base[q] itself.
+ *   values   func_m_d(r) = the predictive mean of draw d at row r, exactly what spx_get_moments returns after a pass:
+ *            curves[d][j][k] = np.mean of the Q values of block (j, k) in numpy's order (its pairwise sum, then ONE true
+ *            division by Q);   base_mean[d][q] = func_m_d(D T Q + q)   (H x Q; may be NULL).
+ * Bit-for-bit contract: the values equal those of the same rows built on the host, spx_set_candidates,
+ * spx_ei_run(SPX_FLAG_KEEP_MOMENTS), spx_get_moments and np.mean(func_m.reshape(H, D, T, Q), axis=-1).  The means go through
+ * the pass's own K(X*,X) + predict-GEMM (or fused N <= 128) path; a candidate's moments do not depend on which other candidates
+ * share a pass, so the rows may be scored in several passes -- spx_set_option "effects_pass_rows" (rows per pass; 0 = the
+ * default, 2^20) bounds what a pass allocates, blocks of Q may straddle a boundary, and every split gives the same bits.
+ * Needs (SPX_ERR_ARG otherwise, decided before any device is touched, the handle exactly as it was, the last pass's results
+ * included): a held factorisation (spx_factor, spx_ei_step or spx_ei_grid has run); no fantasies held (the resident rows would
+ * include pending points, and such a pass keeps no func_m); a single-GPU handle without a communicator and without a 2-D
+ * partition; base, levels, curves non-NULL; 1 <= Q <= 524 288 (the depth of the pairwise walk); 1 <= T;
+ * (D T + 1) Q <= 2^30 rows.
+ * State: the call takes the candidates and the results of the last pass away before its first mutation and leaves them away
+ * (spx_get_best, spx_get_ei_mean, spx_get_moments and spx_ei_run refuse until spx_set_candidates / a new pass); the
+ * factorisation, the time and constraint models, the options and the acquisition setting stay, and the values do not depend
+ * on that setting.  spx_get_stat "last_effects_passes" / "last_effects_rows": passes and rows of the last call.           */
+int spx_main_effects(spx_handle* h,
+                     const double* base,   /* Q x D, row-major: points of the unit cube        */
+                     int32_t Q,
+                     const double* levels, /* T values substituted into one coordinate         */
+                     int32_t T,
+                     double* curves,       /* H x D x T                                         */
+                     double* base_mean);   /* H x Q; may be NULL                                */
+
 /* ---- one-shot convenience: host buffers in, results out ------------------ */
 /* == ei_over_hypers + argmax(mean) (GPEIOptChooser.py:331-341, :294).
  * ei_mean_out (M) and ei_draw_out (M x H) may be NULL.                         */

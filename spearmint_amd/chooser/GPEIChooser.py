@@ -56,6 +56,8 @@ class GPEIChooser(GPEIBase):
                                                  randn=randn)
             if self.recommend:     # (the proposal is fixed; no random numbers from here on)
                 self._recommend(grid, comp, vals, self.current_hyper_row()[None, :])
+            if self.importance:    # (after the recommendation, whose factorisation it reuses)
+                self._importance(grid, comp, vals, self.current_hyper_row()[None, :])
             return int(candidates[best])
         # The reference alternates "sample hypers" and "compute_ei" (:145-151).
         # Without pending experiments compute_ei consumes no random numbers, so
@@ -79,4 +81,6 @@ class GPEIChooser(GPEIBase):
         best, _, _ = self.ei_over_hypers_gpu(comp, pend, cand, vals, np.array(rows), randn=randn)
         if self.recommend:         # (the proposal is fixed; no random numbers from here on)
             self._recommend(grid, comp, vals, np.array(rows))
+        if self.importance:        # (after the recommendation, whose factorisation it reuses)
+            self._importance(grid, comp, vals, np.array(rows))
         return int(candidates[best])

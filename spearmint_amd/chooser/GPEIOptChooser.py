@@ -99,7 +99,21 @@ class GPEIOptChooser(GPEIBase):
                    'var lsdata = [' + ",".join(["%.2f" % v for v in mean_ls]) + '];')
         except Exception:
             return "Chooser not yet ready to display output."
-        return out + 'bar_chart("#lschart", lsdata, ' + str(self.max_ls) + ');</script>'
+        out += 'bar_chart("#lschart", lsdata, ' + str(self.max_ls) + ');</script>'
+        if self.importance and os.path.exists(self.importance_file):
+            # the real thing beside its stand-in: first-order sensitivity indices of the posterior mean (importance.txt)
+            try:
+                with open(self.importance_file) as fh:
+                    rows = [ln.split() for ln in fh.read().splitlines()[1:]]
+                sdata = [float(r[1]) for r in rows]
+            except Exception:
+                return out
+            out += ('<br /><br /><span class="label label-info">Parameter sensitivity'
+                    ' - first-order indices of the posterior mean</span><br /><br />'
+                    '<div id="sensitivity"></div><script type="text/javascript">'
+                    'var sdata = [' + ",".join(["%.2f" % v for v in sdata]) + '];'
+                    'bar_chart("#sensitivity", sdata, 1);</script>')
+        return out
 
     # -- sampling ----------------------------------------------------------------
     def sample_hypers(self, comp, vals):
@@ -209,4 +223,6 @@ class GPEIOptChooser(GPEIBase):
         job = (int(numcand), refined[best - numcand, :]) if best >= numcand else int(candidates[best])
         if self.recommend:         # (the proposal is fixed; no random numbers from here on)
             self._recommend(grid, comp, vals, rows, refine_count=self.grid_subset)
+        if self.importance:        # (after the recommendation, whose factorisation it reuses)
+            self._importance(grid, comp, vals, rows)
         return job

@@ -47,11 +47,13 @@ class GPEIBase(object):
     max_rows_per_call = 32         # spx_gp_logprob: one data-flow launch up to 32 hyper rows (spx_api.hip: do_factor, `rl`)
     acq_allowed = ("EI", "PI", "LCB")   # acq=: what the engine scores candidates with (include/spx.h SPX_ACQ_*)
     recommend_allowed = True       # recommend=1: the model-mean recommendation after every proposal (_recommend)
+    importance_allowed = True      # importance=1: the parameter-sensitivity report after every proposal (_importance)
+    importance_max_points = 128 << 12   # include/spx.h: Q of spx_main_effects
 
     def __init__(self, expt_dir, covar="Matern52", mcmc_iters=10, pending_samples=100,
                  noiseless=False, device=0, ndev=1, lib=None, gpu_logprob="auto", gpu_refine="auto",
                  lookahead="auto", follow="auto", sampler="native", gpu_sobol=0, gpu_fantasies="auto", acq="EI", acq_par=0,
-                 recommend=0, **unused):
+                 recommend=0, importance=0, importance_levels=16, importance_points=256, **unused):
         if covar not in hostgp.COVARS:
             # the reference does getattr(gp, covar) here (GPEIChooser.py:52)
             raise AttributeError("no covariance function %r (gp.py has %s)" % (covar, ", ".join(hostgp.COVARS)))
@@ -62,6 +64,24 @@ class GPEIBase(object):
             raise ValueError("recommend=1 is not available on %s (allowed: recommend=0)" % type(self).__name__)
         self.last_recommendation = None
         self.recommendation_file = os.path.join(expt_dir, "recommendation.txt")
+        self.importance = _as_bool(importance)
+        try:
+            self.importance_levels, self.importance_points = int(importance_levels), int(importance_points)
+        except (TypeError, ValueError):
+            raise ValueError("importance_levels=%r / importance_points=%r are not integers (allowed: importance_levels >= 1, "
+                             "importance_points in 1..%d)" % (importance_levels, importance_points, self.importance_max_points))
+        if self.importance_levels < 1:
+            raise ValueError("importance_levels=%d is out of range (allowed: >= 1)" % self.importance_levels)
+        if not 1 <= self.importance_points <= self.importance_max_points:
+            raise ValueError("importance_points=%d is out of range (allowed: 1..%d)" % (self.importance_points,
+                                                                                        self.importance_max_points))
+        if self.importance and not self.importance_allowed:
+            raise ValueError("importance=1 is not available on %s (allowed: importance=0)" % type(self).__name__)
+        if self.importance and int(ndev) > 1:
+            raise ValueError("importance=1 is not available with ndev=%d (allowed: importance=0, or ndev=1)" % int(ndev))
+        self.last_importance = None
+        self.importance_file = os.path.join(expt_dir, "importance.txt")
+        self._factor_covers = None      # (comp, vals, rows) the engine's factor was last made from by _recommend
         self.expt_dir = expt_dir
         self.locker = Locker()
         self.state_pkl = os.path.join(expt_dir, self.__module__ + ".pkl")
@@ -161,12 +181,14 @@ class GPEIBase(object):
         rows = np.ascontiguousarray(np.atleast_2d(hyper_rows), dtype=np.float64)
         prev = eng.get_acquisition()
         self._lp_key = None
+        self._factor_covers = None
         try:
             eng.set_observations(comp, vals)
             eng.set_candidates(grid)
             eng.set_hypers(rows)
             eng.set_acquisition(ACQ_LCB, 0.0)
             eng.ei_step()
+            self._factor_covers = (comp, vals, rows)     # (_importance, right behind this call, needs no factorisation of its own)
             neg_mean = eng.ei_mean()                     # minus the mean over draws of func_m
             finite = np.nonzero(~np.isnan(neg_mean))[0]
             if finite.size == 0:
@@ -202,6 +224,52 @@ class GPEIBase(object):
         finally:
             self.locker.unlock(self.recommendation_file)
         return rec
+
+    # -- the parameter-sensitivity report (importance=1) ------------------------------
+    def _importance(self, grid, comp, vals, hyper_rows):
+        """Main effects of the posterior mean and first-order sensitivity indices under this call's hyper draws
+        (Engine.main_effects: one structured grid pass on the device).  Completed points only: no pending rows, no fantasies;
+        one factorisation, or none where _recommend has just factored the same inputs.  The base points are the first
+        importance_points rows of `grid` -- the Sobol prefix: with as many pseudo-random points the indices were off by up to
+        0.14 where the prefix is within 0.006 --, the levels the importance_levels midpoints.  Draws no random numbers and
+        changes no proposal.  Leaves self.last_importance = the engine's dict + first_order_mean / first_order_std (over the
+        draws, (D,)) + curves_mean (D, T), and rewrites importance.txt (a temporary file renamed over it, under the chooser's
+        Locker): a header line, then per dimension  j first_order_mean first_order_std effect_var_mean curve_mean[0..T)."""
+        eng = self.engine()
+        grid = np.ascontiguousarray(grid, dtype=np.float64)
+        rows = np.ascontiguousarray(np.atleast_2d(hyper_rows), dtype=np.float64)
+        base = grid[:min(self.importance_points, grid.shape[0]), :]
+        have, self._factor_covers = self._factor_covers, None
+        self._lp_key = None
+        if not (have is not None and have[0] is comp and have[1] is vals and np.array_equal(have[2], rows)):
+            eng.set_observations(comp, vals)
+            eng.set_hypers(rows)
+            eng.factor()
+        rep = dict(eng.main_effects(base, T=self.importance_levels))
+        with np.errstate(invalid="ignore"):
+            rep["first_order_mean"] = np.mean(rep["first_order"], axis=0)
+            rep["first_order_std"] = np.std(rep["first_order"], axis=0)
+        rep["curves_mean"] = np.mean(rep["curves"], axis=0)
+        self.last_importance = rep
+        H, D, T = rep["curves"].shape
+        lines = ["# completed=%d draws=%d levels=%d points=%d f0=%.17g total_var=%.17g"
+                 % (comp.shape[0], H, T, base.shape[0], np.mean(rep["f0"]), np.mean(rep["total_var"]))]
+        ev = np.mean(rep["effect_var"], axis=0)
+        for j in range(D):
+            lines.append("%d %.17g %.17g %.17g %s" % (j, rep["first_order_mean"][j], rep["first_order_std"][j], ev[j],
+                                                    " ".join("%.17g" % v for v in rep["curves_mean"][j])))
+        self.locker.lock_wait(self.importance_file)
+        try:
+            import tempfile
+            fh = tempfile.NamedTemporaryFile(mode="w", delete=False, dir=os.path.dirname(os.path.abspath(self.importance_file)))
+            try:
+                fh.write("\n".join(lines) + "\n")
+            finally:
+                fh.close()
+            os.rename(fh.name, self.importance_file)
+        finally:
+            self.locker.unlock(self.importance_file)
+        return rep
 
     # -- GPU handle -----------------------------------------------------------
     def engine(self):

@@ -156,6 +156,14 @@ void launch_fant_fill(hipStream_t s, const double* post, const double* z, size_t
 // sobol_kernels.hip
 void launch_sobol_grid(hipStream_t s, const uint32_t* dirs, int dim, int64_t n, int64_t skip, double* out);
 
+// effects_kernels.hip: the structured rows of spx_main_effects for rows [r0, r0 + m), and the reduction of the kept means
+// ([H] rows of `mstride` doubles) into curves [H][D T] and base_mean [H][Q] (spx_plan.h: plan_effects)
+struct EffectsPlan;
+void launch_effects_rows(hipStream_t s, const double* base, const double* levels, int D, int T, int Q, int64_t r0, int64_t m,
+                         double* out);
+void launch_effects_mean(hipStream_t s, const EffectsPlan& p, const double* mean, int64_t mstride, int Q, int H, double* curves,
+                         double* base_mean);
+
 // predict_kernels.hip
 void launch_predict_gemm(hipStream_t s, int variant, const double* WT, const double* Kst, const double* gamma,
                          double* part_ss, double* part_bg, int Np, int Mc, int nh, int part_nh, int part_h0,

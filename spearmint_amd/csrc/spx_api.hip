@@ -158,6 +158,11 @@ static int opt_kstar_budget(spx_handle* h, int64_t value)
     h->opt.kst_budget = value > 0 ? value : (512ll << 20);
     return SPX_OK;
 }
+static int opt_effects_pass_rows(spx_handle* h, int64_t value)
+{
+    h->opt.effects_pass_rows = value > 0 ? value : 0;
+    return SPX_OK;
+}
 static int opt_gemm_waves(spx_handle* h, int64_t value)
 {
     if (!predict_gemm_variant_ok((int)value))
@@ -208,6 +213,7 @@ struct OptRow {
 #define OPT_CALL(name, fn) {name, nullptr, 0, 0, fn}
 static const OptRow kOptions[] = {
     OPT_CALL("kstar_budget_bytes", opt_kstar_budget),   // K(X*,X) staging buffer per stream (0 = default, 512 MiB)
+    OPT_CALL("effects_pass_rows", opt_effects_pass_rows),   // spx_main_effects: structured rows per grid pass (0 = default, 2^20); same bits for every value
     OPT_CALL("gemm_waves", opt_gemm_waves),             // predict-GEMM variant of this handle (predict_kernels.hip)
     OPT_CALL("covar", opt_covar),                       // SPX_COVAR_*: the reference's covar= (gp.py:87-132)
     OPT_TRI("lean_lazy", lean_lazy),                    // log-likelihood path: trailing updates two steps at a time (1), one (0), by size (-1, default)
@@ -286,7 +292,7 @@ void spx_destroy(spx_handle* h)
                           &h->am_out_val, &h->am_out_idx, &h->scratch, &h->sobol_dirs, &h->sobol_out, &h->rhs, &h->diagL, &h->ps_flags, &h->flow_flags,
                           &h->alphaS, &h->pt_u, &h->rec_send, &h->rec_recv, &h->rec_out, &h->ei_sum_full,
                           &h->con_tab, &h->con_Cs[0], &h->con_Cs[1], &h->con_s2[0], &h->con_s2[1], &h->con_p[0], &h->con_p[1],
-                          &h->mom_c, &h->rhs_rows};
+                          &h->mom_c, &h->rhs_rows, &h->eff_in, &h->eff_m, &h->eff_out};
         for (DevBuf* b : bufs) b->release();
         h->pin_up.release();
         h->pin_res.release();
@@ -1782,6 +1788,84 @@ int spx_constrained_ei_grad_batch(spx_handle* h, const double* points, int32_t P
                          neg_cei, grad);
 }
 
+// Main effects of the posterior mean (spx.h).  The (D T + 1) Q structured rows are formed on the device (k_effects_rows) and
+// scored by the ordinary pass with the moments kept -- ei_run_impl, one call per plan_effects pass, so a row's func_m is the
+// bits spx_ei_run + spx_get_moments give for it -- and the kept means are reduced on the device (k_effects_mean).  The pass
+// runs as SPX_ACQ_EI whatever the handle is set to (the moments do not depend on it; the setting is put back), and its own
+// results (the winner, the EI values) are not kept: the call drops CAND, and with it RESULTS, before its first mutation and
+// leaves them dropped.
+int spx_main_effects(spx_handle* h, const double* base, int32_t Q, const double* levels, int32_t T, double* curves,
+                     double* base_mean)
+{
+    if (!h) return fail(SPX_ERR_ARG, "spx_main_effects: null handle");
+    if (!base || !levels || !curves) return fail(SPX_ERR_ARG, "spx_main_effects: base, levels and curves must not be NULL");
+    if (Q < 1 || Q > NP_PAIRWISE_MAX_N)
+        return fail(SPX_ERR_ARG, "spx_main_effects: Q=%d base points (allowed: 1 .. %d)", (int)Q, NP_PAIRWISE_MAX_N);
+    if (T < 1) return fail(SPX_ERR_ARG, "spx_main_effects: T=%d levels (allowed: >= 1)", (int)T);
+    if (h->multi) return fail(SPX_ERR_ARG, "spx_main_effects: single-GPU handles only (multi-device handle)");
+    if (h->comm) return fail(SPX_ERR_ARG, "spx_main_effects: single-GPU handles only (communicator attached)");
+    if (h->part_ph > 1 || h->part_M > 0) return fail(SPX_ERR_ARG, "spx_main_effects: not available with a 2-D partition");
+    if (!h->held.has(Held::FACTOR)) return fail(SPX_ERR_ARG, "spx_main_effects: call spx_factor first");
+    if (h->held.has(Held::FANT))
+        return fail(SPX_ERR_ARG, "spx_main_effects: fantasies are held (the resident rows include pending points); clear them first");
+    EffectsShape sh;
+    sh.D = h->D; sh.H = h->H; sh.Q = Q; sh.T = T; sh.pass_rows_opt = h->opt.effects_pass_rows;
+    if (((int64_t)h->D * T + 1) > SPX_EFFECTS_MAX_ROWS / Q)
+        return fail(SPX_ERR_ARG, "spx_main_effects: (D T + 1) Q = (%d x %d + 1) x %d rows (allowed: up to %lld)", h->D, (int)T, (int)Q,
+                    (long long)SPX_EFFECTS_MAX_ROWS);
+    int rc = ensure_init(h);
+    if (rc) return rc;
+    spx_drop(h, Held::CAND);          // and RESULTS, which are made from them
+    EffectsPlan& p = h->effects_plan;
+    p = plan_effects(sh);
+    const int D = h->D, H = h->H;
+    if ((rc = h->eff_in.reserve(p.in_bytes))) return rc;
+    if ((rc = h->eff_out.reserve(p.out_bytes))) return rc;
+    if ((rc = h->cand.reserve(p.cand_bytes))) return rc;
+    if (p.gather && (rc = h->eff_m.reserve(p.gather_bytes))) return rc;
+    double* d_base = h->eff_in.d();
+    double* d_levels = d_base + (size_t)Q * D;
+    double* d_curves = h->eff_out.d();
+    double* d_bmean = d_curves + (size_t)H * p.nblocks;
+    stage_begin(h);
+    if ((rc = stage_h2d(h, d_base, base, (size_t)Q * D * 8, h->stream))) return rc;
+    if ((rc = stage_h2d(h, d_levels, levels, (size_t)T * 8, h->stream))) return rc;
+    const int acq = h->acq;
+    const double acq_par = h->acq_par;
+    h->acq = SPX_ACQ_EI; h->acq_par = 0.0;
+    h->index_base = 0;
+    for (int64_t r0 = 0; r0 < p.rows && !rc; r0 += p.pass_rows) {
+        const int64_t m = std::min<int64_t>(p.pass_rows, p.rows - r0);
+        launch_effects_rows(h->stream, d_base, d_levels, D, T, Q, r0, m, h->cand.d());
+        // (the pass may read the rows on a producer stream of its own: they are complete before it is queued)
+        hipError_t e = hipStreamSynchronize(h->stream);
+        if (e == hipSuccess) e = hipGetLastError();
+        if (e != hipSuccess) { rc = fail(SPX_ERR_HIP, "spx_main_effects: k_effects_rows failed: %s", hipGetErrorString(e)); break; }
+        h->M = m;
+        if ((rc = spx_hold(h, Held::CAND))) break;
+        if ((rc = ei_run_impl(h, SPX_FLAG_KEEP_MOMENTS, false))) break;
+        if (p.gather) {
+            const int64_t Mp = h->ei_plan.Mp;
+            e = hipMemcpy2DAsync(h->eff_m.d() + r0, (size_t)p.rows * 8, h->mom_m.d(), (size_t)Mp * 8, (size_t)m * 8, (size_t)H,
+                                 hipMemcpyDeviceToDevice, h->stream);
+            if (e != hipSuccess) { (void)hipGetLastError(); rc = fail(SPX_ERR_HIP, "spx_main_effects: hipMemcpy2DAsync failed: %s", hipGetErrorString(e)); }
+        }
+    }
+    h->acq = acq; h->acq_par = acq_par;
+    if (!rc) {
+        launch_effects_mean(h->stream, p, p.gather ? h->eff_m.d() : h->mom_m.d(), p.gather ? p.rows : h->ei_plan.Mp, Q, H, d_curves,
+                            d_bmean);
+        hipError_t e = hipGetLastError();
+        if (e != hipSuccess) rc = fail(SPX_ERR_HIP, "spx_main_effects: k_effects_mean failed: %s", hipGetErrorString(e));
+    }
+    if (!rc) rc = stage_d2h(h, curves, d_curves, (size_t)H * p.nblocks * 8, h->stream);
+    if (!rc && base_mean) rc = stage_d2h(h, base_mean, d_bmean, (size_t)H * Q * 8, h->stream);
+    if (rc) { (void)hipStreamSynchronize(h->stream); (void)hipGetLastError(); }
+    spx_drop(h, Held::CAND);          // the rows of the last pass are nobody's candidates
+    h->M = 0;
+    return rc;
+}
+
 int spx_get_stat(spx_handle* h, const char* name, int64_t* value)
 {
     if (!h || !name || !value) return fail(SPX_ERR_ARG, "spx_get_stat: null");
@@ -1807,6 +1891,8 @@ int spx_get_stat(spx_handle* h, const char* name, int64_t* value)
     else if (!strcmp(name, "fantasies_pending_rows")) *value = (h->S > 0 && h->fant_device) ? h->fant_P : 0;   // ... P and
     else if (!strcmp(name, "fantasies_count")) *value = (h->S > 0 && h->fant_device) ? h->S : 0;               // ... S of them
     else if (!strcmp(name, "last_kstar_ring")) *value = h->ei_plan.R;   // slots of the K(X*,X) ring the last EI pass ran with (0: not a streams = 3 pass)
+    else if (!strcmp(name, "last_effects_passes")) *value = h->effects_plan.npass;   // grid passes the last spx_main_effects ran its rows in
+    else if (!strcmp(name, "last_effects_rows")) *value = h->effects_plan.rows;      // ... and how many rows that were
     else if (!strcmp(name, "gemm_lds_bytes")) *value = (int64_t)predict_gemm_lds_bytes();   // dynamic LDS of a predict-GEMM workgroup (two are resident per CU)
     else if (!strcmp(name, "hip_runtime_version") || !strcmp(name, "hip_driver_version")) {
         // what the process runs on: a measurement names it (bench.py's line), two boxes of one pool differed in round 5

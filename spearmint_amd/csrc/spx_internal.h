@@ -161,6 +161,9 @@ struct spx_handle {
     int part_H = 0;
     DevBuf ei_sum_full;
     DevBuf sobol_dirs, sobol_out;                                   // spx_sobol_grid
+    // spx_main_effects: base | levels as uploaded; the kept means of several passes gathered [H][rows]; curves | base_mean
+    DevBuf eff_in, eff_m, eff_out;
+    EffectsPlan effects_plan;                                       // the last spx_main_effects (spx_plan.h)
     // probit constraint model (spx_set_constraint_model): an internal handle on the same device factors
     // (amp2_c (K_c + 1e-6 I) + noise_c I) alpha_c = ff over its own Nc points; the EI pass reads its scaled rows and alpha_c
     spx_handle* con = nullptr;

@@ -25,6 +25,7 @@ struct Options {
     int corun_opt = SPX_DEFAULT_CORUN;  // "kstar_corun"
     int flow_rearm_after = 16;          // (0 = never)
     int flow_spin_limit = 0;            // (0 = the kernel's default)
+    int64_t effects_pass_rows = 0;      // "effects_pass_rows": rows per pass of spx_main_effects (0 = default)
     bool timing = false;
     int lean_lazy = -1, step_overlap = -1, ei_fused = -1, ei_flow = -1, lean_flow_cov = -1, lean_flow_yield = -1,
         lean_flow_cu = -1, lean_flow = -1, lean_ps = -1, lean_merge = -1, lean_one = -1, lean_poll = -1, lean_zc = -1,
@@ -315,5 +316,61 @@ inline EiPlan plan_ei(const Options& o, const EiShape& s)
     p.scratch_bytes = (size_t)p.Hb * S * Mc * 8;
     p.draw_bytes = (size_t)H * Mp * 8;
     p.mean_bytes = (size_t)Mp * 8;
+    return p;
+}
+
+// ---- the main-effects report (spx_main_effects) ---------------------------------------------------------------------
+// (D T + 1) Q structured rows go through ordinary EI passes with the moments kept; the rows of a pass are formed on the
+// device, the kept means are reduced on the device.  What is decided here: how many rows a pass takes (option
+// "effects_pass_rows": the candidate buffer, the scaled rows and the per-draw result rows of a pass grow with it, so it bounds
+// the memory of the call; blocks of Q may straddle a boundary -- the means of all passes are gathered into one [H][rows]
+// array first, so every split gives the same bits) and how k_effects_mean reads a block of Q means.
+#define SPX_EFFECTS_MAX_ROWS (1ll << 30)      // (D T + 1) Q of one call; beyond it spx_main_effects refuses
+#define SPX_EFFECTS_PASS_ROWS (1ll << 20)     // default rows per pass
+#define SPX_EFFECTS_LDS_BYTES (48 << 10)      // k_effects_mean's staging tile (three workgroups per CU)
+#define SPX_EFFECTS_THREADS 256
+struct EffectsShape {
+    int D = 0, H = 0;
+    int64_t Q = 0, T = 0;
+    int64_t pass_rows_opt = 0;      // option "effects_pass_rows" (0 = default)
+};
+
+struct EffectsPlan {
+    int64_t rows = 0;               // (D T + 1) Q
+    int64_t nblocks = 0;            // D T blocks of Q rows that become one entry of `curves` each
+    int64_t pass_rows = 0;
+    int npass = 0;
+    bool gather = false;            // several passes: their kept means are copied into one [H][rows] array
+    // k_effects_mean: a workgroup stages `wg_blocks` whole blocks in LDS with coalesced loads (row stride Q | 1: odd, so the
+    // lanes that then walk one block each start in different banks) and one lane per block walks numpy's pairwise tree;
+    // a block too long for the tile is walked straight from memory, one lane each
+    bool mean_lds = false;
+    int wg_blocks = 0;
+    int64_t mean_tiles = 0;         // workgroups of the reduction, per draw
+    int64_t gather_tiles = 0;       // ... and of the base_mean gather behind them
+    size_t lds_bytes = 0;
+    size_t in_bytes = 0, out_bytes = 0, cand_bytes = 0, gather_bytes = 0;
+};
+
+inline EffectsPlan plan_effects(const EffectsShape& s)
+{
+    EffectsPlan p;
+    p.nblocks = (int64_t)s.D * s.T;
+    p.rows = (p.nblocks + 1) * s.Q;
+    const int64_t want = s.pass_rows_opt > 0 ? s.pass_rows_opt : SPX_EFFECTS_PASS_ROWS;
+    p.pass_rows = std::min<int64_t>(p.rows, want);
+    p.npass = (int)((p.rows + p.pass_rows - 1) / p.pass_rows);
+    p.gather = p.npass > 1;
+    const int64_t ldq = s.Q | 1;
+    const int64_t fit = SPX_EFFECTS_LDS_BYTES / (ldq * 8);
+    p.mean_lds = fit >= 1;
+    p.wg_blocks = p.mean_lds ? (int)std::min<int64_t>(fit, SPX_EFFECTS_THREADS) : SPX_EFFECTS_THREADS;
+    p.mean_tiles = (p.nblocks + p.wg_blocks - 1) / p.wg_blocks;
+    p.gather_tiles = (s.Q + SPX_EFFECTS_THREADS - 1) / SPX_EFFECTS_THREADS;
+    p.lds_bytes = p.mean_lds ? (size_t)p.wg_blocks * ldq * 8 : 0;
+    p.in_bytes = ((size_t)s.Q * s.D + (size_t)s.T) * 8;
+    p.out_bytes = ((size_t)s.H * p.nblocks + (size_t)s.H * s.Q) * 8;
+    p.cand_bytes = (size_t)p.pass_rows * s.D * 8;
+    p.gather_bytes = p.gather ? (size_t)s.H * p.rows * 8 : 0;
     return p;
 }
