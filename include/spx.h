@@ -281,6 +281,32 @@ int spx_main_effects(spx_handle* h,
                      double* curves,       /* H x D x T                                         */
                      double* base_mean);   /* H x Q; may be NULL                                */
 
+/* ---- model check: leave-one-out cross-validation of the resident factorisation ------------------------------------------
+ * For every observation i and every resident hyper draw, the predictive mean and variance at x_i of the GP trained on all the
+ * OTHER observations under that draw's hyper-parameters -- no refit (Rasmussen & Williams, 5.4.2): with K the draw's
+ * amp2 (k + 1e-6 I) + noise I, c_i = (K^-1)_ii and alpha = K^-1 (y - mean),
+ *     kinv_diag[d][i] = c_i        loo_var[d][i] = 1 / c_i        loo_mean[d][i] = y_i - alpha_i / c_i
+ * (loo_var includes the noise: it is the variance of the left-out OBSERVATION).  c_i is the squared norm of row i of the
+ * resident L^-T, summed on the device in an order that depends on i and on N rounded up to 128 alone: the values of a draw
+ * do not depend on how many other draws are resident, on options, on candidates or on earlier passes.  1 / c and alpha / c are
+ * IEEE divisions, the subtraction is one IEEE subtraction.  model = SPX_LOO_OBJECTIVE: y = the observed values;
+ * SPX_LOO_TIME: y = log_durs, K and alpha those of the log-duration GP of spx_set_time_model.
+ * NaN or inf in y propagates by IEEE rules (alpha is NaN throughout, so loo_mean is; loo_var and kinv_diag do not depend on y);
+ * nothing is clamped and no error is returned.  N = 1: loo_mean = the draw's prior mean (up to the rounding of
+ * alpha_0 = K_00^-1 (y_0 - mean)), loo_var = K_00.
+ * Needs (SPX_ERR_ARG otherwise, decided before any device is touched, the handle exactly as it was): a held factorisation
+ * (spx_factor, spx_ei_step or spx_ei_grid has run) -- for SPX_LOO_TIME one made while a time model was held; no fantasies held
+ * (the resident rows would include pending points whose values are placeholders); a single-GPU handle without a communicator
+ * and without a 2-D partition; loo_mean, loo_var non-NULL.
+ * State: a reader, as spx_get_factor is.  Nothing is dropped or set: candidates, the results of the last pass, options and the
+ * acquisition setting are bit for bit what they were.                                                                        */
+#define SPX_LOO_OBJECTIVE 0
+#define SPX_LOO_TIME      1   /* the log-duration GP of spx_set_time_model */
+int spx_loo(spx_handle* h, int32_t model,
+            double* loo_mean,   /* H x N */
+            double* loo_var,    /* H x N */
+            double* kinv_diag); /* H x N; may be NULL */
+
 /* ---- one-shot convenience: host buffers in, results out ------------------ */
 /* == ei_over_hypers + argmax(mean) (GPEIOptChooser.py:331-341, :294).
  * ei_mean_out (M) and ei_draw_out (M x H) may be NULL.                         */

@@ -47,6 +47,7 @@ class GPConstrainedEIChooser(GPEIBase):
     acq_allowed = ("EI",)           # PI / LCB are not defined with a constraint model (include/spx.h: spx_set_acquisition)
     recommend_allowed = False
     importance_allowed = False
+    loo_allowed = False
     max_ls = 2
     noise_scale = 0.1
     amp2_scale = 1

@@ -58,6 +58,8 @@ class GPEIChooser(GPEIBase):
                 self._recommend(grid, comp, vals, self.current_hyper_row()[None, :])
             if self.importance:    # (after the recommendation, whose factorisation it reuses)
                 self._importance(grid, comp, vals, self.current_hyper_row()[None, :])
+            if self.loo:           # (last: it reuses what either of the two has factored)
+                self._loo(complete, comp, vals, self.current_hyper_row()[None, :])
             return int(candidates[best])
         # The reference alternates "sample hypers" and "compute_ei" (:145-151).
         # Without pending experiments compute_ei consumes no random numbers, so
@@ -83,4 +85,6 @@ class GPEIChooser(GPEIBase):
             self._recommend(grid, comp, vals, np.array(rows))
         if self.importance:        # (after the recommendation, whose factorisation it reuses)
             self._importance(grid, comp, vals, np.array(rows))
+        if self.loo:               # (last: it reuses what either of the two has factored)
+            self._loo(complete, comp, vals, np.array(rows))
         return int(candidates[best])

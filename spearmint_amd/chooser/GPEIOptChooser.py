@@ -113,7 +113,42 @@ class GPEIOptChooser(GPEIBase):
                     '<div id="sensitivity"></div><script type="text/javascript">'
                     'var sdata = [' + ",".join(["%.2f" % v for v in sdata]) + '];'
                     'bar_chart("#sensitivity", sdata, 1);</script>')
+        if self.loo and os.path.exists(self.loo_file):
+            out += self._loo_chart_html()
         return out
+
+    def _loo_chart_html(self, size=360, pad=36):
+        """Predicted against observed, from loo.txt: one dot per completed job at (value, loo_mean) with a bar of
+        +- 2 loo_std, and the diagonal a model that believed every run would put them on.  Inline SVG: the page's bar_chart
+        draws bars only.  Rows without a finite value, mean or std are left out; nothing to draw: nothing added."""
+        try:
+            with open(self.loo_file) as fh:
+                rows = np.array([[float(v) for v in ln.split()[1:4]] for ln in fh.read().splitlines()[1:]], dtype=float)
+            rows = rows.reshape(-1, 3)
+            rows = rows[np.all(np.isfinite(rows), axis=1)]
+            if rows.shape[0] == 0:
+                return ""
+            lo = float(min(np.min(rows[:, 0]), np.min(rows[:, 1] - 2 * rows[:, 2])))
+            hi = float(max(np.max(rows[:, 0]), np.max(rows[:, 1] + 2 * rows[:, 2])))
+        except Exception:
+            return ""
+        span = (hi - lo) or 1.0
+
+        def px(v):
+            return pad + (size - 2 * pad) * (v - lo) / span
+
+        def py(v):
+            return size - px(v)
+        marks = []
+        for y, m, s in rows:
+            marks.append('<line x1="%.1f" y1="%.1f" x2="%.1f" y2="%.1f" stroke="#999" />' % (px(y), py(m - 2 * s), px(y), py(m + 2 * s)))
+            marks.append('<circle cx="%.1f" cy="%.1f" r="3" fill="#3a87ad" />' % (px(y), py(m)))
+        return ('<br /><br /><span class="label label-info">Leave-one-out check'
+                ' - predicted against observed, +- 2 std</span><br /><br />'
+                '<svg id="loochart" width="%d" height="%d">' % (size, size) +
+                '<line x1="%.1f" y1="%.1f" x2="%.1f" y2="%.1f" stroke="#ccc" />' % (px(lo), py(lo), px(hi), py(hi)) +
+                "".join(marks) +
+                '<text x="%d" y="%d" font-size="10">observed %.3g .. %.3g</text>' % (pad, size - 8, lo, hi) + '</svg>')
 
     # -- sampling ----------------------------------------------------------------
     def sample_hypers(self, comp, vals):
@@ -225,4 +260,6 @@ class GPEIOptChooser(GPEIBase):
             self._recommend(grid, comp, vals, rows, refine_count=self.grid_subset)
         if self.importance:        # (after the recommendation, whose factorisation it reuses)
             self._importance(grid, comp, vals, rows)
+        if self.loo:               # (last: it reuses what either of the two has factored)
+            self._loo(complete, comp, vals, rows)
         return job

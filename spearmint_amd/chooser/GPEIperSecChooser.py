@@ -34,6 +34,7 @@ class GPEIperSecChooser(GPEIBase):
     acq_allowed = ("EI",)           # PI / LCB are not defined per second (include/spx.h: spx_set_acquisition)
     recommend_allowed = False
     importance_allowed = False
+    loo_allowed = False
     amp2_prior_on_sqrt = False      # objective GP: log(amp2) (:626, :672)
     noiseless_checks_mean = True    # :660-661
     max_ls = 10                     # :74

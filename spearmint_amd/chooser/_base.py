@@ -49,11 +49,12 @@ class GPEIBase(object):
     recommend_allowed = True       # recommend=1: the model-mean recommendation after every proposal (_recommend)
     importance_allowed = True      # importance=1: the parameter-sensitivity report after every proposal (_importance)
     importance_max_points = 128 << 12   # include/spx.h: Q of spx_main_effects
+    loo_allowed = True             # loo=1: the leave-one-out report after every proposal (_loo)
 
     def __init__(self, expt_dir, covar="Matern52", mcmc_iters=10, pending_samples=100,
                  noiseless=False, device=0, ndev=1, lib=None, gpu_logprob="auto", gpu_refine="auto",
                  lookahead="auto", follow="auto", sampler="native", gpu_sobol=0, gpu_fantasies="auto", acq="EI", acq_par=0,
-                 recommend=0, importance=0, importance_levels=16, importance_points=256, **unused):
+                 recommend=0, importance=0, importance_levels=16, importance_points=256, loo=0, **unused):
         if covar not in hostgp.COVARS:
             # the reference does getattr(gp, covar) here (GPEIChooser.py:52)
             raise AttributeError("no covariance function %r (gp.py has %s)" % (covar, ", ".join(hostgp.COVARS)))
@@ -81,7 +82,14 @@ class GPEIBase(object):
             raise ValueError("importance=1 is not available with ndev=%d (allowed: importance=0, or ndev=1)" % int(ndev))
         self.last_importance = None
         self.importance_file = os.path.join(expt_dir, "importance.txt")
-        self._factor_covers = None      # (comp, vals, rows) the engine's factor was last made from by _recommend
+        self._factor_covers = None      # (comp, vals, rows) the engine's factor was last made from by _recommend / _importance
+        self.loo = _as_bool(loo)
+        if self.loo and not self.loo_allowed:
+            raise ValueError("loo=1 is not available on %s (allowed: loo=0)" % type(self).__name__)
+        if self.loo and int(ndev) > 1:
+            raise ValueError("loo=1 is not available with ndev=%d (allowed: loo=0, or ndev=1)" % int(ndev))
+        self.last_loo = None
+        self.loo_file = os.path.join(expt_dir, "loo.txt")
         self.expt_dir = expt_dir
         self.locker = Locker()
         self.state_pkl = os.path.join(expt_dir, self.__module__ + ".pkl")
@@ -246,6 +254,7 @@ class GPEIBase(object):
             eng.set_hypers(rows)
             eng.factor()
         rep = dict(eng.main_effects(base, T=self.importance_levels))
+        self._factor_covers = (comp, vals, rows)         # (main_effects keeps the factorisation: _loo, right behind, reuses it)
         with np.errstate(invalid="ignore"):
             rep["first_order_mean"] = np.mean(rep["first_order"], axis=0)
             rep["first_order_std"] = np.std(rep["first_order"], axis=0)
@@ -269,6 +278,48 @@ class GPEIBase(object):
             os.rename(fh.name, self.importance_file)
         finally:
             self.locker.unlock(self.importance_file)
+        return rep
+
+    # -- the leave-one-out report (loo=1) ---------------------------------------------
+    def _loo(self, complete, comp, vals, hyper_rows):
+        """Does the GP fit these observations, and which runs does it not believe: for every completed point the predictive
+        mean and variance of the model trained on all the others, under this call's hyper draws (Engine.loo: one reduction
+        over the resident factorisation, no refit).  Completed points only: no pending rows, no fantasies; the factorisation
+        _recommend / _importance has just made of the same inputs is reused, otherwise there is one set_observations + factor
+        here (always while a job is pending: the proposal's factorisation covers the pending rows too).  Draws no random
+        numbers and changes no proposal.  Leaves self.last_loo = the engine's dict + grid_index, and rewrites loo.txt (a
+        temporary file renamed over it, under the chooser's Locker): a header line, then per completed job, in the order of
+        `complete`, the mixture over the draws:  grid_index value loo_mean loo_std z lpd."""
+        eng = self.engine()
+        rows = np.ascontiguousarray(np.atleast_2d(hyper_rows), dtype=np.float64)
+        have, self._factor_covers = self._factor_covers, None
+        self._lp_key = None
+        if not (have is not None and have[0] is comp and have[1] is vals and np.array_equal(have[2], rows)):
+            eng.set_observations(comp, vals)
+            eng.set_hypers(rows)
+            eng.factor()
+        rep = dict(eng.loo("objective"))
+        rep["grid_index"] = np.array(complete, dtype=np.int64).ravel()
+        self.last_loo = rep
+        H, N = rep["loo_mean"].shape
+        with np.errstate(invalid="ignore"):
+            std = np.sqrt(rep["var"])
+        lines = ["# completed=%d draws=%d elpd=%.17g rmse=%.17g coverage95=%.17g outliers=%d"
+                 % (N, H, rep["elpd"], rep["rmse"], rep["coverage95"], len(rep["outliers"]))]
+        for i in range(N):
+            lines.append("%d %.17g %.17g %.17g %.17g %.17g" % (rep["grid_index"][i], rep["y"][i], rep["mean"][i], std[i],
+                                                             rep["z_mix"][i], rep["lpd_mix"][i]))
+        self.locker.lock_wait(self.loo_file)
+        try:
+            import tempfile
+            fh = tempfile.NamedTemporaryFile(mode="w", delete=False, dir=os.path.dirname(os.path.abspath(self.loo_file)))
+            try:
+                fh.write("\n".join(lines) + "\n")
+            finally:
+                fh.close()
+            os.rename(fh.name, self.loo_file)
+        finally:
+            self.locker.unlock(self.loo_file)
         return rep
 
     # -- GPU handle -----------------------------------------------------------

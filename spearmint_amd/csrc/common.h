@@ -164,6 +164,11 @@ void launch_effects_rows(hipStream_t s, const double* base, const double* levels
 void launch_effects_mean(hipStream_t s, const EffectsPlan& p, const double* mean, int64_t mstride, int Q, int H, double* curves,
                          double* base_mean);
 
+// loo_kernels.hip: c = diag(K^-1) = the squared row norms of WT, 1 / c and y - alpha / c for rows j < N of nh draws of one model
+// (WT, alpha: that model's first draw; outputs [nh][N])
+void launch_loo_diag(hipStream_t s, const double* WT, const double* alpha, const double* y, int N, int Np, int nh,
+                     double* loo_mean, double* loo_var, double* kinv_diag);
+
 // predict_kernels.hip
 void launch_predict_gemm(hipStream_t s, int variant, const double* WT, const double* Kst, const double* gamma,
                          double* part_ss, double* part_bg, int Np, int Mc, int nh, int part_nh, int part_h0,

@@ -292,7 +292,7 @@ void spx_destroy(spx_handle* h)
                           &h->am_out_val, &h->am_out_idx, &h->scratch, &h->sobol_dirs, &h->sobol_out, &h->rhs, &h->diagL, &h->ps_flags, &h->flow_flags,
                           &h->alphaS, &h->pt_u, &h->rec_send, &h->rec_recv, &h->rec_out, &h->ei_sum_full,
                           &h->con_tab, &h->con_Cs[0], &h->con_Cs[1], &h->con_s2[0], &h->con_s2[1], &h->con_p[0], &h->con_p[1],
-                          &h->mom_c, &h->rhs_rows, &h->eff_in, &h->eff_m, &h->eff_out};
+                          &h->mom_c, &h->rhs_rows, &h->eff_in, &h->eff_m, &h->eff_out, &h->loo_out};
         for (DevBuf* b : bufs) b->release();
         h->pin_up.release();
         h->pin_res.release();
@@ -1863,6 +1863,44 @@ int spx_main_effects(spx_handle* h, const double* base, int32_t Q, const double*
     if (rc) { (void)hipStreamSynchronize(h->stream); (void)hipGetLastError(); }
     spx_drop(h, Held::CAND);          // the rows of the last pass are nobody's candidates
     h->M = 0;
+    return rc;
+}
+
+// Leave-one-out cross-validation of the resident factorisation (spx.h).  A reader, as spx_get_factor is: every refusal is
+// decided before a device is touched, nothing of `held` is set or dropped, and the only thing written on the device is the
+// call's own output buffer.  K^-1 = W^T W, so diag(K^-1) is the squared row norms of the resident WT (k_loo_diag).
+int spx_loo(spx_handle* h, int32_t model, double* loo_mean, double* loo_var, double* kinv_diag)
+{
+    if (!h) return fail(SPX_ERR_ARG, "spx_loo: null handle");
+    if (!loo_mean || !loo_var) return fail(SPX_ERR_ARG, "spx_loo: loo_mean and loo_var must not be NULL");
+    if (model != SPX_LOO_OBJECTIVE && model != SPX_LOO_TIME)
+        return fail(SPX_ERR_ARG, "spx_loo: model=%d (allowed: SPX_LOO_OBJECTIVE, SPX_LOO_TIME)", (int)model);
+    if (h->multi) return fail(SPX_ERR_ARG, "spx_loo: single-GPU handles only (multi-device handle)");
+    if (h->comm) return fail(SPX_ERR_ARG, "spx_loo: single-GPU handles only (communicator attached)");
+    if (h->part_ph > 1 || h->part_M > 0) return fail(SPX_ERR_ARG, "spx_loo: not available with a 2-D partition");
+    if (!h->held.has(Held::FACTOR)) return fail(SPX_ERR_ARG, "spx_loo: call spx_factor first");
+    if (h->held.has(Held::FANT))
+        return fail(SPX_ERR_ARG, "spx_loo: fantasies are held (the resident rows include pending points); clear them first");
+    if (model == SPX_LOO_TIME && h->nmodels < 2)
+        return fail(SPX_ERR_ARG, "spx_loo: SPX_LOO_TIME needs a factorisation made with a time model (spx_set_time_model, then spx_factor)");
+    int rc = ensure_init(h);
+    if (rc) return rc;
+    const int H = h->H, Np = h->Np, N = (int)h->N;
+    const size_t hn = (size_t)H * N;
+    if ((rc = h->loo_out.reserve(3 * hn * 8))) return rc;
+    double* out = h->loo_out.d();
+    const size_t m0 = (size_t)model * H;              // the time model's draws follow the objective's in WT and alpha
+    launch_loo_diag(h->stream, h->WT.d() + m0 * Np * Np, h->alpha.d() + m0 * Np, model ? h->ldur.d() : h->vals.d(), N, Np, H,
+                    out, out + hn, out + 2 * hn);
+    hipError_t e = hipGetLastError();
+    if (e != hipSuccess) {
+        (void)hipStreamSynchronize(h->stream); (void)hipGetLastError();
+        return fail(SPX_ERR_HIP, "spx_loo: k_loo_diag failed: %s", hipGetErrorString(e));
+    }
+    rc = stage_d2h(h, loo_mean, out, hn * 8, h->stream);
+    if (!rc) rc = stage_d2h(h, loo_var, out + hn, hn * 8, h->stream);
+    if (!rc && kinv_diag) rc = stage_d2h(h, kinv_diag, out + 2 * hn, hn * 8, h->stream);
+    if (rc) { (void)hipStreamSynchronize(h->stream); (void)hipGetLastError(); }
     return rc;
 }
 

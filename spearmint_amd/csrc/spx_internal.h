@@ -164,6 +164,7 @@ struct spx_handle {
     // spx_main_effects: base | levels as uploaded; the kept means of several passes gathered [H][rows]; curves | base_mean
     DevBuf eff_in, eff_m, eff_out;
     EffectsPlan effects_plan;                                       // the last spx_main_effects (spx_plan.h)
+    DevBuf loo_out;                                                 // spx_loo: loo_mean | loo_var | kinv_diag, [3][H][N]; scratch of that call, not part of `held`
     // probit constraint model (spx_set_constraint_model): an internal handle on the same device factors
     // (amp2_c (K_c + 1e-6 I) + noise_c I) alpha_c = ff over its own Nc points; the EI pass reads its scaled rows and alpha_c
     spx_handle* con = nullptr;

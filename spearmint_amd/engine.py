@@ -104,6 +104,7 @@ ABI = {
     "spx_set_acquisition": (ctypes.c_int, [_vp, ctypes.c_int32, ctypes.c_double]),
     "spx_get_acquisition": (ctypes.c_int, [_vp, _c_int32_p, _c_double_p]),
     "spx_main_effects": (ctypes.c_int, [_vp, _c_double_p, ctypes.c_int32, _c_double_p, ctypes.c_int32, _c_double_p, _c_double_p]),
+    "spx_loo": (ctypes.c_int, [_vp, ctypes.c_int32, _c_double_p, _c_double_p, _c_double_p]),
     "spx_ei_run": (ctypes.c_int, [_vp, ctypes.c_int32]),
     "spx_ei_step": (ctypes.c_int, [_vp, ctypes.c_int32]),
     "spx_get_best": (ctypes.c_int, [_vp, _c_int64_p, _c_double_p]),
@@ -217,6 +218,38 @@ def effects_summary(levels, curves, base_mean):
             "total_var": total_var, "effect_var": effect_var, "first_order": first_order}
 
 
+LOO_MODEL = {"objective": 0, "time": 1}     # include/spx.h: SPX_LOO_*
+LOO_Z95 = 1.959963984540054                 # the 97.5 % point of the standard normal
+LOO_Z_OUTLIER = 3.0
+
+
+def loo_summary(y, loo_mean, loo_var):
+    """What Engine.loo returns, from the observed values y (N,) and the two (H, N) arrays spx_loo fills (these expressions
+    are the definition).  Per draw: z and the log predictive density lpd of the left-out observation.  Over the draws, the
+    equal-weight mixture that integrating over the hyper draws stands for: mean, var (mean of the variances + variance of the
+    means), z_mix, and lpd_mix = log of the mean of the densities (through the largest term, so that it does not underflow).
+    Scalars: elpd = sum(lpd_mix), rmse, coverage95 = the share of |z_mix| <= 1.96, outliers = the indices with |z_mix| > 3.
+    NaN goes where numpy's rules send it: a NaN z is neither covered nor an outlier."""
+    y = np.asarray(y, dtype=np.float64).ravel()
+    loo_mean = np.atleast_2d(np.asarray(loo_mean, dtype=np.float64))
+    loo_var = np.atleast_2d(np.asarray(loo_var, dtype=np.float64))
+    H = loo_mean.shape[0]
+    with np.errstate(divide="ignore", invalid="ignore", over="ignore"):
+        z = (y - loo_mean) / np.sqrt(loo_var)
+        lpd = -0.5 * np.log(2 * np.pi * loo_var) - 0.5 * z ** 2
+        mean = np.mean(loo_mean, 0)
+        var = np.mean(loo_var, 0) + np.var(loo_mean, 0)
+        z_mix = (y - mean) / np.sqrt(var)
+        top = np.max(lpd, 0)
+        safe = np.where(np.isfinite(top), top, 0.0)          # (-inf everywhere stays -inf, NaN stays NaN, through the sum)
+        lpd_mix = safe + np.log(np.sum(np.exp(lpd - safe), 0)) - np.log(H)
+        res = y - mean
+        return {"y": y, "loo_mean": loo_mean, "loo_var": loo_var, "z": z, "lpd": lpd, "mean": mean, "var": var, "z_mix": z_mix,
+                "lpd_mix": lpd_mix, "elpd": float(np.sum(lpd_mix)), "rmse": float(np.sqrt(np.mean(res ** 2))),
+                "coverage95": float(np.mean(np.abs(z_mix) <= LOO_Z95)),
+                "outliers": np.nonzero(np.abs(z_mix) > LOO_Z_OUTLIER)[0]}
+
+
 TRANSPORT_NAMES = {0: "none", 1: "rccl", 2: "host"}
 
 
@@ -258,6 +291,7 @@ class Engine(object):
             self.device = int(device)
             self.devices = [self.device]
         self.N = self.M = self.D = self.H = 0
+        self._y = {}        # host copies of what the resident models were given to fit: "objective" / "time" -> (N,) (loo)
 
     @property
     def _h(self):
@@ -334,6 +368,7 @@ class Engine(object):
             raise ValueError("comp must be (N, D) and vals (N,)")
         self.N, self.D = comp.shape
         self._check(self._lib.spx_set_observations(self._h, _dp(comp), _dp(vals), self.N, self.D))
+        self._y = {"objective": vals.copy()}
 
     def set_candidates(self, cand, index_base=0):
         cand = _f64(cand)
@@ -352,12 +387,14 @@ class Engine(object):
     def set_time_model(self, log_durs, time_hypers):
         if log_durs is None:
             self._check(self._lib.spx_set_time_model(self._h, None, None))
+            self._y.pop("time", None)
             return
         log_durs = _f64(log_durs).ravel()
         time_hypers = _f64(np.atleast_2d(time_hypers))
         if log_durs.shape[0] != self.N or time_hypers.shape != (self.H, 3 + self.D):
             raise ValueError("log_durs must be (N,), time_hypers (H, 3 + D)")
         self._check(self._lib.spx_set_time_model(self._h, _dp(log_durs), _dp(time_hypers)))
+        self._y["time"] = log_durs.copy()
 
     def set_constraint_model(self, comp_c, ff, c_hypers):
         """Probit constraint GP (spx_set_constraint_model): comp_c (Nc, D) -- Nc = 0 for the all-valid case --, latent
@@ -498,6 +535,24 @@ class Engine(object):
         self.M = 0
         return effects_summary(levels, curves, base_mean)
 
+    # -- model check ---------------------------------------------------------
+    def loo(self, model="objective"):
+        """Leave-one-out cross-validation of the resident factorisation (include/spx.h: spx_loo): for every observation and
+        every hyper draw the predictive mean and variance of the GP trained on all the others, without a refit.  model:
+        "objective", or "time" for the log-duration GP of set_time_model.  Returns loo_summary(y, loo_mean, loo_var) (see
+        there) + kinv_diag (H, N), the diagonal of K^-1.  The handle is left as it was: candidates and the last pass's
+        results stay.  ValueError (SPX_ERR_ARG) without a factorisation, with fantasies held, for "time" without a time
+        model in the factorisation, and on a multi-device handle."""
+        if model not in LOO_MODEL:
+            raise ValueError("no model %r (allowed: %s)" % (model, ", ".join(sorted(LOO_MODEL))))
+        loo_mean = np.empty((self.H, self.N))
+        loo_var = np.empty((self.H, self.N))
+        kinv_diag = np.empty((self.H, self.N))
+        self._check(self._lib.spx_loo(self._h, LOO_MODEL[model], _dp(loo_mean), _dp(loo_var), _dp(kinv_diag)))
+        out = loo_summary(self._y[model], loo_mean, loo_var)
+        out["kinv_diag"] = kinv_diag
+        return out
+
     # -- one-shot (host buffers in, results out) ---------------------------
     def ei_grid(self, comp, vals, cand, hypers, want_mean=True, want_draws=False, flags=0):
         """(best_index, best_value, ei_mean or None, overall_ei[M,H] or None)"""
@@ -514,6 +569,7 @@ class Engine(object):
                                           H, int(flags), _dp(mean), _dp(draws),
                                           ctypes.byref(idx), ctypes.byref(val)))
         self.N, self.D, self.M, self.H = N, D, M, H
+        self._y = {"objective": vals.copy()}
         return int(idx.value), float(val.value), mean, draws
 
     def ei_per_sec_grid(self, comp, vals, log_durs, cand, hypers, time_hypers,
@@ -534,6 +590,7 @@ class Engine(object):
                                                   int(flags), _dp(mean), _dp(draws),
                                                   ctypes.byref(idx), ctypes.byref(val)))
         self.N, self.D, self.M, self.H = N, D, M, H
+        self._y = {"objective": vals.copy(), "time": log_durs.copy()}
         return int(idx.value), float(val.value), mean, draws
 
     # -- building blocks ---------------------------------------------------
@@ -739,3 +796,6 @@ class MultiEngine(Engine):
 
     def __init__(self, devices, lib=None, transport=None):
         Engine.__init__(self, lib=lib, devices=list(devices), transport=transport)
+
+    def loo(self, model="objective"):
+        raise ValueError("loo is not available on a multi-device engine (include/spx.h: spx_loo)")
