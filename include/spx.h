@@ -148,7 +148,13 @@ int spx_set_candidates(spx_handle* h, const double* cand, int64_t M, int32_t D,
 int spx_set_hypers(spx_handle* h, const double* hypers, int32_t H);
 /* second GP on log durations (GPEIperSecChooser.py:176, :437-458):
  * log_durs (N), time_hypers H x (3+D).  Pass NULLs to clear.  Either form
- * drops the factorisation and everything made from it (fantasies, results).    */
+ * drops the factorisation and everything made from it (fantasies, results).
+ * log_durs is not checked (the reference cannot get there: scipy's check_finite
+ * raises).  A NaN in it propagates by IEEE rules: alpha_t of every draw is NaN
+ * throughout, so every predicted duration of every draw and every per-second
+ * value is NaN and spx_get_best returns index 0 (numpy's first NaN); func_m /
+ * func_v of the objective are what they are without it, and the handle is as
+ * good as new after the next spx_set_time_model with finite durations.         */
 int spx_set_time_model(spx_handle* h, const double* log_durs,
                        const double* time_hypers);
 /* Probit constraint GP (GPConstrainedEIChooser.py:816-842): Nc points comp_c (Nc x D, all completed jobs, Nc independent
