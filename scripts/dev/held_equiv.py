@@ -4,6 +4,9 @@ statistics, spx_not_pd_info and (the walks with option timing) the launches per 
 the same state give the same record line for line (profiles/held_refactor_equiv.log: the build before csrc/spx_held.h
 against the build after it, each in its own process).
    python scripts/dev/held_equiv.py LIB|- OUTFILE [walks]          (- : the in-tree library)
+        [--devices 0,0[,0,0] [--hyper-shards P]]                   (the same walks on the front of a multi-device handle over
+                                                                      these device ids, without the constraint calls that it
+                                                                      refuses outright: profiles/multi_held_equiv.log)
    python scripts/dev/held_equiv.py --compare PARENT_OUT CHILD_OUT   (the digest of the child's record and every differing
                                                                       line, sorted by cause)"""
 import hashlib
@@ -18,19 +21,25 @@ sys.path.insert(0, root)
 WALKS, STEPS = 400, 12
 STATS = ("obs_dims", "last_fantasies_device", "fantasies_pending_rows", "fantasies_count", "flow_fallbacks", "flow_enabled",
          "last_step_fused", "last_factor_flow", "last_factor_cov_in_flow", "last_logprob_one_launch", "last_step_skipped_padding")
+FRONT_STATS = ("obs_dims", "last_fantasies_device", "fantasies_pending_rows", "fantasies_count", "flow_fallbacks", "flow_rearms",
+               "ranks_seen")            # what a multi-device handle answers itself
 
 
-def record(lib, out_path, walks):
+def record(lib, out_path, walks, devices=None, hyper_shards=1):
     from tests import held_helpers as hh
     p = hh.Problem()
+    calls = hh.front_calls() if devices else hh.CALLS
+    stats = FRONT_STATS if devices else STATS
     getters = dict(hh.GETTERS)
     getters["get_cross_cov"] = lambda e, p: e.get_cross_cov(hh.H - 1, 0, 5)       # (needs the factor AND candidates)
-    names = sorted(hh.CALLS)
+    names = sorted(calls)
     out = open(out_path, "w")
-    out.write("# getters: %s\n# stats: %s\n" % (",".join(getters), ",".join(STATS)))
+    out.write("# getters: %s\n# stats: %s\n" % (",".join(getters), ",".join(stats)))
+    if devices:
+        out.write("# front: devices=%s hyper_shards=%d\n" % (",".join("%d" % d for d in devices), hyper_shards))
     for w in range(walks):
         rs = np.random.RandomState(1000 + w)
-        e = hh.engine(None if lib == "-" else lib)         # a walk starts on a new handle: no difference outlives its walk
+        e = hh.engine(None if lib == "-" else lib, devices, hyper_shards)    # a walk starts on a new handle: no difference outlives its walk
         timing = w & 1
         e.set_option("timing", timing)
         for k in range(STEPS):
@@ -38,14 +47,14 @@ def record(lib, out_path, walks):
             name = names[rs.randint(len(names))]
             if k < 3 and rs.rand() < 0.8:
                 name = ("set_observations", "set_candidates", "set_hypers")[k]
-            kind, res = hh.outcome(hh.CALLS[name], e, p)
+            kind, res = hh.outcome(calls[name], e, p)
             served = []
             for g, fn in getters.items():
                 gk, gres = hh.outcome(fn, e, p)
                 served.append("%s=%s" % (g, hh.sha(gres) if gk == "ok" else "-"))
             line = "w=%d t=%d k=%d call=%s rc=%s res=%s %s stats=%s npd=%d/%d" % (
                 w, timing, k, name.replace(" ", ""), kind, hh.sha(res) if kind == "ok" and res is not None else "-",
-                " ".join(served), ",".join("%d" % e.stat(s) for s in STATS), *hh.not_pd_info(e))
+                " ".join(served), ",".join("%d" % e.stat(s) for s in stats), *hh.not_pd_info(e))
             if timing:
                 line += " launches=" + ",".join("%d" % v[1] for v in e.timings().values())
             out.write(line + " | err=" + (res if kind != "ok" else "-") + "\n")
@@ -81,7 +90,35 @@ def cause(parent, child, diff):
     return "UNEXPLAINED"
 
 
+def front_cause(parent, child, diff):
+    """The same for two records of a multi-device handle (profiles/multi_held_equiv.log: the build whose front kept six loose
+    flags against the build whose front keeps a Held)."""
+    call = child["call"]
+    if parent["rc"] not in ("ok", "arg"):
+        return "1 a call failed part-way: what it was overwriting is refused by every reader of the front afterwards"
+    if call in ("set_fantasies", "draw_fantasies") and parent["rc"] == "arg" and "2-D partition" in parent["err"]:
+        return "3 %s refused in the 2-D partition no longer drops the results" % call
+    if call in ("set_fantasies(NULL)", "draw_fantasies(NULL)"):
+        return "4 the clear forms keep the last results readable, as on a single handle"
+    if set(diff) == {"err"} and parent["err"].startswith(child["err"] + " (device slot "):
+        return ("5 (further) a refusal the front now makes from its own record, before a kid is asked: the same text without the "
+                "kid's '(device slot i)'")
+    if call.startswith("set_option(covar") and parent["rc"] == "ok" and all(v[0] == "-" for k, v in diff.items() if k != "npd"):
+        return ("6 (further) option covar set to the value it has (whichever of the two calls sets it) drops nothing, as on a "
+                "single handle (row FACTOR: made from option covar -- which did not change); the front used to refuse its own "
+                "results after it")
+    if set(diff) == {"npd"}:
+        return ("7 (further) 'the kids hold the shards of the last spx_gp_logprob' is one fact now, and spx_not_pd_info reports "
+                "that batch, in the handle's numbering, exactly while it holds: spx_set_observations does not end it (the kids "
+                "keep those hypers), the re-broadcast that spx_set_time_model begins with does (rows HYP and FACTOR of the front's "
+                "table in DESIGN.md)")
+    return "UNEXPLAINED"
+
+
 def compare(parent_path, child_path):
+    global cause
+    if any(ln.startswith("# front:") for ln in open(child_path)):
+        cause = front_cause
     pl = [ln for ln in open(parent_path) if not ln.startswith("#")]
     cl = [ln for ln in open(child_path) if not ln.startswith("#")]
     assert len(pl) == len(cl), (len(pl), len(cl))
@@ -115,6 +152,15 @@ def compare(parent_path, child_path):
 
 
 if __name__ == "__main__":
-    if sys.argv[1] == "--compare":
-        sys.exit(compare(sys.argv[2], sys.argv[3]))
-    record(sys.argv[1], sys.argv[2], int(sys.argv[3]) if len(sys.argv) > 3 else WALKS)
+    args, devices, shards = sys.argv[1:], None, 1
+    for flag in ("--devices", "--hyper-shards"):
+        if flag in args:
+            i = args.index(flag)
+            if flag == "--devices":
+                devices = [int(d) for d in args[i + 1].split(",")]
+            else:
+                shards = int(args[i + 1])
+            del args[i:i + 2]
+    if args[0] == "--compare":
+        sys.exit(compare(args[1], args[2]))
+    record(args[0], args[1], int(args[2]) if len(args) > 2 else WALKS, devices, shards)

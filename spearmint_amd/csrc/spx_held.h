@@ -1,5 +1,7 @@
 // What a handle holds, and what each of those things was made from.  Host-only, plain C++17: no HIP, no handle -- spx_api.hip
-// and spx_multi.hip execute it, tests/c/held_client.cpp runs it on a CPU (tests/test_held.py).
+// executes it for a single handle (spx_drop / spx_hold), spx_multi.hip for the front of a multi-device handle, which keeps a
+// record of its own beside those of its per-device handles (multi_drop / multi_hold; CON, CON_FACTOR, FULL_FACTOR and ALPHA_S are
+// never set there); tests/c/held_client.cpp runs it on a CPU (tests/test_held.py).
 //
 // One rule for every entry point: DROP what the call is about to overwrite before its first mutation, SET it after its last
 // check.  Dropping a thing clears it and, transitively, everything made from it; a call that fails in between leaves what it

@@ -28,6 +28,8 @@
 #include <thread>
 
 #include "spx_internal.h"
+#include "np_sum.h"
+#include "spx_shards.h"
 
 // ---- RCCL, bound at run time ----------------------------------------------------------------------
 // The handful of types and constants of the (stable) NCCL / RCCL C API that this file uses, declared here so
@@ -197,38 +199,40 @@ struct spx_multi {
     RcclApi rccl;
     std::vector<ncclComm_t> comms;
     Workers* pool = nullptr;
-    // candidate shards: kid i owns rows [lo[i], hi[i]) of the caller's candidate array
-    int64_t M = 0, index_base = 0;
-    int active = 0;
-    std::vector<int64_t> lo, hi;
+    // What the front holds (spx_held.h: the single handle's record and table; CON, CON_FACTOR, FULL_FACTOR and ALPHA_S are
+    // never set here) and the mirror of who holds which part of it (spx_shards.h).  The record is taken away, and the mirror
+    // cleared, by multi_drop alone; an entry point assigns a shard value whole, after every kid has taken its part.
+    Held held;
+    CandShards cands;             // CAND: kid i owns rows [lo[i], hi[i]) of the caller's candidate array
+    DrawShards draws;             // HYP: kid i holds the draws [hlo[i], hhi[i]) -- all of them without a 2-D partition
+    // spx_gp_logprob shards the draws over the kids and leaves them with different subsets INSTEAD of `draws`: non-empty
+    // exactly then.  The full set is re-broadcast before the next factorisation (sync_hypers).
+    LogprobShards lp;
     int64_t N = 0;
-    int D = 0, H = 0;
-    // replicated hyper draws; spx_gp_logprob shards the draws over the devices and leaves the kids
-    // with different subsets, so the full set is re-broadcast before the next factorisation
-    std::vector<double> hyp_host, thyp_host, ldur_host;
-    bool have_hyp = false, have_time = false, hyp_dirty = false;
-    std::vector<int64_t> lp_lo;   // draw ranges of the last sharded spx_gp_logprob
-    int lp_parts = 0;             // devices that took part in it
-    bool last_was_logprob = false;
-    bool ran = false;
-    SpxRecord best{0.0, -1};
+    int D = 0;
+    std::vector<double> hyp_host, thyp_host, ldur_host;   // HYP / TIME: host copies for that re-broadcast
+    SpxRecord best{0.0, -1};      // RESULTS: the winner every kid agreed on
     // Optional 2-D partition (SURVEY.md 8(e) "hypers x candidates"; spx_set_partition): n = ph x pc devices, device i
     // evaluates the draws of hyper shard i % ph for the candidates of shard i / ph, and the single collective is ONE
-    // all-reduce(SUM) of the zero-padded M-vector of per-candidate EI sums (exchange_sums).  ph = 1: candidates only.
+    // all-reduce(SUM) of the zero-padded M-vector of per-candidate EI sums (results.global2d).  ph = 1: candidates only.
     int ph = 1;
-    std::vector<char> on;             // device i holds candidates
-    std::vector<int64_t> hlo, hhi;    // device i's draws [hlo, hhi)
-    bool ran2d = false;
 };
 
-static inline int kid_rh(const spx_multi* m, int i) { return i % m->ph; }
-static inline int kid_rc(const spx_multi* m, int i) { return i / m->ph; }
-
-static void shard(int64_t total, int parts, int r, int64_t* lo, int64_t* hi)
+// The counterparts of spx_drop / spx_hold.  multi_drop is the only place that takes residency away and the only place that
+// clears the mirror: the shards and host copies mean nothing without their bit.
+static void multi_drop(spx_multi* m, Held::Thing x)
 {
-    const int64_t base = total / parts, extra = total % parts;
-    *lo = r * base + (r < extra ? r : extra);
-    *hi = *lo + base + (r < extra ? 1 : 0);
+    m->held.drop(x);
+    // lost now or before -- what is not held stays cleared; the cleared shards keep one (empty) range per slot
+    if (!m->held.has(Held::CAND)) m->cands = plan_cands(m->n, m->ph, 0, 0);
+    // (the log-likelihood shards go with the draws they replaced; a factor is never held beside them -- spx_multi_factor
+    // re-broadcasts first -- so losing FACTOR finds none to clear)
+    if (!m->held.has(Held::HYP)) { m->draws = no_draws(m->n); m->lp = LogprobShards(); m->hyp_host.clear(); }
+    if (!m->held.has(Held::TIME)) { m->ldur_host.clear(); m->thyp_host.clear(); }
+}
+static int multi_hold(spx_multi* m, Held::Thing x, Held::Results r = Held::Results())
+{
+    return m->held.set(x, r) ? SPX_OK : fail(SPX_ERR_ARG, "internal error: thing %d set on a multi-device handle without what it is made from", (int)x);
 }
 
 // ---- the record kernels ------------------------------------------------------------------------------
@@ -264,6 +268,71 @@ __global__ void k_pick_record(const SpxRecord* __restrict__ table, int n, SpxRec
     *out = best;
 }
 
+// ---- the two collectives, slot by slot ------------------------------------------------------------------------------------------
+// Each collective is two halves on ONE handle's stream with the collective call between them.  The front runs them for every
+// kid around one group call or the host table (exchange); spx_comm_exchange runs them once around its communicator's call.
+//
+// The all-gather of records: k_make_record -> [ncclAllGather of nrec x 16 bytes] -> k_pick_record -> the winner to the host.
+static int record_prepare(spx_handle* k, int nrec, int active)
+{
+    int rc = spx_ensure_init(k);
+    if (rc) return rc;
+    if ((rc = k->rec_send.reserve(sizeof(SpxRecord)))) return rc;
+    if ((rc = k->rec_recv.reserve(sizeof(SpxRecord) * nrec))) return rc;
+    if ((rc = k->rec_out.reserve(sizeof(SpxRecord)))) return rc;
+    hipLaunchKernelGGL(k_make_record, dim3(1), dim3(1), 0, k->stream, (const double*)k->am_out_val.p,
+                       (const int64_t*)k->am_out_idx.p, k->index_base, active, (SpxRecord*)k->rec_send.p);
+    return SPX_OK;
+}
+// queued, not awaited (winner_wait); *out must live until then
+static int record_finish(spx_handle* k, int nrec, SpxRecord* out)
+{
+    HIPCHK(hipSetDevice(k->device));
+    hipLaunchKernelGGL(k_pick_record, dim3(1), dim3(1), 0, k->stream, (const SpxRecord*)k->rec_recv.p, nrec,
+                       (SpxRecord*)k->rec_out.p);
+    HIPCHK(hipMemcpyAsync(out, k->rec_out.p, sizeof(SpxRecord), hipMemcpyDeviceToHost, k->stream));
+    return SPX_OK;
+}
+
+// The all-reduce of the 2-D partition: the handle scatters sum_{its draws} EI[c, h] of its candidates, rows [row0, row0 + k->M)
+// of all Mt, into a zero-padded Mt-vector (k_sum_over_draws: numpy's summation order over the local draws) -> [ONE
+// all-reduce(SUM) of the Mt doubles] -> divide by the total number of draws, numpy's argmax over all Mt candidates -- no per-draw
+// EI leaves the devices, no host-side reduction.  out->idx counts from the first of the Mt candidates.
+static int sums_prepare(spx_handle* k, int64_t Mt, int64_t row0, bool has_rows)
+{
+    int rc = spx_ensure_init(k);
+    if (rc) return rc;
+    const int nab = argmax_blocks(Mt);
+    if ((rc = k->ei_sum_full.reserve((size_t)Mt * 8))) return rc;
+    if ((rc = k->am_val.reserve((size_t)nab * 8))) return rc;
+    if ((rc = k->am_idx.reserve((size_t)nab * 8))) return rc;
+    if ((rc = k->am_out_val.reserve(8))) return rc;
+    if ((rc = k->am_out_idx.reserve(8))) return rc;
+    HIPCHK(hipMemsetAsync(k->ei_sum_full.p, 0, (size_t)Mt * 8, k->stream));
+    if (has_rows)
+        launch_sum_over_draws(k->stream, k->ei_draw.d(), k->ei_sum_full.d() + row0, k->M, round_up(k->M, SPX_BN), k->H);
+    return SPX_OK;
+}
+static int sums_finish(spx_handle* k, int64_t Mt, int H_total, SpxRecord* out)
+{
+    HIPCHK(hipSetDevice(k->device));
+    launch_div_scalar(k->stream, k->ei_sum_full.d(), Mt, (double)H_total);
+    launch_argmax(k->stream, k->ei_sum_full.d(), Mt, k->am_val.d(), (int64_t*)k->am_idx.p, k->am_out_val.d(),
+                  (int64_t*)k->am_out_idx.p);
+    HIPCHK(hipMemcpyAsync(&out->val, k->am_out_val.p, 8, hipMemcpyDeviceToHost, k->stream));
+    HIPCHK(hipMemcpyAsync(&out->idx, k->am_out_idx.p, 8, hipMemcpyDeviceToHost, k->stream));
+    return SPX_OK;
+}
+
+// what record_finish / sums_finish queued has arrived
+static int winner_wait(spx_handle* k)
+{
+    HIPCHK(hipSetDevice(k->device));
+    HIPCHK(hipStreamSynchronize(k->stream));
+    LAUNCHCHK();
+    return SPX_OK;
+}
+
 #define NCCLCHK(m, name, call)                                                                   \
     do {                                                                                         \
         ncclResult_t r_ = (call);                                                                \
@@ -271,188 +340,108 @@ __global__ void k_pick_record(const SpxRecord* __restrict__ table, int n, SpxRec
             return fail(SPX_ERR_HIP, "%s failed: %s", name, (m)->rccl.GetErrorString(r_));       \
     } while (0)
 
-static int exchange_best(spx_multi* m)
+// one collective call per kid on its stream, in ONE group
+static int in_group(spx_multi* m, const char* name, const std::function<ncclResult_t(int)>& call)
 {
-    const int n = m->n;
-    for (int i = 0; i < n; ++i) {
-        spx_handle* k = m->kids[i];
-        int rc = spx_ensure_init(k);
-        if (rc) return rc;
-        if ((rc = k->rec_send.reserve(sizeof(SpxRecord)))) return rc;
-        if ((rc = k->rec_recv.reserve(sizeof(SpxRecord) * n))) return rc;
-        if ((rc = k->rec_out.reserve(sizeof(SpxRecord)))) return rc;
-        const int act = m->on[i] ? 1 : 0;
-        hipLaunchKernelGGL(k_make_record, dim3(1), dim3(1), 0, k->stream, (const double*)k->am_out_val.p,
-                           (const int64_t*)k->am_out_idx.p, k->index_base, act, (SpxRecord*)k->rec_send.p);
-    }
-    if (m->transport == SPX_TRANSPORT_RCCL) {
-        NCCLCHK(m, "ncclGroupStart", m->rccl.GroupStart());
-        for (int i = 0; i < n; ++i) {
-            spx_handle* k = m->kids[i];
-            ncclResult_t r = m->rccl.AllGather(k->rec_send.p, k->rec_recv.p, sizeof(SpxRecord), ncclChar, m->comms[i], k->stream);
-            if (r != ncclSuccess) {
-                (void)m->rccl.GroupEnd();      // the group must not stay open on this thread: the next exchange would nest inside it
-                return fail(SPX_ERR_HIP, "ncclAllGather failed: %s", m->rccl.GetErrorString(r));
-            }
-        }
-        NCCLCHK(m, "ncclGroupEnd (the group of ncclAllGather / ncclAllReduce calls)", m->rccl.GroupEnd());
-    } else {
-        std::vector<SpxRecord> table(n);
-        for (int i = 0; i < n; ++i) {
-            spx_handle* k = m->kids[i];
-            HIPCHK(hipSetDevice(k->device));
-            HIPCHK(hipMemcpyAsync(&table[i], k->rec_send.p, sizeof(SpxRecord), hipMemcpyDeviceToHost, k->stream));
-            HIPCHK(hipStreamSynchronize(k->stream));
-        }
-        for (int i = 0; i < n; ++i) {
-            spx_handle* k = m->kids[i];
-            HIPCHK(hipSetDevice(k->device));
-            HIPCHK(hipMemcpyAsync(k->rec_recv.p, table.data(), sizeof(SpxRecord) * n, hipMemcpyHostToDevice, k->stream));
-            HIPCHK(hipStreamSynchronize(k->stream));   // `table` is pageable host memory
-        }
-    }
-    for (int i = 0; i < n; ++i) {
-        spx_handle* k = m->kids[i];
-        HIPCHK(hipSetDevice(k->device));
-        hipLaunchKernelGGL(k_pick_record, dim3(1), dim3(1), 0, k->stream, (const SpxRecord*)k->rec_recv.p, n,
-                           (SpxRecord*)k->rec_out.p);
-    }
-    std::vector<SpxRecord> outs(n);
-    for (int i = 0; i < n; ++i) {
-        spx_handle* k = m->kids[i];
-        HIPCHK(hipSetDevice(k->device));
-        HIPCHK(hipMemcpyAsync(&outs[i], k->rec_out.p, sizeof(SpxRecord), hipMemcpyDeviceToHost, k->stream));
-        HIPCHK(hipStreamSynchronize(k->stream));
-        LAUNCHCHK();
-    }
-    for (int i = 1; i < n; ++i)   // every device must hold the same winner
-        if (outs[i].idx != outs[0].idx || memcmp(&outs[i].val, &outs[0].val, 8))
-            return fail(SPX_ERR_HIP, "multi-GPU argmax: device slots 0 and %d disagree (%lld vs %lld)", i,
-                        (long long)outs[0].idx, (long long)outs[i].idx);
-    m->best = outs[0];
-    return SPX_OK;
-}
-
-// The collective of the 2-D partition: every device scatters sum_{its draws} EI[c, h] of its candidates into a
-// zero-padded M-vector (k_sum_over_draws: numpy's summation order over the local draws), ONE all-reduce(SUM) of the
-// M doubles completes the sums (ncclAllReduce in one group over the devices' streams; through host memory, summed in
-// device order, when the device ids repeat), and every device divides by the total number of draws and takes numpy's
-// argmax over all M candidates -- no per-draw EI leaves the devices, no host-side reduction.
-static int exchange_sums(spx_multi* m)
-{
-    const int n = m->n;
-    const int64_t M = m->M;
-    for (int i = 0; i < n; ++i) {
-        spx_handle* k = m->kids[i];
-        int rc = spx_ensure_init(k);
-        if (rc) return rc;
-        const int nab = argmax_blocks(M);
-        if ((rc = k->ei_sum_full.reserve((size_t)M * 8))) return rc;
-        if ((rc = k->am_val.reserve((size_t)nab * 8))) return rc;
-        if ((rc = k->am_idx.reserve((size_t)nab * 8))) return rc;
-        if ((rc = k->am_out_val.reserve(8))) return rc;
-        if ((rc = k->am_out_idx.reserve(8))) return rc;
-        HIPCHK(hipMemsetAsync(k->ei_sum_full.p, 0, (size_t)M * 8, k->stream));
-        if (m->on[i])
-            launch_sum_over_draws(k->stream, k->ei_draw.d(), k->ei_sum_full.d() + m->lo[i], k->M, round_up(k->M, SPX_BN), k->H);
-    }
-    if (m->transport == SPX_TRANSPORT_RCCL) {
-        NCCLCHK(m, "ncclGroupStart", m->rccl.GroupStart());
-        for (int i = 0; i < n; ++i) {
-            spx_handle* k = m->kids[i];
-            ncclResult_t r = m->rccl.AllReduce(k->ei_sum_full.p, k->ei_sum_full.p, (size_t)M, ncclFloat64, ncclSum, m->comms[i], k->stream);
-            if (r != ncclSuccess) {
-                (void)m->rccl.GroupEnd();      // (as above)
-                return fail(SPX_ERR_HIP, "ncclAllReduce failed: %s", m->rccl.GetErrorString(r));
-            }
-        }
-        NCCLCHK(m, "ncclGroupEnd (the group of ncclAllGather / ncclAllReduce calls)", m->rccl.GroupEnd());
-    } else {
-        std::vector<double> acc((size_t)M), tmp((size_t)M);
-        for (int i = 0; i < n; ++i) {
-            spx_handle* k = m->kids[i];
-            HIPCHK(hipSetDevice(k->device));
-            HIPCHK(hipMemcpyAsync(i ? tmp.data() : acc.data(), k->ei_sum_full.p, (size_t)M * 8, hipMemcpyDeviceToHost, k->stream));
-            HIPCHK(hipStreamSynchronize(k->stream));
-            if (i) for (int64_t c = 0; c < M; ++c) acc[c] += tmp[c];
-        }
-        for (int i = 0; i < n; ++i) {
-            spx_handle* k = m->kids[i];
-            HIPCHK(hipSetDevice(k->device));
-            HIPCHK(hipMemcpyAsync(k->ei_sum_full.p, acc.data(), (size_t)M * 8, hipMemcpyHostToDevice, k->stream));
-            HIPCHK(hipStreamSynchronize(k->stream));   // `acc` is pageable host memory
-        }
-    }
-    std::vector<SpxRecord> outs(n);
-    for (int i = 0; i < n; ++i) {
-        spx_handle* k = m->kids[i];
-        HIPCHK(hipSetDevice(k->device));
-        launch_div_scalar(k->stream, k->ei_sum_full.d(), M, (double)m->H);
-        launch_argmax(k->stream, k->ei_sum_full.d(), M, k->am_val.d(), (int64_t*)k->am_idx.p, k->am_out_val.d(),
-                      (int64_t*)k->am_out_idx.p);
-        HIPCHK(hipMemcpyAsync(&outs[i].val, k->am_out_val.p, 8, hipMemcpyDeviceToHost, k->stream));
-        HIPCHK(hipMemcpyAsync(&outs[i].idx, k->am_out_idx.p, 8, hipMemcpyDeviceToHost, k->stream));
-    }
-    for (int i = 0; i < n; ++i) {
-        spx_handle* k = m->kids[i];
-        HIPCHK(hipSetDevice(k->device));
-        HIPCHK(hipStreamSynchronize(k->stream));
-        LAUNCHCHK();
-    }
-    for (int i = 1; i < n; ++i)   // every device must hold the same winner
-        if (outs[i].idx != outs[0].idx || memcmp(&outs[i].val, &outs[0].val, 8))
-            return fail(SPX_ERR_HIP, "multi-GPU argmax (2-D partition): device slots 0 and %d disagree (%lld vs %lld)", i,
-                        (long long)outs[0].idx, (long long)outs[i].idx);
-    m->best.val = outs[0].val;
-    m->best.idx = outs[0].idx + m->index_base;
-    return SPX_OK;
-}
-
-// candidate shard of device i for M candidates: pc = n / ph shards, device i takes shard i / ph
-static void plan_cands(const spx_multi* m, int64_t M, std::vector<int64_t>& lo, std::vector<int64_t>& hi,
-                       std::vector<char>& on, int* active)
-{
-    const int pc = m->n / m->ph;
-    const int actc = (int)std::min<int64_t>(pc, M);
-    int act = 0;
-    lo.assign(m->n, M); hi.assign(m->n, M); on.assign(m->n, 0);
+    NCCLCHK(m, "ncclGroupStart", m->rccl.GroupStart());
     for (int i = 0; i < m->n; ++i) {
-        const int rc = kid_rc(m, i);
-        if (rc < actc) { shard(M, actc, rc, &lo[i], &hi[i]); on[i] = 1; ++act; }
+        ncclResult_t r = call(i);
+        if (r != ncclSuccess) {
+            (void)m->rccl.GroupEnd();      // the group must not stay open on this thread: the next exchange would nest inside it
+            return fail(SPX_ERR_HIP, "%s failed: %s", name, m->rccl.GetErrorString(r));
+        }
     }
-    *active = act;
-}
-
-// draw shard of device i: all H draws (ph = 1) or shard i % ph of ph
-static int plan_draws(spx_multi* m, int H)
-{
-    if (m->ph > 1 && H < m->ph)
-        return fail(SPX_ERR_ARG, "2-D partition: %d hyper shards need at least that many draws (H=%d)", m->ph, H);
-    m->hlo.assign(m->n, 0); m->hhi.assign(m->n, H);
-    if (m->ph > 1)
-        for (int i = 0; i < m->n; ++i) shard(H, m->ph, kid_rh(m, i), &m->hlo[i], &m->hhi[i]);
+    NCCLCHK(m, "ncclGroupEnd (the group of ncclAllGather / ncclAllReduce calls)", m->rccl.GroupEnd());
     return SPX_OK;
 }
 
-// (re-)broadcast the hyper draws -- each device its shard -- e.g. after a sharded spx_gp_logprob
-static int push_hypers(spx_multi* m)
+// The same collective through host memory (the device ids repeat): the records gathered into one table, or the vectors
+// summed in device order, then handed to every kid.  The host buffers are pageable: every copy is awaited.
+static int through_host(spx_multi* m, bool sums)
+{
+    const int n = m->n;
+    const size_t each = sums ? (size_t)m->cands.M : sizeof(SpxRecord) / 8;   // doubles per kid
+    std::vector<double> all(sums ? each : each * n), tmp(sums ? each : 0);
+    for (int i = 0; i < n; ++i) {
+        spx_handle* k = m->kids[i];
+        double* dst = sums ? (i ? tmp.data() : all.data()) : all.data() + i * each;
+        HIPCHK(hipSetDevice(k->device));
+        HIPCHK(hipMemcpyAsync(dst, sums ? k->ei_sum_full.p : k->rec_send.p, each * 8, hipMemcpyDeviceToHost, k->stream));
+        HIPCHK(hipStreamSynchronize(k->stream));
+        if (sums && i) for (size_t c = 0; c < each; ++c) all[c] += tmp[c];
+    }
+    for (int i = 0; i < n; ++i) {
+        spx_handle* k = m->kids[i];
+        HIPCHK(hipSetDevice(k->device));
+        HIPCHK(hipMemcpyAsync(sums ? k->ei_sum_full.p : k->rec_recv.p, all.data(), all.size() * 8, hipMemcpyHostToDevice, k->stream));
+        HIPCHK(hipStreamSynchronize(k->stream));
+    }
+    return SPX_OK;
+}
+
+// every slot must hold the same winner
+static int same_winner(const SpxRecord* outs, int n, const char* what)
+{
+    for (int i = 1; i < n; ++i)
+        if (outs[i].idx != outs[0].idx || memcmp(&outs[i].val, &outs[0].val, 8))
+            return fail(SPX_ERR_HIP, "multi-GPU argmax%s: device slots 0 and %d disagree (%lld vs %lld)", what, i,
+                        (long long)outs[0].idx, (long long)outs[i].idx);
+    return SPX_OK;
+}
+
+// The single collective of a pass on the front: the all-gather of the kids' records or, with a 2-D partition, the all-reduce
+// of their EI sums; then every kid reduces for itself and all of them must agree.
+static int exchange(spx_multi* m)
+{
+    const int n = m->n;
+    const bool sums = m->ph > 1;
+    const CandShards& c = m->cands;
+    int rc;
+    for (int i = 0; i < n; ++i)
+        if ((rc = sums ? sums_prepare(m->kids[i], c.M, c.lo[i], c.on[i]) : record_prepare(m->kids[i], n, c.on[i] ? 1 : 0))) return rc;
+    if (m->transport != SPX_TRANSPORT_RCCL)
+        rc = through_host(m, sums);
+    else if (sums)
+        rc = in_group(m, "ncclAllReduce", [m, &c](int i) {
+            spx_handle* k = m->kids[i];
+            return m->rccl.AllReduce(k->ei_sum_full.p, k->ei_sum_full.p, (size_t)c.M, ncclFloat64, ncclSum, m->comms[i], k->stream);
+        });
+    else
+        rc = in_group(m, "ncclAllGather", [m](int i) {
+            spx_handle* k = m->kids[i];
+            return m->rccl.AllGather(k->rec_send.p, k->rec_recv.p, sizeof(SpxRecord), ncclChar, m->comms[i], k->stream);
+        });
+    if (rc) return rc;
+    std::vector<SpxRecord> outs(n);
+    for (int i = 0; i < n; ++i)
+        if ((rc = sums ? sums_finish(m->kids[i], c.M, m->draws.H, &outs[i]) : record_finish(m->kids[i], n, &outs[i]))) return rc;
+    for (int i = 0; i < n; ++i)
+        if ((rc = winner_wait(m->kids[i]))) return rc;
+    if ((rc = same_winner(outs.data(), n, sums ? " (2-D partition)" : ""))) return rc;
+    m->best = outs[0];
+    if (sums) m->best.idx += c.index_base;      // (a record carries its global index already)
+    return SPX_OK;
+}
+
+// (re-)broadcast hyper draws -- each kid its shard -- and, if the front holds one, the time model with them
+static int push_hypers(spx_multi* m, const DrawShards& d, const double* hyp)
 {
     const int hs = 3 + m->D;
-    return m->pool->run([m, hs](int i) {
-        const int64_t a = m->hlo[i], b = m->hhi[i];
-        int r = spx_set_hypers(m->kids[i], m->hyp_host.data() + (size_t)a * hs, (int)(b - a));
-        if (!r && m->have_time)
-            r = spx_set_time_model(m->kids[i], m->ldur_host.data(), m->thyp_host.data() + (size_t)a * hs);
+    const bool with_time = m->held.has(Held::TIME);
+    return m->pool->run([=, &d](int i) {
+        int r = spx_set_hypers(m->kids[i], hyp + (size_t)d.hlo[i] * hs, d.count(i));
+        if (!r && with_time)
+            r = spx_set_time_model(m->kids[i], m->ldur_host.data(), m->thyp_host.data() + (size_t)d.hlo[i] * hs);
         return r;
     });
 }
 
+// the kids hold the shards of the last spx_gp_logprob: give them the front's draws back
 static int sync_hypers(spx_multi* m)
 {
-    if (!m->hyp_dirty) return SPX_OK;
-    if (!m->have_hyp) return fail(SPX_ERR_ARG, "spx_factor: observations and hypers must be set first");
-    int rc = push_hypers(m);
-    if (!rc) m->hyp_dirty = false;
+    if (m->lp.empty()) return SPX_OK;
+    int rc = push_hypers(m, m->draws, m->hyp_host.data());
+    if (!rc) m->lp = LogprobShards();
     return rc;
 }
 
@@ -467,57 +456,27 @@ struct spx_comm {
     int nranks = 1, rank = 0;
 };
 
-static int comm_exchange_sums(spx_handle* k, bool* global_2d)
-{
-    spx_comm* c = k->comm;
-    const int64_t Mt = k->part_M;
-    if (k->index_base < 0 || k->index_base + k->M > Mt)
-        return fail(SPX_ERR_ARG, "spx_ei_run: candidate rows [%lld, %lld) do not fit the partition's M_total=%lld",
-                    (long long)k->index_base, (long long)(k->index_base + k->M), (long long)Mt);
-    int rc;
-    const int nab = argmax_blocks(Mt);
-    if ((rc = k->ei_sum_full.reserve((size_t)Mt * 8))) return rc;
-    if ((rc = k->am_val.reserve((size_t)nab * 8))) return rc;
-    if ((rc = k->am_idx.reserve((size_t)nab * 8))) return rc;
-    HIPCHK(hipMemsetAsync(k->ei_sum_full.p, 0, (size_t)Mt * 8, k->stream));
-    launch_sum_over_draws(k->stream, k->ei_draw.d(), k->ei_sum_full.d() + k->index_base, k->M, round_up(k->M, SPX_BN), k->H);
-    ncclResult_t r = c->rccl.AllReduce(k->ei_sum_full.p, k->ei_sum_full.p, (size_t)Mt, ncclFloat64, ncclSum, c->comm, k->stream);
-    if (r != ncclSuccess) return fail(SPX_ERR_HIP, "ncclAllReduce failed: %s", c->rccl.GetErrorString(r));
-    launch_div_scalar(k->stream, k->ei_sum_full.d(), Mt, (double)k->part_H);
-    launch_argmax(k->stream, k->ei_sum_full.d(), Mt, k->am_val.d(), (int64_t*)k->am_idx.p, k->am_out_val.d(),
-                  (int64_t*)k->am_out_idx.p);
-    HIPCHK(hipMemcpyAsync(&k->best_val, k->am_out_val.p, 8, hipMemcpyDeviceToHost, k->stream));
-    HIPCHK(hipMemcpyAsync(&k->best_idx, k->am_out_idx.p, 8, hipMemcpyDeviceToHost, k->stream));
-    HIPCHK(hipStreamSynchronize(k->stream));
-    LAUNCHCHK();
-    k->best_idx -= k->index_base;   // spx_get_best adds the base back: the index is global
-    *global_2d = true;              // (the pass's results: spx_get_ei_mean serves the all-reduced vector)
-    return SPX_OK;
-}
-
+// the same halves as the front's exchange, once, around this rank's call
 int spx_comm_exchange(spx_handle* k, bool* global_2d)
 {
     spx_comm* c = k->comm;
-    int rc = spx_ensure_init(k);
+    const bool sums = k->part_M > 0;
+    const int64_t Mt = k->part_M;
+    *global_2d = sums;              // (the pass's results: spx_get_ei_mean serves the all-reduced vector)
+    if (sums && (k->index_base < 0 || k->index_base + k->M > Mt))
+        return fail(SPX_ERR_ARG, "spx_ei_run: candidate rows [%lld, %lld) do not fit the partition's M_total=%lld",
+                    (long long)k->index_base, (long long)(k->index_base + k->M), (long long)Mt);
+    int rc = sums ? sums_prepare(k, Mt, k->index_base, true) : record_prepare(k, c->nranks, 1);
     if (rc) return rc;
-    if (k->part_M > 0) return comm_exchange_sums(k, global_2d);
-    *global_2d = false;
-    if ((rc = k->rec_send.reserve(sizeof(SpxRecord)))) return rc;
-    if ((rc = k->rec_recv.reserve(sizeof(SpxRecord) * c->nranks))) return rc;
-    if ((rc = k->rec_out.reserve(sizeof(SpxRecord)))) return rc;
-    hipLaunchKernelGGL(k_make_record, dim3(1), dim3(1), 0, k->stream, (const double*)k->am_out_val.p,
-                       (const int64_t*)k->am_out_idx.p, k->index_base, 1, (SpxRecord*)k->rec_send.p);
-    ncclResult_t r = c->rccl.AllGather(k->rec_send.p, k->rec_recv.p, sizeof(SpxRecord), ncclChar, c->comm, k->stream);
-    if (r != ncclSuccess) return fail(SPX_ERR_HIP, "ncclAllGather failed: %s", c->rccl.GetErrorString(r));
-    hipLaunchKernelGGL(k_pick_record, dim3(1), dim3(1), 0, k->stream, (const SpxRecord*)k->rec_recv.p, c->nranks,
-                       (SpxRecord*)k->rec_out.p);
+    ncclResult_t r = sums ? c->rccl.AllReduce(k->ei_sum_full.p, k->ei_sum_full.p, (size_t)Mt, ncclFloat64, ncclSum, c->comm, k->stream)
+                          : c->rccl.AllGather(k->rec_send.p, k->rec_recv.p, sizeof(SpxRecord), ncclChar, c->comm, k->stream);
+    if (r != ncclSuccess) return fail(SPX_ERR_HIP, "%s failed: %s", sums ? "ncclAllReduce" : "ncclAllGather", c->rccl.GetErrorString(r));
     SpxRecord out;
-    HIPCHK(hipMemcpyAsync(&out, k->rec_out.p, sizeof out, hipMemcpyDeviceToHost, k->stream));
-    HIPCHK(hipStreamSynchronize(k->stream));
-    LAUNCHCHK();
-    k->best_idx = out.idx - k->index_base;   // spx_get_best adds the base back
+    if ((rc = sums ? sums_finish(k, Mt, k->part_H, &out) : record_finish(k, c->nranks, &out))) return rc;
+    if ((rc = winner_wait(k))) return rc;
+    k->best_idx = out.idx - k->index_base;   // spx_get_best adds the base back: the index is global
     k->best_val = out.val;
-    k->ranks_seen = c->nranks;               // the table k_pick_record reduced had this many records
+    if (!sums) k->ranks_seen = c->nranks;    // the table k_pick_record reduced had this many records
     return SPX_OK;
 }
 
@@ -585,11 +544,8 @@ int spx_create_multi_transport(const int* device_ids, int32_t n_dev, int32_t tra
         if (rc) { spx_multi_destroy(m); return rc; }
         m->kids.push_back(k);
     }
-    m->lo.assign(n_dev, 0);
-    m->hi.assign(n_dev, 0);
-    m->on.assign(n_dev, 0);
-    m->hlo.assign(n_dev, 0);
-    m->hhi.assign(n_dev, 0);
+    multi_drop(m, Held::CAND);      // nothing is held: the mirror as multi_drop leaves it, every slot idle
+    multi_drop(m, Held::HYP);
     m->pool = new Workers(n_dev);
     spx_handle* front = new spx_handle();
     front->device = device_ids[0];
@@ -679,7 +635,7 @@ int spx_multi_stat(spx_multi* m, const char* name, int64_t* value)
 {
     if (!strcmp(name, "ranks_seen")) { *value = m->n; return SPX_OK; }   // the device slots of the handle (= the size of its communicator)
     if (!strcmp(name, "last_fantasies_device") || !strcmp(name, "fantasies_pending_rows") || !strcmp(name, "fantasies_count")) return spx_get_stat(m->kids[0], name, value);   // replicated: every slot holds the same
-    if (!strcmp(name, "obs_dims")) { *value = m->N > 0 ? m->D : 0; return SPX_OK; }   // D of the resident observations (0: none)
+    if (!strcmp(name, "obs_dims")) { *value = m->held.has(Held::OBS) ? m->D : 0; return SPX_OK; }   // D of the resident observations (0: none)
     if (!strcmp(name, "flow_fallbacks") || !strcmp(name, "flow_rearms")) {   // summed over the devices' handles
         int64_t sum = 0;
         for (spx_handle* k : m->kids) {
@@ -705,34 +661,34 @@ void spx_multi_destroy(spx_multi* m)
     delete m;
 }
 
+// ---- the entry points: checks that need no kid, then the drops, then the kids, then the commit and the sets ---------------------
+
 // the partition decides who holds which draws and candidates: both must be set again afterwards
 static int multi_set_partition(spx_multi* m, int32_t hyper_shards)
 {
     if (m->n % hyper_shards)
         return fail(SPX_ERR_ARG, "spx_set_partition: %d hyper shards do not divide %d devices", hyper_shards, m->n);
-    if (hyper_shards != m->ph) {
-        m->ph = hyper_shards;
-        m->have_hyp = false; m->have_time = false; m->hyp_dirty = false;
-        m->M = 0; m->active = 0; m->on.assign(m->n, 0);
-        m->ran = false; m->ran2d = false; m->last_was_logprob = false;
-        // the devices' own state must not survive either (a stale factorisation of the full draw set)
-        return m->pool->run([m](int i) { spx_drop(m->kids[i], Held::HYP); spx_drop(m->kids[i], Held::CAND); return (int)SPX_OK; });
-    }
-    return SPX_OK;
+    if (hyper_shards == m->ph) return SPX_OK;
+    multi_drop(m, Held::HYP);
+    multi_drop(m, Held::CAND);
+    multi_drop(m, Held::PARTITION);
+    m->ph = hyper_shards;
+    // the devices' own state must not survive either (a stale factorisation of the full draw set)
+    return m->pool->run([m](int i) { spx_drop(m->kids[i], Held::HYP); spx_drop(m->kids[i], Held::CAND); return (int)SPX_OK; });
 }
 
 int spx_multi_set_option(spx_multi* m, const char* name, int64_t value)
 {
-    int rc = m->pool->run([=](int i) { return spx_set_option(m->kids[i], name, value); });
-    // "covar" invalidates the devices' factorisations and results: so it does here
-    if (!rc && !strcmp(name, "covar")) { m->ran = false; m->ran2d = false; m->last_was_logprob = false; }
-    return rc;
+    // "covar" invalidates the devices' factorisations and results when it changes: so it does here
+    if (!strcmp(name, "covar") && value >= SPX_COVAR_MATERN52 && value <= SPX_COVAR_SE && value != m->kids[0]->opt.cov_kind)
+        multi_drop(m, Held::COVAR);
+    return m->pool->run([=](int i) { return spx_set_option(m->kids[i], name, value); });
 }
 
 // replicated to every device slot, as an option is; the devices drop their results, so the front does
 int spx_multi_set_acquisition(spx_multi* m, int32_t kind, double par)
 {
-    m->ran = false; m->ran2d = false;
+    multi_drop(m, Held::RESULTS);
     return m->pool->run([=](int i) { return spx_set_acquisition(m->kids[i], kind, par); });
 }
 
@@ -743,117 +699,142 @@ int spx_multi_get_acquisition(spx_multi* m, int32_t* kind, double* par)
 
 int spx_multi_set_observations(spx_multi* m, const double* comp, const double* vals, int64_t N, int32_t D)
 {
+    if (!comp || !vals || N < 1 || D < 1 || N > (1 << 20))
+        return fail(SPX_ERR_ARG, "spx_set_observations: bad arguments (N=%lld, D=%d)", (long long)N, D);
+    multi_drop(m, Held::OBS);
+    if (D != m->D) { multi_drop(m, Held::CAND); multi_drop(m, Held::HYP); }   // (candidates and hypers of another dimension)
+    // The kids keep their hypers through this call, so the front keeps saying which they are: after spx_gp_logprob, `lp` stays
+    // (nothing made from those shards is held: FACTOR went with that call) and the next spx_factor re-broadcasts.
     int rc = m->pool->run([=](int i) { return spx_set_observations(m->kids[i], comp, vals, N, D); });
     if (rc) return rc;
-    if (m->have_hyp && D != m->D) { m->have_hyp = false; m->have_time = false; }
-    if (D != m->D) { m->M = 0; m->active = 0; m->on.assign(m->n, 0); }
     m->N = N; m->D = D;
-    m->have_time = false; m->ran = false; m->last_was_logprob = false;
-    return SPX_OK;
+    return multi_hold(m, Held::OBS);
+}
+
+// the one commit path of the candidates: `give(i)` hands kid i its rows; the new shards are the front's when every kid has them
+static int put_cands(spx_multi* m, const CandShards& c, int32_t D, const std::function<int(int)>& give)
+{
+    multi_drop(m, Held::CAND);
+    int rc = m->pool->run([&](int i) { return c.on[i] ? give(i) : (int)SPX_OK; });
+    if (rc) return rc;
+    m->cands = c;
+    if (!m->held.has(Held::OBS)) m->D = D;
+    return multi_hold(m, Held::CAND);
 }
 
 int spx_multi_set_candidates(spx_multi* m, const double* cand, int64_t M, int32_t D, int64_t index_base)
 {
     if (!cand || M < 1 || D < 1)
         return fail(SPX_ERR_ARG, "spx_set_candidates: bad arguments (M=%lld, D=%d)", (long long)M, D);
-    // the new shard bounds are committed only when every device has taken its rows
-    std::vector<int64_t> lo, hi;
-    std::vector<char> on;
-    int act = 0;
-    plan_cands(m, M, lo, hi, on, &act);
-    const int64_t* lop = lo.data(); const int64_t* hip_ = hi.data(); const char* onp = on.data();
-    int rc = m->pool->run([=](int i) {
-        if (!onp[i]) return (int)SPX_OK;
-        return spx_set_candidates(m->kids[i], cand + (size_t)lop[i] * D, hip_[i] - lop[i], D, index_base + lop[i]);
+    if (m->held.has(Held::OBS) && D != m->D)
+        return fail(SPX_ERR_ARG, "spx_set_candidates: D=%d but observations have D=%d", D, m->D);
+    const CandShards c = plan_cands(m->n, m->ph, M, index_base);
+    return put_cands(m, c, D, [&](int i) {
+        return spx_set_candidates(m->kids[i], cand + (size_t)c.lo[i] * D, c.hi[i] - c.lo[i], D, index_base + c.lo[i]);
     });
-    if (rc) { m->M = 0; m->active = 0; m->on.assign(m->n, 0); m->ran = false; return rc; }
-    m->lo = lo; m->hi = hi; m->on = on;
-    m->M = M; m->index_base = index_base; m->active = act; m->ran = false;
-    if (!m->D) m->D = D;
-    return SPX_OK;
 }
 
 int spx_multi_set_hypers(spx_multi* m, const double* hypers, int32_t H)
 {
     if (!hypers || H < 1) return fail(SPX_ERR_ARG, "spx_set_hypers: bad arguments (H=%d)", H);
-    if (!m->D) return fail(SPX_ERR_ARG, "spx_set_hypers: call spx_set_observations first");
-    int rc = plan_draws(m, H);
+    if (H > NP_PAIRWISE_MAX_N)   // (as a single handle refuses them: np_sum.h)
+        return fail(SPX_ERR_ARG, "spx_set_hypers: at most %d hyper-parameter draws (got %d)", NP_PAIRWISE_MAX_N, H);
+    if (!m->held.has(Held::OBS)) return fail(SPX_ERR_ARG, "spx_set_hypers: call spx_set_observations first");
+    DrawShards d;
+    if (!plan_draws(m->n, m->ph, H, &d))
+        return fail(SPX_ERR_ARG, "2-D partition: %d hyper shards need at least that many draws (H=%d)", m->ph, H);
+    multi_drop(m, Held::HYP);       // (and the time model: the kids get the draws alone)
+    std::vector<double> hyp(hypers, hypers + (size_t)H * (3 + m->D));
+    int rc = push_hypers(m, d, hyp.data());
     if (rc) return rc;
-    m->H = H;
-    m->hyp_host.assign(hypers, hypers + (size_t)H * (3 + m->D));
-    m->have_time = false;
-    rc = push_hypers(m);
-    if (rc) { m->have_hyp = false; return rc; }
-    m->have_hyp = true; m->hyp_dirty = false; m->ran = false; m->last_was_logprob = false;
-    return SPX_OK;
+    m->draws = d;
+    m->hyp_host.swap(hyp);
+    return multi_hold(m, Held::HYP);
 }
 
 int spx_multi_set_time_model(spx_multi* m, const double* log_durs, const double* time_hypers)
 {
-    int rc = sync_hypers(m);
+    const bool clear = !log_durs || !time_hypers;
+    if (!clear && !m->held.has(Held::HYP)) return fail(SPX_ERR_ARG, "spx_set_time_model: set observations and hypers first");
+    int rc = sync_hypers(m);        // (a kid takes H rows of time_hypers: its H must be its draw shard's again)
     if (rc) return rc;
-    if (!log_durs || !time_hypers) {
-        m->have_time = false;
-        m->ran = false;
-        return m->pool->run([=](int i) { return spx_set_time_model(m->kids[i], nullptr, nullptr); });
-    }
-    if (!m->have_hyp) return fail(SPX_ERR_ARG, "spx_set_time_model: set observations and hypers first");
-    m->ldur_host.assign(log_durs, log_durs + m->N);
-    m->thyp_host.assign(time_hypers, time_hypers + (size_t)m->H * (3 + m->D));
+    multi_drop(m, Held::TIME);
+    if (clear) return m->pool->run([=](int i) { return spx_set_time_model(m->kids[i], nullptr, nullptr); });
     const int hs = 3 + m->D;
-    rc = m->pool->run([=](int i) {
-        return spx_set_time_model(m->kids[i], m->ldur_host.data(), m->thyp_host.data() + (size_t)m->hlo[i] * hs);
-    });
-    if (rc) { m->have_time = false; return rc; }
-    m->have_time = true;
-    m->ran = false;
-    return SPX_OK;
+    std::vector<double> ldur(log_durs, log_durs + m->N), thyp(time_hypers, time_hypers + (size_t)m->draws.H * hs);
+    rc = m->pool->run([&](int i) { return spx_set_time_model(m->kids[i], ldur.data(), thyp.data() + (size_t)m->draws.hlo[i] * hs); });
+    if (rc) return rc;
+    m->ldur_host.swap(ldur);
+    m->thyp_host.swap(thyp);
+    return multi_hold(m, Held::TIME);
 }
 
 int spx_multi_factor(spx_multi* m)
 {
     int rc = sync_hypers(m);
     if (rc) return rc;
-    m->last_was_logprob = false;
-    m->ran = false;
-    return m->pool->run([=](int i) { return spx_factor(m->kids[i]); });
+    multi_drop(m, Held::FACTOR);
+    rc = m->pool->run([=](int i) { return spx_factor(m->kids[i]); });
+    return rc ? rc : multi_hold(m, Held::FACTOR);
+}
+
+// The clear forms of spx_set_fantasies / spx_draw_fantasies, as on a single handle: the fantasies go, the results of the last
+// pass stay readable (every kid keeps its own in the same way)
+static int multi_clear_fantasies(spx_multi* m, const std::function<int(int)>& clear)
+{
+    const bool had = m->held.has(Held::RESULTS);
+    const Held::Results r = m->held.results;
+    multi_drop(m, Held::FANT);
+    int rc = m->pool->run(clear);
+    if (rc) return rc;
+    return had ? multi_hold(m, Held::RESULTS, r) : (int)SPX_OK;
 }
 
 int spx_multi_set_fantasies(spx_multi* m, const double* fant, const double* bests, int32_t S)
 {
-    m->ran = false;
-    if (m->ph > 1 && fant && bests && S > 0)
-        return fail(SPX_ERR_ARG, "spx_set_fantasies: not available in the 2-D partition (spx_set_partition)");
-    return m->pool->run([=](int i) { return spx_set_fantasies(m->kids[i], fant, bests, S); });
+    if (!fant || !bests || S <= 0)
+        return multi_clear_fantasies(m, [=](int i) { return spx_set_fantasies(m->kids[i], nullptr, nullptr, 0); });
+    if (m->ph > 1) return fail(SPX_ERR_ARG, "spx_set_fantasies: not available in the 2-D partition (spx_set_partition)");
+    multi_drop(m, Held::FANT);
+    int rc = m->pool->run([=](int i) { return spx_set_fantasies(m->kids[i], fant, bests, S); });
+    return rc ? rc : multi_hold(m, Held::FANT);
 }
 
 int spx_multi_draw_fantasies(spx_multi* m, int32_t P, const double* z, int32_t per_draw, int32_t S)
 {
-    m->ran = false;
-    if (m->ph > 1 && z && S > 0)
-        return fail(SPX_ERR_ARG, "spx_draw_fantasies: not available in the 2-D partition (spx_set_partition)");
-    return m->pool->run([=](int i) { return spx_draw_fantasies(m->kids[i], P, z, per_draw, S); });   // replicated, as the factor is
+    if (!z || S <= 0)
+        return multi_clear_fantasies(m, [=](int i) { return spx_draw_fantasies(m->kids[i], P, nullptr, per_draw, 0); });
+    if (m->ph > 1) return fail(SPX_ERR_ARG, "spx_draw_fantasies: not available in the 2-D partition (spx_set_partition)");
+    multi_drop(m, Held::FANT);
+    int rc = m->pool->run([=](int i) { return spx_draw_fantasies(m->kids[i], P, z, per_draw, S); });   // replicated, as the factor is
+    return rc ? rc : multi_hold(m, Held::FANT);
 }
 
 int spx_multi_get_pending_fantasies(spx_multi* m, int32_t draw, double* pend_fant, double* bests)
 {
-    return spx_get_pending_fantasies(m->kids[0], draw, pend_fant, bests);
+    if (!m->held.has(Held::FANT)) return fail(SPX_ERR_ARG, "spx_get_pending_fantasies: call spx_draw_fantasies first");
+    return spx_get_pending_fantasies(m->kids[0], draw, pend_fant, bests);     // (slot 0 says whether they were drawn on the device)
 }
 
 int spx_multi_ei_run(spx_multi* m, int32_t flags)
 {
-    if (m->active < 1) return fail(SPX_ERR_ARG, "spx_ei_run: no candidates set");
-    int rc = m->pool->run([=](int i) { return m->on[i] ? spx_ei_run(m->kids[i], flags) : (int)SPX_OK; });
+    if (!m->held.has(Held::CAND)) return fail(SPX_ERR_ARG, "spx_ei_run: no candidates set");
+    // The checks of the pass's flags are the kids' own, made before a kid touches its results: kids that all refused have
+    // lost nothing, and neither has the front.  Anything else overwrites the results.
+    int rc = m->pool->run([=](int i) { return m->cands.on[i] ? spx_ei_run(m->kids[i], flags) : (int)SPX_OK; });
+    bool untouched = rc != SPX_OK;
+    for (int i = 0; i < m->n; ++i) untouched = untouched && (!m->cands.on[i] || m->kids[i]->held.has(Held::RESULTS));
+    if (!untouched) multi_drop(m, Held::RESULTS);
     if (rc) return rc;
-    if ((rc = (m->ph > 1) ? exchange_sums(m) : exchange_best(m))) return rc;
-    m->ran = true;
-    m->ran2d = m->ph > 1;
-    return SPX_OK;
+    if ((rc = exchange(m))) return rc;
+    Held::Results r = m->kids[0]->held.results;     // what the pass kept: the same on every slot that ran (slot 0 is never idle)
+    r.global2d = m->ph > 1;
+    return multi_hold(m, Held::RESULTS, r);
 }
 
 int spx_multi_get_best(spx_multi* m, int64_t* best_idx, double* best_val)
 {
-    if (!m->ran) return fail(SPX_ERR_ARG, "spx_get_best: no results (call spx_ei_run)");
+    if (!m->held.ei()) return fail(SPX_ERR_ARG, "spx_get_best: no results (call spx_ei_run)");
     if (best_idx) *best_idx = m->best.idx;
     if (best_val) *best_val = m->best.val;
     return SPX_OK;
@@ -861,104 +842,100 @@ int spx_multi_get_best(spx_multi* m, int64_t* best_idx, double* best_val)
 
 int spx_multi_get_ei_mean(spx_multi* m, double* out)
 {
-    if (!out || !m->ran) return fail(SPX_ERR_ARG, "spx_get_ei_mean: no results / null output");
-    if (m->ran2d) {   // every device holds the whole vector
+    if (!out || !m->held.ei()) return fail(SPX_ERR_ARG, "spx_get_ei_mean: no results / null output");
+    const CandShards& c = m->cands;
+    if (m->held.results.global2d) {   // every device holds the whole vector
         spx_handle* k = m->kids[0];
         HIPCHK(hipSetDevice(k->device));
-        HIPCHK(hipMemcpy(out, k->ei_sum_full.p, (size_t)m->M * 8, hipMemcpyDeviceToHost));
+        HIPCHK(hipMemcpy(out, k->ei_sum_full.p, (size_t)c.M * 8, hipMemcpyDeviceToHost));
         return SPX_OK;
     }
-    return m->pool->run([=](int i) { return m->on[i] ? spx_get_ei_mean(m->kids[i], out + m->lo[i]) : (int)SPX_OK; });
+    return m->pool->run([=, &c](int i) { return c.on[i] ? spx_get_ei_mean(m->kids[i], out + c.lo[i]) : (int)SPX_OK; });
 }
 
 int spx_multi_get_ei_draws(spx_multi* m, double* out)
 {
-    if (!out || !m->ran) return fail(SPX_ERR_ARG, "spx_get_ei_draws: no results / null output");
+    if (!out || !m->held.ei()) return fail(SPX_ERR_ARG, "spx_get_ei_draws: no results / null output");
+    const CandShards& c = m->cands;
+    const DrawShards& d = m->draws;
     if (m->ph == 1)
-        return m->pool->run([=](int i) {
-            return m->on[i] ? spx_get_ei_draws(m->kids[i], out + (size_t)m->lo[i] * m->H) : (int)SPX_OK;
+        return m->pool->run([=, &c, &d](int i) {
+            return c.on[i] ? spx_get_ei_draws(m->kids[i], out + (size_t)c.lo[i] * d.H) : (int)SPX_OK;
         });
     // 2-D: device i holds the block [lo, hi) x [hlo, hhi) of overall_ei (M x H)
-    return m->pool->run([=](int i) {
-        if (!m->on[i]) return (int)SPX_OK;
-        const int64_t mc = m->hi[i] - m->lo[i], hl = m->hhi[i] - m->hlo[i];
+    return m->pool->run([=, &c, &d](int i) {
+        if (!c.on[i]) return (int)SPX_OK;
+        const int64_t mc = c.hi[i] - c.lo[i], hl = d.count(i);
         std::vector<double> tmp((size_t)mc * hl);
         int rc = spx_get_ei_draws(m->kids[i], tmp.data());
         if (rc) return rc;
-        for (int64_t c = 0; c < mc; ++c)
-            memcpy(out + (size_t)(m->lo[i] + c) * m->H + m->hlo[i], &tmp[(size_t)c * hl], (size_t)hl * 8);
+        for (int64_t r = 0; r < mc; ++r)
+            memcpy(out + (size_t)(c.lo[i] + r) * d.H + d.hlo[i], &tmp[(size_t)r * hl], (size_t)hl * 8);
         return (int)SPX_OK;
     });
 }
 
-// device i's local index of global draw `draw` of the objective model, or -1
-static inline int local_draw(const spx_multi* m, int i, int32_t draw)
-{
-    return (draw >= m->hlo[i] && draw < m->hhi[i]) ? (int)(draw - m->hlo[i]) : -1;
-}
-
 int spx_multi_get_moments(spx_multi* m, int32_t draw, double* func_m, double* func_v)
 {
-    if (!m->ran) return fail(SPX_ERR_ARG, "spx_get_moments: run spx_ei_run with SPX_FLAG_KEEP_MOMENTS first");
-    if (draw < 0 || draw >= m->H) return fail(SPX_ERR_ARG, "spx_get_moments: draw out of range");
-    return m->pool->run([=](int i) {
-        const int ld = local_draw(m, i, draw);
-        return (m->on[i] && ld >= 0) ? spx_get_moments(m->kids[i], ld, func_m ? func_m + m->lo[i] : nullptr,
-                                                       func_v ? func_v + m->lo[i] : nullptr)
-                                     : (int)SPX_OK;
+    if (!m->held.results.moments) return fail(SPX_ERR_ARG, "spx_get_moments: run spx_ei_run with SPX_FLAG_KEEP_MOMENTS first");
+    if (draw < 0 || draw >= m->draws.H) return fail(SPX_ERR_ARG, "spx_get_moments: draw out of range");
+    const CandShards& c = m->cands;
+    return m->pool->run([=, &c](int i) {
+        const int ld = local_draw(m->draws, i, draw);
+        return (c.on[i] && ld >= 0) ? spx_get_moments(m->kids[i], ld, func_m ? func_m + c.lo[i] : nullptr,
+                                                      func_v ? func_v + c.lo[i] : nullptr)
+                                    : (int)SPX_OK;
     });
 }
 
 int spx_multi_get_time_mean(spx_multi* m, int32_t draw, double* out)
 {
-    if (!out || !m->ran) return fail(SPX_ERR_ARG, "spx_get_time_mean: no results / null output");
-    if (draw < 0 || draw >= m->H) return fail(SPX_ERR_ARG, "spx_get_time_mean: draw out of range");
-    return m->pool->run([=](int i) {
-        const int ld = local_draw(m, i, draw);
-        return (m->on[i] && ld >= 0) ? spx_get_time_mean(m->kids[i], ld, out + m->lo[i]) : (int)SPX_OK;
+    if (!out || !(m->held.results.moments || m->held.results.tmean))     // (and a time model: the kids say)
+        return fail(SPX_ERR_ARG, "spx_get_time_mean: no results / null output");
+    if (draw < 0 || draw >= m->draws.H) return fail(SPX_ERR_ARG, "spx_get_time_mean: draw out of range");
+    const CandShards& c = m->cands;
+    return m->pool->run([=, &c](int i) {
+        const int ld = local_draw(m->draws, i, draw);
+        return (c.on[i] && ld >= 0) ? spx_get_time_mean(m->kids[i], ld, out + c.lo[i]) : (int)SPX_OK;
     });
 }
 
-// draw (objective model: 0..H-1, time model: H..2H-1) -> (device of candidate shard 0 that holds it, local draw)
-static int owner_of_draw(const spx_multi* m, int32_t draw, int* kid, int* ld)
+// the kid of candidate shard 0 that holds `draw` (objective model: 0..H-1, time model: H..2H-1) and its number there
+static int factor_owner(spx_multi* m, const char* who, int32_t draw, int* kid, int* ld)
 {
-    const bool tm = draw >= m->H;
-    const int32_t d = tm ? draw - m->H : draw;
-    if (draw < 0 || d >= m->H) return fail(SPX_ERR_ARG, "draw out of range");
-    for (int i = 0; i < m->ph; ++i) {
-        const int l = local_draw(m, i, d);
-        if (l >= 0) { *kid = i; *ld = l + (tm ? (int)(m->hhi[i] - m->hlo[i]) : 0); return SPX_OK; }
-    }
-    return fail(SPX_ERR_ARG, "draw out of range");
+    if (!m->held.has(Held::FACTOR)) return fail(SPX_ERR_ARG, "%s: call spx_factor first", who);
+    return owner_of_draw(m->draws, m->ph, draw, kid, ld) ? (int)SPX_OK : fail(SPX_ERR_ARG, "%s: draw out of range", who);
 }
 
 int spx_multi_get_factor_rows(spx_multi* m, int32_t draw, int64_t row0, int64_t nrows, double* L_rows, double* gamma)
 {
-    int kid = 0, ld = draw;   // replicated (ph = 1): every device holds every draw
-    if (m->ph > 1) { int rc = owner_of_draw(m, draw, &kid, &ld); if (rc) return rc; }
-    return spx_get_factor_rows(m->kids[kid], ld, row0, nrows, L_rows, gamma);
+    int kid, ld;
+    int rc = factor_owner(m, "spx_get_factor_rows", draw, &kid, &ld);
+    return rc ? rc : spx_get_factor_rows(m->kids[kid], ld, row0, nrows, L_rows, gamma);
 }
 
 int spx_multi_get_factor(spx_multi* m, int32_t draw, double* K, double* L, double* alpha)
 {
-    int kid = 0, ld = draw;   // replicated (ph = 1): every device holds every draw
-    if (m->ph > 1) { int rc = owner_of_draw(m, draw, &kid, &ld); if (rc) return rc; }
-    return spx_get_factor(m->kids[kid], ld, K, L, alpha);
+    int kid, ld;
+    int rc = factor_owner(m, "spx_get_factor", draw, &kid, &ld);
+    return rc ? rc : spx_get_factor(m->kids[kid], ld, K, L, alpha);
 }
 
 int spx_multi_get_cross_cov(spx_multi* m, int32_t draw, int64_t c0, int64_t nc, double* out)
 {
-    if (!out || c0 < 0 || nc < 1 || c0 + nc > m->M) return fail(SPX_ERR_ARG, "spx_get_cross_cov: range error");
-    int kid0 = 0, ld = draw;
-    if (m->ph > 1) { int rc = owner_of_draw(m, draw, &kid0, &ld); if (rc) return rc; }
+    const CandShards& c = m->cands;
+    if (!m->held.has(Held::CAND)) return fail(SPX_ERR_ARG, "spx_get_cross_cov: call spx_factor and set candidates first");
+    if (!out || c0 < 0 || nc < 1 || c0 + nc > c.M) return fail(SPX_ERR_ARG, "spx_get_cross_cov: range error");
+    int kid0, ld;
+    int rc = factor_owner(m, "spx_get_cross_cov", draw, &kid0, &ld);
+    if (rc) return rc;
     const int64_t N = m->N;
     for (int i = kid0; i < m->n; i += m->ph) {       // the devices of this draw shard, one per candidate shard
-        if (!m->on[i]) continue;
-        const int64_t a = std::max(c0, m->lo[i]), b = std::min(c0 + nc, m->hi[i]);
+        if (!c.on[i]) continue;
+        const int64_t a = std::max(c0, c.lo[i]), b = std::min(c0 + nc, c.hi[i]);
         if (a >= b) continue;
         std::vector<double> tmp((size_t)N * (b - a));
-        int rc = spx_get_cross_cov(m->kids[i], ld, a - m->lo[i], b - a, tmp.data());
-        if (rc) return rc;
+        if ((rc = spx_get_cross_cov(m->kids[i], ld, a - c.lo[i], b - a, tmp.data()))) return rc;
         for (int64_t r = 0; r < N; ++r)
             memcpy(out + (size_t)r * nc + (a - c0), &tmp[(size_t)r * (b - a)], (size_t)(b - a) * 8);
     }
@@ -969,22 +946,14 @@ int spx_multi_get_cross_cov(spx_multi* m, int32_t draw, int64_t c0, int64_t nc, 
 int spx_multi_gp_logprob(spx_multi* m, double* out)
 {
     if (!out) return fail(SPX_ERR_ARG, "spx_gp_logprob: null");
-    if (!m->have_hyp) return fail(SPX_ERR_ARG, "spx_factor: observations and hypers must be set first");
-    const int H = m->H, hs = 3 + m->D;
-    const int parts = std::min(m->n, H);
-    m->lp_lo.assign(m->n + 1, H);
-    for (int i = 0; i < parts; ++i) {
-        int64_t lo, hi;
-        shard(H, parts, i, &lo, &hi);
-        m->lp_lo[i] = lo;
-    }
-    m->lp_parts = parts;
-    m->hyp_dirty = true;
-    m->last_was_logprob = true;
-    m->ran = false;
+    if (!m->held.has(Held::HYP)) return fail(SPX_ERR_ARG, "spx_factor: observations and hypers must be set first");
+    multi_drop(m, Held::FACTOR);
+    // not a commit: from the first kid's spx_set_hypers on the kids hold these shards, whether the batch succeeds or not
+    m->lp = plan_logprob(m->n, m->draws.H);
+    const int hs = 3 + m->D;
     return m->pool->run([=](int i) {
-        if (i >= parts) return (int)SPX_OK;
-        const int64_t lo = m->lp_lo[i], hi = m->lp_lo[i + 1];
+        if (i >= m->lp.parts) return (int)SPX_OK;
+        const int64_t lo = m->lp.lo[i], hi = m->lp.lo[i + 1];
         int rc = spx_set_hypers(m->kids[i], m->hyp_host.data() + (size_t)lo * hs, (int)(hi - lo));
         if (!rc) rc = spx_gp_logprob(m->kids[i], out + lo);
         return rc;
@@ -994,7 +963,7 @@ int spx_multi_gp_logprob(spx_multi* m, double* out)
 int spx_multi_ei_grad_batch(spx_multi* m, const double* points, int32_t P, double* neg_ei, double* grad)
 {
     if (m->ph > 1) return fail(SPX_ERR_ARG, "spx_ei_grad_batch: not available in the 2-D partition (spx_set_partition)");
-    if (m->hyp_dirty) return fail(SPX_ERR_ARG, "spx_ei_grad_batch: call spx_factor (or spx_ei_grid) first");
+    if (!m->lp.empty()) return fail(SPX_ERR_ARG, "spx_ei_grad_batch: call spx_factor (or spx_ei_grid) first");
     const int parts = std::min<int>(m->n, P);
     const int D = m->D;
     return m->pool->run([=](int i) {
@@ -1010,54 +979,34 @@ int spx_multi_sobol_grid(spx_multi* m, const uint32_t* dirs, int32_t dim_max, in
 {
     if (!as_candidates) return spx_sobol_grid(m->kids[0], dirs, dim_max, dim, n, skip, grid_out, 0, kernel_ms);
     if (n < 1) return fail(SPX_ERR_ARG, "spx_sobol_grid: bad arguments (n=%lld)", (long long)n);
+    if (m->held.has(Held::OBS) && dim != m->D)
+        return fail(SPX_ERR_ARG, "spx_sobol_grid: dim=%d but observations have D=%d", dim, m->D);
     // the point of seed s has a closed form, so every device generates its own shard in place
-    std::vector<int64_t> lo, hi;
-    std::vector<char> on;
-    int act = 0;
-    plan_cands(m, n, lo, hi, on, &act);
-    const int64_t* lop = lo.data(); const int64_t* hip_ = hi.data(); const char* onp = on.data();
+    const CandShards c = plan_cands(m->n, m->ph, n, 0);
     std::vector<double> ms(m->n, 0.0);
-    double* msp = ms.data();
-    int rc = m->pool->run([=](int i) {
-        if (!onp[i]) return (int)SPX_OK;
+    int rc = put_cands(m, c, dim, [&](int i) {
         // (with a 2-D partition several devices hold the same shard: each writes the same rows of grid_out)
-        int r = spx_sobol_grid(m->kids[i], dirs, dim_max, dim, hip_[i] - lop[i], skip + lop[i],
-                               (grid_out && kid_rh(m, i) == 0) ? grid_out + (size_t)lop[i] * dim : nullptr, 1, msp + i);
-        if (!r) m->kids[i]->index_base = lop[i];
+        int r = spx_sobol_grid(m->kids[i], dirs, dim_max, dim, c.hi[i] - c.lo[i], skip + c.lo[i],
+                               (grid_out && i % m->ph == 0) ? grid_out + (size_t)c.lo[i] * dim : nullptr, 1, &ms[i]);
+        if (!r) m->kids[i]->index_base = c.lo[i];
         return r;
     });
-    if (rc) { m->M = 0; m->active = 0; m->on.assign(m->n, 0); m->ran = false; return rc; }
-    if (kernel_ms) {
-        *kernel_ms = 0.0;
-        for (double v : ms) *kernel_ms = std::max(*kernel_ms, v);
-    }
-    m->lo = lo; m->hi = hi; m->on = on;
-    m->M = n; m->index_base = 0; m->active = act; m->ran = false;
-    if (!m->D) m->D = dim;
-    return SPX_OK;
+    if (!rc && kernel_ms) *kernel_ms = *std::max_element(ms.begin(), ms.end());
+    return rc;
 }
 
 int spx_multi_not_pd_info(spx_multi* m, int32_t* draw, int32_t* pivot)
 {
     int d = -1, p = -1;
-    if (m->last_was_logprob) {
-        // only the devices that took part in the last batch: an idle one still remembers an older call
-        for (int i = 0; i < m->lp_parts && d < 0; ++i) {
-            int32_t di = -1, pi = -1;
-            spx_not_pd_info(m->kids[i], &di, &pi);
-            if (di >= 0) { d = (int)m->lp_lo[i] + di; p = pi; }
-        }
-    } else {
-        // factorisation: the first failing draw in global numbering (objective draws 0..H-1, time model H..2H-1);
-        // the devices of candidate shard 0 hold every draw between them
-        for (int i = 0; i < m->ph && i < m->n; ++i) {
-            int32_t di = -1, pi = -1;
-            spx_not_pd_info(m->kids[i], &di, &pi);
-            if (di < 0) continue;
-            const int hl = (int)(m->hhi[i] - m->hlo[i]);
-            const int gd = (m->ph > 1) ? (di >= hl ? m->H + (int)m->hlo[i] + (di - hl) : (int)m->hlo[i] + di) : di;
-            if (d < 0 || gd < d) { d = gd; p = pi; }
-        }
+    // after spx_gp_logprob only the kids that took part in the batch are asked (an idle one still remembers an older call);
+    // else the first failing draw of a factorisation: the devices of candidate shard 0 hold every draw between them
+    const int asked = m->lp.empty() ? m->ph : m->lp.parts;
+    for (int i = 0; i < asked; ++i) {
+        int32_t di = -1, pi = -1;
+        spx_not_pd_info(m->kids[i], &di, &pi);
+        if (di < 0) continue;
+        const int gd = m->lp.empty() ? global_draw(m->draws, i, di) : (int)m->lp.lo[i] + di;
+        if (d < 0 || gd < d) { d = gd; p = pi; }
     }
     if (draw) *draw = d;
     if (pivot) *pivot = p;

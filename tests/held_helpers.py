@@ -9,8 +9,8 @@ import hashlib
 import numpy as np
 
 from spearmint_amd import sobol
-from spearmint_amd.engine import (FLAG_CONSTRAINED, FLAG_KEEP_MOMENTS, FLAG_PER_SEC, FLAG_TIME_ONLY, Engine, LinAlgError, SpxError,
-                                  _dp)
+from spearmint_amd.engine import (FLAG_CONSTRAINED, FLAG_KEEP_MOMENTS, FLAG_PER_SEC, FLAG_TIME_ONLY, Engine, LinAlgError, MultiEngine,
+                                  SpxError, _dp)
 from spearmint_amd.synthetic import synthetic_problem
 
 N, M, H, D, S, P, NC = 70, 130, 2, 2, 2, 1, 9
@@ -35,11 +35,21 @@ class Problem(object):
         self.dirs = sobol.load_dirs("jk1111")
 
 
-def engine(lib=None):
-    """An Engine whose Python-side shapes are this problem's from the start (its wrappers check them before they call)."""
-    e = Engine(0, lib=lib)
+def engine(lib=None, devices=None, hyper_shards=1):
+    """An Engine whose Python-side shapes are this problem's from the start (its wrappers check them before they call).
+    devices: the front of a multi-device handle over these device ids instead, its slots in `hyper_shards` draw shards
+    (spx_set_partition; "set_partition" of CALLS and reset() ask for the same count again: nothing changes)."""
+    e = Engine(0, lib=lib) if devices is None else MultiEngine(devices, lib=lib)
     e.N, e.D, e.M, e.H = N, D, M, H
+    e.hyper_shards = hyper_shards
+    if hyper_shards != 1:
+        e.set_partition(hyper_shards)
     return e
+
+
+def front_calls():
+    """CALLS without what a multi-device handle refuses outright: the constraint model and its passes."""
+    return {k: f for k, f in CALLS.items() if "constrain" not in k}
 
 
 def outcome(fn, *args):
@@ -74,6 +84,10 @@ GETTERS = {
     "get_pending_fantasies": lambda e, p: np.concatenate([a.ravel() for a in _pending(e)]),
 }
 
+# ... of a multi-device handle: no constraint model; K(X*,X) of the first candidates (needs the factor AND candidates)
+FRONT_GETTERS = {k: f for k, f in GETTERS.items() if k != "get_constraint_prob"}
+FRONT_GETTERS["get_cross_cov"] = lambda e, p: e.get_cross_cov(H - 1, 0, min(5, e.M))
+
 # every entry point that writes, under the name the tables and the walks use
 CALLS = {
     "set_observations": lambda e, p: e.set_observations(p.comp, p.vals),
@@ -88,7 +102,7 @@ CALLS = {
     "set_option(covar, same)": lambda e, p: e.set_covar("Matern52"),
     "gp_logprob": lambda e, p: e.gp_logprob(),
     "sobol_grid(as_candidates)": lambda e, p: e.sobol_grid(p.dirs, D, M, 1, fetch=False, as_candidates=True)[0],
-    "set_partition": lambda e, p: e.set_partition(1, 0, 0),
+    "set_partition": lambda e, p: e.set_partition(e.hyper_shards, 0, 0),
     "factor": lambda e, p: e.factor(),
     "set_fantasies": lambda e, p: e.set_fantasies(p.fant, p.bests),
     "set_fantasies(NULL)": lambda e, p: e.set_fantasies(None, None),
@@ -106,10 +120,10 @@ def sha(a):
     return hashlib.sha256(np.ascontiguousarray(a, dtype=np.float64).tobytes()).hexdigest()[:12]
 
 
-def read_all(e, p):
+def read_all(e, p, getters=GETTERS):
     """{getter: None where it refused, else the SHA-256 of what it served}."""
     out = {}
-    for name, fn in GETTERS.items():
+    for name, fn in getters.items():
         kind, res = outcome(fn, e, p)
         out[name] = sha(res) if kind == "ok" else None
     return out
@@ -118,12 +132,13 @@ def read_all(e, p):
 def reset(e, p):
     """Back to a handle that holds this problem's observations, candidates and hypers and nothing made from them."""
     e.set_covar("Matern52")
-    e.set_partition(1, 0, 0)
+    e.set_partition(e.hyper_shards, 0, 0)
     e.set_observations(p.comp, p.vals)
     e.set_candidates(p.cand)
     e.set_hypers(p.hypers)
     e.set_time_model(None, None)
-    e.set_constraint_model(None, None, None)
+    if not isinstance(e, MultiEngine):
+        e.set_constraint_model(None, None, None)
 
 
 def base(e, p, kind):
@@ -132,7 +147,8 @@ def base(e, p, kind):
     reset(e, p)
     if kind == "plain":
         e.factor()
-        e.draw_fantasies(p.z, P)
+        if e.hyper_shards == 1:                        # (the 2-D partition of a multi-device handle takes no fantasies)
+            e.draw_fantasies(p.z, P)
         e.ei_run(FLAGS["plain"])
     elif kind == "per_sec":
         e.set_time_model(p.log_durs, p.th)

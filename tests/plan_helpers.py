@@ -1,6 +1,7 @@
-"""Shared by tests/test_plan.py, tests/test_held.py (CPU) and tests/test_gpu_r_plan_runs.py: builds a client under tests/c --
-a stand-alone host program over one host-only header of csrc -- with the host C++ compiler and the address /
-undefined-behaviour sanitizers, and asks it: plan_client.cpp for plans, held_client.cpp for what a handle holds.  A case is ("factor" | "ei", {key: value}); keys are the shape's (plan_client.cpp) and option names."""
+"""Shared by tests/test_plan.py, tests/test_held.py, tests/test_shards.py (CPU) and tests/test_gpu_r_plan_runs.py: builds a client
+under tests/c -- a stand-alone host program over one host-only header of csrc -- with the host C++ compiler and the address /
+undefined-behaviour sanitizers, and asks it: plan_client.cpp for plans, held_client.cpp for what a handle holds,
+shards_client.cpp for who holds what on a multi-device handle.  A case is ("factor" | "ei", {key: value}); keys are the shape's (plan_client.cpp) and option names."""
 import json
 import os
 import shutil
@@ -18,7 +19,8 @@ def compiler():
 
 def client(name="plan_client"):
     """Path of the built client tests/c/NAME.cpp (built once per process, into a temporary directory), or None without a
-    compiler.  plan_client is over csrc/spx_plan.h; held_client over csrc/spx_held.h (tests/test_held.py)."""
+    compiler.  plan_client is over csrc/spx_plan.h; held_client over csrc/spx_held.h (tests/test_held.py); shards_client over
+    csrc/spx_shards.h (tests/test_shards.py)."""
     if name not in _clients:
         cxx = compiler()
         if not cxx:

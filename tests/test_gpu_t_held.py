@@ -1,6 +1,7 @@
 """What a handle holds after each entry point (csrc/spx_held.h), seen from outside: every reader after every writer against a
 literal table of accept / refuse, calls that fail without a fault, and the two clear forms that used to leave results
 readable.  The tables are written from the "made from" table of DESIGN.md ("What a handle holds"), not taken from a run."""
+import numpy as np
 import pytest
 
 from tests import held_helpers as hh
@@ -146,6 +147,182 @@ def test_a_call_that_fails_without_a_fault_leaves_nothing_of_what_it_was_overwri
     eng.ei_step(hh.FLAGS["plain"])
     assert hh.read_all(eng, prob) == fresh_bits
     assert hh.not_pd_info(eng) == (-1, -1)
+
+
+# ---- the front of a multi-device handle: the same record and table (csrc/spx_multi.hip) -----------------------------------------
+# On one GPU: two slots that share the candidates, and four slots in two draw shards x two candidate shards (the 2-D partition,
+# which takes no fantasies: its "plain" base has none, so its pass keeps the moments).  What differs from the single handle, by
+# spx_set_partition with the shard count the handle has changes nothing; the front holds no constraint model.
+FRONT_READERS = ["get_best", "get_ei_mean", "get_ei_draws", "get_moments", "get_time_mean", "get_factor", "get_factor_rows",
+                 "get_cross_cov", "get_pending_fantasies", "ei_run(bare)", "ei_grad_batch"]
+F_NONE = "RRRRRRRRRRR"
+#                                           bmdMT FRXP rg
+FRONT_TABLE = {
+    ("2", "plain"): {                       # OBS CAND HYP FACTOR FANT (device) RESULTS; with fantasies a pass keeps no moments
+        None:                               "AAARR" "AAAA" "AA",
+        "set_observations":                 F_NONE,
+        "set_candidates":                   "RRRRR" "AAAA" "AA",
+        "set_hypers":                       F_NONE,
+        "set_time_model":                   F_NONE,
+        "set_time_model(NULL)":             F_NONE,
+        "set_option(covar, other)":         F_NONE,
+        "set_option(covar, same)":          "AAARR" "AAAA" "AA",
+        "gp_logprob":                       F_NONE,
+        "sobol_grid(as_candidates)":        "RRRRR" "AAAA" "AA",
+        "set_partition":                    "AAARR" "AAAA" "AA",      # (the count it has)
+        "factor":                           "RRRRR" "AAAR" "AA",
+        "set_fantasies(NULL)":              "AAARR" "AAAR" "AA",      # the last pass stays readable
+        "draw_fantasies(NULL)":             "AAARR" "AAAR" "AA",
+        "set_fantasies":                    "RRRRR" "AAAR" "AA",      # (fantasies from the host: no pending rows to serve)
+        "draw_fantasies":                   "RRRRR" "AAAA" "AA",
+        "ei_run(plain)":                    "AAARR" "AAAA" "AA",
+        "ei_step(plain)":                   "AAAAR" "AAAR" "AA",      # a new factor: no fantasies, so moments are kept
+        "ei_grad_batch":                    "AAARR" "AAAA" "AA",
+    },
+    ("2", "per_sec"): {                     # OBS CAND HYP TIME FACTOR RESULTS (moments, durations)
+        None:                               "AAAAA" "AAAR" "AA",
+        "set_observations":                 F_NONE,
+        "set_candidates":                   "RRRRR" "AAAR" "AA",
+        "set_hypers":                       F_NONE,
+        "set_time_model":                   F_NONE,
+        "set_time_model(NULL)":             F_NONE,
+        "set_option(covar, other)":         F_NONE,
+        "set_option(covar, same)":          "AAAAA" "AAAR" "AA",
+        "gp_logprob":                       F_NONE,
+        "sobol_grid(as_candidates)":        "RRRRR" "AAAR" "AA",
+        "set_partition":                    "AAAAA" "AAAR" "AA",
+        "factor":                           "RRRRR" "AAAR" "AA",
+        "set_fantasies(NULL)":              "AAAAA" "AAAR" "AA",
+        "draw_fantasies(NULL)":             "AAAAA" "AAAR" "AA",
+        "set_fantasies":                    "RRRRR" "AAAR" "AR",      # (fantasies with a time model: no refinement objective)
+        "draw_fantasies":                   "RRRRR" "AAAA" "AR",
+        "ei_run(per_sec)":                  "AAAAA" "AAAR" "AA",
+        "ei_step(per_sec)":                 "AAAAA" "AAAR" "AA",
+        "ei_grad_batch":                    "AAAAA" "AAAR" "AA",
+    },
+    ("4x2", "plain"): {                     # OBS CAND HYP FACTOR RESULTS (moments); no refinement objective in the 2-D partition
+        None:                               "AAAAR" "AAAR" "AR",
+        "set_observations":                 F_NONE,
+        "set_candidates":                   "RRRRR" "AAAR" "AR",
+        "set_hypers":                       F_NONE,
+        "set_time_model":                   F_NONE,
+        "set_time_model(NULL)":             F_NONE,
+        "set_option(covar, other)":         F_NONE,
+        "set_option(covar, same)":          "AAAAR" "AAAR" "AR",
+        "gp_logprob":                       F_NONE,
+        "sobol_grid(as_candidates)":        "RRRRR" "AAAR" "AR",
+        "set_partition":                    "AAAAR" "AAAR" "AR",
+        "factor":                           "RRRRR" "AAAR" "AR",
+        "set_fantasies(NULL)":              "AAAAR" "AAAR" "AR",
+        "draw_fantasies(NULL)":             "AAAAR" "AAAR" "AR",
+        "set_fantasies":                    "AAAAR" "AAAR" "AR",      # refused: nothing changes
+        "draw_fantasies":                   "AAAAR" "AAAR" "AR",
+        "ei_run(plain)":                    "AAAAR" "AAAR" "AR",
+        "ei_step(plain)":                   "AAAAR" "AAAR" "AR",
+        "ei_grad_batch":                    "AAAAR" "AAAR" "AR",
+    },
+    ("4x2", "per_sec"): {                   # OBS CAND HYP TIME FACTOR RESULTS (moments, durations)
+        None:                               "AAAAA" "AAAR" "AR",
+        "set_observations":                 F_NONE,
+        "set_candidates":                   "RRRRR" "AAAR" "AR",
+        "set_hypers":                       F_NONE,
+        "set_time_model":                   F_NONE,
+        "set_time_model(NULL)":             F_NONE,
+        "set_option(covar, other)":         F_NONE,
+        "set_option(covar, same)":          "AAAAA" "AAAR" "AR",
+        "gp_logprob":                       F_NONE,
+        "sobol_grid(as_candidates)":        "RRRRR" "AAAR" "AR",
+        "set_partition":                    "AAAAA" "AAAR" "AR",
+        "factor":                           "RRRRR" "AAAR" "AR",
+        "set_fantasies(NULL)":              "AAAAA" "AAAR" "AR",
+        "draw_fantasies(NULL)":             "AAAAA" "AAAR" "AR",
+        "set_fantasies":                    "AAAAA" "AAAR" "AR",
+        "draw_fantasies":                   "AAAAA" "AAAR" "AR",
+        "ei_run(per_sec)":                  "AAAAA" "AAAR" "AR",
+        "ei_step(per_sec)":                 "AAAAA" "AAAR" "AR",
+        "ei_grad_batch":                    "AAAAA" "AAAR" "AR",
+    },
+}
+FRONT_CASES = [(front, kind, writer) for (front, kind), rows in FRONT_TABLE.items() for writer in rows]
+REFUSED_ON = {"4x2": ("set_fantasies", "draw_fantasies", "ei_grad_batch")}     # writers that the 2-D partition refuses
+NP_PAIRWISE_MAX_N = 524288              # csrc/np_sum.h: the most draws spx_set_hypers takes
+
+
+@pytest.fixture(scope="module")
+def fronts():
+    es = {"2": hh.engine(devices=[0, 0]), "4x2": hh.engine(devices=[0, 0, 0, 0], hyper_shards=2)}
+    yield es
+    for e in es.values():
+        e.close()
+
+
+def front_row(e, p):
+    row = ""
+    for name in FRONT_READERS:
+        kind, res = hh.outcome(hh.FRONT_GETTERS.get(name) or hh.CALLS[name], e, p)
+        assert kind in ("ok", "arg"), (name, kind, res)
+        row += "A" if kind == "ok" else "R"
+    return row
+
+
+@pytest.mark.parametrize("front,kind,writer", FRONT_CASES, ids=["%s-%s-%s" % (f, k, w or "base") for f, k, w in FRONT_CASES])
+def test_accept_refuse_table_of_the_front(fronts, prob, front, kind, writer):
+    e = fronts[front]
+    assert len(FRONT_TABLE[front, kind][writer]) == len(FRONT_READERS)
+    hh.base(e, prob, kind)
+    if writer is not None:
+        wk, res = hh.outcome(hh.CALLS[writer], e, prob)
+        assert wk == ("arg" if writer in REFUSED_ON.get(front, ()) else "ok"), (writer, wk, res)
+    got = front_row(e, prob)
+    print(front, kind, writer, got)
+    assert got == FRONT_TABLE[front, kind][writer]
+
+
+def raw(e, rc):
+    """The outcome of a raw library call (one that the Engine's own wrapper would not pass on, or not without changing its
+    Python-side shapes)."""
+    return hh.outcome(e._check, rc)[0]
+
+
+# calls that the front refuses from its own record, before any slot is asked: (name, fronts it is refused on, the call)
+REFUSALS = [
+    ("candidates of another D", ("2", "4x2"),
+     lambda e, p: raw(e, e._lib.spx_set_candidates(e._h, hh._dp(np.zeros((5, hh.D + 1))), 5, hh.D + 1, 0))),
+    ("fewer draws than draw shards", ("4x2",),
+     lambda e, p: raw(e, e._lib.spx_set_hypers(e._h, hh._dp(np.ascontiguousarray(p.hypers[:1])), 1))),
+    ("more draws than the mean over draws takes", ("2", "4x2"),
+     lambda e, p: raw(e, e._lib.spx_set_hypers(e._h, hh._dp(np.zeros((NP_PAIRWISE_MAX_N + 1, 3 + hh.D))), NP_PAIRWISE_MAX_N + 1))),
+    ("set_fantasies in the 2-D partition", ("4x2",), lambda e, p: hh.outcome(hh.CALLS["set_fantasies"], e, p)[0]),
+    ("draw_fantasies in the 2-D partition", ("4x2",), lambda e, p: hh.outcome(hh.CALLS["draw_fantasies"], e, p)[0]),
+]
+REFUSAL_CASES = [(f, k, i) for i, r in enumerate(REFUSALS) for f in r[1] for k in ("plain", "per_sec")]
+
+
+@pytest.mark.parametrize("front,kind,which", REFUSAL_CASES, ids=["%s-%s-%s" % (f, k, REFUSALS[i][0]) for f, k, i in REFUSAL_CASES])
+def test_a_call_the_front_refuses_changes_nothing(fronts, prob, front, kind, which):
+    e = fronts[front]
+    hh.base(e, prob, kind)
+    before = hh.read_all(e, prob, hh.FRONT_GETTERS)
+    assert before["get_best"] and before["get_ei_draws"] and before["get_factor"] and before["get_cross_cov"]
+    assert REFUSALS[which][2](e, prob) == "arg"
+    assert hh.read_all(e, prob, hh.FRONT_GETTERS) == before             # the same bytes from every reader, results included
+    assert front_row(e, prob) == FRONT_TABLE[front, kind][None]         # and the draws, the shards and the factor still run
+
+
+def test_fewer_candidates_than_slots_leave_a_slot_idle(eng, prob):
+    m = hh.engine(devices=[0, 0, 0])
+    try:
+        got = {}
+        for e in (m, eng):
+            hh.base(e, prob, "plain")
+            e.set_candidates(prob.cand[:2])
+            e.ei_run(hh.FLAGS["plain"])
+            got[e is m] = hh.read_all(e, prob, hh.FRONT_GETTERS)
+        assert front_row(m, prob) == FRONT_TABLE["2", "plain"][None]
+        assert got[True] == got[False] and got[True]["get_best"] and got[True]["get_cross_cov"]    # the single handle's bits
+    finally:
+        m.close()
+        eng.set_candidates(prob.cand)
 
 
 # ---- the two clear forms that left results readable: each of these read them back before ---------------------------------------
