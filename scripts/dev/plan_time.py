@@ -1,8 +1,11 @@
-"""Dev tool: wall time per call of the three calls where host work shows -- spx_gp_logprob at N = 64 x 1 draw and
-N = 256 x 10 draws, spx_ei_step at N = 128, 20 000 candidates, 10 draws -- with a variant build against the in-tree library
+"""Dev tool: wall time per call of the calls where host work shows, with a variant build against the in-tree library
 (as scripts/dev/lib_ab.py: alternating, each run in its own process).  The variant also runs against ITSELF under a second
 label, which gives the spread of the machine on the day: a difference between builds means something only beyond it.
-   python scripts/dev/plan_time.py _variants/libspx_parent.so [rounds]          (profiles/plan_refactor_time.log)"""
+Call sets: `host` -- spx_gp_logprob at N = 64 x 1 draw and N = 256 x 10 draws, spx_ei_step at N = 128, 20 000 candidates,
+10 draws; `staging` -- spx_ei_step at N = 256, 20 000 candidates, 10 draws through a 1 MiB K(X*,X) staging buffer (40 chunks
+x 10 draws = 400 work items a pass: the event traffic of the hand-off dominates) under streams = 1, 2 and 3.
+   python scripts/dev/plan_time.py _variants/libspx_parent.so [rounds] [host|staging|all]
+(profiles/plan_refactor_time.log: the host set; profiles/staging_ring_time.log: all)"""
 import json
 import os
 import subprocess
@@ -11,7 +14,13 @@ import time
 
 here = os.path.dirname(os.path.abspath(__file__))
 root = os.path.dirname(os.path.dirname(here))
-CALLS = ("logprob N=64 H=1", "logprob N=256 H=10", "ei_step N=128 M=20000 H=10")
+# name: N, M, H, timed calls per loop, options (every call starts from DEFAULTS: none inherits the options of the call before)
+DEFAULTS = {"kstar_budget_bytes": 512 << 20, "streams": 1}
+SETS = {"host": {"logprob N=64 H=1": (64, 16, 1, 400, {}), "logprob N=256 H=10": (256, 16, 10, 300, {}),
+                 "ei_step N=128 M=20000 H=10": (128, 20000, 10, 150, {})},
+        "staging": {"ei_step N=256 M=20000 H=10 1MiB streams=%d" % ns: (256, 20000, 10, 12, {"kstar_budget_bytes": 1 << 20, "streams": ns})
+                    for ns in (1, 2, 3)}}
+SETS["all"] = dict(SETS["host"], **SETS["staging"])
 
 if len(sys.argv) > 1 and sys.argv[1] == "--child":
     sys.path.insert(0, root)
@@ -20,8 +29,10 @@ if len(sys.argv) > 1 and sys.argv[1] == "--child":
     from spearmint_amd.synthetic import synthetic_problem
     eng = Engine(0, lib=None if sys.argv[2] == "-" else sys.argv[2])
     out = {}
-    for name, (N, Mc, H, reps) in zip(CALLS, ((64, 16, 1, 400), (256, 16, 10, 300), (128, 20000, 10, 150))):
+    for name, (N, Mc, H, reps, opts) in SETS[sys.argv[3]].items():
         comp, cand, vals, hypers = synthetic_problem(N, Mc, 6, H, 5)
+        for k, v in dict(DEFAULTS, **opts).items():
+            eng.set_option(k, v)
         eng.set_observations(comp, vals)
         eng.set_candidates(cand)
         eng.set_hypers(hypers)
@@ -47,11 +58,13 @@ if len(sys.argv) > 1 and sys.argv[1] == "--child":
 
 variant = sys.argv[1]
 rounds = int(sys.argv[2]) if len(sys.argv) > 2 else 6
+which = sys.argv[3] if len(sys.argv) > 3 else "host"
+CALLS = tuple(SETS[which])
 runs = (("parent_a", variant), ("parent_b", variant), ("child", "-"))
 res = {label: [] for label, _ in runs}
 for rnd in range(rounds):
     for label, lib in runs:
-        o = subprocess.run([sys.executable, os.path.abspath(__file__), "--child", lib], stdout=subprocess.PIPE, timeout=120, check=True)
+        o = subprocess.run([sys.executable, os.path.abspath(__file__), "--child", lib, which], stdout=subprocess.PIPE, timeout=240, check=True)
         res[label].append(json.loads(o.stdout.decode().strip().splitlines()[-1]))
         print("round %d %-8s %s" % (rnd, label, "  ".join("%s: %.2f us" % (c, res[label][-1][c][0]) for c in CALLS)), flush=True)
 

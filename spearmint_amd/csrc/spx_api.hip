@@ -64,12 +64,12 @@ static int ensure_init(spx_handle* h)
     HIPCHK(hipSetDevice(h->device));
     if (!h->inited) {
         // the main stream (factorisation, predict GEMM, EI) at the device's highest priority, the K(X*,X) producer of option
-        // streams = 3 (ensure_ring) at its lowest: a place that comes free on a CU goes to a waiting GEMM workgroup first
+        // streams = 3 (ensure_stream3) at its lowest: a place that comes free on a CU goes to a waiting GEMM workgroup first
         int prio_least = 0, prio_greatest = 0;
         if (hipDeviceGetStreamPriorityRange(&prio_least, &prio_greatest) != hipSuccess) { (void)hipGetLastError(); prio_least = prio_greatest = 0; }
         HIPCHK(hipStreamCreateWithPriority(&h->stream, hipStreamNonBlocking, prio_greatest));
         HIPCHK(hipStreamCreateWithFlags(&h->stream2, hipStreamNonBlocking));
-        for (int i = 0; i < 6; ++i) HIPCHK(hipEventCreateWithFlags(&h->ev_sync[i], hipEventDisableTiming));
+        for (auto& cb : h->chunk) HIPCHK(hipEventCreateWithFlags(&cb.consumed, hipEventDisableTiming));
         HIPCHK(hipEventCreate(&h->ev_t0));
         HIPCHK(hipEventCreate(&h->ev_t1));
         HIPCHK(hipEventCreateWithFlags(&h->ev_obs, hipEventDisableTiming));
@@ -82,15 +82,19 @@ static int ensure_init(spx_handle* h)
     return SPX_OK;
 }
 
-// option streams = 3: the producer stream and `R` ring slots (events only: the buffers are reserved by the pass)
-static int ensure_ring(spx_handle* h, int R)
+// option streams = 3: the producer stream
+static int ensure_stream3(spx_handle* h)
 {
-    if (!h->stream3) {
-        int prio_least = 0, prio_greatest = 0;
-        if (hipDeviceGetStreamPriorityRange(&prio_least, &prio_greatest) != hipSuccess) { (void)hipGetLastError(); prio_least = prio_greatest = 0; }
-        HIPCHK(hipStreamCreateWithPriority(&h->stream3, hipStreamNonBlocking, prio_least));
-    }
-    while ((int)h->ring.size() < R) {
+    if (h->stream3) return SPX_OK;
+    int prio_least = 0, prio_greatest = 0;
+    if (hipDeviceGetStreamPriorityRange(&prio_least, &prio_greatest) != hipSuccess) { (void)hipGetLastError(); prio_least = prio_greatest = 0; }
+    HIPCHK(hipStreamCreateWithPriority(&h->stream3, hipStreamNonBlocking, prio_least));
+    return SPX_OK;
+}
+// `n` staging slots (events only: the buffers are reserved by the pass)
+static int ensure_slots(spx_handle* h, int n)
+{
+    while ((int)h->ring.size() < n) {
         spx_handle::RingSlot sl;
         HIPCHK(hipEventCreateWithFlags(&sl.ready, hipEventDisableTiming));
         hipError_t e = hipEventCreateWithFlags(&sl.consumed, hipEventDisableTiming);
@@ -103,10 +107,14 @@ static int ensure_ring(spx_handle* h, int R)
     }
     return SPX_OK;
 }
-// the ring's buffers beyond the first `keep` slots go back to the device (a pass that needs fewer, or another mode)
-static void ring_trim(spx_handle* h, int keep)
+// record `ev` on `from` and make `to` wait for it: what `from` has queued so far is done before what `to` queues from here
+// on; nothing when they are one stream
+static int hand_off(hipStream_t from, hipStream_t to, hipEvent_t ev)
 {
-    for (size_t i = (size_t)std::max(keep, 0); i < h->ring.size(); ++i) { h->ring[i].Kst.release(); h->ring[i].part_bgS.release(); }
+    if (from == to) return SPX_OK;
+    HIPCHK(hipEventRecord(ev, from));
+    HIPCHK(hipStreamWaitEvent(to, ev, 0));
+    return SPX_OK;
 }
 
 static int ev_begin(spx_handle* h, int stage, hipStream_t strm)
@@ -282,23 +290,23 @@ void spx_destroy(spx_handle* h)
         }
         h->ring.clear();
         if (h->stream3) (void)hipStreamDestroy(h->stream3);
+        for (auto& cb : h->chunk) {
+            for (DevBuf* b : {&cb.Cs, &cb.s2, &cb.time_m, &cb.con_Cs, &cb.con_s2, &cb.con_p}) b->release();
+            (void)hipEventDestroy(cb.consumed);
+        }
         DevBuf* bufs[] = {&h->comp, &h->vals, &h->ldur, &h->cand, &h->hyp, &h->htab, &h->Xs, &h->X2s,
-                          &h->s1, &h->Lm, &h->WT, &h->Dinv, &h->gamma, &h->alpha, &h->info, &h->lp,
-                          &h->Cs[0], &h->s2[0], &h->Kst[0], &h->part_ss[0], &h->part_bg[0], &h->time_m[0],
-                          &h->Cs[1], &h->s2[1], &h->Kst[1], &h->part_ss[1], &h->part_bg[1], &h->time_m[1],
-                          &h->fantT, &h->gammaS, &h->bests, &h->part_bgS[0], &h->part_bgS[1], &h->fant_z, &h->fant_post, &h->fant_pend, &h->fant_info,
+                          &h->s1, &h->Lm, &h->WT, &h->Dinv, &h->gamma, &h->alpha, &h->info, &h->lp, &h->part_ss, &h->part_bg,
+                          &h->fantT, &h->gammaS, &h->bests, &h->fant_z, &h->fant_post, &h->fant_pend, &h->fant_info,
                           &h->pt_x, &h->pt_k, &h->pt_dk, &h->pt_t, &h->pt_z, &h->pt_out, &h->pt_kt, &h->pt_dkt,
                           &h->ei_draw, &h->ei_mean, &h->mom_m, &h->mom_v, &h->mom_t, &h->am_val, &h->am_idx,
                           &h->am_out_val, &h->am_out_idx, &h->scratch, &h->sobol_dirs, &h->sobol_out, &h->rhs, &h->diagL, &h->ps_flags, &h->flow_flags,
                           &h->alphaS, &h->pt_u, &h->rec_send, &h->rec_recv, &h->rec_out, &h->ei_sum_full,
-                          &h->con_tab, &h->con_Cs[0], &h->con_Cs[1], &h->con_s2[0], &h->con_s2[1], &h->con_p[0], &h->con_p[1],
-                          &h->mom_c, &h->rhs_rows, &h->eff_in, &h->eff_m, &h->eff_out, &h->loo_out};
+                          &h->con_tab, &h->mom_c, &h->rhs_rows, &h->eff_in, &h->eff_m, &h->eff_out, &h->loo_out};
         for (DevBuf* b : bufs) b->release();
         h->pin_up.release();
         h->pin_res.release();
         h->pin_stage.release();
         for (auto& e : h->ev_pool) { (void)hipEventDestroy(e.a); (void)hipEventDestroy(e.b); }
-        for (int i = 0; i < 6; ++i) (void)hipEventDestroy(h->ev_sync[i]);
         (void)hipEventDestroy(h->ev_t0);
         (void)hipEventDestroy(h->ev_t1);
         (void)hipEventDestroy(h->ev_obs);
@@ -956,6 +964,50 @@ int spx_ei_step(spx_handle* h, int32_t flags)
     return rc;
 }
 
+// everything an EI pass writes on the device, reserved as its plan says before anything is queued
+static int ei_reserve(spx_handle* h, const EiPlan& p)
+{
+    int rc;
+    const bool fant = h->S > 0, con_gp = p.constrained && h->con_n > 0;
+    if (p.ns == 3 && (rc = ensure_stream3(h))) return rc;   // (a time-only pass too: it stages nothing, but produces there)
+    // the staging slots: K(X*,X) of a work item and, with fantasies, its partial means; the buffers of slots that the pass
+    // does not use go back to the device first
+    if (p.trim_ring)
+        for (size_t k = p.slots; k < h->ring.size(); ++k) { h->ring[k].Kst.release(); h->ring[k].part_bgS.release(); }
+    if ((rc = ensure_slots(h, p.slots))) return rc;
+    for (int k = 0; k < p.slots; ++k) {
+        if ((rc = h->ring[k].Kst.reserve(p.kst_bytes))) return rc;
+        if (fant && (rc = h->ring[k].part_bgS.reserve(p.bgS_bytes))) return rc;
+    }
+    // scaled candidates (all draws), predicted durations and P(feasible) are double-buffered by chunk parity
+    for (auto& cb : h->chunk) {
+        if ((rc = cb.Cs.reserve(p.cs_bytes))) return rc;
+        if ((rc = cb.s2.reserve(p.s2_bytes))) return rc;
+        if (p.per_sec && (rc = cb.time_m.reserve(p.s2_bytes))) return rc;
+        if (p.constrained && (rc = cb.con_p.reserve(p.s2_bytes))) return rc;
+        if (con_gp && (rc = cb.con_Cs.reserve(p.cs_bytes))) return rc;
+        if (con_gp && (rc = cb.con_s2.reserve(p.s2_bytes))) return rc;
+    }
+    // column sums of beta^2 and beta*gamma per row block for ALL draws of a chunk: written by the
+    // GEMM launches and read by one EI-finalize launch per chunk, all on the consumer stream
+    if (p.gemm_path && (rc = h->part_ss.reserve(p.part_bytes))) return rc;
+    if (p.gemm_path && (rc = h->part_bg.reserve(p.part_bytes))) return rc;
+    if (fant && (rc = h->scratch.reserve(p.scratch_bytes))) return rc;   // EI per (draw of the group, fantasy, candidate)
+    if ((rc = h->ei_draw.reserve(p.draw_bytes))) return rc;
+    if ((rc = h->ei_mean.reserve(p.mean_bytes))) return rc;
+    if (p.keep_mom) {
+        if ((rc = h->mom_m.reserve(p.draw_bytes))) return rc;
+        if ((rc = h->mom_v.reserve(p.draw_bytes))) return rc;
+        if (p.per_sec && (rc = h->mom_t.reserve(p.draw_bytes))) return rc;
+        if (p.constrained && (rc = h->mom_c.reserve(p.draw_bytes))) return rc;
+    }
+    const int nab = argmax_blocks(h->M);
+    if ((rc = h->am_val.reserve((size_t)nab * 8))) return rc;
+    if ((rc = h->am_idx.reserve((size_t)nab * 8))) return rc;
+    if ((rc = h->am_out_val.reserve(8))) return rc;
+    return h->am_out_idx.reserve(8);
+}
+
 static int ei_run_impl(spx_handle* h, int32_t flags, bool factor_pending)
 {
     if (!h->held.has(Held::FACTOR) && !factor_pending) return fail(SPX_ERR_ARG, "spx_ei_run: call spx_factor first");
@@ -977,8 +1029,9 @@ static int ei_run_impl(spx_handle* h, int32_t flags, bool factor_pending)
         size_t mem_free = 0, mem_total = 0;
         int64_t b = 2048ll << 20;
         if (hipMemGetInfo(&mem_free, &mem_total) == hipSuccess) {
-            const int64_t have = (int64_t)(mem_free / 8) + (int64_t)(h->part_bgS[0].cap + h->part_bgS[1].cap + h->scratch.cap) / 2;
-            b = std::max<int64_t>(64ll << 20, std::min<int64_t>(b, have));
+            size_t held = h->scratch.cap;
+            for (auto& sl : h->ring) held += sl.part_bgS.cap;
+            b = std::max<int64_t>(64ll << 20, std::min<int64_t>(b, (int64_t)(mem_free / 8) + (int64_t)held / 2));
         } else (void)hipGetLastError();
         h->fant_budget = b;
         h->fant_budget_S = sh.S;
@@ -1003,50 +1056,10 @@ static int ei_run_impl(spx_handle* h, int32_t flags, bool factor_pending)
         p = plan_ei(h->opt, sh);
     }
     const bool per_sec = p.per_sec, keep_mom = p.keep_mom, time_only = p.time_only, constrained = p.constrained, fused = p.fused;
-    const int H = h->H, D = h->D, Dp = p.Dp, Np = h->Np, hs = 3 + D, nrb = p.nrb, Hb = p.Hb, S = h->S, ns = p.ns, R = p.R;
+    const int H = h->H, D = h->D, Dp = p.Dp, Np = h->Np, hs = 3 + D, nrb = p.nrb, Hb = p.Hb, S = h->S, ns = p.ns;
     const int64_t N = h->N, M = h->M, Mp = p.Mp, Mc = p.Mc;
-    if (p.ringed) {
-        if ((rc = ensure_ring(h, R))) return rc;
-        for (int k = 0; k < R; ++k) {
-            if ((rc = h->ring[k].Kst.reserve(p.kst_bytes))) return rc;
-            if (S > 0 && (rc = h->ring[k].part_bgS.reserve(p.bgS_bytes))) return rc;
-        }
-    }
-    if (ns == 3 && !p.ringed && (rc = ensure_ring(h, 0))) return rc;   // (a time-only pass: the producer stream alone)
-    if (p.trim_ring) ring_trim(h, R);
+    if ((rc = ei_reserve(h, p))) return rc;
     h->corun_launches = 0;
-    for (int b = 0; b < 2; ++b) {
-        // scaled candidates (all draws) and predicted durations are double-buffered by chunk parity,
-        // the K(X*,X) staging buffer and the partial sums by stream
-        if ((rc = h->Cs[b].reserve(p.cs_bytes))) return rc;
-        if ((rc = h->s2[b].reserve(p.s2_bytes))) return rc;
-        if (per_sec && (rc = h->time_m[b].reserve(p.s2_bytes))) return rc;
-        if (constrained && (rc = h->con_p[b].reserve(p.s2_bytes))) return rc;
-        if (constrained && h->con_n > 0 && (rc = h->con_Cs[b].reserve(p.cs_bytes))) return rc;
-        if (constrained && h->con_n > 0 && (rc = h->con_s2[b].reserve(p.s2_bytes))) return rc;
-        if (b < p.kst_bufs) {
-            if ((rc = h->Kst[b].reserve(p.kst_bytes))) return rc;
-            if (S > 0 && (rc = h->part_bgS[b].reserve(p.bgS_bytes))) return rc;
-        }
-    }
-    // column sums of beta^2 and beta*gamma per row block for ALL draws of a chunk: written by the
-    // GEMM launches and read by one EI-finalize launch per chunk, all on the consumer stream
-    if (p.gemm_path && (rc = h->part_ss[0].reserve(p.part_bytes))) return rc;
-    if (p.gemm_path && (rc = h->part_bg[0].reserve(p.part_bytes))) return rc;
-    if (S > 0 && (rc = h->scratch.reserve(p.scratch_bytes))) return rc;   // EI per (draw of the group, fantasy, candidate)
-    if ((rc = h->ei_draw.reserve(p.draw_bytes))) return rc;
-    if ((rc = h->ei_mean.reserve(p.mean_bytes))) return rc;
-    if (keep_mom) {
-        if ((rc = h->mom_m.reserve(p.draw_bytes))) return rc;
-        if ((rc = h->mom_v.reserve(p.draw_bytes))) return rc;
-        if (per_sec && (rc = h->mom_t.reserve(p.draw_bytes))) return rc;
-        if (constrained && (rc = h->mom_c.reserve(p.draw_bytes))) return rc;
-    }
-    const int nab = argmax_blocks(M);
-    if ((rc = h->am_val.reserve((size_t)nab * 8))) return rc;
-    if ((rc = h->am_idx.reserve((size_t)nab * 8))) return rc;
-    if ((rc = h->am_out_val.reserve(8))) return rc;
-    if ((rc = h->am_out_idx.reserve(8))) return rc;
 
     hipStream_t s = h->stream;
     if (flags & SPX_FLAG_TIMING) h->opt.timing = true;
@@ -1057,14 +1070,14 @@ static int ei_run_impl(spx_handle* h, int32_t flags, bool factor_pending)
     const double* ls = h->hyp.d() + 3;
     const size_t nn = (size_t)Np * Np;
     // Streams: G (consumer: predict GEMM + EI finalize) and P (producer: candidate scaling and
-    // K(X*,X)).  With one stream P == G and everything is in order.  With two, the K(X*,X)
-    // staging buffer is double-buffered per work item and item i+1 is produced while item i is
-    // consumed (whether the two share a SIMD depends on the kernels' registers: two GEMM waves of 176 VGPRs leave room for
-    // a producer wave of at most 152 -- k_cov_corun, used by streams = 3 only; k_cov_flat at D = 32 takes 184).
-    // events: [0..1] K* of buffer b ready, [2..3] buffer b consumed, [4..5] chunk parity consumed
-    // With three (option streams = 3) P is a stream of the device's lowest priority and the hand-off is the ring: item i
-    // waits for slot i % R to be consumed (item i - R's GEMM), so K(X*,X) runs beside the GEMMs -- and, in a step, beside
-    // the factorisation -- instead of in front of each.  events per slot: K* ready (P -> G), consumed (G -> P).
+    // K(X*,X)): the main stream with one stream, the second with two, with three a stream of the device's lowest priority.
+    // K(X*,X) of item i goes through staging slot i % slots (the plan: one slot, two, or the ring's R), by one rule: the
+    // producer of item i waits for the slot's `consumed` of item i - slots, G waits for the slot's `ready` before the item's
+    // GEMM, and records `consumed` behind the item's last launch where a later item will wait for it.  An event between a
+    // stream and itself is left out, so with P == G everything is in order without any; with more slots the producer runs
+    // that many items ahead, beside the GEMMs and, in a step, beside the factorisation (whether the two share a SIMD depends
+    // on the kernels' registers: two GEMM waves of 176 VGPRs leave room for a producer wave of at most 152 -- k_cov_corun,
+    // used by streams = 3 only; k_cov_flat at D = 32 takes 184).  The chunk-level buffers go by chunk parity the same way.
     hipStream_t G = h->stream, P = (ns == 3) ? h->stream3 : (ns == 2) ? h->stream2 : h->stream;
     // A step (factor_pending): the factorisation is still running on G -- a chain of small launches that leaves most of the
     // chip idle -- and the first producer work of the pass (candidate scaling, K(X*,X) of the first group of draws) depends
@@ -1084,18 +1097,17 @@ static int ei_run_impl(spx_handle* h, int32_t flags, bool factor_pending)
         const int mc = (int)std::min<int64_t>(Mc, Mp - c0);       // multiple of 128
         const int64_t nreal = std::min<int64_t>(mc, M - c0);      // real candidates in the chunk
         const double* xc = h->cand.d() + (size_t)c0 * D;
-        const int par = chunk & 1;
-        double* Cs = h->Cs[par].d();
-        double* s2 = h->s2[par].d();
-        double* tm = per_sec ? h->time_m[par].d() : nullptr;
+        spx_handle::ChunkBufs& cb = h->chunk[chunk & 1];
+        double *Cs = cb.Cs.d(), *s2 = cb.s2.d();
+        double* tm = per_sec ? cb.time_m.d() : nullptr;
         // the chunk-level buffers of this parity were last read (by EI finalize on G) two chunks ago
-        if (ns >= 2 && chunk >= 2) HIPCHK(hipStreamWaitEvent(P, h->ev_sync[4 + par], 0));
+        if (P != G && chunk >= 2) HIPCHK(hipStreamWaitEvent(P, cb.consumed, 0));
         if (per_sec) {
             // log-duration GP: predicted duration of every candidate of the chunk, all draws in one launch
             const bool side = overlap && chunk == 0;         // (a step's first chunk: the objective's scaling runs on P0 meanwhile)
             hipStream_t T = side ? G : P;
-            double* CsT = side ? h->Cs[par ^ 1].d() : Cs;
-            double* s2T = side ? h->s2[par ^ 1].d() : s2;
+            double* CsT = side ? h->chunk[1].Cs.d() : Cs;
+            double* s2T = side ? h->chunk[1].s2.d() : s2;
             TIMED_S(ST_SCALE, T, launch_scale_rows(T, xc, nreal, mc, D, Dp, ls + (size_t)H * hs, hs, H, 2.0, CsT, s2T));
             TIMED_S(ST_CROSS_MEAN, T, launch_cross_mean(T, h->Xs.d() + (size_t)H * Np * Dp, h->s1.d() + (size_t)H * Np, CsT, s2T,
                                                         h->htab.d() + (size_t)H * SPX_HT, h->alpha.d() + (size_t)H * Np, tm,
@@ -1105,16 +1117,16 @@ static int ei_run_impl(spx_handle* h, int32_t flags, bool factor_pending)
                                         (size_t)std::min<int64_t>(mc, Mp - c0) * 8, (size_t)H, hipMemcpyDeviceToDevice, T));
         }
         if (time_only) continue;      // (the predicted durations of the chunk are in mom_t: nothing else was asked for)
-        double* cp = constrained ? h->con_p[par].d() : nullptr;
+        double* cp = constrained ? cb.con_p.d() : nullptr;
         if (constrained) {
             // P_d(x) of the chunk, all draws, on the producer stream ahead of the objective's work there: with one stream P is G,
             // with two the EI epilogues on G wait for K(X*,X) recorded on P after it.  alpha_c was made (and synchronised) by
             // factor_constraint.
             if (h->con_n > 0) {
                 spx_handle* c = h->con;
-                TIMED_S(ST_SCALE, P, launch_scale_rows(P, xc, nreal, mc, D, Dp, c->hyp.d() + 3, hs, H, 2.0, h->con_Cs[par].d(),
-                                                       h->con_s2[par].d()));
-                TIMED_S(ST_CROSS_MEAN, P, launch_constraint_prob(P, c->Xs.d(), c->s1.d(), h->con_Cs[par].d(), h->con_s2[par].d(),
+                TIMED_S(ST_SCALE, P, launch_scale_rows(P, xc, nreal, mc, D, Dp, c->hyp.d() + 3, hs, H, 2.0, cb.con_Cs.d(),
+                                                       cb.con_s2.d()));
+                TIMED_S(ST_CROSS_MEAN, P, launch_constraint_prob(P, c->Xs.d(), c->s1.d(), cb.con_Cs.d(), cb.con_s2.d(),
                                                                  h->con_tab.d(), c->alpha.d(), cp, (int)c->N, c->Np, mc, Dp, H,
                                                                  dev_kind(h)));
             } else {
@@ -1127,10 +1139,7 @@ static int ei_run_impl(spx_handle* h, int32_t flags, bool factor_pending)
         // 2 * cand / ls and |cand / ls|^2 for every draw (one launch per chunk)
         hipStream_t Pc = (chunk == 0) ? P0 : P;       // (the first chunk's producer work of a step: beside the factorisation)
         TIMED_S(ST_SCALE, Pc, launch_scale_rows(Pc, xc, nreal, mc, D, Dp, ls, hs, H, 2.0, Cs, s2));
-        if (fused && Pc != G) {
-            HIPCHK(hipEventRecord(h->ev_p0, Pc));
-            HIPCHK(hipStreamWaitEvent(G, h->ev_p0, 0));
-        }
+        if (fused && (rc = hand_off(Pc, G, h->ev_p0))) return rc;
         if (fused)
             TIMED_S(ST_PREDICT_GEMM, G, launch_ei_fused128(G, dev_kind(h), h->WT.d(), h->gamma.d(), h->Xs.d(), h->s1.d(), Cs, s2,
                                                            h->htab.d(), tm, cp, h->best, h->ei_draw.d(), keep_mom ? h->mom_m.d() : nullptr,
@@ -1138,56 +1147,42 @@ static int ei_run_impl(spx_handle* h, int32_t flags, bool factor_pending)
                                                            h->acq, h->acq_par));
         for (int h0 = 0; h0 < (fused ? 0 : H); h0 += Hb, ++item) {
             const int nhb = std::min(Hb, H - h0);
-            const int k = (ns == 3) ? item % R : (ns == 2) ? (item & 1) : 0;
-            if (ns == 2 && item >= 2) HIPCHK(hipStreamWaitEvent(P, h->ev_sync[2 + k], 0));   // buffer k consumed
-            if (ns == 3 && item >= R) HIPCHK(hipStreamWaitEvent(P, h->ring[k].consumed, 0)); // slot k consumed (item - R)
+            spx_handle::RingSlot& sl = h->ring[item % p.slots];
+            if (P != G && item >= p.slots) HIPCHK(hipStreamWaitEvent(P, sl.consumed, 0));   // (by item - slots)
             hipStream_t Pi = (item == 0) ? Pc : P;
-            double* Kst_k = (ns == 3) ? h->ring[k].Kst.d() : h->Kst[k].d();
-            double* bgS_k = S > 0 ? ((ns == 3) ? h->ring[k].part_bgS.d() : h->part_bgS[k].d()) : nullptr;
+            double *Kst_k = sl.Kst.d(), *bgS_k = S > 0 ? sl.part_bgS.d() : nullptr;
             const bool corun = p.corun && item > 0;
             h->corun_launches += corun ? 1 : 0;
             TIMED_S(ST_COV_CROSS, Pi, launch_cov_cross(Pi, h->Xs.d() + (size_t)h0 * Np * Dp, h->s1.d() + (size_t)h0 * Np,
                                                       Cs + (size_t)h0 * mc * Dp, s2 + (size_t)h0 * mc,
                                                       h->htab.d() + (size_t)h0 * SPX_HT, Kst_k, (int)N, Np, mc, Dp, nhb, dev_kind(h),
                                                       p.cov_live_rows, p.cov_flat, corun));
-            if (ns == 3) {
-                HIPCHK(hipEventRecord(h->ring[k].ready, P));
-                HIPCHK(hipStreamWaitEvent(G, h->ring[k].ready, 0));
-            } else if (ns == 2) {
-                HIPCHK(hipEventRecord(h->ev_sync[k], P));
-                HIPCHK(hipStreamWaitEvent(G, h->ev_sync[k], 0));
-            } else if (Pi != G) {
-                HIPCHK(hipEventRecord(h->ev_p0, Pi));
-                HIPCHK(hipStreamWaitEvent(G, h->ev_p0, 0));
-            }
+            if ((rc = hand_off(Pi, G, sl.ready))) return rc;
             // with fantasies the launch's partial sums are consumed right away and sit at draws 0 .. nhb-1
             TIMED_S(ST_PREDICT_GEMM, G, launch_predict_gemm(G, h->opt.gemm_variant, h->WT.d() + (size_t)h0 * nn, Kst_k,
-                                                            h->gamma.d() + (size_t)h0 * Np, h->part_ss[0].d(),
-                                                            h->part_bg[0].d(), Np, mc, nhb, S > 0 ? nhb : H, S > 0 ? 0 : h0,
+                                                            h->gamma.d() + (size_t)h0 * Np, h->part_ss.d(),
+                                                            h->part_bg.d(), Np, mc, nhb, S > 0 ? nhb : H, S > 0 ? 0 : h0,
                                                             S > 0 ? h->gammaS.d() + (size_t)h0 * S * Np : nullptr, S,
                                                             bgS_k, gemm_nlive));
             if (S > 0)
-                TIMED_S(ST_EI_FINALIZE, G, launch_ei_finalize_fant(G, h->part_ss[0].d(), bgS_k,
+                TIMED_S(ST_EI_FINALIZE, G, launch_ei_finalize_fant(G, h->part_ss.d(), bgS_k,
                                                                    h->htab.d() + (size_t)h0 * SPX_HT,
                                                                    h->bests.d() + (size_t)h0 * S,
                                                                    per_sec ? tm + (size_t)h0 * mc : nullptr,
                                                                    constrained ? cp + (size_t)h0 * mc : nullptr,
                                                                    h->ei_draw.d(), nrb, mc, nhb, S, c0, M, Mp, h0,
                                                                    h->scratch.d(), h->acq, h->acq_par));
-            if (ns == 2) HIPCHK(hipEventRecord(h->ev_sync[2 + k], G));
-            if (ns == 3 && (int64_t)item + R < p.ring_items) HIPCHK(hipEventRecord(h->ring[k].consumed, G));   // (only where an item waits for it)
+            if (P != G && (int64_t)item + p.slots < p.ring_items) HIPCHK(hipEventRecord(sl.consumed, G));   // (only where an item waits for it)
         }
         if (S == 0 && !fused)   // every draw of the chunk in one launch
-            TIMED_S(ST_EI_FINALIZE, G, launch_ei_finalize(G, h->part_ss[0].d(), h->part_bg[0].d(), h->htab.d(), tm, cp, h->best,
+            TIMED_S(ST_EI_FINALIZE, G, launch_ei_finalize(G, h->part_ss.d(), h->part_bg.d(), h->htab.d(), tm, cp, h->best,
                                                           h->ei_draw.d(), keep_mom ? h->mom_m.d() : nullptr,
                                                           keep_mom ? h->mom_v.d() : nullptr, nrb, mc, H, c0, M, Mp, 0, h->acq,
                                                           h->acq_par));
-        if (ns >= 2) HIPCHK(hipEventRecord(h->ev_sync[4 + par], G));
+        if (P != G) HIPCHK(hipEventRecord(cb.consumed, G));
     }
-    if (ns >= 2 && (per_sec || constrained) && keep_mom) {   // the duration / probability copies ran on P
-        HIPCHK(hipEventRecord(h->ev_sync[0], P));
-        HIPCHK(hipStreamWaitEvent(G, h->ev_sync[0], 0));
-    }
+    // the duration / probability copies ran on P
+    if ((per_sec || constrained) && keep_mom && (rc = hand_off(P, G, h->ev_p0))) return rc;
     // the winner (and, in a step, the factorisation's flags) go home through pinned memory with the last kernel's own stores
     const int n_info = p.n_info;
     if ((rc = h->pin_res.reserve(16 + (size_t)n_info * sizeof(int)))) return rc;

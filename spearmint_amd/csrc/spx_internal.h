@@ -108,18 +108,20 @@ struct spx_handle {
     hipStream_t stream = nullptr;    // main stream (also the only one the factorization uses)
     hipStream_t stream2 = nullptr;   // optional producer stream (option "streams" = 2): K(X*,X) of the next
                                      // work item is generated (VALU) while the GEMM of the current one runs (MFMA)
-    hipEvent_t ev_sync[6] = {nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};
-    // option "streams" = 3: K(X*,X) runs AHEAD of the predict GEMM on a low-priority stream of its own, through a ring of
-    // staging slots (ei_run_impl); the stream, the slots and their events are made on the first such pass
-    hipStream_t stream3 = nullptr;
+    hipStream_t stream3 = nullptr;   // option "streams" = 3: K(X*,X) runs AHEAD of the predict GEMM on a low-priority stream, made on the first such pass
+    // the staging slots of an EI pass under every stream count (ei_run_impl): K(X*,X) of a work item with its fantasy
+    // partials, and the two events of the slot's hand-off; made as passes ask for them
     struct RingSlot { DevBuf Kst, part_bgS; hipEvent_t ready = nullptr, consumed = nullptr; };
     std::vector<RingSlot> ring;
+    // a pass's buffers per candidate chunk, by chunk parity: scaled candidates and norms (objective / constraint model),
+    // predicted durations, P(feasible); `consumed`: the chunk's last reader is queued on the main stream
+    struct ChunkBufs { DevBuf Cs, s2, time_m, con_Cs, con_s2, con_p; hipEvent_t consumed = nullptr; } chunk[2];
     int64_t ring_budget = 0;            // bytes the ring may take (a share of free device memory) ...
     int64_t ring_budget_slot = -1;      // ... as found when the size of a slot last changed
     int corun_launches = 0;             // K(X*,X) launches of the last pass that took k_cov_corun (spx_get_stat "last_corun_launches")
     hipEvent_t ev_t0 = nullptr, ev_t1 = nullptr;   // whole-stage timers (factor / ei_run)
     hipEvent_t ev_fac = nullptr;                   // spx_ei_step: the whole factorisation (alpha included) is done (stream)
-    hipEvent_t ev_obs = nullptr, ev_p0 = nullptr;  // spx_ei_step: observations scaled (stream) / first K(X*,X) ready (stream2)
+    hipEvent_t ev_obs = nullptr, ev_p0 = nullptr;  // spx_ei_step: observations scaled (stream) / a pass's producer work outside the slots done
 
     int64_t N = 0, M = 0, index_base = 0;
     int D = 0, Dp = 0, Np = 0, H = 0;
@@ -143,11 +145,11 @@ struct spx_handle {
 
     DevBuf comp, vals, ldur, cand, hyp, htab;
     DevBuf Xs, X2s, s1, Lm, WT, Dinv, gamma, alpha, info, lp;
-    DevBuf Cs[2], s2[2], Kst[2], part_ss[2], part_bg[2], time_m[2], ei_draw, ei_mean, mom_m, mom_v, mom_t;
+    DevBuf part_ss, part_bg, ei_draw, ei_mean, mom_m, mom_v, mom_t;
     DevBuf am_val, am_idx, am_out_val, am_out_idx, scratch;
     // pending-experiment fantasies (spx_set_fantasies): S right-hand sides per draw; S > 0 exactly when FANT is held
     int S = 0;
-    DevBuf fantT, gammaS, bests, part_bgS[2];
+    DevBuf fantT, gammaS, bests;
     DevBuf alphaS;                 // [H][S][Np] = W^T Gamma_s, built on the first spx_ei_grad_batch after spx_set_fantasies (ALPHA_S)
     // spx_draw_fantasies: the resident fantasies were formed on the device from P trailing pending rows
     bool fant_device = false;
@@ -170,7 +172,7 @@ struct spx_handle {
     spx_handle* con = nullptr;
     int64_t con_n = 0;                                              // Nc (0: all valid, P_d = Phi(gain_d))
     std::vector<double> con_tab_host;                               // [H][SPX_HT]: gain, noise_c, amp2_c, amp2_c
-    DevBuf con_tab, con_Cs[2], con_s2[2], con_p[2], mom_c;
+    DevBuf con_tab, mom_c;
     // spx_constrained_ei_grad_batch: the objective's hypers over the constraint model's points X_c (the variance of the
     // reference's no-pending refinement objective, GPConstrainedEIChooser.py:692-803) -- a third internal handle, factored
     // on the first call and kept until observations, hypers, the constraint points or option "covar" change

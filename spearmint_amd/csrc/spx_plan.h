@@ -201,12 +201,13 @@ struct EiPlan {
     bool gemm_path = false;         // K(X*,X) -> predict GEMM -> EI finalize
     bool timing_on = false;
     int ns = 1;                     // streams the pass runs on
-    int kst_bufs = 0;               // staging buffers of the handle itself (streams <= 2)
-    bool ringed = false;
-    int64_t slot_bytes = 0;         // one ring slot: K(X*,X) of a work item and its fantasy partials
+    int64_t ring_items = 0;         // work items of the pass (chunks x draw groups; the GEMM path, ringed or not)
+    int slots = 0;                  // staging slots the pass uses: item i goes through slot i % slots (0: it stages nothing)
+    int kst_bufs = 0;               // `slots` of a pass that is not ringed: read by nothing here, printed for the plan clients of earlier trees
+    bool ringed = false;            // streams = 3: the slots are a ring of R, sized by a byte budget
+    int64_t slot_bytes = 0;         // one slot of that ring: K(X*,X) of a work item and its fantasy partials
     int R = 0;
-    int64_t ring_items = 0;
-    bool trim_ring = false;         // ring slots beyond R go back to the device
+    bool trim_ring = false;         // slots beyond `slots` go back to the device
     bool overlap = false;           // a step's first producer work runs beside the factorisation
     bool cov_flat = false, corun = false;   // K(X*,X) launches: equal shares / (behind the pass's first) the co-resident form
     int gemm_nlive = 0, cov_live_rows = 0;
@@ -278,24 +279,26 @@ inline EiPlan plan_ei(const Options& o, const EiShape& s)
     // stage's kernels alone (the stage table, bench.py --full's roofline)
     p.timing_on = o.timing || (s.flags & SPX_FLAG_TIMING);
     p.ns = p.fused ? 1 : ((o.nstreams == 3 && p.timing_on) ? 1 : o.nstreams);
-    p.kst_bufs = (p.ns <= 2 && p.gemm_path) ? p.ns : 0;
-    // streams = 3: K(X*,X) of work item i goes to slot i % R of a ring of staging buffers (each with its own fantasy
-    // partials), so the producer stream runs up to R items ahead of the GEMM.  R comes from a byte budget -- a sixteenth of
-    // what the device has free, at most 10 GiB (C3: one chunk's twenty draws, 9.4 GB of 288) -- or from option "kstar_ring";
-    // never more slots than the pass has items.
+    // K(X*,X) of work item i goes to staging slot i % slots (each slot with its own fantasy partials): one slot on one
+    // stream, two on two, and with streams = 3 a ring of R, so that the producer stream runs up to R items ahead of the GEMM.
+    // R comes from a byte budget -- a sixteenth of what the device has free, at most 10 GiB (C3: one chunk's twenty draws,
+    // 9.4 GB of 288) -- or from option "kstar_ring"; never more slots than the pass has items.
     p.ringed = p.ns == 3 && !p.time_only;
     p.kst_bytes = (size_t)p.Hb * Np * Mc * 8;
     p.bgS_bytes = S > 0 ? (size_t)nrb * 2 * p.Hb * S * Mc * 8 : 0;
+    if (p.gemm_path) p.ring_items = ((Mp + Mc - 1) / Mc) * ((H + p.Hb - 1) / p.Hb);
     if (p.ringed) {
         p.slot_bytes = (int64_t)(p.kst_bytes + p.bgS_bytes);
-        p.ring_items = ((Mp + Mc - 1) / Mc) * ((H + p.Hb - 1) / p.Hb);
         int64_t r = o.ring_opt > 0 ? o.ring_opt : s.ring_budget / p.slot_bytes;
         r = std::max<int64_t>(1, std::min<int64_t>(std::min<int64_t>(r, p.ring_items), 4096));
         p.R = (int)r;
     }
-    // slots the pass does not use go back to the device -- but a streams = 3 handle that runs ONE pass another way (per-launch
-    // timing, the fused path, time only) keeps its ring: the next pass would only allocate the same gigabytes again
-    p.trim_ring = p.ringed || o.nstreams != 3;
+    p.slots = !p.gemm_path ? 0 : p.ringed ? p.R : p.ns;
+    p.kst_bufs = p.ringed ? 0 : p.slots;
+    // slots the pass does not use go back to the device.  A pass that stages nothing releases nothing (a chooser whose
+    // proposal pass is staged and whose recommendation pass is fused keeps its staging buffer), and a streams = 3 handle that
+    // runs ONE pass another way (per-launch timing) keeps its ring: the next pass would only allocate the same gigabytes again
+    p.trim_ring = p.gemm_path && (p.ringed || o.nstreams != 3);
     // A step (factor_pending): the factorisation is still running on the main stream -- a chain of small launches that leaves
     // most of the chip idle -- and the first producer work of the pass (candidate scaling, K(X*,X) of the first group of
     // draws) depends only on what the factorisation's FIRST kernel wrote.  It goes to the second stream, beside the

@@ -76,7 +76,7 @@ int main()
             const EiPlan p = plan_ei(o, s);
             printf("{");
             J(per_sec); J(keep_mom); J(time_only); J(constrained); J(Mp); J(Mc); J(Hb); J(nrb); J(Dp); J(fused); J(gemm_path);
-            J(timing_on); J(ns); J(kst_bufs); J(ringed); J(slot_bytes); J(R); J(ring_items); J(trim_ring); J(overlap);
+            J(timing_on); J(ns); J(kst_bufs); J(slots); J(ringed); J(slot_bytes); J(R); J(ring_items); J(trim_ring); J(overlap);
             J(cov_flat); J(corun); J(gemm_nlive); J(cov_live_rows); J(n_info); J(cs_bytes); J(s2_bytes); J(kst_bytes);
             J(bgS_bytes); J(part_bytes); J(scratch_bytes); J(draw_bytes); J(mean_bytes);
             printf("\"kind\": \"ei\"}\n");

@@ -182,6 +182,28 @@ def test_ring_step_waits_for_the_pending_factorisation(one, ring):
             _same(got, want, (rep, kind))
 
 
+def test_one_handle_through_every_stream_count(one):
+    """The staging slots and their events are one set for every stream count: a handle that goes 1 -> 2 -> 3 -> 2 -> 1 -> 3
+    -> 1 streams (ring depths from the budget, 2 and 64) runs each pass on what the pass before left behind, with two
+    problems whose slots differ in size (Np = 256 and 512; with fantasies a slot carries partial means too)."""
+    probs = [_problem(130, 4999, 8100), _problem(390, 4999, 8101)]
+    runs = (("plain", False), ("fantasies", False), ("plain", True))
+    want = [[_run(one, p, kind, step) for kind, step in runs] for p in probs]
+    e = Engine(0)
+    try:
+        e.set_option("kstar_budget_bytes", BUDGET)
+        for i, (streams, depth) in enumerate(((1, 0), (2, 0), (3, 0), (3, 2), (2, 0), (1, 0), (3, 64), (1, 0))):
+            e.set_option("streams", streams)
+            e.set_option("kstar_ring", depth)
+            for j, (kind, step) in enumerate(runs):
+                got = _run(e, probs[i % 2], kind, step)
+                used = e.stat("last_kstar_ring")
+                assert used >= 1 if streams == 3 else used == 0, (i, streams, depth, kind, used)
+                _same(got, want[i % 2][j], (i, streams, depth, kind, step))
+    finally:
+        e.close()
+
+
 def test_fused_path_is_untouched(one, ring):
     p = _problem(100, 4999, 55)
     want = _run(one, p, "plain")

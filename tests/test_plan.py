@@ -163,10 +163,10 @@ def test_ei_pass_small_n_is_fused():
     # per launch 2^29 / (8 * 128 * 20 096) = 26 -> capped at H = 10.  Np == 128, no fantasies -> k_ei_fused128, one stream
     p = ei(128, 20000, 10)
     assert (p["Mp"], p["Mc"], p["Hb"], p["nrb"]) == (20096, 20096, 10, 1)
-    assert (p["fused"], p["ns"], p["gemm_path"], p["kst_bufs"]) == (1, 1, 0, 0)
+    assert (p["fused"], p["ns"], p["gemm_path"], p["slots"], p["ring_items"]) == (1, 1, 0, 0, 0)
     assert ei(128, 20000, 10, streams=2)["ns"] == 1                     # (the fused path never uses more than one stream)
     p = ei(128, 20000, 10, ei_fused=0)
-    assert (p["fused"], p["gemm_path"], p["kst_bufs"]) == (0, 1, 1)
+    assert (p["fused"], p["gemm_path"], p["slots"], p["ring_items"]) == (0, 1, 1, 1)
     assert ei(128, 20000, 10, S=2, fant_budget=1 << 31)["fused"] == 0   # fantasies: the three-stage path
 
 
@@ -176,8 +176,19 @@ def test_ei_pass_chunks():
     # number of tiles per XCD would be 1024 > budget, and 512 < 16 tiles: unchanged); 2^20 / (8 * 256 * 512) = 1 draw
     p = ei(130, 1000, 3, kstar_budget_bytes=1 << 20)
     assert (p["Mp"], p["Mc"], p["Hb"], p["nrb"], p["ns"], p["ringed"], p["R"]) == (1024, 512, 1, 2, 1, 0, 0)
-    assert p["kst_bytes"] == 1 << 20 and p["kst_bufs"] == 1
-    assert ei(130, 1000, 3, kstar_budget_bytes=1 << 20, streams=2)["kst_bufs"] == 2
+    assert p["kst_bytes"] == 1 << 20 and (p["slots"], p["kst_bufs"]) == (1, 1)
+    p2 = ei(130, 1000, 3, kstar_budget_bytes=1 << 20, streams=2)
+    assert (p2["slots"], p2["kst_bufs"]) == (2, 2)                      # (kst_bufs: slots of a pass that is not ringed)
+    # items = 2 chunks x 3 draw groups under every stream count
+    for streams in (1, 2, 3):
+        assert ei(130, 1000, 3, kstar_budget_bytes=1 << 20, streams=streams, ring_budget=10 << 30)["ring_items"] == 6
+    # slots the pass does not use are given back by a pass that stages -- not by a fused or a time-only one (slots = 0:
+    # they would free the staging buffer of the passes around them)
+    for streams in (1, 2):
+        assert ei(130, 1000, 3, kstar_budget_bytes=1 << 20, streams=streams)["trim_ring"] == 1
+        assert (ei(128, 1000, 3, streams=streams)["fused"], ei(128, 1000, 3, streams=streams)["trim_ring"]) == (1, 0)
+        p = ei(130, 1000, 3, streams=streams, nmodels=2, flags=PER_SEC | KEEP_MOMENTS | TIME_ONLY)
+        assert (p["ns"], p["slots"], p["ring_items"], p["trim_ring"]) == (streams, 0, 0, 0)
 
 
 @needs_cxx
@@ -186,14 +197,18 @@ def test_ei_pass_ring():
     # one slot = Hb Np Mc 8 = 1 MiB; items = 2 chunks x 3 draw groups = 6; R = min(budget / slot, items) in [1, 4096]
     for budget, R in ((0, 1), ((7 << 20) // 2, 3), (6 << 20, 6), (10 << 30, 6)):
         p = ei(130, 1000, 3, ring_budget=budget, **base)
-        assert (p["ns"], p["ringed"], p["slot_bytes"], p["ring_items"], p["R"], p["kst_bufs"]) == (3, 1, 1 << 20, 6, R, 0)
+        assert (p["ns"], p["ringed"], p["slot_bytes"], p["ring_items"], p["R"], p["slots"], p["trim_ring"]) == (3, 1, 1 << 20, 6, R, R, 1)
+        assert p["kst_bufs"] == 0
     assert ei(130, 1000, 3, ring_budget=10 << 30, kstar_ring=2, **base)["R"] == 2
     assert ei(130, 1000, 3, ring_budget=0, kstar_ring=9, **base)["R"] == 6          # never more slots than items
     for kw in (dict(timing=1), dict(flags=TIMING)):                     # per-launch events: in order on one stream
         p = ei(130, 1000, 3, ring_budget=10 << 30, **dict(base, **kw))
         assert (p["ns"], p["ringed"], p["R"], p["trim_ring"], p["timing_on"]) == (1, 0, 0, 0, 1)
+        assert (p["slots"], p["ring_items"]) == (1, 6)                       # one slot of the ring it keeps
     p = ei(130, 1000, 3, ring_budget=10 << 30, nmodels=2, flags=PER_SEC | KEEP_MOMENTS | TIME_ONLY, **base)
     assert (p["ns"], p["ringed"], p["R"], p["gemm_path"], p["time_only"]) == (3, 0, 0, 0, 1)
+    assert (p["slots"], p["ring_items"], p["trim_ring"]) == (0, 0, 0)
+    assert ei(128, 1000, 3, ring_budget=10 << 30, **base)["trim_ring"] == 0         # fused on a streams = 3 handle: the ring stays
     assert ei(130, 1000, 3, ring_budget=10 << 30, **base)["corun"] == 1
     assert ei(130, 1000, 3, ring_budget=10 << 30, kstar_corun=0, **base)["corun"] == 0
     assert ei(130, 1000, 3, ring_budget=10 << 30, cov_flat=0, **base)["corun"] == 0
