@@ -273,6 +273,51 @@ int spx_get_acquisition(spx_handle* h, int32_t* kind, double* par);   /* either 
  * pointer may be NULL.                                                                                                    */
 int spx_get_mes(spx_handle* h, int32_t draw, double* ystar /* K */, double* fit /* 8 */, double* G /* J */);
 
+/* ---- two objectives: expected hypervolume improvement (SPX_ACQ_EHVI) -----------------------------------------------------
+ * Both objectives are minimised.  The first is the handle's own GP; the SECOND objective's GP is the model that
+ * spx_set_time_model holds: its `log_durs` argument is "the second objective's values" of the resident rows (the chooser passes
+ * log durations; the engine takes any vector) and `time_hypers` its draws.  The two predictions are taken as independent
+ * Gaussians per draw d: (m1, v1) = func_m / func_v of the objective, (m2, v2) = func_m / func_v of the second GP -- its FULL
+ * predictive moments, the ones a separate plain handle given (comp, second values, second hypers) and the same candidates
+ * returns from spx_ei_run(SPX_FLAG_KEEP_MOMENTS) + spx_get_moments(d), bit for bit.
+ * The front (spx_set_pareto_front): n mutually non-dominated points with a_1 < ... < a_n (first objective) and
+ * b_1 > ... > b_n (second), and a reference point (r1, r2) with a_n < r1 and b_1 < r2.  With a_0 = -inf, a_{n+1} = r1, b_0 = r2
+ * a new point (u, v) adds the area  I(u, v) = sum_{i=0..n} (a_{i+1} - max(u, a_i))+ (b_i - v)+,  and because
+ * (A - max(u, a))+ = (A - u)+ - (a - u)+ for a <= A its expectation is
+ *     EHVI = sum_{i=0..n} [G1(a_{i+1}) - G1(a_i)] G2(b_i),    G_k(y) = E[(y - f_k)+] = EI of (m_k, v_k) with best = y,
+ *     G1(a_0) := +0.0
+ * evaluated per (draw, candidate) sequentially in i = 0 .. n, every G1(a_i) once, every strip evaluated, nothing contracted
+ * into a fused multiply-add; G is the EI formula of every pass itself, so v1 < 0 or v2 < 0 gives NaN.  n = 0: G1(r1) G2(r2).
+ * spx_set_acquisition(h, SPX_ACQ_EHVI, 0) (a non-zero parameter is SPX_ERR_ARG).  With it set, spx_ei_run / spx_ei_step /
+ * spx_ei_grid / spx_ei_per_sec_grid (which pass the second values on; their SPX_FLAG_PER_SEC is left out under EHVI) run
+ *   1  the second GP's factorisation (when what it was made from changed) and its pass over the same candidates, on an internal
+ *      handle of the same device with the caller's options, which takes the resident rows and candidates by device-to-device
+ *      copies and synchronises on its own, as the constraint model's factorisation does, before anything else is queued;
+ *   2  the ordinary pass over the objective as EI with the moments kept (SPX_FLAG_KEEP_MOMENTS is implied);
+ *   3  the EHVI kernel over (draw, candidate) into the per-draw values, behind the pass on the same stream (with option
+ *      "timing": stage "ehvi");
+ *   4  the numpy-order mean over the draws, the argmax rule and the result getters of every pass.
+ * Afterwards spx_get_moments(h, d, ...) serves the objective's moments for d < H and the second GP's for draw H + d.
+ * Under EHVI spx_factor / spx_ei_step factor the objective's covariance alone (the time model is not factored a second time
+ * inside the handle: a factorisation made under EHVI serves no per-second pass, and one made under another acquisition is
+ * made again by the next step).  A covariance of the second GP that is not positive definite is SPX_ERR_NOT_PD with
+ * spx_not_pd_info reporting draw 5H + d.  Which report comes first when both GPs fail: spx_ei_step runs the second GP before
+ * the objective's factorisation, so 5H + d; spx_factor + spx_ei_run (and a step with option "timing") factor the objective
+ * first, so d.
+ * The front is a setting of the handle, as the acquisition is: it stays until replaced or cleared, and setting or clearing it
+ * takes away the results of the last pass and nothing else.
+ * REFUSED with SPX_ERR_ARG before any device is touched, the handle as it was: EHVI without a time model or without a front;
+ * with SPX_FLAG_PER_SEC (spx_ei_run / spx_ei_step), SPX_FLAG_CONSTRAINED or SPX_FLAG_TIME_ONLY; with fantasies held; on a
+ * multi-device handle, with a communicator attached or with a 2-D partition; spx_ei_grad_batch / spx_ei_grad /
+ * spx_constrained_ei_grad_batch under EHVI (refinement needs the second GP's variance gradient: out of scope).
+ * spx_set_pareto_front: n in 0 .. SPX_MAX_FRONT (a / b may be NULL when n = 0); n < 0 clears the front.  SPX_ERR_ARG, the
+ * handle as it was: a non-finite number, a not strictly increasing, b not strictly decreasing, a_n >= r1 or b_1 >= r2, n out
+ * of range.  spx_get_pareto_front: *n = -1 when no front is set; a / b receive n doubles each; any pointer may be NULL.   */
+#define SPX_ACQ_EHVI 4
+#define SPX_MAX_FRONT 4096
+int spx_set_pareto_front(spx_handle* h, const double* a, const double* b, int32_t n, double r1, double r2);
+int spx_get_pareto_front(spx_handle* h, double* a, double* b, int32_t* n, double* r1, double* r2);
+
 /* Hot path, stage 2: K(X*,X) (:187), triangular solve (:195), predictive
  * mean/variance (:198-199), EI (:202-206) for every (candidate, draw); then the
  * MCMC mean and the argmax (:153).  Results stay on the device.               */

@@ -187,6 +187,35 @@ class GPEIperSecChooser(GPEIBase):
             out[i, :] = spo.fmin_l_bfgs_b(objective, out[i, :].flatten(), bounds=bounds, disp=0)[0]
         return out
 
+    # -- what every call does before it scores anything: shared with GPParetoChooser, so that both consume numpy's generator
+    # alike and sample the same hyper chains from one seed -----------------------------------------------------------
+    @staticmethod
+    def _spray(comp, vals):
+        """The ten points sprayed around the incumbent for the refinement (:202): the call's first use of the generator."""
+        best_comp = np.argmin(vals)
+        return np.random.randn(10, comp.shape[1]) * 0.001 + comp[best_comp, :]
+
+    def _sample_call(self, comp, vals, durs):
+        """Burn-in on the first call, then mcmc_iters samples of both GPs into hyper_samples / time_hyper_samples (:208-223)."""
+        if self.mcmc_iters <= 0:
+            raise NotImplementedError("mcmc_iters=0: the reference's own branch (GPEIperSecChooser.py:243-281) cannot run -- it reads "
+                                      "overall_ei before assigning it (UnboundLocalError); use mcmc_iters >= 1")
+        if self.needs_burnin:
+            for it in range(self.burnin):
+                self.sample_hypers(comp, vals, durs)
+                self._log_hypers("BURN %d/%d] " % (it + 1, self.burnin))
+            self.needs_burnin = False
+        self.hyper_samples = []
+        if not self.ref_compat:
+            self.time_hyper_samples = []
+        for it in range(self.mcmc_iters):
+            self.sample_hypers(comp, vals, durs)
+            self._log_hypers("%d/%d] " % (it + 1, self.mcmc_iters))
+            log("%d/%d] time_mean: %.2fs time_amp: %.2f  time_noise: %.4f time_min_ls: %.4f  time_max_ls: %.4f"
+                % (it + 1, self.mcmc_iters, np.exp(self.time_mean), np.sqrt(self.time_amp2),
+                   np.exp(self.time_noise), np.min(self.time_ls), np.max(self.time_ls)))
+        self.dump_hypers()
+
     # -- plugin entry (:155-281) -------------------------------------------------------
     def next(self, grid, values, durations, candidates, pending, complete):
         if complete.shape[0] < 2:
@@ -198,29 +227,8 @@ class GPEIperSecChooser(GPEIBase):
         comp, cand, pend, vals = self._split(grid, values, candidates, pending, complete)
         durs = np.log(durations[complete]).squeeze()   # log domain keeps times positive (:174-176)
         numcand = cand.shape[0]
-        best_comp = np.argmin(vals)
-        cand2 = np.vstack((np.random.randn(10, comp.shape[1]) * 0.001 + comp[best_comp, :], cand))
-
-        if self.mcmc_iters <= 0:
-            raise NotImplementedError("mcmc_iters=0: the reference's own branch (GPEIperSecChooser.py:243-281) cannot run -- it reads "
-                                      "overall_ei before assigning it (UnboundLocalError); use mcmc_iters >= 1")
-
-        if self.needs_burnin:
-            for it in range(self.burnin):
-                self.sample_hypers(comp, vals, durs)
-                self._log_hypers("BURN %d/%d] " % (it + 1, self.burnin))
-            self.needs_burnin = False
-
-        self.hyper_samples = []
-        if not self.ref_compat:
-            self.time_hyper_samples = []
-        for it in range(self.mcmc_iters):
-            self.sample_hypers(comp, vals, durs)
-            self._log_hypers("%d/%d] " % (it + 1, self.mcmc_iters))
-            log("%d/%d] time_mean: %.2fs time_amp: %.2f  time_noise: %.4f time_min_ls: %.4f  time_max_ls: %.4f"
-                % (it + 1, self.mcmc_iters, np.exp(self.time_mean), np.sqrt(self.time_amp2),
-                   np.exp(self.time_noise), np.min(self.time_ls), np.max(self.time_ls)))
-        self.dump_hypers()
+        cand2 = np.vstack((self._spray(comp, vals), cand))
+        self._sample_call(comp, vals, durs)
 
         _, mean1 = self.ei_per_s_over_hypers_gpu(comp, pend, cand2, vals, durs)
         keep = np.argsort(mean1)[-self.grid_subset:]

@@ -25,6 +25,7 @@ typedef double d2 __attribute__((ext_vector_type(2)));
 #define SPX_ACQ_DEV_EI 0
 #define SPX_ACQ_DEV_PI 1
 #define SPX_ACQ_DEV_LCB 2
+#define SPX_ACQ_DEV_EHVI 4  // expected hypervolume improvement over two GPs: likewise a stage behind the pass (ehvi_kernels.hip)
 #define SPX_ACQ_DEV_MES 3   // max-value entropy search: a second stage behind the pass (mes_kernels.hip), never a template argument of the pass's own kernels
 
 // The launchers below return nothing: a kernel that needs more dynamic LDS than the default asks for it right before its
@@ -179,6 +180,11 @@ int mes_bound_blocks(int64_t M);
 void launch_mes(hipStream_t s, const double* mom_m, const double* mom_v, const double* hyp, int hs, double best, int64_t M,
                 int64_t Mp, int H, int J, int K, double* bpart, double* part, double* G, double* ystar, double* fit,
                 double* ei_draw);
+
+// ehvi_kernels.hip: expected hypervolume improvement of every (draw, candidate) from the kept moments of the two GPs ([H][Mp]
+// each) against the front in k_ehvi's form (edges: a_1 .. a_n, r1; levels: r2, b_1 .. b_n; nstrips = n + 1), into ei_draw
+void launch_ehvi(hipStream_t s, const double* m1, const double* v1, const double* m2, const double* v2, const double* edges,
+                 const double* levels, int nstrips, int64_t M, int64_t Mp, int H, double* ei_draw);
 
 // predict_kernels.hip
 void launch_predict_gemm(hipStream_t s, int variant, const double* WT, const double* Kst, const double* gamma,

@@ -1,7 +1,9 @@
 // EI from the predictive moments: shared by k_ei_finalize / k_ei_finalize_fant (predict_kernels.hip) and the fused small-N
 // kernel (fused_kernels.hip) -- one source, the same bits.
 #pragma once
+#ifndef SPX_EHVI_HOST   // (ehvi_device.h compiled for the host supplies what this text needs of common.h itself)
 #include "common.h"
+#endif
 
 // ---------------------------------------------------------------------------
 // EI from the partial sums.  Phi follows scipy.special.ndtr (cephes): erf for

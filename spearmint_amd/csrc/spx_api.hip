@@ -17,7 +17,7 @@
 
 static const char* kStageNames[ST_COUNT] = {
     "scale_rows", "cov_self", "chol_diag", "chol_panel", "trinv", "gamma_alpha",
-    "cov_cross", "cross_mean", "predict_gemm", "ei_finalize", "mean_argmax", "mes",
+    "cov_cross", "cross_mean", "predict_gemm", "ei_finalize", "mean_argmax", "mes", "ehvi",
     "factor_total", "ei_run_total"};
 
 
@@ -287,6 +287,7 @@ void spx_destroy(spx_handle* h)
     spx_comm_release(h);
     if (h->con) { spx_destroy(h->con); h->con = nullptr; }
     if (h->full) { spx_destroy(h->full); h->full = nullptr; }
+    if (h->sec) { spx_destroy(h->sec); h->sec = nullptr; }
     if (h->inited) {
         (void)hipSetDevice(h->device);
         (void)hipStreamSynchronize(h->stream);
@@ -312,7 +313,7 @@ void spx_destroy(spx_handle* h)
                           &h->am_out_val, &h->am_out_idx, &h->scratch, &h->sobol_dirs, &h->sobol_out, &h->rhs, &h->diagL, &h->ps_flags, &h->flow_flags,
                           &h->alphaS, &h->pt_u, &h->rec_send, &h->rec_recv, &h->rec_out, &h->ei_sum_full,
                           &h->con_tab, &h->mom_c, &h->rhs_rows, &h->eff_in, &h->eff_m, &h->eff_out, &h->loo_out,
-                          &h->mes_bpart, &h->mes_part, &h->mes_G, &h->mes_ystar, &h->mes_fit};
+                          &h->mes_bpart, &h->mes_part, &h->mes_G, &h->mes_ystar, &h->mes_fit, &h->front_dev};
         for (DevBuf* b : bufs) b->release();
         h->pin_up.release();
         h->pin_res.release();
@@ -335,8 +336,14 @@ int spx_set_option(spx_handle* h, const char* name, int64_t value)
     if (h->multi) return spx_multi_set_option(h->multi, name, value);
     for (const OptRow& r : kOptions) {
         if (strcmp(name, r.name)) continue;
-        if (r.call) return r.call(h, value);
-        h->opt.*r.member = r.max ? (value < 0 ? r.neg : (int)std::min<int64_t>(value, r.max)) : (value < 0 ? -1 : (value != 0));
+        if (r.call) {
+            const int rc = r.call(h, value);
+            if (rc) return rc;
+        } else {
+            h->opt.*r.member = r.max ? (value < 0 ? r.neg : (int)std::min<int64_t>(value, r.max)) : (value < 0 ? -1 : (value != 0));
+        }
+        // the second GP of an EHVI pass runs with the caller's options (its timers are not the caller's)
+        if (h->sec && strcmp(name, "timing")) (void)spx_set_option(h->sec, name, value);
         return SPX_OK;
     }
     return fail(SPX_ERR_ARG, "spx_set_option: unknown option '%s'", name);
@@ -345,14 +352,14 @@ int spx_set_option(spx_handle* h, const char* name, int64_t value)
 // The acquisition every later pass and refinement call computes in EI's place (spx.h).  Nothing but the results of the last
 // pass depends on it: the factor, the fantasies and alpha_s stay.
 static_assert(SPX_ACQ_EI == SPX_ACQ_DEV_EI && SPX_ACQ_PI == SPX_ACQ_DEV_PI && SPX_ACQ_LCB == SPX_ACQ_DEV_LCB
-                  && SPX_ACQ_MES == SPX_ACQ_DEV_MES,
+                  && SPX_ACQ_MES == SPX_ACQ_DEV_MES && SPX_ACQ_EHVI == SPX_ACQ_DEV_EHVI,
               "spx.h and common.h number the acquisitions alike");
 int spx_set_acquisition(spx_handle* h, int32_t kind, double par)
 {
     if (!h) return fail(SPX_ERR_ARG, "spx_set_acquisition: null handle");
-    if (kind != SPX_ACQ_EI && kind != SPX_ACQ_PI && kind != SPX_ACQ_LCB && kind != SPX_ACQ_MES)
-        return fail(SPX_ERR_ARG, "spx_set_acquisition: unknown acquisition %d (SPX_ACQ_EI, SPX_ACQ_PI, SPX_ACQ_LCB, SPX_ACQ_MES)",
-                    (int)kind);
+    if (kind != SPX_ACQ_EI && kind != SPX_ACQ_PI && kind != SPX_ACQ_LCB && kind != SPX_ACQ_MES && kind != SPX_ACQ_EHVI)
+        return fail(SPX_ERR_ARG, "spx_set_acquisition: unknown acquisition %d (SPX_ACQ_EI, SPX_ACQ_PI, SPX_ACQ_LCB, SPX_ACQ_MES, "
+                                 "SPX_ACQ_EHVI are known)", (int)kind);
     if (!(par >= 0.0) || !std::isfinite(par))
         return fail(SPX_ERR_ARG, "spx_set_acquisition: the parameter must be finite and >= 0 (got %g)", par);
     if (kind == SPX_ACQ_EI && par != 0.0)
@@ -366,6 +373,15 @@ int spx_set_acquisition(spx_handle* h, int32_t kind, double par)
         if (h->comm) return fail(SPX_ERR_ARG, "spx_set_acquisition: SPX_ACQ_MES is single-device only (communicator attached)");
         if (h->part_ph > 1 || h->part_M > 0)
             return fail(SPX_ERR_ARG, "spx_set_acquisition: SPX_ACQ_MES is not available with a 2-D partition");
+    }
+    if (kind == SPX_ACQ_EHVI) {
+        if (par != 0.0)
+            return fail(SPX_ERR_ARG, "spx_set_acquisition: SPX_ACQ_EHVI takes no parameter (par must be 0, got %g)", par);
+        // the second GP's moments of every candidate live on an internal handle of the same device
+        if (h->multi) return fail(SPX_ERR_ARG, "spx_set_acquisition: SPX_ACQ_EHVI is single-device only (multi-device handle)");
+        if (h->comm) return fail(SPX_ERR_ARG, "spx_set_acquisition: SPX_ACQ_EHVI is single-device only (communicator attached)");
+        if (h->part_ph > 1 || h->part_M > 0)
+            return fail(SPX_ERR_ARG, "spx_set_acquisition: SPX_ACQ_EHVI is not available with a 2-D partition");
     }
     if (h->multi) return spx_multi_set_acquisition(h->multi, kind, par);
     spx_drop(h, Held::RESULTS);
@@ -504,6 +520,59 @@ int spx_set_time_model(spx_handle* h, const double* log_durs, const double* time
     return spx_hold(h, Held::TIME);
 }
 
+// The Pareto front of an EHVI pass (spx.h): a setting of the handle.  Everything is checked before anything is touched; the
+// device copy is in k_ehvi's form, n + 1 strips: their upper edges a_1 .. a_n, r1 and their levels r2, b_1 .. b_n.
+int spx_set_pareto_front(spx_handle* h, const double* a, const double* b, int32_t n, double r1, double r2)
+{
+    if (!h) return fail(SPX_ERR_ARG, "spx_set_pareto_front: null handle");
+    if (h->multi) return fail(SPX_ERR_ARG, "spx_set_pareto_front: SPX_ACQ_EHVI is single-device only (multi-device handle)");
+    if (n < 0) { spx_drop(h, Held::FRONT); h->front_n = -1; h->front_a.clear(); h->front_b.clear(); return SPX_OK; }
+    if (n > SPX_MAX_FRONT) return fail(SPX_ERR_ARG, "spx_set_pareto_front: n=%d front points (allowed: 0 .. %d)", (int)n, SPX_MAX_FRONT);
+    if (n > 0 && (!a || !b)) return fail(SPX_ERR_ARG, "spx_set_pareto_front: null front with n=%d", (int)n);
+    if (!std::isfinite(r1) || !std::isfinite(r2))
+        return fail(SPX_ERR_ARG, "spx_set_pareto_front: the reference point must be finite (got %g, %g)", r1, r2);
+    for (int i = 0; i < n; ++i) {
+        if (!std::isfinite(a[i]) || !std::isfinite(b[i]))
+            return fail(SPX_ERR_ARG, "spx_set_pareto_front: front point %d is not finite (%g, %g)", i, a[i], b[i]);
+        if (i > 0 && !(a[i - 1] < a[i]))
+            return fail(SPX_ERR_ARG, "spx_set_pareto_front: the first objective must be strictly increasing (point %d)", i);
+        if (i > 0 && !(b[i - 1] > b[i]))
+            return fail(SPX_ERR_ARG, "spx_set_pareto_front: the second objective must be strictly decreasing (point %d)", i);
+    }
+    if (n > 0 && (!(a[n - 1] < r1) || !(b[0] < r2)))
+        return fail(SPX_ERR_ARG, "spx_set_pareto_front: the reference point (%g, %g) must lie beyond every front point", r1, r2);
+    int rc = ensure_init(h);
+    if (rc) return rc;
+    std::vector<double> strips(2 * ((size_t)n + 1));
+    for (int i = 0; i < n; ++i) { strips[i] = a[i]; strips[(size_t)n + 2 + i] = b[i]; }
+    strips[n] = r1;
+    strips[(size_t)n + 1] = r2;
+    // (a reservation that fails has released the old buffer: the front it belonged to goes first)
+    spx_drop(h, Held::FRONT);
+    h->front_n = -1;
+    if ((rc = h->front_dev.reserve(strips.size() * 8))) return rc;
+    stage_begin(h);
+    if ((rc = stage_h2d(h, h->front_dev.p, strips.data(), strips.size() * 8, h->stream))) return rc;
+    HIPCHK(hipStreamSynchronize(h->stream));
+    h->front_a.assign(a, a + n);
+    h->front_b.assign(b, b + n);
+    h->front_r1 = r1; h->front_r2 = r2; h->front_n = n;
+    return spx_hold(h, Held::FRONT);
+}
+
+int spx_get_pareto_front(spx_handle* h, double* a, double* b, int32_t* n, double* r1, double* r2)
+{
+    if (!h) return fail(SPX_ERR_ARG, "spx_get_pareto_front: null handle");
+    const bool have = !h->multi && h->held.has(Held::FRONT);
+    if (n) *n = have ? h->front_n : -1;
+    if (!have) return SPX_OK;
+    if (a) std::copy(h->front_a.begin(), h->front_a.end(), a);
+    if (b) std::copy(h->front_b.begin(), h->front_b.end(), b);
+    if (r1) *r1 = h->front_r1;
+    if (r2) *r2 = h->front_r2;
+    return SPX_OK;
+}
+
 // ---------------------------------------------------------------------------
 static int finish_factor(spx_handle* h, const std::vector<int>& info, bool tolerate_not_pd, bool lean);
 
@@ -603,7 +672,8 @@ static int do_factor(spx_handle* h, bool tolerate_not_pd, bool lean = false, boo
     spx_drop(h, Held::FACTOR);      // both paths overwrite Xs, the hyper tables and L; finish_factor sets it again (not the lean path)
     FactorShape sh;
     sh.N = h->N; sh.D = h->D; sh.H = h->H; sh.Np = h->Np;
-    sh.have_time = h->held.has(Held::TIME); sh.lean = lean; sh.defer_sync = defer_sync; sh.have_dest = h->fused_lp != nullptr;
+    // (under SPX_ACQ_EHVI the time model is the second objective's GP, factored on its own internal handle: ehvi_second)
+    sh.have_time = h->held.has(Held::TIME) && h->acq != SPX_ACQ_EHVI; sh.lean = lean; sh.defer_sync = defer_sync; sh.have_dest = h->fused_lp != nullptr;
     sh.flow_demoted = h->flow_demoted; sh.rhs_rows_on = h->rhs_rows_on;
     FactorPlan& p = lean ? h->lean_plan : h->factor_plan;
     p = plan_factor(h->opt, sh);              // every decision of this call (spx_plan.h); below: reserve, upload, launch
@@ -907,17 +977,43 @@ int spx_get_pending_fantasies(spx_handle* h, int32_t draw, double* pend_fant, do
 // factor_pending (spx_ei_step): the factorisation is queued on the stream but not yet checked -- its not-PD flags travel
 // home with the winner, and ONE synchronisation ends the step
 static int ei_run_impl(spx_handle* h, int32_t flags, bool factor_pending);
+static int ehvi_second(spx_handle* h);
 
 // what an EI pass refuses because of its flags alone (nmodels: 2 when a time model is / will be factored)
+static const char* acq_name(int acq)
+{
+    return acq == SPX_ACQ_PI ? "PI" : acq == SPX_ACQ_LCB ? "LCB" : acq == SPX_ACQ_MES ? "MES" : acq == SPX_ACQ_EHVI ? "EHVI" : "EI";
+}
+
+// what a pass under SPX_ACQ_EHVI refuses, decided from the host's record alone (who: the entry point's name)
+static int check_ehvi(const spx_handle* h, int32_t flags, const char* who)
+{
+    if (h->acq != SPX_ACQ_EHVI) return SPX_OK;
+    if (flags & (SPX_FLAG_PER_SEC | SPX_FLAG_CONSTRAINED | SPX_FLAG_TIME_ONLY))
+        return fail(SPX_ERR_ARG, "%s: SPX_FLAG_PER_SEC / SPX_FLAG_CONSTRAINED / SPX_FLAG_TIME_ONLY are defined for "
+                                 "SPX_ACQ_EI only (spx_set_acquisition chose EHVI)", who);
+    if (h->comm || h->part_ph > 1 || h->part_M > 0)
+        return fail(SPX_ERR_ARG, "%s: SPX_ACQ_EHVI is single-device only (communicator attached or 2-D partition set)", who);
+    if (!h->held.has(Held::TIME))
+        return fail(SPX_ERR_ARG, "%s: SPX_ACQ_EHVI needs the second objective's GP (spx_set_time_model)", who);
+    if (!h->held.has(Held::FRONT))
+        return fail(SPX_ERR_ARG, "%s: SPX_ACQ_EHVI needs a front (spx_set_pareto_front)", who);
+    if (h->S > 0)
+        return fail(SPX_ERR_ARG, "%s: SPX_ACQ_EHVI is not defined over fantasies (clear them first)", who);
+    return SPX_OK;
+}
+
 static int check_run_flags(const spx_handle* h, int32_t flags, int nmodels)
 {
+    int rc_ehvi = check_ehvi(h, flags, "spx_ei_run");
+    if (rc_ehvi) return rc_ehvi;
     const bool per_sec = (flags & SPX_FLAG_PER_SEC) != 0;
     const bool keep_mom = (flags & SPX_FLAG_KEEP_MOMENTS) != 0;
     const bool time_only = (flags & SPX_FLAG_TIME_ONLY) != 0;
     if (h->acq != SPX_ACQ_EI && (flags & (SPX_FLAG_PER_SEC | SPX_FLAG_CONSTRAINED | SPX_FLAG_TIME_ONLY)))
         return fail(SPX_ERR_ARG, "spx_ei_run: SPX_FLAG_PER_SEC / SPX_FLAG_CONSTRAINED / SPX_FLAG_TIME_ONLY are defined for "
                                  "SPX_ACQ_EI only (spx_set_acquisition chose %s)",
-                    h->acq == SPX_ACQ_PI ? "PI" : h->acq == SPX_ACQ_LCB ? "LCB" : "MES");
+                    acq_name(h->acq));
     // (a communicator or a partition attached after spx_set_acquisition accepted MES)
     if (h->acq == SPX_ACQ_MES && (h->comm || h->part_ph > 1 || h->part_M > 0))
         return fail(SPX_ERR_ARG, "spx_ei_run: SPX_ACQ_MES is single-device only: y* of a draw needs every shard's moments "
@@ -961,6 +1057,10 @@ int spx_ei_step(spx_handle* h, int32_t flags)
         int rc = spx_multi_factor(h->multi);
         return rc ? rc : spx_multi_ei_run(h->multi, flags & ~SPX_FLAG_TIME_ONLY);
     }
+    {   // EHVI's refusals come before the factorisation in either form below (which would drop the fantasies it refuses)
+        int rc = check_ehvi(h, flags, "spx_ei_step");
+        if (rc) return rc;
+    }
     if (h->opt.timing || (flags & SPX_FLAG_TIMING) || !h->held.has(Held::CAND)) {   // stage timers bracket each call: keep the two-call form
         int rc = spx_factor(h);
         return rc ? rc : ei_run_impl(h, flags, false);
@@ -969,6 +1069,10 @@ int spx_ei_step(spx_handle* h, int32_t flags)
     int rc = check_run_flags(h, flags, h->held.has(Held::TIME) ? 2 : 1);
     if (rc) return rc;
     if ((rc = factor_constraint(h))) return rc;
+    // EHVI: the second GP's factorisation and pass run to their end first, as the constraint model's factorisation does -- one
+    // data-flow factorisation on the device at a time, and nothing of this handle is queued when a failure returns
+    if (h->acq == SPX_ACQ_EHVI && (rc = ensure_init(h))) return rc;
+    if (h->acq == SPX_ACQ_EHVI && (rc = ehvi_second(h))) return rc;
     h->handoff_timeout = false;
     rc = do_factor(h, false, false, true);
     if (rc) return rc;
@@ -1036,6 +1140,60 @@ static int ei_reserve(spx_handle* h, const EiPlan& p)
     return h->am_out_idx.reserve(8);
 }
 
+// The second GP of an EHVI pass (spx.h): an internal handle on the same device holds (comp, second values, second hypers) and
+// the candidates -- copied over from the resident ones when what they were made from changed (SEC / SEC_CAND) -- and runs the
+// ordinary factorisation and pass with the moments kept, so func_m / func_v are those of a plain handle to the bit.  Its own
+// handle, its own synchronisation, as the constraint model's factorisation; not positive definite: draw 5H + d.
+static int ehvi_second(spx_handle* h)
+{
+    int rc;
+    if (!h->sec) {
+        if ((rc = spx_create(h->device, &h->sec))) return rc;
+        h->sec->opt = h->opt;               // (from here on spx_set_option reaches it)
+        h->sec->opt.timing = false;
+    }
+    spx_handle* c = h->sec;
+    const int64_t N = h->N, M = h->M;
+    const int D = h->D, H = h->H;
+    if ((int64_t)h->thyp_host.size() != (int64_t)H * (3 + D))
+        return fail(SPX_ERR_ARG, "spx_ei_run: the second objective's hypers do not match H / D (spx_set_time_model again)");
+    if ((rc = ensure_init(c))) return rc;
+    // What spx_set_observations / spx_set_candidates do with a caller's host buffer, from the resident copies: device to device on
+    // the internal handle's stream (the caller's streams are idle: every entry point returns so).  `best` of the internal
+    // handle is not read by anything kept -- its EI values are never served -- and stays 0.
+    if (!h->held.has(Held::SEC)) {
+        spx_drop(c, Held::OBS);
+        if (D != c->D) { spx_drop(c, Held::CAND); spx_drop(c, Held::HYP); }
+        c->N = N; c->D = D; c->Dp = padded_dim(D); c->Np = (int)round_up(N, SPX_PADN);
+        c->best = 0.0;
+        if ((rc = c->comp.reserve((size_t)N * D * 8))) return rc;
+        if ((rc = c->vals.reserve((size_t)N * 8))) return rc;
+        HIPCHK(hipMemcpyAsync(c->comp.p, h->comp.p, (size_t)N * D * 8, hipMemcpyDeviceToDevice, c->stream));
+        HIPCHK(hipMemcpyAsync(c->vals.p, h->ldur.p, (size_t)N * 8, hipMemcpyDeviceToDevice, c->stream));
+        HIPCHK(hipStreamSynchronize(c->stream));
+        if ((rc = spx_hold(c, Held::OBS))) return rc;
+        if ((rc = spx_set_hypers(c, h->thyp_host.data(), H))) return rc;
+        if ((rc = spx_hold(h, Held::SEC))) return rc;
+    }
+    if (!h->held.has(Held::SEC_CAND)) {
+        spx_drop(c, Held::CAND);
+        c->M = M; c->index_base = 0;
+        if ((rc = c->cand.reserve((size_t)M * D * 8))) return rc;
+        HIPCHK(hipMemcpyAsync(c->cand.p, h->cand.p, (size_t)M * D * 8, hipMemcpyDeviceToDevice, c->stream));
+        HIPCHK(hipStreamSynchronize(c->stream));
+        if ((rc = spx_hold(c, Held::CAND))) return rc;
+        if ((rc = spx_hold(h, Held::SEC_CAND))) return rc;
+    }
+    rc = c->held.has(Held::FACTOR) ? spx_ei_run(c, SPX_FLAG_KEEP_MOMENTS) : spx_ei_step(c, SPX_FLAG_KEEP_MOMENTS);
+    if (rc == SPX_ERR_NOT_PD) {
+        h->not_pd_draw = 5 * H + c->not_pd_draw;
+        h->not_pd_pivot = c->not_pd_pivot;
+        return fail(SPX_ERR_NOT_PD, "%d-th leading minor of the array is not positive definite (draw %d, second objective)",
+                    c->not_pd_pivot + 1, c->not_pd_draw);
+    }
+    return rc;
+}
+
 static int ei_run_impl(spx_handle* h, int32_t flags, bool factor_pending)
 {
     if (!h->held.has(Held::FACTOR) && !factor_pending) return fail(SPX_ERR_ARG, "spx_ei_run: call spx_factor first");
@@ -1049,13 +1207,17 @@ static int ei_run_impl(spx_handle* h, int32_t flags, bool factor_pending)
     if (mes && h->S > 0)
         return fail(SPX_ERR_ARG, "spx_ei_run: SPX_ACQ_MES is not defined over fantasies (clear them, or score the call with "
                                  "SPX_ACQ_EI)");
-    if (mes) flags |= SPX_FLAG_KEEP_MOMENTS;
-    const int pass_acq = mes ? SPX_ACQ_EI : h->acq;
-    const double pass_par = mes ? 0.0 : h->acq_par;
+    // Expected hypervolume improvement: the same shape -- the pass as EI with the moments kept, k_ehvi behind it on the same
+    // stream -- after the second GP's pass over the same candidates (ehvi_second, below)
+    const bool ehvi = h->acq == SPX_ACQ_EHVI;
+    if (mes || ehvi) flags |= SPX_FLAG_KEEP_MOMENTS;
+    const int pass_acq = (mes || ehvi) ? SPX_ACQ_EI : h->acq;
+    const double pass_par = (mes || ehvi) ? 0.0 : h->acq_par;
     if ((rc = ensure_init(h))) return rc;
     if ((flags & SPX_FLAG_CONSTRAINED) && h->con_n > 0 && !h->held.has(Held::CON_FACTOR))
         return fail(SPX_ERR_ARG, "spx_ei_run: the constraint model is not factored (spx_factor after spx_set_constraint_model)");
     spx_drop(h, Held::RESULTS);     // the pass overwrites them; a failed one keeps the factor and the fantasies
+    if (ehvi && !factor_pending && (rc = ehvi_second(h))) return rc;     // (a pending step ran it before its own factorisation)
     EiShape sh;
     sh.N = h->N; sh.M = h->M; sh.Np = h->Np; sh.D = h->D; sh.H = h->H; sh.S = h->S; sh.nmodels = h->nmodels;
     sh.flags = flags; sh.factor_pending = factor_pending; sh.kst_budget = h->opt.kst_budget;
@@ -1236,6 +1398,14 @@ static int ei_run_impl(spx_handle* h, int32_t flags, bool factor_pending)
     if (mes)   // behind the last finalize on the main stream: every draw's moments are complete
         TIMED(ST_MES, launch_mes(s, h->mom_m.d(), h->mom_v.d(), h->htab.d(), SPX_HT, h->best, M, Mp, H, mesJ, mesK, h->mes_bpart.d(),
                                  h->mes_part.d(), h->mes_G.d(), h->mes_ystar.d(), h->mes_fit.d(), h->ei_draw.d()));
+    if (ehvi) {   // likewise; the second GP's moments were complete (and synchronised) before this pass began
+        const spx_handle* c = h->sec;
+        if (c->M != M || c->H != H || c->ei_plan.Mp != Mp)
+            return fail(SPX_ERR_ARG, "internal error: the second GP's pass does not match the objective's (M, H, Mp)");
+        const int nstrips = h->front_n + 1;
+        TIMED(ST_EHVI, launch_ehvi(s, h->mom_m.d(), h->mom_v.d(), c->mom_m.d(), c->mom_v.d(), h->front_dev.d(),
+                                   h->front_dev.d() + nstrips, nstrips, M, Mp, H, h->ei_draw.d()));
+    }
     TIMED(ST_MEAN_ARGMAX, {
         launch_mean_argmax(s, h->ei_draw.d(), h->ei_mean.d(), M, Mp, H, h->am_val.d(), (int64_t*)h->am_idx.p, h->am_out_val.d(),
                            (int64_t*)h->am_out_idx.p, mirror, (const int*)h->info.p, n_info);
@@ -1260,6 +1430,7 @@ static int ei_run_impl(spx_handle* h, int32_t flags, bool factor_pending)
     r.moments = keep_mom && S == 0 && !time_only;
     r.tmean = keep_mom && per_sec;   // (with fantasies the pass keeps no func_m / func_v, but mom_t is written all the same)
     r.con = constrained && keep_mom && !time_only;
+    r.ehvi = ehvi;
     r.mes = mes;
     if (mes) { h->mes_K = mesK; h->mes_J = mesJ; }
     if (h->comm && (rc = spx_comm_exchange(h, &r.global2d))) return rc;   // one process per GPU: the winner over all ranks
@@ -1319,6 +1490,8 @@ int spx_get_moments(spx_handle* h, int32_t draw, double* func_m, double* func_v)
     if (h && h->multi) return spx_multi_get_moments(h->multi, draw, func_m, func_v);
     if (!h || !h->held.results.moments)
         return fail(SPX_ERR_ARG, "spx_get_moments: run spx_ei_run with SPX_FLAG_KEEP_MOMENTS first");
+    if (h->held.results.ehvi && draw >= h->H && draw < 2 * h->H)    // the second GP's moments of an EHVI pass
+        return spx_get_moments(h->sec, draw - h->H, func_m, func_v);
     return get_draw_rows(h, "spx_get_moments", draw, h->mom_m, func_m, &h->mom_v, func_v);
 }
 
@@ -1606,7 +1779,10 @@ int spx_ei_per_sec_grid(spx_handle* h, const double* comp, const double* vals, c
                         double* ei_draw_out, int64_t* best_idx, double* best_val)
 {
     if (!h || !log_durs || !time_hypers) return fail(SPX_ERR_ARG, "spx_ei_per_sec_grid: null argument");
-    return run_grid(h, comp, vals, log_durs, N, D, cand, M, hypers, time_hypers, H, flags | SPX_FLAG_PER_SEC,
+    // (under SPX_ACQ_EHVI log_durs / time_hypers are the second objective's values and draws, and nothing is per second)
+    const bool ehvi = !h->multi && h->acq == SPX_ACQ_EHVI;
+    return run_grid(h, comp, vals, log_durs, N, D, cand, M, hypers, time_hypers, H,
+                    ehvi ? (flags & ~SPX_FLAG_PER_SEC) : (flags | SPX_FLAG_PER_SEC),
                     ei_mean_out, ei_draw_out, best_idx, best_val);
 }
 
@@ -1762,6 +1938,9 @@ int spx_ei_grad_batch(spx_handle* h, const double* points, int32_t P, double* ne
 {
     if (!h || !points || !neg_ei || !grad || P < 1) return fail(SPX_ERR_ARG, "spx_ei_grad_batch: bad argument");
     if (h->multi) return spx_multi_ei_grad_batch(h->multi, points, P, neg_ei, grad);
+    if (h->acq == SPX_ACQ_EHVI)
+        return fail(SPX_ERR_ARG, "spx_ei_grad_batch: not defined under SPX_ACQ_EHVI (its refinement needs the second GP's variance "
+                                 "gradient; the grid pass is the whole of it)");
     if (!h->held.has(Held::FACTOR)) return fail(SPX_ERR_ARG, "spx_ei_grad_batch: call spx_factor (or spx_ei_grid) first");
     const bool per_sec = (h->nmodels == 2);   // a time model was factored: EI per second (GPEIperSecChooser.py:349-434)
     if (per_sec && h->acq != SPX_ACQ_EI)

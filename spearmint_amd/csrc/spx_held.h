@@ -18,6 +18,8 @@ struct HeldResults {
     bool global2d = false;     // spx_get_ei_mean serves the all-reduced vector of a 2-D partition
     bool mes = false;          // the pass was a max-value entropy search: its y* table, fit and G are resident (spx_get_mes,
                                // spx_ei_grad_batch under SPX_ACQ_MES); gone with the results, so with everything that drops them
+    bool ehvi = false;         // the pass was an expected-hypervolume-improvement pass: the second GP's func_m / func_v of the same
+                               // candidates are resident on its internal handle (spx_get_moments, draws H .. 2H-1)
 };
 
 struct Held {
@@ -26,6 +28,10 @@ struct Held {
         FACTOR, CON_FACTOR, FULL_FACTOR, FANT, ALPHA_S, RESULTS,     // products
         COVAR, PARTITION,   // never held: option "covar" / the communicator and the partition -- named so that the table can
                             // say what is made from them, and drop(COVAR) / drop(PARTITION) is what a change of either does
+        // two objectives (SPX_ACQ_EHVI), numbered behind the two above so that nothing before them moves:
+        FRONT,              // input: the Pareto front and its reference point (spx_set_pareto_front)
+        SEC,                // product: the second GP's internal handle holds (comp, second values, second hypers)
+        SEC_CAND,           // product: ... and the candidates
         COUNT
     };
     using Results = HeldResults;
@@ -54,9 +60,12 @@ static constexpr HeldRow kHeldMadeFrom[Held::COUNT] = {
     /* FULL_FACTOR */ {SPX_HB(OBS) | SPX_HB(HYP) | SPX_HB(CON), SPX_HB(COVAR)},
     /* FANT        */ {SPX_HB(FACTOR), 0},                          // S > 0 exactly when FANT is held
     /* ALPHA_S     */ {SPX_HB(FANT), 0},
-    /* RESULTS     */ {SPX_HB(FACTOR) | SPX_HB(CAND), SPX_HB(FANT) | SPX_HB(CON) | SPX_HB(PARTITION)},
+    /* RESULTS     */ {SPX_HB(FACTOR) | SPX_HB(CAND), SPX_HB(FANT) | SPX_HB(CON) | SPX_HB(PARTITION) | SPX_HB(FRONT)},
     /* COVAR       */ {0, 0},
     /* PARTITION   */ {0, 0},
+    /* FRONT       */ {0, 0},                                       // a new front drops the results of the last pass alone
+    /* SEC         */ {SPX_HB(TIME), 0},                            // (option "covar" reaches the internal handle itself: it drops its own factor)
+    /* SEC_CAND    */ {SPX_HB(CAND), 0},
 };
 #undef SPX_HB
 
@@ -74,7 +83,7 @@ inline void Held::drop(Thing x)
 
 inline bool Held::set(Thing x, Results r)
 {
-    if (x >= COVAR || (kHeldMadeFrom[x].needs & ~bits)) return false;
+    if (x == COVAR || x == PARTITION || x >= COUNT || (kHeldMadeFrom[x].needs & ~bits)) return false;
     bits |= 1u << x;
     if (x == RESULTS) results = r;
     return true;

@@ -93,6 +93,7 @@ enum Stage {
     ST_SCALE = 0, ST_COV_SELF, ST_CHOL_DIAG, ST_CHOL_PANEL, ST_TRINV, ST_GAMMA_ALPHA,
     ST_COV_CROSS, ST_CROSS_MEAN, ST_PREDICT_GEMM, ST_EI_FINALIZE, ST_MEAN_ARGMAX,
     ST_MES,               // the four kernels of a max-value entropy search pass (launch_mes), as one stage
+    ST_EHVI,              // k_ehvi of an expected-hypervolume-improvement pass (launch_ehvi)
     ST_FACTOR_TOTAL, ST_EI_RUN_TOTAL, ST_COUNT
 };
 struct spx_handle {
@@ -171,6 +172,14 @@ struct spx_handle {
     // last MES pass and its sizes; part of RESULTS (held.results.mes)
     DevBuf mes_bpart, mes_part, mes_G, mes_ystar, mes_fit;
     int mes_K = 0, mes_J = 0;
+    // two objectives (SPX_ACQ_EHVI): the front as spx_set_pareto_front received it (FRONT held: front_n >= 0) and as k_ehvi reads
+    // it -- [2][front_n + 1]: the strips' upper edges a_1 .. a_n, r1, then their heights' levels r2, b_1 .. b_n; the second GP's
+    // internal handle on the same device (SEC / SEC_CAND: what of the caller's data it holds), its moments are the pass's
+    int front_n = -1;
+    double front_r1 = 0.0, front_r2 = 0.0;
+    std::vector<double> front_a, front_b;
+    DevBuf front_dev;
+    spx_handle* sec = nullptr;
     DevBuf loo_out;                                                 // spx_loo: loo_mean | loo_var | kinv_diag, [3][H][N]; scratch of that call, not part of `held`
     // probit constraint model (spx_set_constraint_model): an internal handle on the same device factors
     // (amp2_c (K_c + 1e-6 I) + noise_c I) alpha_c = ff over its own Nc points; the EI pass reads its scaled rows and alpha_c

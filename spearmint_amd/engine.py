@@ -38,7 +38,9 @@ ACQ_EI = 0
 ACQ_PI = 1            # probability of improvement, parameter xi
 ACQ_LCB = 2           # negated lower confidence bound kappa * func_s - func_m, parameter kappa
 ACQ_MES = 3           # max-value entropy search, parameter K = number of y* levels (1 .. 1024); single-GPU handles only
-ACQ = {"EI": ACQ_EI, "PI": ACQ_PI, "LCB": ACQ_LCB, "MES": ACQ_MES}
+ACQ_EHVI = 4          # expected hypervolume improvement over (objective, second objective); par 0; single-GPU handles only
+ACQ = {"EI": ACQ_EI, "PI": ACQ_PI, "LCB": ACQ_LCB, "MES": ACQ_MES, "EHVI": ACQ_EHVI}
+MAX_FRONT = 4096      # include/spx.h SPX_MAX_FRONT: front points spx_set_pareto_front takes
 MES_FIT_FIELDS = ("lo", "hi", "y25", "y50", "y75", "a", "b", "cap")    # include/spx.h: the fit record of spx_get_mes
 
 _c_double_p = ctypes.POINTER(ctypes.c_double)
@@ -106,6 +108,8 @@ ABI = {
     "spx_set_acquisition": (ctypes.c_int, [_vp, ctypes.c_int32, ctypes.c_double]),
     "spx_get_acquisition": (ctypes.c_int, [_vp, _c_int32_p, _c_double_p]),
     "spx_get_mes": (ctypes.c_int, [_vp, ctypes.c_int32, _c_double_p, _c_double_p, _c_double_p]),
+    "spx_set_pareto_front": (ctypes.c_int, [_vp, _c_double_p, _c_double_p, ctypes.c_int32, ctypes.c_double, ctypes.c_double]),
+    "spx_get_pareto_front": (ctypes.c_int, [_vp, _c_double_p, _c_double_p, _c_int32_p, _c_double_p, _c_double_p]),
     "spx_main_effects": (ctypes.c_int, [_vp, _c_double_p, ctypes.c_int32, _c_double_p, ctypes.c_int32, _c_double_p, _c_double_p]),
     "spx_loo": (ctypes.c_int, [_vp, ctypes.c_int32, _c_double_p, _c_double_p, _c_double_p]),
     "spx_ei_run": (ctypes.c_int, [_vp, ctypes.c_int32]),
@@ -425,9 +429,9 @@ class Engine(object):
 
     def set_acquisition(self, kind, par=0.0):
         """What the next passes and refinement calls score with (include/spx.h: spx_set_acquisition): ACQ_EI (par 0),
-        ACQ_PI (par = xi >= 0), ACQ_LCB (par = kappa >= 0) or ACQ_MES (par = K, the number of y* levels, 1 .. 1024); a name
-        of ACQ ("EI", "PI", "LCB", "MES") is taken too.  Drops the results of the last pass, keeps the factor and the
-        fantasies."""
+        ACQ_PI (par = xi >= 0), ACQ_LCB (par = kappa >= 0), ACQ_MES (par = K, the number of y* levels, 1 .. 1024) or ACQ_EHVI
+        (par 0; needs set_time_model and set_pareto_front); a name of ACQ ("EI", "PI", "LCB", "MES", "EHVI") is taken too.
+        Drops the results of the last pass, keeps the factor and the fantasies."""
         if not isinstance(kind, int):
             if kind not in ACQ:
                 raise ValueError("no acquisition %r (allowed: %s)" % (kind, ", ".join(sorted(ACQ))))
@@ -440,6 +444,31 @@ class Engine(object):
         par = ctypes.c_double(0.0)
         self._check(self._lib.spx_get_acquisition(self._h, ctypes.byref(kind), ctypes.byref(par)))
         return int(kind.value), float(par.value)
+
+    def set_pareto_front(self, front, ref):
+        """The front and reference point of an ACQ_EHVI pass (include/spx.h: spx_set_pareto_front): front (n, 2) rows
+        (first objective, second objective), the first strictly increasing and the second strictly decreasing, n in
+        0 .. MAX_FRONT; ref = (r1, r2) beyond every front point.  front None clears it.  Drops the results of the last pass."""
+        if front is None:
+            self._check(self._lib.spx_set_pareto_front(self._h, None, None, -1, 0.0, 0.0))
+            return
+        front = np.asarray(front, dtype=np.float64).reshape(-1, 2)
+        a, b = _f64(front[:, 0].copy()), _f64(front[:, 1].copy())
+        n = a.shape[0]
+        r1, r2 = float(ref[0]), float(ref[1])
+        self._check(self._lib.spx_set_pareto_front(self._h, _dp(a) if n else None, _dp(b) if n else None, n, r1, r2))
+
+    def get_pareto_front(self):
+        """(front (n, 2), (r1, r2)) as the handle holds them, or None when no front is set."""
+        n = ctypes.c_int32(-1)
+        self._check(self._lib.spx_get_pareto_front(self._h, None, None, ctypes.byref(n), None, None))
+        if n.value < 0:
+            return None
+        a, b = np.empty(n.value), np.empty(n.value)
+        r1, r2 = ctypes.c_double(0.0), ctypes.c_double(0.0)
+        self._check(self._lib.spx_get_pareto_front(self._h, _dp(a) if n.value else None, _dp(b) if n.value else None,
+                                                   ctypes.byref(n), ctypes.byref(r1), ctypes.byref(r2)))
+        return np.stack((a, b), axis=1), (float(r1.value), float(r2.value))
 
     def mes_info(self, draw):
         """What the last max-value entropy search pass fitted for one draw (include/spx.h: spx_get_mes): a dict with ystar
