@@ -318,6 +318,61 @@ int spx_get_mes(spx_handle* h, int32_t draw, double* ystar /* K */, double* fit 
 int spx_set_pareto_front(spx_handle* h, const double* a, const double* b, int32_t n, double r1, double r2);
 int spx_get_pareto_front(spx_handle* h, double* a, double* b, int32_t* n, double* r1, double* r2);
 
+/* ---- Thompson sampling: posterior sample paths over the candidates (pathwise conditioning) ---------------------------------
+ * Wilson et al. (2020): a draw from the GP posterior is a draw from the prior plus a data-dependent update,
+ *     f_s(x) = mean + p_s(x) + k(x, X)' (K + sig^2 I)^-1 (y - mean - p_s(X) - sig eps_s),      sig^2 = noise + 1e-6 amp2
+ * (sig^2 is the diagonal term of the chooser covariance amp2 (k + 1e-6 I) + noise I).  The prior sample p_s comes from F random
+ * Fourier features of the covariance's spectral density (Rahimi & Recht 2007); everything behind p_s(x) is a predictive mean
+ * with another right-hand side, computed with the exact K(X*,X) and the resident factor by the pass's S > 0 GEMM branch (the
+ * one the pending fantasies use) -- the feature approximation touches the prior alone.  The library draws no random numbers:
+ * as with spx_draw_fantasies the caller supplies the base randoms.
+ * D = dimension of the resident observations, H = resident draws, N = resident rows, M = resident candidates, nu_s = the
+ * smoothness 5/2 (Matern52) or 3/2 (Matern32).  The arithmetic, a contract: every operation below is ONE IEEE rounding and
+ * nothing is contracted into a fused multiply-add except where fma is written.
+ *   frequencies, in TURNS (formed on the host)
+ *              t_f = sqrt(2 nu_s / chi_f)  (ARDSE / SE: t_f = 1);   nu[d][f][j] = (omega_z[f][j] * t_f) / (TWO_PI * ls[d][j]),
+ *              TWO_PI = 6.283185307179586 (2 * np.pi), ls = 1 for SE; the pad dimensions are zero
+ *   feature    u = sum_j nu_j x_j + phase_f: the dot product on v_mfma_f64_16x16x4_f64 (its summation order is the kernel's
+ *              own), then ONE addition of the phase;  r = u - rint(u), exact, so no argument reduction of a large angle is ever
+ *              needed;  c = cos2pi(r), the polynomial of csrc/ts_device.h (SPX_TS_COS_ULPS = 4 ulp of the result; the text there
+ *              is the definition).  A NaN or infinite coordinate gives NaN; |u| >= 2^52 gives r = 0
+ *   prior      p_{d,s}(x) = scale_d * (sum_f w[s][f] c_f),   scale_d = sqrt((2 * amp2_d) / F).  The sum runs over f in a fixed
+ *              order (16 features at a time, on the MFMA), so a row's value depends on its coordinates, the draw, s, F and the
+ *              randoms alone -- not on M, the chunking, the row's position, the other paths of the call or any option
+ *   conditioning
+ *              rhs[d][s][i] = (y_i - p_{d,s}(x_i)) - sig_d * eps[s][i],   sig_d = sqrt(noise_d + 1e-6 * amp2_d);
+ *              Gamma = L^-1 (rhs - mean_d) as spx_set_fantasies forms it from its fantasy columns; the pass over the candidates is
+ *              spx_ei_run's over S fantasies: every chunk, draw group, "streams" 1 / 2 / 3 and "gemm_partial"
+ *   finish     path = (bg + mean_d) + p_{d,s}(c), bg summed as the pass sums it for a fantasy; the paths are kept, [H S][M];
+ *              then per (d, s) numpy's argmin -- the first NaN wins, else the first minimum -- and index_base is added.
+ * State: takes the results of the last pass away (spx_get_best and the other result getters refuse afterwards) and holds the
+ * paths and their priors as a results kind of their own: whatever drops a pass's results drops them.  The factorisation, the
+ * candidates, the options and the acquisition setting stay (the call does not read that setting): an EI pass afterwards gives
+ * the bits it gave before.  spx_get_stat "last_ts_paths" / "last_ts_features": S and F of the held paths (0: none).  With option
+ * "timing" the stages are "ts_prior" (k_ts_prior over observations and candidates, k_ts_rhs) and "ts_finish" (k_ts_finish,
+ * k_ts_argmin).  S > 16: every block of 16 paths forms the features again.
+ * REFUSED with SPX_ERR_ARG before any device is touched, the handle as it was: no held factorisation or no candidates; fantasies
+ * held; a multi-device handle, a communicator or a 2-D partition; F or S out of range; a NULL pointer where one is read; a chi
+ * that is not finite and > 0; a phase outside [0, 1); H S Mp 8 bytes (Mp = M rounded up to 128) above 4 GiB, or H S > 65535.
+ * spx_ei_grad_batch does not know paths: the gradient of a path is out of scope.                                            */
+#define SPX_TS_MAX_FEATURES 8192
+#define SPX_TS_MAX_PATHS    256
+int spx_thompson(spx_handle* h,
+                 int32_t F,               /* features: a multiple of 16 in 16 .. SPX_TS_MAX_FEATURES  */
+                 int32_t S,               /* paths per resident draw, 1 .. SPX_TS_MAX_PATHS           */
+                 const double* omega_z,   /* F x D standard normals (shared by the draws)             */
+                 const double* chi,       /* F chi-square(2 nu) draws: 5 dof Matern52, 3 Matern32;
+                                             not read (may be NULL) for ARDSE / SE                    */
+                 const double* phase,     /* F uniforms in [0, 1): the phase in TURNS                 */
+                 const double* w,         /* per_draw ? H x S x F : S x F standard normals            */
+                 const double* eps,       /* per_draw ? H x S x N : S x N standard normals            */
+                 int32_t per_draw,
+                 int64_t* idx_out,        /* H x S: index_base + argmin_c f_{d,s}(c), numpy's rule    */
+                 double*  min_out);       /* H x S: that minimum                                      */
+int spx_get_thompson_path (spx_handle* h, int32_t draw, int32_t s, double* path /* M */);
+int spx_get_thompson_prior(spx_handle* h, int32_t draw, int32_t s,
+                           double* prior_cand /* M */, double* prior_obs /* N */);  /* either may be NULL */
+
 /* Hot path, stage 2: K(X*,X) (:187), triangular solve (:195), predictive
  * mean/variance (:198-199), EI (:202-206) for every (candidate, draw); then the
  * MCMC mean and the argmax (:153).  Results stay on the device.               */

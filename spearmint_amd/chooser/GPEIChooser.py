@@ -24,6 +24,7 @@ class GPEIChooser(GPEIBase):
     amp2_prior_on_sqrt = False
     noiseless_checks_mean = False
     max_ls = 2
+    ts_allowed = True               # acq=TS: the grid argmin of one posterior sample path (_base.py: _thompson_gpu)
 
     def __del__(self):
         # the reference persists its hypers when the object dies (:66-83)
@@ -51,9 +52,12 @@ class GPEIChooser(GPEIBase):
                 self.amp2 = np.std(vals)
                 self.noise = 1e-3
             self._log_hypers()
-            randn = [npr.randn(pend.shape[0], self.pending_samples)] if pend.shape[0] > 0 else []
-            best, _, _ = self.ei_over_hypers_gpu(comp, pend, cand, vals, self.current_hyper_row()[None, :],
-                                                 randn=randn)
+            if self.acq == "TS":   # (pending jobs are ignored: no fantasies, no normals for them)
+                best = self._thompson_gpu(comp, cand, vals, self.current_hyper_row()[None, :])
+            else:
+                randn = [npr.randn(pend.shape[0], self.pending_samples)] if pend.shape[0] > 0 else []
+                best, _, _ = self.ei_over_hypers_gpu(comp, pend, cand, vals, self.current_hyper_row()[None, :],
+                                                     randn=randn)
             if self.recommend:     # (the proposal is fixed; no random numbers from here on)
                 self._recommend(grid, comp, vals, self.current_hyper_row()[None, :])
             if self.importance:    # (after the recommendation, whose factorisation it reuses)
@@ -67,7 +71,7 @@ class GPEIChooser(GPEIBase):
         # same computation; with pending ones its fantasy normals are drawn here,
         # right after the sample they belong to.
         rows, randn = [], []
-        if pend.shape[0] > 0:
+        if pend.shape[0] > 0 and self.acq != "TS":
             for _ in range(self.mcmc_iters):
                 self.sample_hypers(comp, vals)
                 self._log_hypers()
@@ -80,7 +84,10 @@ class GPEIChooser(GPEIBase):
                 rows.append(self.current_hyper_row())
             self._lp_key = None
             self.sample_hypers_many(comp, vals, self.mcmc_iters, after)
-        best, _, _ = self.ei_over_hypers_gpu(comp, pend, cand, vals, np.array(rows), randn=randn)
+        if self.acq == "TS":       # the chain above is that of a call without pending jobs; then one draw, one sample path
+            best = self._thompson_gpu(comp, cand, vals, np.array(rows))
+        else:
+            best, _, _ = self.ei_over_hypers_gpu(comp, pend, cand, vals, np.array(rows), randn=randn)
         if self.recommend:         # (the proposal is fixed; no random numbers from here on)
             self._recommend(grid, comp, vals, np.array(rows))
         if self.importance:        # (after the recommendation, whose factorisation it reuses)

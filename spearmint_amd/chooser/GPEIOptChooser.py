@@ -30,6 +30,7 @@ class GPEIOptChooser(GPEIBase):
     amp2_prior_on_sqrt = True       # :668
     noiseless_checks_mean = True    # :685-686
     max_ls = 2
+    ts_allowed = True               # acq=TS: the grid argmin of one posterior sample path (_base.py: _thompson_gpu)
 
     def __init__(self, expt_dir, covar="Matern52", mcmc_iters=10, pending_samples=100,
                  noiseless=False, burnin=100, grid_subset=20, use_multiprocessing=True, rescore_grid=0, **kw):
@@ -44,7 +45,7 @@ class GPEIOptChooser(GPEIBase):
         self.use_multiprocessing = _as_bool(use_multiprocessing)
         self.rescore_grid = _as_bool(rescore_grid)   # 1: score [grid; refined] again in the second pass, as the reference does
         # the host refinement (gpu_refine=0, or SPX_REFINE_MIN_N keeping the first proposals on the host) knows EI alone
-        if self.acq != "EI" and not self._use_gpu_refine(0):
+        if self.acq not in ("EI", "TS") and not self._use_gpu_refine(0):      # (acq=TS proposes a grid point: nothing is refined)
             raise ValueError("acq=%s needs the refinement on the GPU at every size (allowed with gpu_refine=0 or "
                              "SPX_REFINE_MIN_N > 0: acq=EI)" % self.acq)
         self.hyper_samples = []
@@ -237,6 +238,19 @@ class GPEIOptChooser(GPEIBase):
         self._sample_and_collect(comp, vals, self.mcmc_iters, "%d/%d] ")
         self.dump_hypers()
         rows = self.hyper_rows()
+
+        if self.acq == "TS":
+            # Thompson sampling: the argmin of ONE sample path over the grid.  No sprayed points (their normals above are drawn
+            # all the same: the generator is where an acq=EI call leaves it at this point), no pending fantasies, and no
+            # L-BFGS-B refinement -- the gradient of a path is not part of the library (include/spx.h: spx_thompson).
+            job = int(candidates[self._thompson_gpu(comp, cand, vals, rows)])
+            if self.recommend:
+                self._recommend(grid, comp, vals, rows, refine_count=self.grid_subset)
+            if self.importance:
+                self._importance(grid, comp, vals, rows)
+            if self.loo:
+                self._loo(complete, comp, vals, rows)
+            return job
 
         # pass 1 over grid + sprayed points, keep the grid_subset best (:269-271)
         randn = self._fantasy_normals(pend) if pend.shape[0] > 0 else None

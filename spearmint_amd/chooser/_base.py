@@ -46,7 +46,10 @@ class GPEIBase(object):
     state_keys = ("dims", "ls", "amp2", "noise", "mean")
     max_rows_per_call = 32         # spx_gp_logprob: one data-flow launch up to 32 hyper rows (spx_api.hip: do_factor, `rl`)
     acq_allowed = ("EI", "PI", "LCB", "MES")   # acq=: what the engine scores candidates with (include/spx.h SPX_ACQ_*)
+    ts_allowed = False             # acq=TS: Thompson sampling (include/spx.h: spx_thompson) -- not an acquisition of the pass but
+    #                                a call of its own; GPEIChooser and GPEIOptChooser switch it on
     mes_default_levels = 10        # acq=MES with acq_par=0: K, the number of y* levels
+    ts_default_features = 1024     # acq=TS with acq_par=0: F, the random Fourier features of the prior sample
     recommend_allowed = True       # recommend=1: the model-mean recommendation after every proposal (_recommend)
     importance_allowed = True      # importance=1: the parameter-sensitivity report after every proposal (_importance)
     importance_max_points = 128 << 12   # include/spx.h: Q of spx_main_effects
@@ -64,7 +67,11 @@ class GPEIBase(object):
         if self.acq == "MES" and int(ndev) > 1:
             raise ValueError("acq=MES is not available with ndev=%d: y* of a draw needs the moments of every candidate on one "
                              "device (allowed: ndev=1, or acq=EI, PI, LCB)" % int(ndev))
+        if self.acq == "TS" and int(ndev) > 1:
+            raise ValueError("acq=TS is not available with ndev=%d: a sample path is drawn over every candidate on one "
+                             "device (allowed: ndev=1, or acq=EI, PI, LCB)" % int(ndev))
         self.last_acq_used = None      # the acquisition that scored the last call ("EI" under acq=MES while jobs are pending)
+        self.last_thompson = None      # acq=TS: {"draw", "grid_index", "path_min", "features"} of the last call
         self.recommend = _as_bool(recommend)
         if self.recommend and not self.recommend_allowed:
             raise ValueError("recommend=1 is not available on %s (allowed: recommend=0)" % type(self).__name__)
@@ -155,11 +162,13 @@ class GPEIBase(object):
     # -- acquisition -----------------------------------------------------------
     @classmethod
     def _parse_acquisition(cls, acq, acq_par):
-        """acq=EI|PI|LCB|MES and acq_par=<xi, kappa or K>: finite, >= 0, 0 for EI, an integer in 0 .. 1024 for MES (0: the default
-        of 10 levels) (include/spx.h: spx_set_acquisition)."""
+        """acq=EI|PI|LCB|MES|TS and acq_par=<xi, kappa, K or F>: finite, >= 0, 0 for EI, an integer in 0 .. 1024 for MES (0: the
+        default of 10 levels), a multiple of 16 in 16 .. 8192 for TS (0: the default of 1024 features) (include/spx.h:
+        spx_set_acquisition, spx_thompson)."""
         name = str(acq).strip().upper()
-        if name not in cls.acq_allowed:
-            raise ValueError("acq=%s is not available on %s (allowed: %s)" % (acq, cls.__name__, ", ".join(cls.acq_allowed)))
+        allowed = cls.acq_allowed + (("TS",) if cls.ts_allowed else ())
+        if name not in allowed:
+            raise ValueError("acq=%s is not available on %s (allowed: %s)" % (acq, cls.__name__, ", ".join(allowed)))
         try:
             par = float(acq_par)
         except (TypeError, ValueError):
@@ -174,6 +183,11 @@ class GPEIBase(object):
                 raise ValueError("acq_par=%r is not a number of y* levels (allowed with acq=MES: an integer in 1 .. 1024, or 0 for "
                                  "the default of %d)" % (acq_par, cls.mes_default_levels))
             par = float(int(par) or cls.mes_default_levels)
+        if name == "TS":
+            if par != int(par) or int(par) % 16 or (par != 0 and not 16 <= par <= 8192):
+                raise ValueError("acq_par=%r is not a number of features (allowed with acq=TS: a multiple of 16 in 16 .. 8192, or "
+                                 "0 for the default of %d)" % (acq_par, cls.ts_default_features))
+            par = float(int(par) or cls.ts_default_features)
         return name, par
 
     def _apply_acquisition(self, eng, pending=False):
@@ -188,6 +202,32 @@ class GPEIBase(object):
         if self.acq != "EI":
             from ..engine import ACQ
             eng.set_acquisition(ACQ[acq], par)
+
+    # -- Thompson sampling (acq=TS) ---------------------------------------------------
+    def _thompson_gpu(self, comp, cand, vals, hyper_rows):
+        """The proposal of an acq=TS call: one of this call's hyper draws, d = np.random.randint(H), then ONE posterior sample
+        path of the GP under that draw over the candidate grid (Engine.thompson, S = 1, F = acq_par features; its base randoms
+        come from numpy's global generator in thompson_randoms' order) and the index of the path's minimum.  The engine holds
+        the completed points and the single hyper row d: the pass costs 1/H of an EI pass.  Pending jobs play no part -- every
+        worker minimises a sample of its own (parallel Thompson sampling), so there are no fantasies."""
+        rows = np.ascontiguousarray(np.atleast_2d(hyper_rows), dtype=np.float64)
+        d = int(np.random.randint(rows.shape[0]))
+        eng = self.engine()
+        self._lp_key = None
+        self._factor_covers = None
+        eng.set_observations(comp, vals)
+        eng.set_candidates(cand)
+        eng.set_hypers(rows[d:d + 1])
+        eng.factor()
+        F = int(self.acq_par)
+        idx, mn, _ = eng.thompson(S=1, F=F)
+        warning = eng.last_warning()
+        if warning:
+            log("libspx " + warning)
+        self.last_acq_used = "TS"
+        self.last_overall_ei = None
+        self.last_thompson = {"draw": d, "grid_index": int(idx[0, 0]), "path_min": float(mn[0, 0]), "features": F}
+        return int(idx[0, 0])
 
     # -- the model-mean recommendation (recommend=1) ---------------------------------
     def _recommend(self, grid, comp, vals, hyper_rows, refine_count=0):

@@ -186,6 +186,22 @@ void launch_mes(hipStream_t s, const double* mom_m, const double* mom_v, const d
 void launch_ehvi(hipStream_t s, const double* m1, const double* v1, const double* m2, const double* v2, const double* edges,
                  const double* levels, int nstrips, int64_t M, int64_t Mp, int H, double* ei_draw);
 
+// ts_kernels.hip: Thompson sampling by pathwise conditioning (spx.h: spx_thompson).  The prior p_{d,s} of rows x [n][D] under
+// nu [H][F Dp] in operand order (ts_nu_index within a draw), phase [F], w [H or 1][S][F] (w_stride doubles between draws, 0: shared) and scale [H], into
+// out[(d S + s) ldo + col0 + row];  the right-hand sides rhs [H][S][N] = (vals - prior) - sig eps;  the finish of a work item of
+// the S > 0 GEMM branch, path = (bg + mean) + prior, both [H][S][Mp];  numpy's argmin of every path, index_base added
+void launch_ts_prior(hipStream_t s, const double* x, int64_t n, int D, int Dp, const double* nu, const double* phase,
+                     const double* w, size_t w_stride, const double* scale, int F, int S, int H, double* out, int64_t ldo,
+                     int64_t col0);
+void launch_ts_rhs(hipStream_t s, const double* vals, const double* prior, const double* eps, size_t eps_stride,
+                   const double* sig, int64_t N, int S, int H, double* rhs);
+void launch_ts_finish(hipStream_t s, const double* part_bgS, const double* htab, const double* prior, int nrb, int Mc, int nh,
+                      int S, int64_t c0, int64_t M, int64_t Mp, int h0, double* path);
+size_t ts_nu_index(int f, int j, int Dp);
+int ts_argmin_blocks(int64_t M);
+void launch_ts_argmin(hipStream_t s, const double* path, int64_t M, int64_t Mp, int npaths, double* blk_val, int64_t* blk_idx,
+                      double* out_val, int64_t* out_idx, int64_t index_base);
+
 // predict_kernels.hip
 void launch_predict_gemm(hipStream_t s, int variant, const double* WT, const double* Kst, const double* gamma,
                          double* part_ss, double* part_bg, int Np, int Mc, int nh, int part_nh, int part_h0,

@@ -12,13 +12,14 @@
 
 #include "spx_internal.h"
 #include "np_sum.h"
+#include "ts_device.h"   // SPX_TS_TWO_PI
 
 #define SPX_VERSION 200
 
 static const char* kStageNames[ST_COUNT] = {
     "scale_rows", "cov_self", "chol_diag", "chol_panel", "trinv", "gamma_alpha",
     "cov_cross", "cross_mean", "predict_gemm", "ei_finalize", "mean_argmax", "mes", "ehvi",
-    "factor_total", "ei_run_total"};
+    "ts_prior", "ts_finish", "factor_total", "ei_run_total"};
 
 
 std::string& spx_err_slot()
@@ -313,7 +314,9 @@ void spx_destroy(spx_handle* h)
                           &h->am_out_val, &h->am_out_idx, &h->scratch, &h->sobol_dirs, &h->sobol_out, &h->rhs, &h->diagL, &h->ps_flags, &h->flow_flags,
                           &h->alphaS, &h->pt_u, &h->rec_send, &h->rec_recv, &h->rec_out, &h->ei_sum_full,
                           &h->con_tab, &h->mom_c, &h->rhs_rows, &h->eff_in, &h->eff_m, &h->eff_out, &h->loo_out,
-                          &h->mes_bpart, &h->mes_part, &h->mes_G, &h->mes_ystar, &h->mes_fit, &h->front_dev};
+                          &h->mes_bpart, &h->mes_part, &h->mes_G, &h->mes_ystar, &h->mes_fit, &h->front_dev,
+                          &h->ts_par, &h->ts_w, &h->ts_eps, &h->ts_pobs, &h->ts_rhs, &h->ts_gammaS, &h->ts_pcand, &h->ts_path,
+                          &h->ts_am_val, &h->ts_am_idx, &h->ts_out_val, &h->ts_out_idx};
         for (DevBuf* b : bufs) b->release();
         h->pin_up.release();
         h->pin_res.release();
@@ -976,7 +979,9 @@ int spx_get_pending_fantasies(spx_handle* h, int32_t draw, double* pend_fant, do
 
 // factor_pending (spx_ei_step): the factorisation is queued on the stream but not yet checked -- its not-PD flags travel
 // home with the winner, and ONE synchronisation ends the step
-static int ei_run_impl(spx_handle* h, int32_t flags, bool factor_pending);
+// ts_S > 0 (spx_thompson): the pass's S > 0 GEMM branch over the ts_S right-hand sides per draw in h->ts_gammaS instead of the
+// fantasies, k_ts_prior per chunk, k_ts_finish in place of the acquisition, a per-path argmin in place of the mean and argmax
+static int ei_run_impl(spx_handle* h, int32_t flags, bool factor_pending, int ts_S = 0);
 static int ehvi_second(spx_handle* h);
 
 // what an EI pass refuses because of its flags alone (nmodels: 2 when a time model is / will be factored)
@@ -1097,10 +1102,10 @@ int spx_ei_step(spx_handle* h, int32_t flags)
 }
 
 // everything an EI pass writes on the device, reserved as its plan says before anything is queued
-static int ei_reserve(spx_handle* h, const EiPlan& p)
+static int ei_reserve(spx_handle* h, const EiPlan& p, int S)
 {
     int rc;
-    const bool fant = h->S > 0, con_gp = p.constrained && h->con_n > 0;
+    const bool fant = S > 0, con_gp = p.constrained && h->con_n > 0;
     if (p.ns == 3 && (rc = ensure_stream3(h))) return rc;   // (a time-only pass too: it stages nothing, but produces there)
     // the staging slots: K(X*,X) of a work item and, with fantasies, its partial means; the buffers of slots that the pass
     // does not use go back to the device first
@@ -1194,22 +1199,23 @@ static int ehvi_second(spx_handle* h)
     return rc;
 }
 
-static int ei_run_impl(spx_handle* h, int32_t flags, bool factor_pending)
+static int ei_run_impl(spx_handle* h, int32_t flags, bool factor_pending, int ts_S)
 {
     if (!h->held.has(Held::FACTOR) && !factor_pending) return fail(SPX_ERR_ARG, "spx_ei_run: call spx_factor first");
     if (!h->held.has(Held::CAND)) return fail(SPX_ERR_ARG, "spx_ei_run: no candidates set");
-    int rc = check_run_flags(h, flags, h->nmodels);
+    const bool ts = ts_S > 0;       // (spx_thompson made every check of its own; the acquisition setting is not read)
+    int rc = ts ? (int)SPX_OK : check_run_flags(h, flags, h->nmodels);
     if (rc) return rc;
     // Max-value entropy search: the ordinary pass as EI with the moments kept (the way spx_main_effects runs it; the handle's
     // setting is not touched: the pass's kernels are handed pass_acq), then the MES stages on the same stream, which
     // overwrite the per-draw values before the mean and the argmax -- still ONE synchronisation.
-    const bool mes = h->acq == SPX_ACQ_MES;
+    const bool mes = !ts && h->acq == SPX_ACQ_MES;
     if (mes && h->S > 0)
         return fail(SPX_ERR_ARG, "spx_ei_run: SPX_ACQ_MES is not defined over fantasies (clear them, or score the call with "
                                  "SPX_ACQ_EI)");
     // Expected hypervolume improvement: the same shape -- the pass as EI with the moments kept, k_ehvi behind it on the same
     // stream -- after the second GP's pass over the same candidates (ehvi_second, below)
-    const bool ehvi = h->acq == SPX_ACQ_EHVI;
+    const bool ehvi = !ts && h->acq == SPX_ACQ_EHVI;
     if (mes || ehvi) flags |= SPX_FLAG_KEEP_MOMENTS;
     const int pass_acq = (mes || ehvi) ? SPX_ACQ_EI : h->acq;
     const double pass_par = (mes || ehvi) ? 0.0 : h->acq_par;
@@ -1219,13 +1225,17 @@ static int ei_run_impl(spx_handle* h, int32_t flags, bool factor_pending)
     spx_drop(h, Held::RESULTS);     // the pass overwrites them; a failed one keeps the factor and the fantasies
     if (ehvi && !factor_pending && (rc = ehvi_second(h))) return rc;     // (a pending step ran it before its own factorisation)
     EiShape sh;
-    sh.N = h->N; sh.M = h->M; sh.Np = h->Np; sh.D = h->D; sh.H = h->H; sh.S = h->S; sh.nmodels = h->nmodels;
+    sh.N = h->N; sh.M = h->M; sh.Np = h->Np; sh.D = h->D; sh.H = h->H; sh.S = ts ? ts_S : h->S; sh.nmodels = h->nmodels;
     sh.flags = flags; sh.factor_pending = factor_pending; sh.kst_budget = h->opt.kst_budget;
     // The byte budgets of the plan are shares of what the device has free (a smaller or fuller GPU takes smaller chunks
     // instead of an allocation failure).  They are queried when the number of fantasies / the size of a ring slot changes, not
     // per pass: the plan -- buffer sizes, launch counts -- then stays what it was from pass to pass and across ranks that
     // share a device.  Fantasies: an eighth of free memory, at most 2 GB.
-    if (sh.S > 0 && h->fant_budget_S != sh.S) {
+    // (spx_thompson's paths keep a budget of their own: the one cached for the fantasies, and with it the chunking of a later
+    // fantasy pass, is what it is on a handle that never drew a path)
+    int64_t& fant_budget = ts ? h->ts_fant_budget : h->fant_budget;
+    int& fant_budget_S = ts ? h->ts_fant_budget_S : h->fant_budget_S;
+    if (sh.S > 0 && fant_budget_S != sh.S) {
         size_t mem_free = 0, mem_total = 0;
         int64_t b = 2048ll << 20;
         if (hipMemGetInfo(&mem_free, &mem_total) == hipSuccess) {
@@ -1233,10 +1243,10 @@ static int ei_run_impl(spx_handle* h, int32_t flags, bool factor_pending)
             for (auto& sl : h->ring) held += sl.part_bgS.cap;
             b = std::max<int64_t>(64ll << 20, std::min<int64_t>(b, (int64_t)(mem_free / 8) + (int64_t)held / 2));
         } else (void)hipGetLastError();
-        h->fant_budget = b;
-        h->fant_budget_S = sh.S;
+        fant_budget = b;
+        fant_budget_S = sh.S;
     }
-    sh.fant_budget = h->fant_budget;
+    sh.fant_budget = fant_budget;
     sh.ring_budget = h->ring_budget;
     EiPlan& p = h->ei_plan;
     p = plan_ei(h->opt, sh);                  // every decision of this pass (spx_plan.h); below: reserve and launch
@@ -1256,9 +1266,10 @@ static int ei_run_impl(spx_handle* h, int32_t flags, bool factor_pending)
         p = plan_ei(h->opt, sh);
     }
     const bool per_sec = p.per_sec, keep_mom = p.keep_mom, time_only = p.time_only, constrained = p.constrained, fused = p.fused;
-    const int H = h->H, D = h->D, Dp = p.Dp, Np = h->Np, hs = 3 + D, nrb = p.nrb, Hb = p.Hb, S = h->S, ns = p.ns;
+    const int H = h->H, D = h->D, Dp = p.Dp, Np = h->Np, hs = 3 + D, nrb = p.nrb, Hb = p.Hb, S = sh.S, ns = p.ns;
     const int64_t N = h->N, M = h->M, Mp = p.Mp, Mc = p.Mc;
-    if ((rc = ei_reserve(h, p))) return rc;
+    if ((rc = ei_reserve(h, p, S))) return rc;
+    const double* gammaS_all = ts ? h->ts_gammaS.d() : h->gammaS.d();
     const int mesK = mes ? (int)h->acq_par : 0, mesJ = h->opt.mes_grid;
     if (mes) {
         if ((rc = h->mes_bpart.reserve((size_t)H * mes_bound_blocks(M) * 3 * 8))) return rc;
@@ -1271,7 +1282,7 @@ static int ei_run_impl(spx_handle* h, int32_t flags, bool factor_pending)
 
     hipStream_t s = h->stream;
     if (flags & SPX_FLAG_TIMING) h->opt.timing = true;
-    h->ev_used = 0;
+    if (!ts) h->ev_used = 0;         // (spx_thompson's own stages in front of the pass are in the pool already)
     hipEvent_t t0 = h->ev_t0, t1 = h->ev_t1;
     HIPCHK(hipEventRecord(t0, s));
     const int gemm_nlive = p.gemm_nlive;
@@ -1347,6 +1358,12 @@ static int ei_run_impl(spx_handle* h, int32_t flags, bool factor_pending)
         // 2 * cand / ls and |cand / ls|^2 for every draw (one launch per chunk)
         hipStream_t Pc = (chunk == 0) ? P0 : P;       // (the first chunk's producer work of a step: beside the factorisation)
         TIMED_S(ST_SCALE, Pc, launch_scale_rows(Pc, xc, nreal, mc, D, Dp, ls, hs, H, 2.0, Cs, s2));
+        if (ts) {   // the prior of the chunk's rows under every draw and path, on the consumer stream in front of the finishes that read it
+            const double* par = h->ts_par.d();
+            const size_t nnu = (size_t)H * h->ts_F * Dp;
+            TIMED_S(ST_TS_PRIOR, G, launch_ts_prior(G, xc, nreal, D, Dp, par, par + nnu, h->ts_w.d(), h->ts_w_stride, par + nnu + h->ts_F,
+                                                    h->ts_F, S, H, h->ts_pcand.d(), Mp, c0));
+        }
         if (fused && (rc = hand_off(Pc, G, h->ev_p0))) return rc;
         if (fused)
             TIMED_S(ST_PREDICT_GEMM, G, launch_ei_fused128(G, dev_kind(h), h->WT.d(), h->gamma.d(), h->Xs.d(), h->s1.d(), Cs, s2,
@@ -1370,9 +1387,12 @@ static int ei_run_impl(spx_handle* h, int32_t flags, bool factor_pending)
             TIMED_S(ST_PREDICT_GEMM, G, launch_predict_gemm(G, h->opt.gemm_variant, h->WT.d() + (size_t)h0 * nn, Kst_k,
                                                             h->gamma.d() + (size_t)h0 * Np, h->part_ss.d(),
                                                             h->part_bg.d(), Np, mc, nhb, S > 0 ? nhb : H, S > 0 ? 0 : h0,
-                                                            S > 0 ? h->gammaS.d() + (size_t)h0 * S * Np : nullptr, S,
+                                                            S > 0 ? gammaS_all + (size_t)h0 * S * Np : nullptr, S,
                                                             bgS_k, gemm_nlive));
-            if (S > 0)
+            if (ts)
+                TIMED_S(ST_TS_FINISH, G, launch_ts_finish(G, bgS_k, h->htab.d() + (size_t)h0 * SPX_HT, h->ts_pcand.d(), nrb, mc, nhb, S,
+                                                          c0, M, Mp, h0, h->ts_path.d()));
+            else if (S > 0)
                 TIMED_S(ST_EI_FINALIZE, G, launch_ei_finalize_fant(G, h->part_ss.d(), bgS_k,
                                                                    h->htab.d() + (size_t)h0 * SPX_HT,
                                                                    h->bests.d() + (size_t)h0 * S,
@@ -1406,15 +1426,20 @@ static int ei_run_impl(spx_handle* h, int32_t flags, bool factor_pending)
         TIMED(ST_EHVI, launch_ehvi(s, h->mom_m.d(), h->mom_v.d(), c->mom_m.d(), c->mom_v.d(), h->front_dev.d(),
                                    h->front_dev.d() + nstrips, nstrips, M, Mp, H, h->ei_draw.d()));
     }
-    TIMED(ST_MEAN_ARGMAX, {
+    if (ts)
+        TIMED(ST_TS_FINISH, launch_ts_argmin(s, h->ts_path.d(), M, Mp, H * S, h->ts_am_val.d(), (int64_t*)h->ts_am_idx.p,
+                                             h->ts_out_val.d(), (int64_t*)h->ts_out_idx.p, h->index_base));
+    else TIMED(ST_MEAN_ARGMAX, {
         launch_mean_argmax(s, h->ei_draw.d(), h->ei_mean.d(), M, Mp, H, h->am_val.d(), (int64_t*)h->am_idx.p, h->am_out_val.d(),
                            (int64_t*)h->am_out_idx.p, mirror, (const int*)h->info.p, n_info);
     });
     HIPCHK(hipEventRecord(t1, s));
     HIPCHK(hipStreamSynchronize(s));
     LAUNCHCHK();
-    h->best_val = mirror[0];
-    h->best_idx = ((const int64_t*)mirror)[1];
+    if (!ts) {
+        h->best_val = mirror[0];
+        h->best_idx = ((const int64_t*)mirror)[1];
+    }
     if (factor_pending) {
         std::vector<int> info((const int*)(mirror + 2), (const int*)(mirror + 2) + n_info);
         if ((rc = finish_factor(h, info, false, false))) return rc;
@@ -1427,6 +1452,7 @@ static int ei_run_impl(spx_handle* h, int32_t flags, bool factor_pending)
     }
     Held::Results r;
     r.time_only = time_only;         // (a time-only pass has no EI results: spx_get_best & co. refuse)
+    r.ts = ts;                       // (paths and priors, nothing else: every EI getter refuses)
     r.moments = keep_mom && S == 0 && !time_only;
     r.tmean = keep_mom && per_sec;   // (with fantasies the pass keeps no func_m / func_v, but mom_t is written all the same)
     r.con = constrained && keep_mom && !time_only;
@@ -2149,6 +2175,148 @@ int spx_loo(spx_handle* h, int32_t model, double* loo_mean, double* loo_var, dou
     return rc;
 }
 
+// Thompson sampling by pathwise conditioning (spx.h).  Every refusal is decided from the host's record and the caller's arrays
+// before a device is touched.  Then: the frequencies on the host (one IEEE operation each), one upload, the prior at the
+// observations (k_ts_prior), the right-hand sides (k_ts_rhs), Gamma through launch_gamma_multi, and the candidates through
+// ei_run_impl's S > 0 GEMM branch -- every chunk, draw group, stream count and the padding skip are that pass's -- with
+// k_ts_prior per chunk, k_ts_finish per work item and the per-path argmin behind the last one; ONE synchronisation.
+int spx_thompson(spx_handle* h, int32_t F, int32_t S, const double* omega_z, const double* chi, const double* phase,
+                 const double* w, const double* eps, int32_t per_draw, int64_t* idx_out, double* min_out)
+{
+#pragma clang fp contract(off)
+    if (!h) return fail(SPX_ERR_ARG, "spx_thompson: null handle");
+    if (h->multi) return fail(SPX_ERR_ARG, "spx_thompson: single-GPU handles only (multi-device handle)");
+    if (h->comm) return fail(SPX_ERR_ARG, "spx_thompson: single-GPU handles only (communicator attached)");
+    if (h->part_ph > 1 || h->part_M > 0) return fail(SPX_ERR_ARG, "spx_thompson: not available with a 2-D partition");
+    if (!h->held.has(Held::FACTOR)) return fail(SPX_ERR_ARG, "spx_thompson: call spx_factor first");
+    if (!h->held.has(Held::CAND)) return fail(SPX_ERR_ARG, "spx_thompson: no candidates set");
+    if (h->held.has(Held::FANT))
+        return fail(SPX_ERR_ARG, "spx_thompson: fantasies are held (the resident rows include pending points); clear them first");
+    if (F < 16 || F > SPX_TS_MAX_FEATURES || F % 16)
+        return fail(SPX_ERR_ARG, "spx_thompson: F=%d features (allowed: a multiple of 16 in 16 .. %d)", (int)F, SPX_TS_MAX_FEATURES);
+    if (S < 1 || S > SPX_TS_MAX_PATHS) return fail(SPX_ERR_ARG, "spx_thompson: S=%d paths (allowed: 1 .. %d)", (int)S, SPX_TS_MAX_PATHS);
+    const int kind = h->opt.cov_kind;
+    const bool matern = kind == SPX_COVAR_MATERN52 || kind == SPX_COVAR_MATERN32;
+    if (!omega_z || !phase || !w || !eps || !idx_out || !min_out || (matern && !chi))
+        return fail(SPX_ERR_ARG, "spx_thompson: omega_z, phase, w, eps, idx_out and min_out must not be NULL%s",
+                    matern ? " (nor chi under a Matern covariance)" : "");
+    for (int f = 0; f < F; ++f) {
+        if (matern && !(chi[f] > 0.0 && chi[f] <= 1.79769313486231570815e308))
+            return fail(SPX_ERR_ARG, "spx_thompson: chi[%d] = %g (must be finite and > 0)", f, chi[f]);
+        if (!(phase[f] >= 0.0 && phase[f] < 1.0))
+            return fail(SPX_ERR_ARG, "spx_thompson: phase[%d] = %g (must lie in [0, 1): the phase in turns)", f, phase[f]);
+    }
+    TsShape tsh;
+    tsh.N = h->N; tsh.M = h->M; tsh.Np = h->Np; tsh.D = h->D; tsh.H = h->H; tsh.S = S; tsh.F = F; tsh.per_draw = per_draw != 0;
+    const TsPlan tp = plan_ts(tsh);
+    if (!tp.fits)
+        return fail(SPX_ERR_ARG, "spx_thompson: H S Mp 8 = %d x %d x %lld x 8 bytes of paths (allowed: up to %lld bytes, H S <= 65535)",
+                    h->H, (int)S, (long long)tp.Mp, (long long)SPX_TS_MAX_PATH_BYTES);
+    if ((int64_t)h->hyp_host.size() != (int64_t)h->H * (3 + h->D))
+        return fail(SPX_ERR_ARG, "spx_thompson: internal error: the resident hypers do not match H / D");
+    int rc = ensure_init(h);
+    if (rc) return rc;
+    spx_drop(h, Held::RESULTS);      // the call overwrites them; the factor, the candidates and every setting stay
+    const int H = h->H, D = h->D, Dp = tp.Dp, Np = h->Np, hs = 3 + D;
+    const int64_t N = h->N, M = h->M;
+    // frequencies in turns, nu[d][f][j] = (omega_z[f][j] t_f) / (TWO_PI ls[d][j]) with t_f = sqrt(2 nu / chi_f) (1 for ARDSE / SE;
+    // SE: unit length scales), zero in the pad dimensions; scale_d = sqrt(2 amp2_d / F); sig_d = sqrt(noise_d + 1e-6 amp2_d)
+    std::vector<double> par(tp.par_doubles, 0.0);
+    double* nu = par.data();
+    double* ph = nu + (size_t)H * F * Dp;
+    double* scale = ph + F;
+    double* sig = scale + H;
+    const double two_nu = kind == SPX_COVAR_MATERN52 ? 5.0 : 3.0;
+    for (int f = 0; f < F; ++f) {
+        const double t = matern ? sqrt(two_nu / chi[f]) : 1.0;
+        for (int j = 0; j < D; ++j) {
+            const double num = omega_z[(size_t)f * D + j] * t;
+            for (int d = 0; d < H; ++d) {
+                const double ls = kind == SPX_COVAR_SE ? 1.0 : h->hyp_host[(size_t)d * hs + 3 + j];
+                nu[(size_t)d * F * Dp + ts_nu_index(f, j, Dp)] = num / (SPX_TS_TWO_PI * ls);
+            }
+        }
+        ph[f] = phase[f];
+    }
+    for (int d = 0; d < H; ++d) {
+        const double noise = h->hyp_host[(size_t)d * hs + 1], amp2 = h->hyp_host[(size_t)d * hs + 2];
+        const double two_amp2 = 2.0 * amp2, jit = 1e-6 * amp2;
+        scale[d] = sqrt(two_amp2 / (double)F);
+        sig[d] = sqrt(noise + jit);
+    }
+    if ((rc = h->ts_par.reserve(tp.par_doubles * 8))) return rc;
+    if ((rc = h->ts_w.reserve(tp.w_bytes))) return rc;
+    if ((rc = h->ts_eps.reserve(tp.eps_bytes))) return rc;
+    if ((rc = h->ts_pobs.reserve(tp.obs_bytes))) return rc;
+    if ((rc = h->ts_rhs.reserve(tp.obs_bytes))) return rc;
+    if ((rc = h->ts_gammaS.reserve(tp.gamma_bytes))) return rc;
+    if ((rc = h->ts_pcand.reserve(tp.path_bytes))) return rc;
+    if ((rc = h->ts_path.reserve(tp.path_bytes))) return rc;
+    const size_t nab = (size_t)H * S * ts_argmin_blocks(M);
+    if ((rc = h->ts_am_val.reserve(nab * 8))) return rc;
+    if ((rc = h->ts_am_idx.reserve(nab * 8))) return rc;
+    if ((rc = h->ts_out_val.reserve((size_t)H * S * 8))) return rc;
+    if ((rc = h->ts_out_idx.reserve((size_t)H * S * 8))) return rc;
+    h->ts_S = S; h->ts_F = F;
+    h->ts_w_stride = per_draw ? (size_t)S * F : 0;
+    hipStream_t s = h->stream;
+    stage_begin(h);
+    if ((rc = stage_h2d(h, h->ts_par.p, par.data(), tp.par_doubles * 8, s))) return rc;
+    if ((rc = stage_h2d(h, h->ts_w.p, w, tp.w_bytes, s))) return rc;
+    if ((rc = stage_h2d(h, h->ts_eps.p, eps, tp.eps_bytes, s))) return rc;
+    h->ev_used = 0;
+    const double* dpar = h->ts_par.d();
+    const size_t nnu = (size_t)H * F * Dp;
+    TIMED(ST_TS_PRIOR, {
+        launch_ts_prior(s, h->comp.d(), N, D, Dp, dpar, dpar + nnu, h->ts_w.d(), h->ts_w_stride, dpar + nnu + F, F, S, H, h->ts_pobs.d(), N, 0);
+        launch_ts_rhs(s, h->vals.d(), h->ts_pobs.d(), h->ts_eps.d(), per_draw ? (size_t)S * N : 0, dpar + nnu + F + H, N, S, H,
+                      h->ts_rhs.d());
+    });
+    for (int d = 0; d < H; ++d)      // Gamma_d = W_d (rhs_d - mean_d): what spx_set_fantasies does with its fantasy columns
+        TIMED(ST_GAMMA_ALPHA, launch_gamma_multi(s, h->WT.d() + (size_t)d * Np * Np, h->ts_rhs.d() + (size_t)d * S * N,
+                                                 h->htab.d() + (size_t)d * SPX_HT, h->ts_gammaS.d() + (size_t)d * S * Np, (int)N, Np, S));
+    if ((rc = ei_run_impl(h, 0, false, S))) {
+        (void)hipStreamSynchronize(h->stream);
+        (void)hipStreamSynchronize(h->stream2);
+        if (h->stream3) (void)hipStreamSynchronize(h->stream3);
+        (void)hipGetLastError();
+        return rc;
+    }
+    if ((rc = stage_d2h(h, idx_out, h->ts_out_idx.p, (size_t)H * S * 8, s))) return rc;
+    return stage_d2h(h, min_out, h->ts_out_val.p, (size_t)H * S * 8, s);
+}
+
+static int ts_getter_checks(spx_handle* h, const char* who, int32_t draw, int32_t sidx)
+{
+    if (!h) return fail(SPX_ERR_ARG, "%s: null handle", who);
+    if (h->multi) return fail(SPX_ERR_ARG, "%s: single-GPU handles only (multi-device handle)", who);
+    if (!h->held.results.ts) return fail(SPX_ERR_ARG, "%s: no sample paths are held (call spx_thompson first)", who);
+    if (draw < 0 || draw >= h->H) return fail(SPX_ERR_ARG, "%s: draw out of range", who);
+    if (sidx < 0 || sidx >= h->ts_S) return fail(SPX_ERR_ARG, "%s: path out of range", who);
+    return ensure_init(h);
+}
+
+int spx_get_thompson_path(spx_handle* h, int32_t draw, int32_t sidx, double* path)
+{
+    int rc = ts_getter_checks(h, "spx_get_thompson_path", draw, sidx);
+    if (rc) return rc;
+    if (!path) return fail(SPX_ERR_ARG, "spx_get_thompson_path: null output");
+    const int64_t Mp = round_up(h->M, SPX_BN);
+    HIPCHK(hipMemcpy(path, h->ts_path.d() + ((size_t)draw * h->ts_S + sidx) * Mp, (size_t)h->M * 8, hipMemcpyDeviceToHost));
+    return SPX_OK;
+}
+
+int spx_get_thompson_prior(spx_handle* h, int32_t draw, int32_t sidx, double* prior_cand, double* prior_obs)
+{
+    int rc = ts_getter_checks(h, "spx_get_thompson_prior", draw, sidx);
+    if (rc) return rc;
+    const int64_t Mp = round_up(h->M, SPX_BN);
+    const size_t p = (size_t)draw * h->ts_S + sidx;
+    if (prior_cand) HIPCHK(hipMemcpy(prior_cand, h->ts_pcand.d() + p * Mp, (size_t)h->M * 8, hipMemcpyDeviceToHost));
+    if (prior_obs) HIPCHK(hipMemcpy(prior_obs, h->ts_pobs.d() + p * h->N, (size_t)h->N * 8, hipMemcpyDeviceToHost));
+    return SPX_OK;
+}
+
 int spx_get_stat(spx_handle* h, const char* name, int64_t* value)
 {
     if (!h || !name || !value) return fail(SPX_ERR_ARG, "spx_get_stat: null");
@@ -2178,6 +2346,8 @@ int spx_get_stat(spx_handle* h, const char* name, int64_t* value)
     else if (!strcmp(name, "last_effects_rows")) *value = h->effects_plan.rows;      // ... and how many rows that were
     else if (!strcmp(name, "last_mes_samples")) *value = h->held.results.mes ? h->mes_K : 0;   // K and
     else if (!strcmp(name, "last_mes_grid")) *value = h->held.results.mes ? h->mes_J : 0;      // ... J of the held MES results (0: none)
+    else if (!strcmp(name, "last_ts_paths")) *value = h->held.results.ts ? h->ts_S : 0;        // S and
+    else if (!strcmp(name, "last_ts_features")) *value = h->held.results.ts ? h->ts_F : 0;     // ... F of the held sample paths (0: none)
     else if (!strcmp(name, "gemm_lds_bytes")) *value = (int64_t)predict_gemm_lds_bytes();   // dynamic LDS of a predict-GEMM workgroup (two are resident per CU)
     else if (!strcmp(name, "hip_runtime_version") || !strcmp(name, "hip_driver_version")) {
         // what the process runs on: a measurement names it (bench.py's line), two boxes of one pool differed in round 5

@@ -20,6 +20,8 @@ struct HeldResults {
                                // spx_ei_grad_batch under SPX_ACQ_MES); gone with the results, so with everything that drops them
     bool ehvi = false;         // the pass was an expected-hypervolume-improvement pass: the second GP's func_m / func_v of the same
                                // candidates are resident on its internal handle (spx_get_moments, draws H .. 2H-1)
+    bool ts = false;           // the "pass" was spx_thompson: what is resident are posterior sample paths and their priors
+                               // (spx_get_thompson_path / _prior), a results kind of its own -- no EI values, no winner
 };
 
 struct Held {
@@ -40,7 +42,7 @@ struct Held {
     Results results;
 
     bool has(Thing x) const { return (bits >> x) & 1u; }
-    bool ei() const { return has(RESULTS) && !results.time_only; }    // EI results, not durations only
+    bool ei() const { return has(RESULTS) && !results.time_only && !results.ts; }   // EI results, not durations or paths only
     inline void drop(Thing x);                                        // clears x and everything made from it; never adds a bit
     inline bool set(Thing x, Results r = Results());                  // false (nothing changes): a thing x needs is not held
 };

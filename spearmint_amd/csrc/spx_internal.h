@@ -94,6 +94,8 @@ enum Stage {
     ST_COV_CROSS, ST_CROSS_MEAN, ST_PREDICT_GEMM, ST_EI_FINALIZE, ST_MEAN_ARGMAX,
     ST_MES,               // the four kernels of a max-value entropy search pass (launch_mes), as one stage
     ST_EHVI,              // k_ehvi of an expected-hypervolume-improvement pass (launch_ehvi)
+    ST_TS_PRIOR,          // spx_thompson: k_ts_prior over the observations and over every candidate chunk (+ k_ts_rhs)
+    ST_TS_FINISH,         // ... and k_ts_finish per work item + the two k_ts_argmin launches
     ST_FACTOR_TOTAL, ST_EI_RUN_TOTAL, ST_COUNT
 };
 struct spx_handle {
@@ -180,6 +182,15 @@ struct spx_handle {
     std::vector<double> front_a, front_b;
     DevBuf front_dev;
     spx_handle* sec = nullptr;
+    // Thompson sampling (spx_thompson): frequencies nu [H][F Dp] (operand order) | phase [F] | scale [H] | sig [H]; w and eps as uploaded; the
+    // prior at the observations [H][S][N], the right-hand sides [H][S][N] and their Gamma [H][S][Np]; the prior at the candidates
+    // and the paths, [H][S][Mp] each; the argmin's partials and results.  ts_S / ts_F: sizes of the held paths (RESULTS with
+    // held.results.ts), 0 otherwise
+    DevBuf ts_par, ts_w, ts_eps, ts_pobs, ts_rhs, ts_gammaS, ts_pcand, ts_path, ts_am_val, ts_am_idx, ts_out_val, ts_out_idx;
+    int ts_S = 0, ts_F = 0;
+    int64_t ts_fant_budget = 0;    // the per-path partial means' byte budget, as fant_budget / fant_budget_S are the fantasies'
+    int ts_fant_budget_S = -1;
+    size_t ts_w_stride = 0;        // doubles between the draws' blocks of w (0: shared)
     DevBuf loo_out;                                                 // spx_loo: loo_mean | loo_var | kinv_diag, [3][H][N]; scratch of that call, not part of `held`
     // probit constraint model (spx_set_constraint_model): an internal handle on the same device factors
     // (amp2_c (K_c + 1e-6 I) + noise_c I) alpha_c = ff over its own Nc points; the EI pass reads its scaled rows and alpha_c

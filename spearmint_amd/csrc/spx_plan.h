@@ -323,6 +323,43 @@ inline EiPlan plan_ei(const Options& o, const EiShape& s)
     return p;
 }
 
+// ---- Thompson sampling (spx_thompson) -------------------------------------------------------------------------------
+// The call runs the EI pass's S > 0 GEMM branch (plan_ei with S = the paths per draw and no flags: chunks, draw groups, slots
+// and the per-fantasy partial sums are that plan's) with right-hand sides of its own; what it holds beside that plan's buffers
+// is decided here, next to the fantasy buffers' sizes.
+#define SPX_TS_MAX_PATH_BYTES (4ll << 30)     // H S Mp 8 of one call; beyond it spx_thompson refuses
+struct TsShape {
+    int64_t N = 0, M = 0;
+    int Np = 0, D = 0, H = 0, S = 0, F = 0;
+    bool per_draw = false;
+};
+struct TsPlan {
+    int64_t Mp = 0;
+    int Dp = 0, sblocks = 0;                // blocks of 16 paths: k_ts_prior forms the features once per block
+    size_t par_doubles = 0;                 // nu [H][F Dp] | phase [F] | scale [H] | sig [H], one upload
+    size_t w_bytes = 0, eps_bytes = 0;      // the caller's normals as uploaded ([H or 1][S][F], [H or 1][S][N])
+    size_t obs_bytes = 0;                   // the prior at the observations, and the right-hand sides: [H][S][N] each
+    size_t gamma_bytes = 0;                 // Gamma [H][S][Np], the layout of launch_gamma_multi
+    size_t path_bytes = 0;                  // the prior at the candidates, and the paths: [H][S][Mp] each
+    bool fits = false;                      // path_bytes <= SPX_TS_MAX_PATH_BYTES and the per-path launches' grids (H S <= 65535)
+};
+inline TsPlan plan_ts(const TsShape& s)
+{
+    TsPlan p;
+    p.Mp = round_up(s.M, SPX_BN);
+    p.Dp = padded_dim(s.D);
+    p.sblocks = (s.S + 15) / 16;
+    const size_t nd = s.per_draw ? (size_t)s.H : 1;
+    p.par_doubles = (size_t)s.H * s.F * p.Dp + (size_t)s.F + 2 * (size_t)s.H;
+    p.w_bytes = nd * s.S * s.F * 8;
+    p.eps_bytes = nd * s.S * (size_t)s.N * 8;
+    p.obs_bytes = (size_t)s.H * s.S * (size_t)s.N * 8;
+    p.gamma_bytes = (size_t)s.H * s.S * (size_t)s.Np * 8;
+    p.path_bytes = (size_t)s.H * s.S * (size_t)p.Mp * 8;
+    p.fits = (int64_t)s.H * s.S <= 65535 && (double)s.H * s.S * (double)p.Mp * 8.0 <= (double)SPX_TS_MAX_PATH_BYTES;
+    return p;
+}
+
 // ---- the main-effects report (spx_main_effects) ---------------------------------------------------------------------
 // (D T + 1) Q structured rows go through ordinary EI passes with the moments kept; the rows of a pass are formed on the
 // device, the kept means are reduced on the device.  What is decided here: how many rows a pass takes (option

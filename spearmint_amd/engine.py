@@ -145,6 +145,10 @@ ABI = {
                                               _c_double_p, _c_double_p, _c_double_p, _c_int64_p]),
     "spx_rng_draw": (ctypes.c_int, [ctypes.POINTER(RngState), ctypes.c_int32, _c_double_p, ctypes.c_int32, _c_double_p,
                                     ctypes.c_int32, _c_int32_p]),
+    "spx_thompson": (ctypes.c_int, [_vp, ctypes.c_int32, ctypes.c_int32, _c_double_p, _c_double_p, _c_double_p, _c_double_p,
+                                    _c_double_p, ctypes.c_int32, _c_int64_p, _c_double_p]),
+    "spx_get_thompson_path": (ctypes.c_int, [_vp, ctypes.c_int32, ctypes.c_int32, _c_double_p]),
+    "spx_get_thompson_prior": (ctypes.c_int, [_vp, ctypes.c_int32, ctypes.c_int32, _c_double_p, _c_double_p]),
     "spx_get_timings": (ctypes.c_int, [_vp, _c_double_p, _c_int64_p, ctypes.c_int]),
     "spx_get_stat": (ctypes.c_int, [_vp, ctypes.c_char_p, ctypes.POINTER(ctypes.c_int64)]),
     "spx_timing_name": (ctypes.c_char_p, [ctypes.c_int]),
@@ -213,6 +217,32 @@ def _sampler_result(lib, rc, rows, stats):
         err = SpxError(msg)
     err.rows_done, err.stats = rows[:st["iterations"]], st
     raise err
+
+
+TS_MAX_FEATURES = 8192
+TS_MAX_PATHS = 256
+TS_CHI_DOF = {"Matern52": 5, "Matern32": 3}      # 2 nu: the chi-square law of the Matern spectral density's mixing variable
+
+
+def thompson_randoms(rng, covar, D, H, N, F, S, per_draw=False):
+    """The base randoms of one spx_thompson call (include/spx.h), drawn from a numpy.random.RandomState (None: numpy's global
+    one) in this order -- tests and tests/ts_oracle.py share it:
+        omega_z = randn(F, D)
+        chi     = chisquare(2 nu, F)      Matern52: 5 degrees of freedom, Matern32: 3; NOT drawn for ARDSE / SE (chi = None)
+        phase   = rand(F)                 the phase in turns, [0, 1)
+        w       = randn([H,] S, F)        the leading H only with per_draw
+        eps     = randn([H,] S, N)
+    Returns a dict with those five entries."""
+    r = np.random if rng is None else rng
+    if covar not in COVAR:
+        raise AttributeError("no covariance function %r (gp.py has %s)" % (covar, ", ".join(sorted(COVAR))))
+    lead = (int(H),) if per_draw else ()
+    out = {"omega_z": r.randn(int(F), int(D))}
+    out["chi"] = r.chisquare(TS_CHI_DOF[covar], int(F)) if covar in TS_CHI_DOF else None
+    out["phase"] = r.rand(int(F))
+    out["w"] = r.randn(*(lead + (int(S), int(F))))
+    out["eps"] = r.randn(*(lead + (int(S), int(N))))
+    return out
 
 
 def effects_summary(levels, curves, base_mean):
@@ -298,6 +328,7 @@ class Engine(object):
             self.device = int(device)
             self.devices = [self.device]
         self.N = self.M = self.D = self.H = 0
+        self.covar = "Matern52"   # the gp.py name of option "covar" (thompson draws the spectral law that belongs to it)
         self._y = {}        # host copies of what the resident models were given to fit: "objective" / "time" -> (N,) (loo)
 
     @property
@@ -420,6 +451,8 @@ class Engine(object):
 
     def set_option(self, name, value):
         self._check(self._lib.spx_set_option(self._h, name.encode("ascii"), int(value)))
+        if name == "covar":
+            self.covar = [k for k, v in COVAR.items() if v == int(value)][0]
 
     def set_covar(self, name):
         """The GP's correlation function by its gp.py name (the choosers' covar=)."""
@@ -527,6 +560,41 @@ class Engine(object):
         b = np.empty(S)
         self._check(self._lib.spx_get_pending_fantasies(self._h, int(draw), _dp(pf), _dp(b)))
         return pf, b
+
+    def thompson(self, S=1, F=1024, rng=None, per_draw=False, randoms=None):
+        """S posterior sample paths per resident draw over the resident candidates by pathwise conditioning on F random
+        Fourier features (include/spx.h: spx_thompson).  The base randoms come from thompson_randoms(rng, ...) (rng None:
+        numpy's global generator) or, given, from `randoms` (a dict of that function's layout).  Returns (idx (H, S): each
+        path's grid argmin with index_base added, min (H, S): that minimum, the randoms).  The paths stay resident
+        (thompson_path / thompson_prior) until something drops the results of a pass; best() & co. refuse meanwhile."""
+        S, F = int(S), int(F)
+        if randoms is None:
+            randoms = thompson_randoms(rng, self.covar, self.D, self.H, self.N, F, S, per_draw)
+        lead = (self.H,) if per_draw else ()
+        oz = _f64(randoms["omega_z"], (F, self.D))
+        chi = None if randoms.get("chi") is None else _f64(randoms["chi"], (F,))
+        ph = _f64(randoms["phase"], (F,))
+        w = _f64(randoms["w"], lead + (S, F))
+        eps = _f64(randoms["eps"], lead + (S, self.N))
+        idx = np.empty((max(self.H, 1), S), dtype=np.int64)
+        mn = np.empty((max(self.H, 1), S))
+        self._check(self._lib.spx_thompson(self._h, F, S, _dp(oz), None if chi is None else _dp(chi), _dp(ph), _dp(w), _dp(eps),
+                                           1 if per_draw else 0, idx.ctypes.data_as(_c_int64_p), _dp(mn)))
+        return idx, mn, randoms
+
+    def thompson_path(self, d, s):
+        """Sample path s of draw d over the resident candidates, (M,), as the last thompson() left it."""
+        out = np.empty(self.M)
+        self._check(self._lib.spx_get_thompson_path(self._h, int(d), int(s), _dp(out)))
+        return out
+
+    def thompson_prior(self, d, s):
+        """(prior at the candidates (M,), prior at the observations (N,)) of path s of draw d: the random-Fourier-feature
+        prior sample p_{d,s} of the last thompson()."""
+        pc = np.empty(self.M)
+        po = np.empty(self.N)
+        self._check(self._lib.spx_get_thompson_prior(self._h, int(d), int(s), _dp(pc), _dp(po)))
+        return pc, po
 
     def ei_run(self, flags=0):
         self._check(self._lib.spx_ei_run(self._h, int(flags)))
@@ -847,3 +915,6 @@ class MultiEngine(Engine):
 
     def loo(self, model="objective"):
         raise ValueError("loo is not available on a multi-device engine (include/spx.h: spx_loo)")
+
+    def thompson(self, S=1, F=1024, rng=None, per_draw=False, randoms=None):
+        raise ValueError("thompson is not available on a multi-device engine (include/spx.h: spx_thompson)")
