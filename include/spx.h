@@ -354,7 +354,32 @@ int spx_get_pareto_front(spx_handle* h, double* a, double* b, int32_t* n, double
  * REFUSED with SPX_ERR_ARG before any device is touched, the handle as it was: no held factorisation or no candidates; fantasies
  * held; a multi-device handle, a communicator or a 2-D partition; F or S out of range; a NULL pointer where one is read; a chi
  * that is not finite and > 0; a phase outside [0, 1); H S Mp 8 bytes (Mp = M rounded up to 128) above 4 GiB, or H S > 65535.
- * spx_ei_grad_batch does not know paths: the gradient of a path is out of scope.                                            */
+ *
+ * spx_thompson_grad_batch: value and gradient of held paths OFF the grid.  A path is a closed-form function of x,
+ *     f_{d,s}(x) = mean_d + p_{d,s}(x) + k_d(x, X)' alpha_{d,s},      alpha_{d,s} = W_d^T Gamma_{d,s} = (K + sig^2 I)^-1 (rhs - mean),
+ * and everything it needs is resident after spx_thompson.  Point p is evaluated under path path_of[p] = draw * S + s (NULL: path 0 of
+ * draw 0 for every point).  The arithmetic, a contract in the same sense as above:
+ *   prior      spx_thompson's own arithmetic -- the dot product on v_mfma_f64_16x16x4_f64 in k_ts_prior's order, ONE addition of the
+ *              phase, r = u - rint(u), cos2pi, the contraction with the path's weights 16 features at a time on the MFMA, ONE
+ *              multiplication by scale_d -- so at a point whose coordinates equal a resident candidate row (or observation row)
+ *              `prior` equals spx_get_thompson_prior's entry BIT FOR BIT
+ *   its gradient
+ *              gp[j] = -(scale_d * TWO_PI) * sum_f nu[d][f][j] * (w[s][f] * sin2pi(r_f)),  sin2pi the polynomial of csrc/ts_device.h
+ *              (SPX_TS_SIN_ULPS = 4 ulp of the result); the sum over f in a fixed order of the kernel's own (on the MFMA)
+ *   update     m = sum_j k_j alpha_j with k and dk/dr^2 exactly as spx_ei_grad_batch forms them (the expanded r^2, the clamp at 0,
+ *              the three correlation kinds, SE = ARDSE on unit length scales);  gu[j'] = sum_j (dk_j / dx_j') alpha_j, the TRUE
+ *              partial derivative: no factor one half (a path is not an acquisition of the reference and inherits no scaling).
+ *              alpha is built for all H S held paths by the first call after a spx_thompson and kept with the paths
+ *   result     value = (m + mean_d) + prior,  grad[j] = gu[j] + gp[j], one rounding each.  grad is d value / d x: a minimiser of the
+ *              path takes (value, grad) as they are.  Every point is computed by its own threads in a fixed order: its numbers do
+ *              not depend on P, on its position in the batch, on the other points' paths or on how many paths and draws are
+ *              resident.  A NaN or infinite coordinate gives NaN value and gradient for that point alone.
+ * State: a reader.  Paths, priors, factorisation, candidates, options and the acquisition setting stay bit for bit (an EI pass
+ * afterwards gives the bits it gave before); the cached alpha lives with the paths -- whatever drops a pass's results drops it.
+ * After the first call: two kernel launches and one host synchronisation per call, no allocation once the buffers have grown.
+ * REFUSED with SPX_ERR_ARG before any device is touched, the handle as it was: no sample paths held (a multi-device handle, a
+ * communicator or a 2-D partition cannot hold any); points, value or grad NULL; P < 1 or P > SPX_TS_GRAD_MAX_POINTS (the most a
+ * launch grid of spx_ei_grad_batch takes); a path_of entry outside 0 .. H S - 1.                                              */
 #define SPX_TS_MAX_FEATURES 8192
 #define SPX_TS_MAX_PATHS    256
 int spx_thompson(spx_handle* h,
@@ -372,6 +397,11 @@ int spx_thompson(spx_handle* h,
 int spx_get_thompson_path (spx_handle* h, int32_t draw, int32_t s, double* path /* M */);
 int spx_get_thompson_prior(spx_handle* h, int32_t draw, int32_t s,
                            double* prior_cand /* M */, double* prior_obs /* N */);  /* either may be NULL */
+#define SPX_TS_GRAD_MAX_POINTS 65535
+int spx_thompson_grad_batch(spx_handle* h, const double* points /* P x D */,
+                            const int32_t* path_of /* P: draw * S + s of each point; NULL: path 0 of draw 0 for all */,
+                            int32_t P, double* value /* P */, double* grad /* P x D */,
+                            double* prior /* P, may be NULL: p_{d,s}(x) alone */);
 
 /* Hot path, stage 2: K(X*,X) (:187), triangular solve (:195), predictive
  * mean/variance (:198-199), EI (:202-206) for every (candidate, draw); then the

@@ -31,6 +31,7 @@ class GPEIOptChooser(GPEIBase):
     noiseless_checks_mean = True    # :685-686
     max_ls = 2
     ts_allowed = True               # acq=TS: the grid argmin of one posterior sample path (_base.py: _thompson_gpu)
+    ts_refine_allowed = True        # ts_refine=1: ... minimised off the grid from its grid_subset lowest rows (_thompson_refine)
 
     def __init__(self, expt_dir, covar="Matern52", mcmc_iters=10, pending_samples=100,
                  noiseless=False, burnin=100, grid_subset=20, use_multiprocessing=True, rescore_grid=0, **kw):
@@ -45,7 +46,7 @@ class GPEIOptChooser(GPEIBase):
         self.use_multiprocessing = _as_bool(use_multiprocessing)
         self.rescore_grid = _as_bool(rescore_grid)   # 1: score [grid; refined] again in the second pass, as the reference does
         # the host refinement (gpu_refine=0, or SPX_REFINE_MIN_N keeping the first proposals on the host) knows EI alone
-        if self.acq not in ("EI", "TS") and not self._use_gpu_refine(0):      # (acq=TS proposes a grid point: nothing is refined)
+        if self.acq not in ("EI", "TS") and not self._use_gpu_refine(0):      # (acq=TS: the path's own objective, on the GPU always)
             raise ValueError("acq=%s needs the refinement on the GPU at every size (allowed with gpu_refine=0 or "
                              "SPX_REFINE_MIN_N > 0: acq=EI)" % self.acq)
         self.hyper_samples = []
@@ -212,6 +213,33 @@ class GPEIOptChooser(GPEIBase):
             out[i, :] = spo.fmin_l_bfgs_b(objective, out[i, :].flatten(), bounds=bounds, disp=0)[0]
         return out
 
+    # -- acq=TS, ts_refine=1 ----------------------------------------------------------
+    def _thompson_refine(self, cand, idx):
+        """The sample path _thompson_gpu left resident, minimised off the grid: L-BFGS-B from its grid_subset lowest rows
+        (stable order) with Engine.thompson_grad_batch as the objective, all instances in one call per step
+        (refine.lbfgs_many).  The refined points and the grid's winner are then valued together by that one function, and a
+        refined point displaces the winner only if it is STRICTLY lower -- the MES rule, for the same reason: a point the
+        optimiser did not move is a copy of a grid row with the row's value, and keeps its index.  A path with a NaN proposes
+        the grid index (numpy's rule: the first NaN).  Draws no random numbers.  Returns None (the grid index stands) or x."""
+        eng = self.engine()
+        path = np.asarray(eng.thompson_path(0, 0), dtype=float)
+        t = self.last_thompson
+        t.update({"refined": False, "x": np.array(cand[idx], dtype=float, copy=True), "value": float(path[idx])})
+        if np.isnan(path).any():
+            return None
+        keep = np.argsort(path, kind="stable")[:self.grid_subset]
+        refined = refine.lbfgs_many(eng.thompson_grad_batch, cand[keep, :], [(0, 1)] * cand.shape[1], log=log)
+        f_all, _ = eng.thompson_grad_batch(np.vstack((refined, cand[idx:idx + 1])))
+        f_all = np.asarray(f_all, dtype=float)
+        t["value"] = float(f_all[-1])
+        if refined.shape[0] == 0:
+            return None
+        k = int(np.argmin(f_all[:-1]))
+        if not f_all[k] < f_all[-1]:
+            return None
+        t.update({"refined": True, "x": np.array(refined[k], dtype=float, copy=True), "value": float(f_all[k])})
+        return t["x"]
+
     # -- plugin entry ---------------------------------------------------------------
     def next(self, grid, values, durations, candidates, pending, complete):
         if complete.shape[0] < 2:
@@ -241,9 +269,11 @@ class GPEIOptChooser(GPEIBase):
 
         if self.acq == "TS":
             # Thompson sampling: the argmin of ONE sample path over the grid.  No sprayed points (their normals above are drawn
-            # all the same: the generator is where an acq=EI call leaves it at this point), no pending fantasies, and no
-            # L-BFGS-B refinement -- the gradient of a path is not part of the library (include/spx.h: spx_thompson).
-            job = int(candidates[self._thompson_gpu(comp, cand, vals, rows)])
+            # all the same: the generator is where an acq=EI call leaves it at this point) and no pending fantasies.
+            # ts_refine=1: the path is then minimised off the grid (include/spx.h: spx_thompson_grad_batch).
+            idx = self._thompson_gpu(comp, cand, vals, rows)
+            x = self._thompson_refine(cand, idx) if self.ts_refine else None
+            job = int(candidates[idx]) if x is None else (int(numcand), x)
             if self.recommend:
                 self._recommend(grid, comp, vals, rows, refine_count=self.grid_subset)
             if self.importance:

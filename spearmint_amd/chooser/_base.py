@@ -50,6 +50,7 @@ class GPEIBase(object):
     #                                a call of its own; GPEIChooser and GPEIOptChooser switch it on
     mes_default_levels = 10        # acq=MES with acq_par=0: K, the number of y* levels
     ts_default_features = 1024     # acq=TS with acq_par=0: F, the random Fourier features of the prior sample
+    ts_refine_allowed = False      # ts_refine=1: the sample path is minimised off the grid (GPEIOptChooser switches it on)
     recommend_allowed = True       # recommend=1: the model-mean recommendation after every proposal (_recommend)
     importance_allowed = True      # importance=1: the parameter-sensitivity report after every proposal (_importance)
     importance_max_points = 128 << 12   # include/spx.h: Q of spx_main_effects
@@ -58,7 +59,7 @@ class GPEIBase(object):
     def __init__(self, expt_dir, covar="Matern52", mcmc_iters=10, pending_samples=100,
                  noiseless=False, device=0, ndev=1, lib=None, gpu_logprob="auto", gpu_refine="auto",
                  lookahead="auto", follow="auto", sampler="native", gpu_sobol=0, gpu_fantasies="auto", acq="EI", acq_par=0,
-                 recommend=0, importance=0, importance_levels=16, importance_points=256, loo=0, **unused):
+                 recommend=0, importance=0, importance_levels=16, importance_points=256, loo=0, ts_refine=0, **unused):
         if covar not in hostgp.COVARS:
             # the reference does getattr(gp, covar) here (GPEIChooser.py:52)
             raise AttributeError("no covariance function %r (gp.py has %s)" % (covar, ", ".join(hostgp.COVARS)))
@@ -70,8 +71,15 @@ class GPEIBase(object):
         if self.acq == "TS" and int(ndev) > 1:
             raise ValueError("acq=TS is not available with ndev=%d: a sample path is drawn over every candidate on one "
                              "device (allowed: ndev=1, or acq=EI, PI, LCB)" % int(ndev))
+        self.ts_refine = _as_bool(ts_refine)
+        if self.ts_refine and not self.ts_refine_allowed:
+            raise ValueError("ts_refine=1 is not available on %s (allowed: ts_refine=0; GPEIOptChooser refines a sample path)"
+                             % type(self).__name__)
+        if self.ts_refine and self.acq != "TS":
+            raise ValueError("ts_refine=1 refines the sample path of acq=TS (allowed with acq=%s: ts_refine=0)" % self.acq)
         self.last_acq_used = None      # the acquisition that scored the last call ("EI" under acq=MES while jobs are pending)
-        self.last_thompson = None      # acq=TS: {"draw", "grid_index", "path_min", "features"} of the last call
+        self.last_thompson = None      # acq=TS: {"draw", "grid_index", "path_min", "features"} of the last call; with
+        #                                ts_refine=1 also {"refined", "x", "value"}
         self.recommend = _as_bool(recommend)
         if self.recommend and not self.recommend_allowed:
             raise ValueError("recommend=1 is not available on %s (allowed: recommend=0)" % type(self).__name__)

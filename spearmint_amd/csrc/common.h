@@ -202,6 +202,17 @@ int ts_argmin_blocks(int64_t M);
 void launch_ts_argmin(hipStream_t s, const double* path, int64_t M, int64_t Mp, int npaths, double* blk_val, int64_t* blk_idx,
                       double* out_val, int64_t* out_idx, int64_t index_base);
 
+// ts_grad_kernels.hip: value and gradient of sample paths at points x [P][D], point p under path path_of[p] = draw S + s (null:
+// path 0 of draw 0) (spx.h: spx_thompson_grad_batch).  The prior and its gradient into prior [P] and gp [P][D]; then, one
+// workgroup per point, the update term against alpha [H S][Np] and the combine into out [P][2 + D] = {value, prior, grad};
+// dkw [P][Np]: work vector
+void launch_ts_grad_prior(hipStream_t s, const double* x, const int32_t* path_of, int P, int D, int Dp, const double* nu,
+                          const double* phase, const double* w, size_t w_stride, const double* scale, int F, int S, int H,
+                          double* prior, double* gp);
+void launch_ts_grad_update(hipStream_t s, const double* Xs, const double* s1, const double* hyp, const double* htab,
+                           const double* alpha, const double* x, const int32_t* path_of, const double* prior, const double* gp,
+                           double* dkw, double* out, int N, int Np, int D, int Dp, int S, int P, int kind);
+
 // predict_kernels.hip
 void launch_predict_gemm(hipStream_t s, int variant, const double* WT, const double* Kst, const double* gamma,
                          double* part_ss, double* part_bg, int Np, int Mc, int nh, int part_nh, int part_h0,

@@ -316,7 +316,8 @@ void spx_destroy(spx_handle* h)
                           &h->con_tab, &h->mom_c, &h->rhs_rows, &h->eff_in, &h->eff_m, &h->eff_out, &h->loo_out,
                           &h->mes_bpart, &h->mes_part, &h->mes_G, &h->mes_ystar, &h->mes_fit, &h->front_dev,
                           &h->ts_par, &h->ts_w, &h->ts_eps, &h->ts_pobs, &h->ts_rhs, &h->ts_gammaS, &h->ts_pcand, &h->ts_path,
-                          &h->ts_am_val, &h->ts_am_idx, &h->ts_out_val, &h->ts_out_idx};
+                          &h->ts_am_val, &h->ts_am_idx, &h->ts_out_val, &h->ts_out_idx,
+                          &h->ts_alpha, &h->ts_gin, &h->ts_gwork, &h->ts_gout};
         for (DevBuf* b : bufs) b->release();
         h->pin_up.release();
         h->pin_res.release();
@@ -2314,6 +2315,78 @@ int spx_get_thompson_prior(spx_handle* h, int32_t draw, int32_t sidx, double* pr
     const size_t p = (size_t)draw * h->ts_S + sidx;
     if (prior_cand) HIPCHK(hipMemcpy(prior_cand, h->ts_pcand.d() + p * Mp, (size_t)h->M * 8, hipMemcpyDeviceToHost));
     if (prior_obs) HIPCHK(hipMemcpy(prior_obs, h->ts_pobs.d() + p * h->N, (size_t)h->N * 8, hipMemcpyDeviceToHost));
+    return SPX_OK;
+}
+
+// Value and gradient of held sample paths at a batch of points (spx.h).  A reader: every refusal comes from the host's record
+// and the caller's arrays; alpha = W^T Gamma of every held path is built once per spx_thompson (launch_trimvT_multi over
+// ts_gammaS) and kept with the results.  After that a call is one staged upload, k_ts_grad_prior, k_ts_grad_update, one
+// download and ONE synchronisation.
+int spx_thompson_grad_batch(spx_handle* h, const double* points, const int32_t* path_of, int32_t P, double* value, double* grad,
+                            double* prior)
+{
+    if (!h) return fail(SPX_ERR_ARG, "spx_thompson_grad_batch: null handle");
+    if (h->multi || !h->held.results.ts)
+        return fail(SPX_ERR_ARG, "spx_thompson_grad_batch: no sample paths are held (call spx_thompson first)");
+    if (!points || !value || !grad) return fail(SPX_ERR_ARG, "spx_thompson_grad_batch: points, value and grad must not be NULL");
+    if (P < 1 || P > SPX_TS_GRAD_MAX_POINTS)
+        return fail(SPX_ERR_ARG, "spx_thompson_grad_batch: P=%d points (allowed: 1 .. %d)", (int)P, SPX_TS_GRAD_MAX_POINTS);
+    const int H = h->H, D = h->D, Dp = h->Dp, Np = h->Np, S = h->ts_S, F = h->ts_F;
+    if (path_of)
+        for (int p = 0; p < P; ++p)
+            if (path_of[p] < 0 || path_of[p] >= H * S)
+                return fail(SPX_ERR_ARG, "spx_thompson_grad_batch: path_of[%d] = %d (allowed: 0 .. H S - 1 = %d)", p, (int)path_of[p],
+                            H * S - 1);
+    int rc = ensure_init(h);
+    if (rc) return rc;
+    hipStream_t s = h->stream;
+    const size_t x_bytes = (size_t)P * D * 8, in_bytes = x_bytes + (path_of ? (size_t)P * 4 : 0);
+    const size_t out_doubles = (size_t)P * (2 + D);
+    if ((rc = h->ts_gin.reserve(in_bytes))) return rc;
+    if ((rc = h->ts_gwork.reserve(((size_t)P * (1 + D) + (size_t)P * Np) * 8))) return rc;
+    if ((rc = h->ts_gout.reserve(out_doubles * 8))) return rc;
+    // inputs and outputs share the pinned staging buffer, the outputs behind the inputs: nothing waits for the upload alone
+    const size_t stage_in = ((x_bytes + 255) & ~(size_t)255) + (((size_t)P * 4 + 255) & ~(size_t)255);
+    const bool one_stage = h->opt.stage_copies != 0 && stage_in + out_doubles * 8 <= SPX_STAGE_MAX;
+    if (one_stage && (rc = h->pin_stage.reserve(std::max<size_t>(stage_in + out_doubles * 8, 1u << 20)))) return rc;
+    const bool build_alpha = !h->held.results.ts_alpha;
+    if (build_alpha) {
+        if ((rc = h->ts_alpha.reserve((size_t)H * S * Np * 8))) return rc;
+        launch_trimvT_multi(s, h->WT.d(), h->ts_gammaS.d(), h->ts_alpha.d(), Np, H, S);
+    }
+    stage_begin(h);
+    double* dx = h->ts_gin.d();
+    const int32_t* dpath = path_of ? (const int32_t*)((const char*)h->ts_gin.p + x_bytes) : nullptr;
+    if ((rc = stage_h2d(h, dx, points, x_bytes, s))) return rc;
+    if (path_of && (rc = stage_h2d(h, (void*)dpath, path_of, (size_t)P * 4, s))) return rc;
+    const double* par = h->ts_par.d();
+    const size_t nnu = (size_t)H * F * Dp;
+    double* d_prior = h->ts_gwork.d();
+    double* d_gp = d_prior + P;
+    double* d_dk = d_gp + (size_t)P * D;
+    launch_ts_grad_prior(s, dx, dpath, P, D, Dp, par, par + nnu, h->ts_w.d(), h->ts_w_stride, par + nnu + F, F, S, H, d_prior, d_gp);
+    launch_ts_grad_update(s, h->Xs.d(), h->s1.d(), h->hyp.d(), h->htab.d(), h->ts_alpha.d(), dx, dpath, d_prior, d_gp, d_dk,
+                          h->ts_gout.d(), (int)h->N, Np, D, Dp, S, P, dev_kind(h));
+    std::vector<double> pageable;
+    const double* out;
+    if (one_stage) {
+        double* st = (double*)((char*)h->pin_stage.p + stage_in);
+        HIPCHK(hipMemcpyAsync(st, h->ts_gout.p, out_doubles * 8, hipMemcpyDeviceToHost, s));
+        HIPCHK(hipStreamSynchronize(s));
+        out = st;
+    } else {
+        pageable.resize(out_doubles);
+        if ((rc = stage_d2h(h, pageable.data(), h->ts_gout.p, out_doubles * 8, s))) return rc;
+        out = pageable.data();
+    }
+    LAUNCHCHK();
+    if (build_alpha) h->held.results.ts_alpha = true;      // (a flag of the held results: whatever drops them drops it)
+    for (int p = 0; p < P; ++p) {
+        const double* o = out + (size_t)p * (2 + D);
+        value[p] = o[0];
+        if (prior) prior[p] = o[1];
+        memcpy(grad + (size_t)p * D, o + 2, (size_t)D * 8);
+    }
     return SPX_OK;
 }
 

@@ -22,6 +22,8 @@ struct HeldResults {
                                // candidates are resident on its internal handle (spx_get_moments, draws H .. 2H-1)
     bool ts = false;           // the "pass" was spx_thompson: what is resident are posterior sample paths and their priors
                                // (spx_get_thompson_path / _prior), a results kind of its own -- no EI values, no winner
+    bool ts_alpha = false;     // ... and alpha = W^T Gamma of every held path is resident too (built by the first
+                               // spx_thompson_grad_batch after a spx_thompson); gone with the paths, so with everything that drops them
 };
 
 struct Held {

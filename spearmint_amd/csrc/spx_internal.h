@@ -187,6 +187,9 @@ struct spx_handle {
     // and the paths, [H][S][Mp] each; the argmin's partials and results.  ts_S / ts_F: sizes of the held paths (RESULTS with
     // held.results.ts), 0 otherwise
     DevBuf ts_par, ts_w, ts_eps, ts_pobs, ts_rhs, ts_gammaS, ts_pcand, ts_path, ts_am_val, ts_am_idx, ts_out_val, ts_out_idx;
+    // spx_thompson_grad_batch: alpha [H][S][Np] = W^T Gamma of every held path (held.results.ts_alpha); the points [P][D] | path_of
+    // [P] as uploaded; prior [P] | its gradient [P][D] | dk/dr^2 [P][Np] between the two kernels; {value, prior, grad[D]} per point
+    DevBuf ts_alpha, ts_gin, ts_gwork, ts_gout;
     int ts_S = 0, ts_F = 0;
     int64_t ts_fant_budget = 0;    // the per-path partial means' byte budget, as fant_budget / fant_budget_S are the fantasies'
     int ts_fant_budget_S = -1;

@@ -149,6 +149,7 @@ ABI = {
                                     _c_double_p, ctypes.c_int32, _c_int64_p, _c_double_p]),
     "spx_get_thompson_path": (ctypes.c_int, [_vp, ctypes.c_int32, ctypes.c_int32, _c_double_p]),
     "spx_get_thompson_prior": (ctypes.c_int, [_vp, ctypes.c_int32, ctypes.c_int32, _c_double_p, _c_double_p]),
+    "spx_thompson_grad_batch": (ctypes.c_int, [_vp, _c_double_p, _c_int32_p, ctypes.c_int32, _c_double_p, _c_double_p, _c_double_p]),
     "spx_get_timings": (ctypes.c_int, [_vp, _c_double_p, _c_int64_p, ctypes.c_int]),
     "spx_get_stat": (ctypes.c_int, [_vp, ctypes.c_char_p, ctypes.POINTER(ctypes.c_int64)]),
     "spx_timing_name": (ctypes.c_char_p, [ctypes.c_int]),
@@ -221,6 +222,7 @@ def _sampler_result(lib, rc, rows, stats):
 
 TS_MAX_FEATURES = 8192
 TS_MAX_PATHS = 256
+TS_GRAD_MAX_POINTS = 65535    # include/spx.h SPX_TS_GRAD_MAX_POINTS: points one spx_thompson_grad_batch takes
 TS_CHI_DOF = {"Matern52": 5, "Matern32": 3}      # 2 nu: the chi-square law of the Matern spectral density's mixing variable
 
 
@@ -596,6 +598,26 @@ class Engine(object):
         self._check(self._lib.spx_get_thompson_prior(self._h, int(d), int(s), _dp(pc), _dp(po)))
         return pc, po
 
+    def thompson_grad_batch(self, points, path_of=None, want_prior=False):
+        """Value and gradient of held sample paths at P points off the grid: (f[P], g[P, D]), and with want_prior the prior
+        term p_{d,s}(x) alone as a third array (include/spx.h: spx_thompson_grad_batch).  path_of[p] = draw * S + s names the
+        path point p is evaluated under (None: path 0 of draw 0 for all).  g is d f / d x: refine.lbfgs_many minimises a path
+        with this method as its objective.  A point's result does not depend on which other points share the call."""
+        x = _f64(np.atleast_2d(points))
+        if x.ndim != 2 or x.shape[1] != self.D:
+            raise ValueError("points must be (P, D)")
+        po = None
+        if path_of is not None:
+            po = np.ascontiguousarray(path_of, dtype=np.int32)
+            if po.shape != (x.shape[0],):
+                raise ValueError("path_of must be (P,)")
+        f = np.empty(x.shape[0])
+        g = np.empty(x.shape)
+        pr = np.empty(x.shape[0]) if want_prior else None
+        self._check(self._lib.spx_thompson_grad_batch(self._h, _dp(x), None if po is None else po.ctypes.data_as(_c_int32_p),
+                                                      x.shape[0], _dp(f), _dp(g), _dp(pr)))
+        return (f, g, pr) if want_prior else (f, g)
+
     def ei_run(self, flags=0):
         self._check(self._lib.spx_ei_run(self._h, int(flags)))
 
@@ -918,3 +940,7 @@ class MultiEngine(Engine):
 
     def thompson(self, S=1, F=1024, rng=None, per_draw=False, randoms=None):
         raise ValueError("thompson is not available on a multi-device engine (include/spx.h: spx_thompson)")
+
+    def thompson_grad_batch(self, points, path_of=None, want_prior=False):
+        raise ValueError("thompson_grad_batch is not available on a multi-device engine: it holds no sample paths "
+                         "(include/spx.h: spx_thompson_grad_batch)")
