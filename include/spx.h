@@ -234,6 +234,7 @@ int spx_get_pending_fantasies(spx_handle* h, int32_t draw, double* pend_fant, do
 #define SPX_ACQ_PI  1
 #define SPX_ACQ_LCB 2
 #define SPX_ACQ_MES 3   /* max-value entropy search, below; par = K */
+                        /* (4: SPX_ACQ_EHVI, 5: SPX_ACQ_KG, both below) */
 int spx_set_acquisition(spx_handle* h, int32_t kind, double par);
 int spx_get_acquisition(spx_handle* h, int32_t* kind, double* par);   /* either may be NULL */
 
@@ -317,6 +318,56 @@ int spx_get_mes(spx_handle* h, int32_t draw, double* ystar /* K */, double* fit 
 #define SPX_MAX_FRONT 4096
 int spx_set_pareto_front(spx_handle* h, const double* a, const double* b, int32_t n, double r1, double r2);
 int spx_get_pareto_front(spx_handle* h, double* a, double* b, int32_t* n, double* r1, double* r2);
+
+/* ---- the knowledge gradient (SPX_ACQ_KG): the acquisition for noisy objectives ---------------------------------------------
+ * Frazier, Powell & Dayanik (2009); Scott, Frazier & Powell (2011), the discrete form: a candidate c is valued by the expected
+ * drop of the minimum of the posterior MEAN -- over c itself and A representer points -- after one more noisy evaluation at c.
+ * (EI, PI and MES measure against `best`, the minimum OBSERVED value: on a noisy objective the luckiest draw.)
+ * Everything is per hyper draw d.  A = number of representer points, 1 .. SPX_KG_MAX_POINTS; a contract:
+ *   mu_c      = func_m(c) of the pass;   func_v(c) its variance;   s_c = sqrt(func_v(c) + noise_d), the standard deviation of a
+ *               new OBSERVATION at c
+ *   Gamma_a   = L^-1 k(X, a), no mean subtracted; k(X, a) from the library's own cross-covariance launch with the points as rows
+ *   mu_a      = mean_d + sum_i Gamma_a[i] gamma[i]: the posterior mean at a -- what a kept-moments pass over a as a candidate
+ *               returns for func_m, summed here per point (lane i mod 64 takes row i, then a butterfly over the 64 lanes) and
+ *               not by the predict GEMM, so the two may differ in their last bits
+ *   q(c, a)   = sum_i beta_c[i] Gamma_a[i], summed exactly as the pass sums bg for a fantasy column (the S > 0 GEMM branch with
+ *               S = A + 1: column 0 is the ordinary gamma and gives func_m, column a + 1 is Gamma_a)
+ *   C(c, a)   = amp2_d k(c, a) - q(c, a): the posterior covariance of c and a; amp2_d k(c, a) from the same launch over the
+ *               chunk's candidates (a coincident pair gives what that kernel gives for r2 = 0: amp2_d)
+ *   the A + 1 lines in Z ~ N(0, 1):  line 0 = (mu_c, func_v(c) / s_c),  line a = (mu_a, C(c, a) / s_c)
+ *   KG_d(c)   = min_i mu_i - E_Z[min_i (mu_i + b_i Z)] = sum_k (b_k - b_{k+1}) f(-|z_k|),   f(z) = phi(z) + z Phi(z),
+ *               over the lines ON the lower envelope in order of falling slope, z_k their breakpoints; f(-|z|) is the EI
+ *               formula of every pass at unit sigma, func_m = 0 and best = -|z|, clamped at +0.0 from below.
+ * The envelope is found without a sort, every line on its own (csrc/kg_device.h states it operation for operation): z_ij =
+ * (mu_j - mu_i) / (b_i - b_j) for b_j < b_i, one expression per pair; line i is on the envelope when max over the steeper lines
+ * of z_ji < min over the flatter lines of z_ij (strictly) and no line of its slope has a lower intercept -- the TIE RULE: among
+ * lines of equal slope the lowest intercept stays, among equal lines the lowest index; the successor of an envelope line is the
+ * envelope line of the largest slope below its own.  The terms are added in the order of the lines from +0.0.
+ * EXACT cases: all slopes equal (duplicated points included): +0.0;  the value is never negative;  func_v(c) + noise_d not > 0,
+ * or a non-finite mu or slope among the lines of (d, c): NaN for that (d, c) alone.
+ * The value of (d, c) depends on its own lines and on the order of the points only: not on M, the chunking, the draw groups,
+ * options "streams" / "gemm_partial", the position of c or the other draws.
+ * spx_set_acquisition(h, SPX_ACQ_KG, 0) (a non-zero parameter is SPX_ERR_ARG).  With it set spx_ei_run / spx_ei_step /
+ * spx_ei_grid form k(X, A), Gamma_a and mu_a per draw, run the pass's S > 0 branch over the A + 1 columns, form k(A, c) per work
+ * item and run the KG kernels in place of the acquisition (option "timing": stage "kg"), then the numpy-order mean over the
+ * draws, the argmax rule and the result getters of every pass behind one synchronisation.  SPX_FLAG_KEEP_MOMENTS keeps func_m /
+ * func_v (spx_get_moments) and the covariances C[d][a][c]; refused when H A Mp 8 bytes exceed SPX_KG_MAX_LINE_BYTES.
+ * spx_set_kg_points(h, pts, A): pts A x D row-major, D the handle's; a setting of the handle, as the front is: it stays until
+ * replaced or cleared (A < 0) or until observations / candidates of another D arrive, and setting it takes away the results of the
+ * last pass and nothing else.  spx_get_kg_points: *A = -1 when none are set; pts receives A x D doubles; either may be NULL.
+ * spx_get_kg_lines: of draw `draw` of the held KG results, mu_a (A) and cov (A x M row-major; needs SPX_FLAG_KEEP_MOMENTS);
+ * either may be NULL.  spx_get_stat "kg_points" / "last_kg_points" / "last_kg_lines": A of the held points, A of the held KG
+ * results, and whether their covariances are kept (0: none).
+ * REFUSED with SPX_ERR_ARG before any device is touched, the handle as it was: KG without points; with SPX_FLAG_PER_SEC,
+ * SPX_FLAG_CONSTRAINED or SPX_FLAG_TIME_ONLY; with fantasies held; on a multi-device handle, with a communicator attached or
+ * with a 2-D partition; spx_ei_grad_batch / spx_ei_grad / spx_constrained_ei_grad_batch under KG (refinement needs the gradient
+ * of the envelope: out of scope); a non-finite coordinate in the points, A out of range.                                    */
+#define SPX_ACQ_KG 5
+#define SPX_KG_MAX_POINTS 255
+#define SPX_KG_MAX_LINE_BYTES (4ll << 30)
+int spx_set_kg_points(spx_handle* h, const double* pts /* A x D */, int32_t A);
+int spx_get_kg_points(spx_handle* h, double* pts /* A x D */, int32_t* A);
+int spx_get_kg_lines(spx_handle* h, int32_t draw, double* mu_a /* A */, double* cov /* A x M */);
 
 /* ---- Thompson sampling: posterior sample paths over the candidates (pathwise conditioning) ---------------------------------
  * Wilson et al. (2020): a draw from the GP posterior is a draw from the prior plus a data-dependent update,

@@ -25,6 +25,7 @@ class GPEIChooser(GPEIBase):
     noiseless_checks_mean = False
     max_ls = 2
     ts_allowed = True               # acq=TS: the grid argmin of one posterior sample path (_base.py: _thompson_gpu)
+    kg_allowed = True               # acq=KG: the knowledge gradient over the grid (_base.py: _kg_gpu)
 
     def __del__(self):
         # the reference persists its hypers when the object dies (:66-83)
@@ -54,6 +55,8 @@ class GPEIChooser(GPEIBase):
             self._log_hypers()
             if self.acq == "TS":   # (pending jobs are ignored: no fantasies, no normals for them)
                 best = self._thompson_gpu(comp, cand, vals, self.current_hyper_row()[None, :])
+            elif self.acq == "KG" and pend.shape[0] == 0:
+                best = self._kg_gpu(grid, comp, cand, vals, self.current_hyper_row()[None, :])
             else:
                 randn = [npr.randn(pend.shape[0], self.pending_samples)] if pend.shape[0] > 0 else []
                 best, _, _ = self.ei_over_hypers_gpu(comp, pend, cand, vals, self.current_hyper_row()[None, :],
@@ -86,6 +89,8 @@ class GPEIChooser(GPEIBase):
             self.sample_hypers_many(comp, vals, self.mcmc_iters, after)
         if self.acq == "TS":       # the chain above is that of a call without pending jobs; then one draw, one sample path
             best = self._thompson_gpu(comp, cand, vals, np.array(rows))
+        elif self.acq == "KG" and pend.shape[0] == 0:   # (with pending jobs: EI over the fantasies, below -- the MES rule)
+            best = self._kg_gpu(grid, comp, cand, vals, np.array(rows))
         else:
             best, _, _ = self.ei_over_hypers_gpu(comp, pend, cand, vals, np.array(rows), randn=randn)
         if self.recommend:         # (the proposal is fixed; no random numbers from here on)

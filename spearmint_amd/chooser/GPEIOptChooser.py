@@ -31,6 +31,7 @@ class GPEIOptChooser(GPEIBase):
     noiseless_checks_mean = True    # :685-686
     max_ls = 2
     ts_allowed = True               # acq=TS: the grid argmin of one posterior sample path (_base.py: _thompson_gpu)
+    kg_allowed = True               # acq=KG: the knowledge gradient over the grid, not refined (_base.py: _kg_gpu)
     ts_refine_allowed = True        # ts_refine=1: ... minimised off the grid from its grid_subset lowest rows (_thompson_refine)
 
     def __init__(self, expt_dir, covar="Matern52", mcmc_iters=10, pending_samples=100,
@@ -274,6 +275,19 @@ class GPEIOptChooser(GPEIBase):
             idx = self._thompson_gpu(comp, cand, vals, rows)
             x = self._thompson_refine(cand, idx) if self.ts_refine else None
             job = int(candidates[idx]) if x is None else (int(numcand), x)
+            if self.recommend:
+                self._recommend(grid, comp, vals, rows, refine_count=self.grid_subset)
+            if self.importance:
+                self._importance(grid, comp, vals, rows)
+            if self.loo:
+                self._loo(complete, comp, vals, rows)
+            return job
+
+        if self.acq == "KG" and pend.shape[0] == 0:
+            # The knowledge gradient: the grid point of the highest value.  No sprayed points (their normals above are drawn all
+            # the same: the generator is where an acq=EI call leaves it) and no refinement -- it needs the gradient of the
+            # envelope, which the library does not have.  With pending jobs the call is scored with EI below: the MES rule.
+            job = int(candidates[self._kg_gpu(grid, comp, cand, vals, rows)])
             if self.recommend:
                 self._recommend(grid, comp, vals, rows, refine_count=self.grid_subset)
             if self.importance:

@@ -48,7 +48,10 @@ class GPEIBase(object):
     acq_allowed = ("EI", "PI", "LCB", "MES")   # acq=: what the engine scores candidates with (include/spx.h SPX_ACQ_*)
     ts_allowed = False             # acq=TS: Thompson sampling (include/spx.h: spx_thompson) -- not an acquisition of the pass but
     #                                a call of its own; GPEIChooser and GPEIOptChooser switch it on
+    kg_allowed = False             # acq=KG: the knowledge gradient (include/spx.h: SPX_ACQ_KG) -- a pass of its own behind a
+    #                                model-mean pass that picks its representer points; GPEIChooser and GPEIOptChooser switch it on
     mes_default_levels = 10        # acq=MES with acq_par=0: K, the number of y* levels
+    kg_default_points = 64         # acq=KG with acq_par=0: A, the number of representer points
     ts_default_features = 1024     # acq=TS with acq_par=0: F, the random Fourier features of the prior sample
     ts_refine_allowed = False      # ts_refine=1: the sample path is minimised off the grid (GPEIOptChooser switches it on)
     recommend_allowed = True       # recommend=1: the model-mean recommendation after every proposal (_recommend)
@@ -71,6 +74,10 @@ class GPEIBase(object):
         if self.acq == "TS" and int(ndev) > 1:
             raise ValueError("acq=TS is not available with ndev=%d: a sample path is drawn over every candidate on one "
                              "device (allowed: ndev=1, or acq=EI, PI, LCB)" % int(ndev))
+        if self.acq == "KG" and int(ndev) > 1:
+            raise ValueError("acq=KG is not available with ndev=%d: the representer points' columns live on one device "
+                             "(allowed: ndev=1, or acq=EI, PI, LCB)" % int(ndev))
+        self.last_kg = None            # acq=KG: {"points_index", "points", "grid_index", "value"} of the last call scored with KG
         self.ts_refine = _as_bool(ts_refine)
         if self.ts_refine and not self.ts_refine_allowed:
             raise ValueError("ts_refine=1 is not available on %s (allowed: ts_refine=0; GPEIOptChooser refines a sample path)"
@@ -174,7 +181,7 @@ class GPEIBase(object):
         default of 10 levels), a multiple of 16 in 16 .. 8192 for TS (0: the default of 1024 features) (include/spx.h:
         spx_set_acquisition, spx_thompson)."""
         name = str(acq).strip().upper()
-        allowed = cls.acq_allowed + (("TS",) if cls.ts_allowed else ())
+        allowed = cls.acq_allowed + (("TS",) if cls.ts_allowed else ()) + (("KG",) if cls.kg_allowed else ())
         if name not in allowed:
             raise ValueError("acq=%s is not available on %s (allowed: %s)" % (acq, cls.__name__, ", ".join(allowed)))
         try:
@@ -191,6 +198,11 @@ class GPEIBase(object):
                 raise ValueError("acq_par=%r is not a number of y* levels (allowed with acq=MES: an integer in 1 .. 1024, or 0 for "
                                  "the default of %d)" % (acq_par, cls.mes_default_levels))
             par = float(int(par) or cls.mes_default_levels)
+        if name == "KG":
+            if par != int(par) or par > 255:
+                raise ValueError("acq_par=%r is not a number of representer points (allowed with acq=KG: an integer in 1 .. 255, "
+                                 "or 0 for the default of %d)" % (acq_par, cls.kg_default_points))
+            par = float(int(par) or cls.kg_default_points)
         if name == "TS":
             if par != int(par) or int(par) % 16 or (par != 0 and not 16 <= par <= 8192):
                 raise ValueError("acq_par=%r is not a number of features (allowed with acq=TS: a multiple of 16 in 16 .. 8192, or "
@@ -204,8 +216,10 @@ class GPEIBase(object):
         MES over fantasies, so the call is scored with EI over the fantasies, exactly as an acq=EI chooser scores it
         (last_acq_used says which one it was)."""
         acq, par = self.acq, self.acq_par
-        if acq == "MES" and pending:
+        if acq in ("MES", "KG") and pending:     # (KG likewise: the library refuses it over fantasies -- the MES rule)
             acq, par = "EI", 0.0
+        if acq == "KG":                          # (A is the chooser's; the handle's acquisition takes no parameter)
+            par = 0.0
         self.last_acq_used = acq
         if self.acq != "EI":
             from ..engine import ACQ
@@ -237,6 +251,68 @@ class GPEIBase(object):
         self.last_thompson = {"draw": d, "grid_index": int(idx[0, 0]), "path_min": float(mn[0, 0]), "features": F}
         return int(idx[0, 0])
 
+    # -- the knowledge gradient (acq=KG) -------------------------------------------------
+    def _neg_mean_over_grid(self, eng, grid, comp, vals, rows):
+        """recommend=1's pass, shared with acq=KG: the engine takes the completed points, the grid and the hyper rows and runs
+        one negated-lower-confidence-bound pass with kappa = 0; returns minus the mean over the draws of func_m per grid row.
+        The handle's acquisition is left at LCB: the caller restores it."""
+        from ..engine import ACQ_LCB
+        kept, self._kg_mean_pass = getattr(self, "_kg_mean_pass", None), None
+        if kept is not None and all(np.array_equal(a, b) for a, b in zip(kept[:4], (grid, comp, vals, rows))):
+            # _recommend right behind _kg_gpu (acq=KG with recommend=1): the same pass over the same inputs has just run and its
+            # factor is still held -- nothing else has touched the engine.  Only the setting a refinement reads is made again.
+            eng.set_acquisition(ACQ_LCB, 0.0)
+            self._factor_covers = (comp, vals, rows)
+            return kept[4]
+        eng.set_observations(comp, vals)
+        eng.set_candidates(grid)
+        eng.set_hypers(rows)
+        eng.set_acquisition(ACQ_LCB, 0.0)
+        eng.ei_step()
+        self._factor_covers = (comp, vals, rows)
+        return eng.ei_mean()
+
+    def _kg_gpu(self, grid, comp, cand, vals, hyper_rows):
+        """The proposal of an acq=KG call without pending jobs: the model-mean pass over the grid (which holds the completed
+        points), the A = acq_par grid rows of the lowest mean over the draws as representer points -- a stable argsort, NaN rows
+        skipped, fewer if fewer exist -- then the KG pass over the candidates against the factor the first pass left.  Draws no
+        random numbers.  Leaves self.last_kg; returns the index of the winner among the candidates.  No grid row with a mean:
+        nothing to represent the minimum, and the call is scored with EI (last_acq_used says so)."""
+        from ..engine import ACQ_KG
+        eng = self.engine()
+        grid = np.ascontiguousarray(grid, dtype=np.float64)
+        rows = np.ascontiguousarray(np.atleast_2d(hyper_rows), dtype=np.float64)
+        prev = eng.get_acquisition()
+        self._lp_key = None
+        self._factor_covers = None
+        self._kg_mean_pass = None
+        try:
+            neg_mean = self._neg_mean_over_grid(eng, grid, comp, vals, rows)
+            mean = -np.asarray(neg_mean, dtype=np.float64)
+            order = np.argsort(mean, kind="stable")
+            pidx = order[~np.isnan(mean[order])][:int(self.acq_par)]
+            if pidx.size == 0:
+                self.last_kg = None
+                eng.set_acquisition(*prev)
+                return self.ei_over_hypers_gpu(comp, np.zeros((0, grid.shape[1])), cand, vals, rows)[0]
+            eng.set_kg_points(grid[pidx, :])
+            eng.set_candidates(cand)
+            eng.set_acquisition(ACQ_KG, 0.0)
+            eng.ei_run()
+            idx, val = eng.best()
+            self.last_ei_mean = eng.ei_mean()
+            self.last_overall_ei = eng.ei_draws()
+            self._kg_mean_pass = (grid, comp, vals, rows, neg_mean)     # (for a _recommend right behind this call)
+        finally:
+            eng.set_acquisition(*prev)
+        warning = eng.last_warning()
+        if warning:
+            log("libspx " + warning)
+        self.last_acq_used = "KG"
+        self.last_kg = {"points_index": np.array(pidx, dtype=int), "points": np.array(grid[pidx, :], dtype=float),
+                        "grid_index": int(idx), "value": float(val)}
+        return int(idx)
+
     # -- the model-mean recommendation (recommend=1) ---------------------------------
     def _recommend(self, grid, comp, vals, hyper_rows, refine_count=0):
         """Where the posterior mean, averaged over this call's hyper draws, is lowest: the negated lower confidence bound with
@@ -248,7 +324,7 @@ class GPEIBase(object):
         the opposite kind of answer -- a point to USE -- so a point whose mean is NaN is never refined and never recommended;
         if no point has a mean, nothing is recommended: last_recommendation is None and no line is written."""
         from .. import refine
-        from ..engine import ACQ_LCB, FLAG_KEEP_MOMENTS
+        from ..engine import FLAG_KEEP_MOMENTS
         eng = self.engine()
         grid = np.ascontiguousarray(grid, dtype=np.float64)
         rows = np.ascontiguousarray(np.atleast_2d(hyper_rows), dtype=np.float64)
@@ -256,13 +332,8 @@ class GPEIBase(object):
         self._lp_key = None
         self._factor_covers = None
         try:
-            eng.set_observations(comp, vals)
-            eng.set_candidates(grid)
-            eng.set_hypers(rows)
-            eng.set_acquisition(ACQ_LCB, 0.0)
-            eng.ei_step()
-            self._factor_covers = (comp, vals, rows)     # (_importance, right behind this call, needs no factorisation of its own)
-            neg_mean = eng.ei_mean()                     # minus the mean over draws of func_m
+            # (_importance, right behind this call, needs no factorisation of its own: _factor_covers)
+            neg_mean = self._neg_mean_over_grid(eng, grid, comp, vals, rows)     # minus the mean over draws of func_m
             finite = np.nonzero(~np.isnan(neg_mean))[0]
             if finite.size == 0:
                 self.last_recommendation = None
@@ -811,7 +882,8 @@ class GPEIBase(object):
             return self._ei_with_pending_gpu(comp, pend, cand, vals, hyper_rows, randn, want_draws)
         hyper_rows = np.ascontiguousarray(np.atleast_2d(hyper_rows), dtype=np.float64)
         self._lp_key = None     # the one-shot call below replaces the engine's resident observations
-        self._apply_acquisition(self.engine())
+        # (acq=KG reaches this pass only where _kg_gpu found no representer point: pending=True is the EI scoring of both rules)
+        self._apply_acquisition(self.engine(), pending=(self.acq == "KG"))
         idx, val, mean, draws = self.engine().ei_grid(comp, vals, cand, hyper_rows,
                                                       want_mean=True, want_draws=want_draws)
         warning = self.engine().last_warning()    # (a hand-off time-out of the one-launch factorisation: results are unaffected)

@@ -1903,6 +1903,14 @@ void launch_gamma_multi(hipStream_t s, const double* WT_h, const double* rhs, co
                        (size_t)0, rhs, (size_t)N, htab_h, 0, gamma, N, Np);
 }
 
+// S right-hand sides `rhs_stride` doubles apart against ONE draw's W, no mean subtracted: Gamma_a = W k(X, a) of the knowledge
+// gradient's representer points (rows of a K(A, X) launch, Np doubles apart)
+void launch_gamma_cols(hipStream_t s, const double* WT_h, const double* rhs, size_t rhs_stride, double* gamma, int N, int Np, int S)
+{
+    hipLaunchKernelGGL(k_gamma, dim3(Np / 256 + (Np % 256 != 0), S), dim3(256), 0, s, WT_h,
+                       (size_t)0, rhs, rhs_stride, (const double*)nullptr, 0, gamma, N, Np);
+}
+
 // alpha = W^T gamma  == K^-1 (vals - mean);  one wavefront per row j of WT
 __global__ __launch_bounds__(256) void k_alpha(const double* __restrict__ WT,
                                                const double* __restrict__ gamma,

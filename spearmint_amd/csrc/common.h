@@ -26,6 +26,7 @@ typedef double d2 __attribute__((ext_vector_type(2)));
 #define SPX_ACQ_DEV_PI 1
 #define SPX_ACQ_DEV_LCB 2
 #define SPX_ACQ_DEV_EHVI 4  // expected hypervolume improvement over two GPs: likewise a stage behind the pass (ehvi_kernels.hip)
+#define SPX_ACQ_DEV_KG 5    // knowledge gradient: a stage behind the pass's S > 0 branch over the representer points' columns (kg_kernels.hip)
 #define SPX_ACQ_DEV_MES 3   // max-value entropy search: a second stage behind the pass (mes_kernels.hip), never a template argument of the pass's own kernels
 
 // The launchers below return nothing: a kernel that needs more dynamic LDS than the default asks for it right before its
@@ -94,6 +95,8 @@ void launch_gamma(hipStream_t s, const double* WT, const double* vals, const dou
                   double* gamma, int N, int Np, int nh);
 void launch_gamma_multi(hipStream_t s, const double* WT_h, const double* rhs, const double* htab_h,
                         double* gamma, int N, int Np, int S);
+void launch_gamma_cols(hipStream_t s, const double* WT_h, const double* rhs, size_t rhs_stride, double* gamma, int N, int Np,
+                       int S);
 void launch_gemv_lower(hipStream_t s, const double* WT, const double* rhs, double* out, int Np, int nh);
 void launch_alpha(hipStream_t s, const double* WT, const double* gamma, double* alpha, int Np, int nh);
 void launch_rhs_init(hipStream_t s, const double* vals, const double* htab, double* rhs, int N, int Np, int nh,
@@ -212,6 +215,18 @@ void launch_ts_grad_prior(hipStream_t s, const double* x, const int32_t* path_of
 void launch_ts_grad_update(hipStream_t s, const double* Xs, const double* s1, const double* hyp, const double* htab,
                            const double* alpha, const double* x, const int32_t* path_of, const double* prior, const double* gp,
                            double* dkw, double* out, int N, int Np, int D, int Dp, int S, int P, int kind);
+
+// kg_kernels.hip: the knowledge gradient behind the S > 0 GEMM branch with S = A + 1 columns per draw (spx.h SPX_ACQ_KG).
+// mu_a [H][A] from gammaS [H][S][Np] (column 0: gamma);  the lines of a work item -- slopes [nh][S][Mc], mu_c [nh][Mc], and with
+// mom_m / cov given func_m, func_v [H][Mp] and C [H][A][Mp] -- from its partial sums and Kac [nh][Ap][Mc] = amp2 k(a, c);  the
+// values of the work item into ei_draw (mua: the group's first draw)
+void launch_kg_mu(hipStream_t s, const double* gammaS, const double* htab, int Np, int S, int H, double* mua);
+void launch_kg_lines(hipStream_t s, const double* part_ss, const double* part_bgS, const double* htab, const double* Kac, int nrb,
+                     int Mc, int nh, int S, int Ap, int64_t c0, int64_t M, int64_t Mp, int h0, double* slope, double* muc,
+                     double* mom_m, double* mom_v, double* cov);
+void launch_kg_value(hipStream_t s, const double* slope, const double* muc, const double* mua, int Mc, int nh, int n, int64_t c0,
+                     int64_t M, int64_t Mp, int h0, double* ei_draw);
+int kg_tile_candidates(int n);
 
 // predict_kernels.hip
 void launch_predict_gemm(hipStream_t s, int variant, const double* WT, const double* Kst, const double* gamma,

@@ -19,7 +19,7 @@
 static const char* kStageNames[ST_COUNT] = {
     "scale_rows", "cov_self", "chol_diag", "chol_panel", "trinv", "gamma_alpha",
     "cov_cross", "cross_mean", "predict_gemm", "ei_finalize", "mean_argmax", "mes", "ehvi",
-    "ts_prior", "ts_finish", "factor_total", "ei_run_total"};
+    "ts_prior", "ts_finish", "kg", "factor_total", "ei_run_total"};
 
 
 std::string& spx_err_slot()
@@ -317,7 +317,8 @@ void spx_destroy(spx_handle* h)
                           &h->mes_bpart, &h->mes_part, &h->mes_G, &h->mes_ystar, &h->mes_fit, &h->front_dev,
                           &h->ts_par, &h->ts_w, &h->ts_eps, &h->ts_pobs, &h->ts_rhs, &h->ts_gammaS, &h->ts_pcand, &h->ts_path,
                           &h->ts_am_val, &h->ts_am_idx, &h->ts_out_val, &h->ts_out_idx,
-                          &h->ts_alpha, &h->ts_gin, &h->ts_gwork, &h->ts_gout};
+                          &h->ts_alpha, &h->ts_gin, &h->ts_gwork, &h->ts_gout,
+                          &h->kg_pts, &h->kg_As, &h->kg_sA, &h->kg_kxa, &h->kg_gammaS, &h->kg_mua, &h->kg_Kac, &h->kg_muc, &h->kg_cov};
         for (DevBuf* b : bufs) b->release();
         h->pin_up.release();
         h->pin_res.release();
@@ -356,14 +357,15 @@ int spx_set_option(spx_handle* h, const char* name, int64_t value)
 // The acquisition every later pass and refinement call computes in EI's place (spx.h).  Nothing but the results of the last
 // pass depends on it: the factor, the fantasies and alpha_s stay.
 static_assert(SPX_ACQ_EI == SPX_ACQ_DEV_EI && SPX_ACQ_PI == SPX_ACQ_DEV_PI && SPX_ACQ_LCB == SPX_ACQ_DEV_LCB
-                  && SPX_ACQ_MES == SPX_ACQ_DEV_MES && SPX_ACQ_EHVI == SPX_ACQ_DEV_EHVI,
+                  && SPX_ACQ_MES == SPX_ACQ_DEV_MES && SPX_ACQ_EHVI == SPX_ACQ_DEV_EHVI && SPX_ACQ_KG == SPX_ACQ_DEV_KG,
               "spx.h and common.h number the acquisitions alike");
 int spx_set_acquisition(spx_handle* h, int32_t kind, double par)
 {
     if (!h) return fail(SPX_ERR_ARG, "spx_set_acquisition: null handle");
-    if (kind != SPX_ACQ_EI && kind != SPX_ACQ_PI && kind != SPX_ACQ_LCB && kind != SPX_ACQ_MES && kind != SPX_ACQ_EHVI)
+    if (kind != SPX_ACQ_EI && kind != SPX_ACQ_PI && kind != SPX_ACQ_LCB && kind != SPX_ACQ_MES && kind != SPX_ACQ_EHVI
+        && kind != SPX_ACQ_KG)
         return fail(SPX_ERR_ARG, "spx_set_acquisition: unknown acquisition %d (SPX_ACQ_EI, SPX_ACQ_PI, SPX_ACQ_LCB, SPX_ACQ_MES, "
-                                 "SPX_ACQ_EHVI are known)", (int)kind);
+                                 "SPX_ACQ_EHVI, SPX_ACQ_KG are known)", (int)kind);
     if (!(par >= 0.0) || !std::isfinite(par))
         return fail(SPX_ERR_ARG, "spx_set_acquisition: the parameter must be finite and >= 0 (got %g)", par);
     if (kind == SPX_ACQ_EI && par != 0.0)
@@ -386,6 +388,15 @@ int spx_set_acquisition(spx_handle* h, int32_t kind, double par)
         if (h->comm) return fail(SPX_ERR_ARG, "spx_set_acquisition: SPX_ACQ_EHVI is single-device only (communicator attached)");
         if (h->part_ph > 1 || h->part_M > 0)
             return fail(SPX_ERR_ARG, "spx_set_acquisition: SPX_ACQ_EHVI is not available with a 2-D partition");
+    }
+    if (kind == SPX_ACQ_KG) {
+        if (par != 0.0)
+            return fail(SPX_ERR_ARG, "spx_set_acquisition: SPX_ACQ_KG takes no parameter (par must be 0, got %g)", par);
+        // the representer points' columns and mu_a live on one device
+        if (h->multi) return fail(SPX_ERR_ARG, "spx_set_acquisition: SPX_ACQ_KG is single-device only (multi-device handle)");
+        if (h->comm) return fail(SPX_ERR_ARG, "spx_set_acquisition: SPX_ACQ_KG is single-device only (communicator attached)");
+        if (h->part_ph > 1 || h->part_M > 0)
+            return fail(SPX_ERR_ARG, "spx_set_acquisition: SPX_ACQ_KG is not available with a 2-D partition");
     }
     if (h->multi) return spx_multi_set_acquisition(h->multi, kind, par);
     spx_drop(h, Held::RESULTS);
@@ -458,6 +469,7 @@ int spx_set_observations(spx_handle* h, const double* comp, const double* vals, 
     if (rc) return rc;
     spx_drop(h, Held::OBS);
     if (D != h->D) { spx_drop(h, Held::CAND); spx_drop(h, Held::HYP); }   // (candidates and hypers of another dimension)
+    if (D != h->D && h->held.has(Held::KGPTS)) { spx_drop(h, Held::KGPTS); h->kg_A = -1; h->kg_pts_host.clear(); }   // (and representer points)
     h->N = N; h->D = D; h->Dp = padded_dim(D); h->Np = (int)round_up(N, SPX_PADN);
     if ((rc = h->comp.reserve((size_t)N * D * 8))) return rc;
     if ((rc = h->vals.reserve((size_t)N * 8))) return rc;
@@ -484,7 +496,10 @@ int spx_set_candidates(spx_handle* h, const double* cand, int64_t M, int32_t D, 
     int rc = ensure_init(h);
     if (rc) return rc;
     spx_drop(h, Held::CAND);
-    if (!h->held.has(Held::OBS)) { h->D = D; h->Dp = padded_dim(D); }
+    if (!h->held.has(Held::OBS)) {
+        if (D != h->D && h->held.has(Held::KGPTS)) { spx_drop(h, Held::KGPTS); h->kg_A = -1; h->kg_pts_host.clear(); }
+        h->D = D; h->Dp = padded_dim(D);
+    }
     h->M = M; h->index_base = index_base;
     if ((rc = h->cand.reserve((size_t)M * D * 8))) return rc;
     stage_begin(h);
@@ -574,6 +589,46 @@ int spx_get_pareto_front(spx_handle* h, double* a, double* b, int32_t* n, double
     if (b) std::copy(h->front_b.begin(), h->front_b.end(), b);
     if (r1) *r1 = h->front_r1;
     if (r2) *r2 = h->front_r2;
+    return SPX_OK;
+}
+
+// The representer points of a knowledge-gradient pass (spx.h): a setting of the handle, as the front is.  Everything is
+// checked before anything is touched; D is the handle's (observations or candidates set it).
+int spx_set_kg_points(spx_handle* h, const double* pts, int32_t A)
+{
+    if (!h) return fail(SPX_ERR_ARG, "spx_set_kg_points: null handle");
+    if (h->multi) return fail(SPX_ERR_ARG, "spx_set_kg_points: SPX_ACQ_KG is single-device only (multi-device handle)");
+    if (A < 0) { spx_drop(h, Held::KGPTS); h->kg_A = -1; h->kg_pts_host.clear(); return SPX_OK; }
+    if (A < 1 || A > SPX_KG_MAX_POINTS)
+        return fail(SPX_ERR_ARG, "spx_set_kg_points: A=%d representer points (allowed: 1 .. %d)", (int)A, SPX_KG_MAX_POINTS);
+    if (!pts) return fail(SPX_ERR_ARG, "spx_set_kg_points: null points with A=%d", (int)A);
+    if (!h->held.has(Held::OBS) && !h->held.has(Held::CAND))
+        return fail(SPX_ERR_ARG, "spx_set_kg_points: set observations or candidates first (they give the dimension)");
+    const int D = h->D;
+    for (size_t i = 0; i < (size_t)A * D; ++i)
+        if (!std::isfinite(pts[i]))
+            return fail(SPX_ERR_ARG, "spx_set_kg_points: coordinate %d of point %d is not finite (%g)", (int)(i % D), (int)(i / D), pts[i]);
+    int rc = ensure_init(h);
+    if (rc) return rc;
+    // (a reservation that fails has released the old buffer: the points it belonged to go first)
+    spx_drop(h, Held::KGPTS);
+    h->kg_A = -1;
+    h->kg_pts_host.clear();
+    if ((rc = h->kg_pts.reserve((size_t)A * D * 8))) return rc;
+    stage_begin(h);
+    if ((rc = stage_h2d(h, h->kg_pts.p, pts, (size_t)A * D * 8, h->stream))) return rc;
+    HIPCHK(hipStreamSynchronize(h->stream));
+    h->kg_pts_host.assign(pts, pts + (size_t)A * D);
+    h->kg_A = A;
+    return spx_hold(h, Held::KGPTS);
+}
+
+int spx_get_kg_points(spx_handle* h, double* pts, int32_t* A)
+{
+    if (!h) return fail(SPX_ERR_ARG, "spx_get_kg_points: null handle");
+    const bool have = !h->multi && h->held.has(Held::KGPTS);
+    if (A) *A = have ? h->kg_A : -1;
+    if (have && pts) std::copy(h->kg_pts_host.begin(), h->kg_pts_host.end(), pts);
     return SPX_OK;
 }
 
@@ -980,15 +1035,41 @@ int spx_get_pending_fantasies(spx_handle* h, int32_t draw, double* pend_fant, do
 
 // factor_pending (spx_ei_step): the factorisation is queued on the stream but not yet checked -- its not-PD flags travel
 // home with the winner, and ONE synchronisation ends the step
-// ts_S > 0 (spx_thompson): the pass's S > 0 GEMM branch over the ts_S right-hand sides per draw in h->ts_gammaS instead of the
-// fantasies, k_ts_prior per chunk, k_ts_finish in place of the acquisition, a per-path argmin in place of the mean and argmax
-static int ei_run_impl(spx_handle* h, int32_t flags, bool factor_pending, int ts_S = 0);
+// rhs: what the pass's S > 0 GEMM branch runs over when it is not the handle's fantasies (FANT, S = h->S):
+//   TS (spx_thompson)  the rhs.S right-hand sides per draw in h->ts_gammaS, k_ts_prior per chunk, k_ts_finish in place of the
+//                      acquisition, a per-path argmin in place of the mean and argmax
+//   KG (decided inside, from the handle's acquisition: no caller passes it)  gamma | Gamma_a of the A representer points in
+//                      h->kg_gammaS, S = A + 1; k(A, c) per work item and the two kg kernels in place of the acquisition
+struct PassRhs { enum Kind { FANT, TS, KG } kind = FANT; int S = 0; };
+static int ei_run_impl(spx_handle* h, int32_t flags, bool factor_pending, PassRhs rhs = PassRhs());
 static int ehvi_second(spx_handle* h);
 
 // what an EI pass refuses because of its flags alone (nmodels: 2 when a time model is / will be factored)
 static const char* acq_name(int acq)
 {
-    return acq == SPX_ACQ_PI ? "PI" : acq == SPX_ACQ_LCB ? "LCB" : acq == SPX_ACQ_MES ? "MES" : acq == SPX_ACQ_EHVI ? "EHVI" : "EI";
+    return acq == SPX_ACQ_PI ? "PI" : acq == SPX_ACQ_LCB ? "LCB" : acq == SPX_ACQ_MES ? "MES" : acq == SPX_ACQ_EHVI ? "EHVI"
+         : acq == SPX_ACQ_KG ? "KG" : "EI";
+}
+
+// what a pass under SPX_ACQ_KG refuses, decided from the host's record alone (who: the entry point's name)
+static int check_kg(const spx_handle* h, int32_t flags, const char* who)
+{
+    if (h->acq != SPX_ACQ_KG) return SPX_OK;
+    if (flags & (SPX_FLAG_PER_SEC | SPX_FLAG_CONSTRAINED | SPX_FLAG_TIME_ONLY))
+        return fail(SPX_ERR_ARG, "%s: SPX_FLAG_PER_SEC / SPX_FLAG_CONSTRAINED / SPX_FLAG_TIME_ONLY are defined for "
+                                 "SPX_ACQ_EI only (spx_set_acquisition chose KG)", who);
+    if (h->comm || h->part_ph > 1 || h->part_M > 0)
+        return fail(SPX_ERR_ARG, "%s: SPX_ACQ_KG is single-device only (communicator attached or 2-D partition set)", who);
+    if (!h->held.has(Held::KGPTS))
+        return fail(SPX_ERR_ARG, "%s: SPX_ACQ_KG needs representer points (spx_set_kg_points)", who);
+    if (h->S > 0)
+        return fail(SPX_ERR_ARG, "%s: SPX_ACQ_KG is not defined over fantasies (clear them, or score the call with SPX_ACQ_EI)", who);
+    if ((flags & SPX_FLAG_KEEP_MOMENTS) && h->held.has(Held::CAND) && h->held.has(Held::HYP)
+        && (double)h->H * h->kg_A * (double)round_up(h->M, SPX_BN) * 8.0 > (double)SPX_KG_MAX_LINE_BYTES)
+        return fail(SPX_ERR_ARG, "%s: H A Mp 8 = %d x %d x %lld x 8 bytes of kept covariances (SPX_FLAG_KEEP_MOMENTS under SPX_ACQ_KG "
+                                 "allows up to %lld bytes)", who, h->H, h->kg_A, (long long)round_up(h->M, SPX_BN),
+                    (long long)SPX_KG_MAX_LINE_BYTES);
+    return SPX_OK;
 }
 
 // what a pass under SPX_ACQ_EHVI refuses, decided from the host's record alone (who: the entry point's name)
@@ -1013,6 +1094,7 @@ static int check_run_flags(const spx_handle* h, int32_t flags, int nmodels)
 {
     int rc_ehvi = check_ehvi(h, flags, "spx_ei_run");
     if (rc_ehvi) return rc_ehvi;
+    if ((rc_ehvi = check_kg(h, flags, "spx_ei_run"))) return rc_ehvi;
     const bool per_sec = (flags & SPX_FLAG_PER_SEC) != 0;
     const bool keep_mom = (flags & SPX_FLAG_KEEP_MOMENTS) != 0;
     const bool time_only = (flags & SPX_FLAG_TIME_ONLY) != 0;
@@ -1066,6 +1148,7 @@ int spx_ei_step(spx_handle* h, int32_t flags)
     {   // EHVI's refusals come before the factorisation in either form below (which would drop the fantasies it refuses)
         int rc = check_ehvi(h, flags, "spx_ei_step");
         if (rc) return rc;
+        if ((rc = check_kg(h, flags, "spx_ei_step"))) return rc;   // (likewise)
     }
     if (h->opt.timing || (flags & SPX_FLAG_TIMING) || !h->held.has(Held::CAND)) {   // stage timers bracket each call: keep the two-call form
         int rc = spx_factor(h);
@@ -1200,11 +1283,11 @@ static int ehvi_second(spx_handle* h)
     return rc;
 }
 
-static int ei_run_impl(spx_handle* h, int32_t flags, bool factor_pending, int ts_S)
+static int ei_run_impl(spx_handle* h, int32_t flags, bool factor_pending, PassRhs rhs)
 {
     if (!h->held.has(Held::FACTOR) && !factor_pending) return fail(SPX_ERR_ARG, "spx_ei_run: call spx_factor first");
     if (!h->held.has(Held::CAND)) return fail(SPX_ERR_ARG, "spx_ei_run: no candidates set");
-    const bool ts = ts_S > 0;       // (spx_thompson made every check of its own; the acquisition setting is not read)
+    const bool ts = rhs.kind == PassRhs::TS;       // (spx_thompson made every check of its own; the acquisition setting is not read)
     int rc = ts ? (int)SPX_OK : check_run_flags(h, flags, h->nmodels);
     if (rc) return rc;
     // Max-value entropy search: the ordinary pass as EI with the moments kept (the way spx_main_effects runs it; the handle's
@@ -1218,15 +1301,19 @@ static int ei_run_impl(spx_handle* h, int32_t flags, bool factor_pending, int ts
     // stream -- after the second GP's pass over the same candidates (ehvi_second, below)
     const bool ehvi = !ts && h->acq == SPX_ACQ_EHVI;
     if (mes || ehvi) flags |= SPX_FLAG_KEEP_MOMENTS;
-    const int pass_acq = (mes || ehvi) ? SPX_ACQ_EI : h->acq;
-    const double pass_par = (mes || ehvi) ? 0.0 : h->acq_par;
+    // Knowledge gradient: the S > 0 branch over gamma | Gamma_a (column 0 gives func_m, the others q(c, a)), the lines and the
+    // values per work item in place of the acquisition; then the mean and the argmax of every pass (check_kg passed above)
+    const bool kg = !ts && h->acq == SPX_ACQ_KG;
+    if (kg) rhs = PassRhs{PassRhs::KG, h->kg_A + 1};
+    const int pass_acq = (mes || ehvi || kg) ? SPX_ACQ_EI : h->acq;
+    const double pass_par = (mes || ehvi || kg) ? 0.0 : h->acq_par;
     if ((rc = ensure_init(h))) return rc;
     if ((flags & SPX_FLAG_CONSTRAINED) && h->con_n > 0 && !h->held.has(Held::CON_FACTOR))
         return fail(SPX_ERR_ARG, "spx_ei_run: the constraint model is not factored (spx_factor after spx_set_constraint_model)");
     spx_drop(h, Held::RESULTS);     // the pass overwrites them; a failed one keeps the factor and the fantasies
     if (ehvi && !factor_pending && (rc = ehvi_second(h))) return rc;     // (a pending step ran it before its own factorisation)
     EiShape sh;
-    sh.N = h->N; sh.M = h->M; sh.Np = h->Np; sh.D = h->D; sh.H = h->H; sh.S = ts ? ts_S : h->S; sh.nmodels = h->nmodels;
+    sh.N = h->N; sh.M = h->M; sh.Np = h->Np; sh.D = h->D; sh.H = h->H; sh.S = (ts || kg) ? rhs.S : h->S; sh.nmodels = h->nmodels;
     sh.flags = flags; sh.factor_pending = factor_pending; sh.kst_budget = h->opt.kst_budget;
     // The byte budgets of the plan are shares of what the device has free (a smaller or fuller GPU takes smaller chunks
     // instead of an allocation failure).  They are queried when the number of fantasies / the size of a ring slot changes, not
@@ -1234,8 +1321,8 @@ static int ei_run_impl(spx_handle* h, int32_t flags, bool factor_pending, int ts
     // share a device.  Fantasies: an eighth of free memory, at most 2 GB.
     // (spx_thompson's paths keep a budget of their own: the one cached for the fantasies, and with it the chunking of a later
     // fantasy pass, is what it is on a handle that never drew a path)
-    int64_t& fant_budget = ts ? h->ts_fant_budget : h->fant_budget;
-    int& fant_budget_S = ts ? h->ts_fant_budget_S : h->fant_budget_S;
+    int64_t& fant_budget = ts ? h->ts_fant_budget : kg ? h->kg_fant_budget : h->fant_budget;
+    int& fant_budget_S = ts ? h->ts_fant_budget_S : kg ? h->kg_fant_budget_S : h->fant_budget_S;
     if (sh.S > 0 && fant_budget_S != sh.S) {
         size_t mem_free = 0, mem_total = 0;
         int64_t b = 2048ll << 20;
@@ -1270,7 +1357,19 @@ static int ei_run_impl(spx_handle* h, int32_t flags, bool factor_pending, int ts
     const int H = h->H, D = h->D, Dp = p.Dp, Np = h->Np, hs = 3 + D, nrb = p.nrb, Hb = p.Hb, S = sh.S, ns = p.ns;
     const int64_t N = h->N, M = h->M, Mp = p.Mp, Mc = p.Mc;
     if ((rc = ei_reserve(h, p, S))) return rc;
-    const double* gammaS_all = ts ? h->ts_gammaS.d() : h->gammaS.d();
+    const int kgA = kg ? h->kg_A : 0, kgAp = (int)round_up(kgA, SPX_PADN);     // (rows of a K(A, .) launch: padded as N is)
+    if (kg) {
+        if ((rc = h->kg_As.reserve((size_t)H * kgAp * Dp * 8))) return rc;
+        if ((rc = h->kg_sA.reserve((size_t)H * kgAp * 8))) return rc;
+        if ((rc = h->kg_kxa.reserve((size_t)H * kgAp * Np * 8))) return rc;
+        if ((rc = h->kg_gammaS.reserve((size_t)H * S * Np * 8))) return rc;
+        if ((rc = h->kg_mua.reserve((size_t)H * kgA * 8))) return rc;
+        if ((rc = h->kg_Kac.reserve((size_t)Hb * kgAp * Mc * 8))) return rc;
+        if ((rc = h->kg_muc.reserve((size_t)Hb * Mc * 8))) return rc;
+        if (keep_mom && (rc = h->kg_cov.reserve((size_t)H * kgA * Mp * 8))) return rc;
+    }
+    // (read AFTER the reservations above: a buffer that grows moves)
+    const double* gammaS_all = ts ? h->ts_gammaS.d() : kg ? h->kg_gammaS.d() : h->gammaS.d();
     const int mesK = mes ? (int)h->acq_par : 0, mesJ = h->opt.mes_grid;
     if (mes) {
         if ((rc = h->mes_bpart.reserve((size_t)H * mes_bound_blocks(M) * 3 * 8))) return rc;
@@ -1312,6 +1411,21 @@ static int ei_run_impl(spx_handle* h, int32_t flags, bool factor_pending, int ts
     // factorisation's first kernel: ev_obs); a time model's predicted durations read alpha of the duration GP -- the END of
     // the factorisation (ev_fac).
     if (factor_pending && ns >= 2) HIPCHK(hipStreamWaitEvent(P, per_sec ? h->ev_fac : h->ev_obs, 0));
+    if (kg) {
+        // Once per pass, on the consumer stream (in a step: behind the factorisation queued there): the points scaled per draw;
+        // k(A, X) with the points as the rows and the observations -- the factorisation's pre-doubled rows -- as the columns of
+        // the library's own cross-covariance launch, [H][Ap][Np]; Gamma_a = W k(X, a), no mean subtracted, behind column 0 =
+        // the ordinary gamma; mu_a
+        TIMED_S(ST_SCALE, G, launch_scale_rows(G, h->kg_pts.d(), kgA, kgAp, D, Dp, ls, hs, H, 1.0, h->kg_As.d(), h->kg_sA.d()));
+        TIMED_S(ST_COV_CROSS, G, launch_cov_cross(G, h->kg_As.d(), h->kg_sA.d(), h->X2s.d(), h->s1.d(), h->htab.d(), h->kg_kxa.d(), kgA,
+                                                  kgAp, Np, Dp, H, dev_kind(h)));
+        HIPCHK(hipMemcpy2DAsync(h->kg_gammaS.d(), (size_t)S * Np * 8, h->gamma.d(), (size_t)Np * 8, (size_t)Np * 8, (size_t)H,
+                                hipMemcpyDeviceToDevice, G));
+        for (int d = 0; d < H; ++d)
+            TIMED_S(ST_GAMMA_ALPHA, G, launch_gamma_cols(G, h->WT.d() + (size_t)d * nn, h->kg_kxa.d() + (size_t)d * kgAp * Np, (size_t)Np,
+                                                         h->kg_gammaS.d() + ((size_t)d * S + 1) * Np, (int)N, Np, kgA));
+        TIMED_S(ST_KG, G, launch_kg_mu(G, h->kg_gammaS.d(), h->htab.d(), Np, S, H, h->kg_mua.d()));
+    }
     int item = 0, chunk = 0;
     for (int64_t c0 = 0; c0 < Mp; c0 += Mc, ++chunk) {
         const int mc = (int)std::min<int64_t>(Mc, Mp - c0);       // multiple of 128
@@ -1390,7 +1504,19 @@ static int ei_run_impl(spx_handle* h, int32_t flags, bool factor_pending, int ts
                                                             h->part_bg.d(), Np, mc, nhb, S > 0 ? nhb : H, S > 0 ? 0 : h0,
                                                             S > 0 ? gammaS_all + (size_t)h0 * S * Np : nullptr, S,
                                                             bgS_k, gemm_nlive));
-            if (ts)
+            if (kg) {   // k(A, c) of the work item (the points as rows: the pass's own K(X*,X) launch over A rows), its lines, its values
+                TIMED_S(ST_COV_CROSS, G, launch_cov_cross(G, h->kg_As.d() + (size_t)h0 * kgAp * Dp, h->kg_sA.d() + (size_t)h0 * kgAp,
+                                                          Cs + (size_t)h0 * mc * Dp, s2 + (size_t)h0 * mc,
+                                                          h->htab.d() + (size_t)h0 * SPX_HT, h->kg_Kac.d(), kgA, kgAp, mc, Dp, nhb,
+                                                          dev_kind(h)));
+                TIMED_S(ST_KG, G, {
+                    launch_kg_lines(G, h->part_ss.d(), bgS_k, h->htab.d() + (size_t)h0 * SPX_HT, h->kg_Kac.d(), nrb, mc, nhb, S, kgAp, c0, M,
+                                    Mp, h0, h->scratch.d(), h->kg_muc.d(), keep_mom ? h->mom_m.d() : nullptr,
+                                    keep_mom ? h->mom_v.d() : nullptr, keep_mom ? h->kg_cov.d() : nullptr);
+                    launch_kg_value(G, h->scratch.d(), h->kg_muc.d(), h->kg_mua.d() + (size_t)h0 * kgA, mc, nhb, S, c0, M, Mp, h0,
+                                    h->ei_draw.d());
+                });
+            } else if (ts)
                 TIMED_S(ST_TS_FINISH, G, launch_ts_finish(G, bgS_k, h->htab.d() + (size_t)h0 * SPX_HT, h->ts_pcand.d(), nrb, mc, nhb, S,
                                                           c0, M, Mp, h0, h->ts_path.d()));
             else if (S > 0)
@@ -1454,7 +1580,10 @@ static int ei_run_impl(spx_handle* h, int32_t flags, bool factor_pending, int ts
     Held::Results r;
     r.time_only = time_only;         // (a time-only pass has no EI results: spx_get_best & co. refuse)
     r.ts = ts;                       // (paths and priors, nothing else: every EI getter refuses)
-    r.moments = keep_mom && S == 0 && !time_only;
+    r.moments = keep_mom && (S == 0 || kg) && !time_only;   // (KG: k_kg_lines wrote func_m / func_v from column 0)
+    r.kg = kg;
+    r.kg_lines = kg && keep_mom;
+    if (kg) h->kg_last_A = kgA;
     r.tmean = keep_mom && per_sec;   // (with fantasies the pass keeps no func_m / func_v, but mom_t is written all the same)
     r.con = constrained && keep_mom && !time_only;
     r.ehvi = ehvi;
@@ -1534,6 +1663,25 @@ int spx_get_mes(spx_handle* h, int32_t draw, double* ystar, double* fit, double*
     if (ystar) HIPCHK(hipMemcpy(ystar, h->mes_ystar.d() + (size_t)draw * K, K * 8, hipMemcpyDeviceToHost));
     if (fit) HIPCHK(hipMemcpy(fit, h->mes_fit.d() + (size_t)draw * 8, 8 * 8, hipMemcpyDeviceToHost));
     if (G) HIPCHK(hipMemcpy(G, h->mes_G.d() + (size_t)draw * J, J * 8, hipMemcpyDeviceToHost));
+    return SPX_OK;
+}
+
+int spx_get_kg_lines(spx_handle* h, int32_t draw, double* mu_a, double* cov)
+{
+    if (!h) return fail(SPX_ERR_ARG, "spx_get_kg_lines: null handle");
+    if (h->multi) return fail(SPX_ERR_ARG, "spx_get_kg_lines: SPX_ACQ_KG is single-device only (multi-device handle)");
+    if (!h->held.results.kg) return fail(SPX_ERR_ARG, "spx_get_kg_lines: no knowledge-gradient results (run a pass with SPX_ACQ_KG set)");
+    if (draw < 0 || draw >= h->H) return fail(SPX_ERR_ARG, "spx_get_kg_lines: draw out of range");
+    if (cov && !h->held.results.kg_lines)
+        return fail(SPX_ERR_ARG, "spx_get_kg_lines: the covariances are kept by a pass with SPX_FLAG_KEEP_MOMENTS");
+    int rc = ensure_init(h);
+    if (rc) return rc;
+    const size_t A = (size_t)h->kg_last_A;
+    const int64_t Mp = round_up(h->M, SPX_BN);
+    if (mu_a) HIPCHK(hipMemcpy(mu_a, h->kg_mua.d() + (size_t)draw * A, A * 8, hipMemcpyDeviceToHost));
+    if (cov)
+        HIPCHK(hipMemcpy2D(cov, (size_t)h->M * 8, h->kg_cov.d() + (size_t)draw * A * Mp, (size_t)Mp * 8, (size_t)h->M * 8, A,
+                           hipMemcpyDeviceToHost));
     return SPX_OK;
 }
 
@@ -1968,6 +2116,9 @@ int spx_ei_grad_batch(spx_handle* h, const double* points, int32_t P, double* ne
     if (h->acq == SPX_ACQ_EHVI)
         return fail(SPX_ERR_ARG, "spx_ei_grad_batch: not defined under SPX_ACQ_EHVI (its refinement needs the second GP's variance "
                                  "gradient; the grid pass is the whole of it)");
+    if (h->acq == SPX_ACQ_KG)
+        return fail(SPX_ERR_ARG, "spx_ei_grad_batch: not defined under SPX_ACQ_KG (its refinement needs the gradient of the "
+                                 "envelope; the grid pass is the whole of it)");
     if (!h->held.has(Held::FACTOR)) return fail(SPX_ERR_ARG, "spx_ei_grad_batch: call spx_factor (or spx_ei_grid) first");
     const bool per_sec = (h->nmodels == 2);   // a time model was factored: EI per second (GPEIperSecChooser.py:349-434)
     if (per_sec && h->acq != SPX_ACQ_EI)
@@ -2276,7 +2427,7 @@ int spx_thompson(spx_handle* h, int32_t F, int32_t S, const double* omega_z, con
     for (int d = 0; d < H; ++d)      // Gamma_d = W_d (rhs_d - mean_d): what spx_set_fantasies does with its fantasy columns
         TIMED(ST_GAMMA_ALPHA, launch_gamma_multi(s, h->WT.d() + (size_t)d * Np * Np, h->ts_rhs.d() + (size_t)d * S * N,
                                                  h->htab.d() + (size_t)d * SPX_HT, h->ts_gammaS.d() + (size_t)d * S * Np, (int)N, Np, S));
-    if ((rc = ei_run_impl(h, 0, false, S))) {
+    if ((rc = ei_run_impl(h, 0, false, PassRhs{PassRhs::TS, S}))) {
         (void)hipStreamSynchronize(h->stream);
         (void)hipStreamSynchronize(h->stream2);
         if (h->stream3) (void)hipStreamSynchronize(h->stream3);
@@ -2421,6 +2572,9 @@ int spx_get_stat(spx_handle* h, const char* name, int64_t* value)
     else if (!strcmp(name, "last_mes_grid")) *value = h->held.results.mes ? h->mes_J : 0;      // ... J of the held MES results (0: none)
     else if (!strcmp(name, "last_ts_paths")) *value = h->held.results.ts ? h->ts_S : 0;        // S and
     else if (!strcmp(name, "last_ts_features")) *value = h->held.results.ts ? h->ts_F : 0;     // ... F of the held sample paths (0: none)
+    else if (!strcmp(name, "kg_points")) *value = h->held.has(Held::KGPTS) ? h->kg_A : 0;       // A of the held representer points (0: none)
+    else if (!strcmp(name, "last_kg_points")) *value = h->held.results.kg ? h->kg_last_A : 0;  // ... and of the held KG results
+    else if (!strcmp(name, "last_kg_lines")) *value = h->held.results.kg_lines ? 1 : 0;        // ... whose covariances are kept
     else if (!strcmp(name, "gemm_lds_bytes")) *value = (int64_t)predict_gemm_lds_bytes();   // dynamic LDS of a predict-GEMM workgroup (two are resident per CU)
     else if (!strcmp(name, "hip_runtime_version") || !strcmp(name, "hip_driver_version")) {
         // what the process runs on: a measurement names it (bench.py's line), two boxes of one pool differed in round 5

@@ -24,6 +24,8 @@ struct HeldResults {
                                // (spx_get_thompson_path / _prior), a results kind of its own -- no EI values, no winner
     bool ts_alpha = false;     // ... and alpha = W^T Gamma of every held path is resident too (built by the first
                                // spx_thompson_grad_batch after a spx_thompson); gone with the paths, so with everything that drops them
+    bool kg = false;           // the pass was a knowledge-gradient pass: mu_a of its representer points is resident
+    bool kg_lines = false;     // ... and, kept with the moments, the covariances C[d][a][c] (spx_get_kg_lines)
 };
 
 struct Held {
@@ -36,6 +38,8 @@ struct Held {
         FRONT,              // input: the Pareto front and its reference point (spx_set_pareto_front)
         SEC,                // product: the second GP's internal handle holds (comp, second values, second hypers)
         SEC_CAND,           // product: ... and the candidates
+        // the knowledge gradient (SPX_ACQ_KG), behind those again:
+        KGPTS,              // input: the representer points (spx_set_kg_points)
         COUNT
     };
     using Results = HeldResults;
@@ -64,12 +68,13 @@ static constexpr HeldRow kHeldMadeFrom[Held::COUNT] = {
     /* FULL_FACTOR */ {SPX_HB(OBS) | SPX_HB(HYP) | SPX_HB(CON), SPX_HB(COVAR)},
     /* FANT        */ {SPX_HB(FACTOR), 0},                          // S > 0 exactly when FANT is held
     /* ALPHA_S     */ {SPX_HB(FANT), 0},
-    /* RESULTS     */ {SPX_HB(FACTOR) | SPX_HB(CAND), SPX_HB(FANT) | SPX_HB(CON) | SPX_HB(PARTITION) | SPX_HB(FRONT)},
+    /* RESULTS     */ {SPX_HB(FACTOR) | SPX_HB(CAND), SPX_HB(FANT) | SPX_HB(CON) | SPX_HB(PARTITION) | SPX_HB(FRONT) | SPX_HB(KGPTS)},
     /* COVAR       */ {0, 0},
     /* PARTITION   */ {0, 0},
     /* FRONT       */ {0, 0},                                       // a new front drops the results of the last pass alone
     /* SEC         */ {SPX_HB(TIME), 0},                            // (option "covar" reaches the internal handle itself: it drops its own factor)
     /* SEC_CAND    */ {SPX_HB(CAND), 0},
+    /* KGPTS       */ {0, 0},                                       // new points drop the results of the last pass alone
 };
 #undef SPX_HB
 

@@ -96,6 +96,7 @@ enum Stage {
     ST_EHVI,              // k_ehvi of an expected-hypervolume-improvement pass (launch_ehvi)
     ST_TS_PRIOR,          // spx_thompson: k_ts_prior over the observations and over every candidate chunk (+ k_ts_rhs)
     ST_TS_FINISH,         // ... and k_ts_finish per work item + the two k_ts_argmin launches
+    ST_KG,                // a knowledge-gradient pass: k_kg_lines + k_kg_value per work item (and k_kg_mu once)
     ST_FACTOR_TOTAL, ST_EI_RUN_TOTAL, ST_COUNT
 };
 struct spx_handle {
@@ -194,6 +195,15 @@ struct spx_handle {
     int64_t ts_fant_budget = 0;    // the per-path partial means' byte budget, as fant_budget / fant_budget_S are the fantasies'
     int ts_fant_budget_S = -1;
     size_t ts_w_stride = 0;        // doubles between the draws' blocks of w (0: shared)
+    // knowledge gradient (SPX_ACQ_KG): the representer points as spx_set_kg_points received them (KGPTS held: kg_A >= 1) and on
+    // the device; per pass: the points scaled per draw [H][Ap][Dp] and their norms [H][Ap], k(A, X) [H][Ap][Np], the columns
+    // gamma | Gamma_a [H][A + 1][Np], mu_a [H][A]; per work item: k(A, c) [Hb][Ap][Mc] and mu_c [Hb][Mc] (the slopes take `scratch`);
+    // with the moments kept C [H][A][Mp].  kg_last_A: A of the held KG results (held.results.kg)
+    int kg_A = -1, kg_last_A = 0;
+    std::vector<double> kg_pts_host;
+    DevBuf kg_pts, kg_As, kg_sA, kg_kxa, kg_gammaS, kg_mua, kg_Kac, kg_muc, kg_cov;
+    int64_t kg_fant_budget = 0;    // the per-column partial means' byte budget, as fant_budget / fant_budget_S are the fantasies'
+    int kg_fant_budget_S = -1;
     DevBuf loo_out;                                                 // spx_loo: loo_mean | loo_var | kinv_diag, [3][H][N]; scratch of that call, not part of `held`
     // probit constraint model (spx_set_constraint_model): an internal handle on the same device factors
     // (amp2_c (K_c + 1e-6 I) + noise_c I) alpha_c = ff over its own Nc points; the EI pass reads its scaled rows and alpha_c

@@ -39,7 +39,9 @@ ACQ_PI = 1            # probability of improvement, parameter xi
 ACQ_LCB = 2           # negated lower confidence bound kappa * func_s - func_m, parameter kappa
 ACQ_MES = 3           # max-value entropy search, parameter K = number of y* levels (1 .. 1024); single-GPU handles only
 ACQ_EHVI = 4          # expected hypervolume improvement over (objective, second objective); par 0; single-GPU handles only
-ACQ = {"EI": ACQ_EI, "PI": ACQ_PI, "LCB": ACQ_LCB, "MES": ACQ_MES, "EHVI": ACQ_EHVI}
+ACQ_KG = 5            # knowledge gradient over representer points (set_kg_points); par 0; single-GPU handles only
+ACQ = {"EI": ACQ_EI, "PI": ACQ_PI, "LCB": ACQ_LCB, "MES": ACQ_MES, "EHVI": ACQ_EHVI, "KG": ACQ_KG}
+KG_MAX_POINTS = 255   # include/spx.h SPX_KG_MAX_POINTS: representer points spx_set_kg_points takes
 MAX_FRONT = 4096      # include/spx.h SPX_MAX_FRONT: front points spx_set_pareto_front takes
 MES_FIT_FIELDS = ("lo", "hi", "y25", "y50", "y75", "a", "b", "cap")    # include/spx.h: the fit record of spx_get_mes
 
@@ -110,6 +112,9 @@ ABI = {
     "spx_get_mes": (ctypes.c_int, [_vp, ctypes.c_int32, _c_double_p, _c_double_p, _c_double_p]),
     "spx_set_pareto_front": (ctypes.c_int, [_vp, _c_double_p, _c_double_p, ctypes.c_int32, ctypes.c_double, ctypes.c_double]),
     "spx_get_pareto_front": (ctypes.c_int, [_vp, _c_double_p, _c_double_p, _c_int32_p, _c_double_p, _c_double_p]),
+    "spx_set_kg_points": (ctypes.c_int, [_vp, _c_double_p, ctypes.c_int32]),
+    "spx_get_kg_points": (ctypes.c_int, [_vp, _c_double_p, _c_int32_p]),
+    "spx_get_kg_lines": (ctypes.c_int, [_vp, ctypes.c_int32, _c_double_p, _c_double_p]),
     "spx_main_effects": (ctypes.c_int, [_vp, _c_double_p, ctypes.c_int32, _c_double_p, ctypes.c_int32, _c_double_p, _c_double_p]),
     "spx_loo": (ctypes.c_int, [_vp, ctypes.c_int32, _c_double_p, _c_double_p, _c_double_p]),
     "spx_ei_run": (ctypes.c_int, [_vp, ctypes.c_int32]),
@@ -465,7 +470,8 @@ class Engine(object):
     def set_acquisition(self, kind, par=0.0):
         """What the next passes and refinement calls score with (include/spx.h: spx_set_acquisition): ACQ_EI (par 0),
         ACQ_PI (par = xi >= 0), ACQ_LCB (par = kappa >= 0), ACQ_MES (par = K, the number of y* levels, 1 .. 1024) or ACQ_EHVI
-        (par 0; needs set_time_model and set_pareto_front); a name of ACQ ("EI", "PI", "LCB", "MES", "EHVI") is taken too.
+        (par 0; needs set_time_model and set_pareto_front) or ACQ_KG (par 0; needs set_kg_points); a name of ACQ ("EI", "PI",
+        "LCB", "MES", "EHVI", "KG") is taken too.
         Drops the results of the last pass, keeps the factor and the fantasies."""
         if not isinstance(kind, int):
             if kind not in ACQ:
@@ -504,6 +510,39 @@ class Engine(object):
         self._check(self._lib.spx_get_pareto_front(self._h, _dp(a) if n.value else None, _dp(b) if n.value else None,
                                                    ctypes.byref(n), ctypes.byref(r1), ctypes.byref(r2)))
         return np.stack((a, b), axis=1), (float(r1.value), float(r2.value))
+
+    def set_kg_points(self, points):
+        """The representer points of an ACQ_KG pass (include/spx.h: spx_set_kg_points): points (A, D), A in 1 .. KG_MAX_POINTS,
+        D the resident observations' / candidates'.  None clears them.  Drops the results of the last pass and nothing else."""
+        if points is None:
+            self._check(self._lib.spx_set_kg_points(self._h, None, -1))
+            return
+        points = _f64(points)
+        if points.ndim != 2 or points.shape[0] < 1 or (self.D and points.shape[1] != self.D):
+            raise ValueError("set_kg_points: points must be (A, D) with A >= 1 and D = %d (got %r)" % (self.D, points.shape))
+        self._check(self._lib.spx_set_kg_points(self._h, _dp(points), points.shape[0]))
+
+    def get_kg_points(self):
+        """The representer points (A, D) as the handle holds them, or None when none are set."""
+        A = ctypes.c_int32(-1)
+        self._check(self._lib.spx_get_kg_points(self._h, None, ctypes.byref(A)))
+        if A.value < 0:
+            return None
+        pts = np.empty((A.value, self.D))
+        self._check(self._lib.spx_get_kg_points(self._h, _dp(pts), ctypes.byref(A)))
+        return pts
+
+    def kg_lines(self, draw, want_cov=True):
+        """The device's own lines of the last ACQ_KG pass for one draw (include/spx.h: spx_get_kg_lines): (mu_a (A,), cov (A, M));
+        cov -- C[a][c], the posterior covariance of candidate c and point a -- needs a pass with FLAG_KEEP_MOMENTS
+        (want_cov=False: None in its place).  ValueError when no KG pass's results are held."""
+        A = self.stat("last_kg_points")
+        if A < 1:
+            raise ValueError("kg_lines: no knowledge-gradient results (run a pass with ACQ_KG set)")
+        mu = np.empty(A)
+        cov = np.empty((A, self.M)) if want_cov else None
+        self._check(self._lib.spx_get_kg_lines(self._h, int(draw), _dp(mu), _dp(cov)))
+        return mu, cov
 
     def mes_info(self, draw):
         """What the last max-value entropy search pass fitted for one draw (include/spx.h: spx_get_mes): a dict with ystar
@@ -940,6 +979,12 @@ class MultiEngine(Engine):
 
     def thompson(self, S=1, F=1024, rng=None, per_draw=False, randoms=None):
         raise ValueError("thompson is not available on a multi-device engine (include/spx.h: spx_thompson)")
+
+    def set_kg_points(self, points):
+        raise ValueError("the knowledge gradient is not available on a multi-device engine (include/spx.h: SPX_ACQ_KG)")
+
+    def kg_lines(self, draw, want_cov=True):
+        raise ValueError("the knowledge gradient is not available on a multi-device engine (include/spx.h: SPX_ACQ_KG)")
 
     def thompson_grad_batch(self, points, path_of=None, want_prior=False):
         raise ValueError("thompson_grad_batch is not available on a multi-device engine: it holds no sample paths "
