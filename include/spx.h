@@ -274,6 +274,30 @@ int spx_get_acquisition(spx_handle* h, int32_t* kind, double* par);   /* either 
  * pointer may be NULL.                                                                                                    */
 int spx_get_mes(spx_handle* h, int32_t draw, double* ystar /* K */, double* fit /* 8 */, double* G /* J */);
 
+/* ---- ... while jobs are pending: MES over the fantasies (option "mes_fantasies") -------------------------------------------------
+ * spx_set_option(h, "mes_fantasies", 1) (default 0: the refusal above stands): with SPX_ACQ_MES set and fantasies held
+ * (spx_set_fantasies / spx_draw_fantasies, S per draw), spx_ei_run runs the pending branch's predict GEMM -- the same launches as an
+ * EI pass over the fantasies -- and then the rule above per (draw d, fantasy s) instead of per draw:
+ *   mu[d][s][c]  the predictive mean of candidate c under fantasy s (the sum the EI branch forms for that column, bit for bit),
+ *   v[d][c]      the predictive variance, which does not depend on the fantasy; sigma = sqrt(v),
+ *   steps 1-4 over the candidates for every (d, s), with best = bests[d][s] in the cap, giving y*[d][s][k]; a candidate is left
+ *   out of (d, s) when mu[d][s][c] is not finite, and of every fantasy of d when v[d][c] is not > 0 and finite,
+ *   MES_ds(c) by step 5, and the value of (d, c) = the mean of MES_ds(c) over s in numpy's pairwise order (np.mean),
+ * then the mean over the draws, the argmax rule and the result getters of every pass.  A (d, s) without a valid candidate is NaN
+ * throughout, and so is every value of draw d.  Same bits for every chunking, draw grouping, "streams" and "gemm_partial".  The
+ * stages run behind the last chunk, before the pass's single synchronisation, and are part of the stage "mes".
+ * The tables are results of the pass: they go with the fantasies, with everything that drops a plain MES table, and whenever the
+ * option is set (an unchanged value included).  spx_get_stat "last_mes_fantasies": S of a held table over fantasies (0: none,
+ * or a plain table).  While such a table is held spx_get_mes refuses (naming spx_get_mes_fantasy) and spx_ei_grad_batch under
+ * SPX_ACQ_MES refuses: refinement against H S tables is not defined.
+ * REFUSED with SPX_ERR_ARG as for plain MES (flags, multi-device handles, communicators, partitions), and, from the host's record
+ * alone, when the means (H S Mp 8 bytes, Mp = M rounded up to 128) or the partial sums (H S ceil(M / 512) J 8 bytes) exceed
+ * SPX_KG_MAX_LINE_BYTES; the message names the size.
+ * spx_get_mes_fantasy: of (draw, s) of the held table, ystar (K), fit (8) and G (J), as spx_get_mes lays them out.
+ * spx_get_mes_fantasy_moments: mu[draw][s][.] and v[draw][.] (M each).  Any pointer may be NULL.                                  */
+int spx_get_mes_fantasy(spx_handle* h, int32_t draw, int32_t s, double* ystar /* K */, double* fit /* 8 */, double* G /* J */);
+int spx_get_mes_fantasy_moments(spx_handle* h, int32_t draw, int32_t s, double* func_m /* M */, double* func_v /* M */);
+
 /* ---- two objectives: expected hypervolume improvement (SPX_ACQ_EHVI) -----------------------------------------------------
  * Both objectives are minimised.  The first is the handle's own GP; the SECOND objective's GP is the model that
  * spx_set_time_model holds: its `log_durs` argument is "the second objective's values" of the resident rows (the chooser passes

@@ -296,6 +296,21 @@ class GPEIOptChooser(GPEIBase):
                 self._loo(complete, comp, vals, rows)
             return job
 
+        if self.acq == "MES" and self.mes_pending and pend.shape[0] > 0:
+            # MES over the fantasies of the pending jobs: the grid point of the highest value.  One pass over the grid alone (y* is
+            # a property of the candidate set; the sprayed points' normals above are drawn all the same) and no refinement: the
+            # library defines none against H S tables.  The fantasy normals leave the generator where an acq=EI call leaves it.
+            randn = self._fantasy_normals(pend)
+            best, _, _ = self.ei_over_hypers_gpu(comp, pend, cand, vals, rows, want_draws=False, randn=randn)
+            job = int(candidates[best])
+            if self.recommend:
+                self._recommend(grid, comp, vals, rows, refine_count=self.grid_subset)
+            if self.importance:
+                self._importance(grid, comp, vals, rows)
+            if self.loo:
+                self._loo(complete, comp, vals, rows)
+            return job
+
         # pass 1 over grid + sprayed points, keep the grid_subset best (:269-271)
         randn = self._fantasy_normals(pend) if pend.shape[0] > 0 else None
         _, mean1, _ = self.ei_over_hypers_gpu(comp, pend, cand2, vals, rows, want_draws=False, randn=randn)

@@ -62,7 +62,8 @@ class GPEIBase(object):
     def __init__(self, expt_dir, covar="Matern52", mcmc_iters=10, pending_samples=100,
                  noiseless=False, device=0, ndev=1, lib=None, gpu_logprob="auto", gpu_refine="auto",
                  lookahead="auto", follow="auto", sampler="native", gpu_sobol=0, gpu_fantasies="auto", acq="EI", acq_par=0,
-                 recommend=0, importance=0, importance_levels=16, importance_points=256, loo=0, ts_refine=0, **unused):
+                 recommend=0, importance=0, importance_levels=16, importance_points=256, loo=0, ts_refine=0, mes_pending=0,
+                 **unused):
         if covar not in hostgp.COVARS:
             # the reference does getattr(gp, covar) here (GPEIChooser.py:52)
             raise AttributeError("no covariance function %r (gp.py has %s)" % (covar, ", ".join(hostgp.COVARS)))
@@ -77,6 +78,12 @@ class GPEIBase(object):
         if self.acq == "KG" and int(ndev) > 1:
             raise ValueError("acq=KG is not available with ndev=%d: the representer points' columns live on one device "
                              "(allowed: ndev=1, or acq=EI, PI, LCB)" % int(ndev))
+        # mes_pending=1: acq=MES scores a call with pending jobs itself, over the fantasies (include/spx.h: option
+        # "mes_fantasies"); 0: such a call is scored with EI over the fantasies
+        self.mes_pending = _as_bool(mes_pending)
+        if self.mes_pending and self.acq != "MES":
+            raise ValueError("mes_pending=1 is max-value entropy search over the fantasies of pending jobs (allowed with acq=%s: "
+                             "mes_pending=0)" % self.acq)
         self.last_kg = None            # acq=KG: {"points_index", "points", "grid_index", "value"} of the last call scored with KG
         self.ts_refine = _as_bool(ts_refine)
         if self.ts_refine and not self.ts_refine_allowed:
@@ -212,11 +219,14 @@ class GPEIBase(object):
 
     def _apply_acquisition(self, eng, pending=False):
         """Before a pass: the handle scores with this chooser's acquisition.  EI is the handle's default and is left
-        untouched, so an engine that knows nothing else is never asked.  acq=MES while jobs are pending: the library refuses
-        MES over fantasies, so the call is scored with EI over the fantasies, exactly as an acq=EI chooser scores it
-        (last_acq_used says which one it was)."""
+        untouched, so an engine that knows nothing else is never asked.  acq=MES while jobs are pending: by default the
+        library refuses MES over fantasies, so the call is scored with EI over the fantasies, exactly as an acq=EI chooser
+        scores it (last_acq_used says which one it was); with mes_pending=1 the handle's option "mes_fantasies" is set and
+        the pass is MES per (draw, fantasy), averaged over the fantasies."""
         acq, par = self.acq, self.acq_par
-        if acq in ("MES", "KG") and pending:     # (KG likewise: the library refuses it over fantasies -- the MES rule)
+        if acq == "MES" and pending and self.mes_pending:
+            eng.set_option("mes_fantasies", 1)
+        elif acq in ("MES", "KG") and pending:   # (KG likewise: the library refuses it over fantasies -- the MES rule)
             acq, par = "EI", 0.0
         if acq == "KG":                          # (A is the chooser's; the handle's acquisition takes no parameter)
             par = 0.0

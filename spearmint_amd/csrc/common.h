@@ -205,6 +205,19 @@ int ts_argmin_blocks(int64_t M);
 void launch_ts_argmin(hipStream_t s, const double* path, int64_t M, int64_t Mp, int npaths, double* blk_val, int64_t* blk_idx,
                       double* out_val, int64_t* out_idx, int64_t index_base);
 
+// mes_fant_kernels.hip: max-value entropy search over the fantasies of the S > 0 GEMM branch (spx.h: option "mes_fantasies").  Per
+// work item the means mu [H][S][Mp] and the shared variance v [H][Mp] from its partial sums; behind the last chunk the bounds,
+// the log-survival sums, the fit per (draw, fantasy) and the values, their mean over the fantasies into ei_draw.
+// bpart: [H][S][mes_fant_bound_blocks(M)][3], bnd: [H][S][3], part: [H][S][mes_fant_sum_blocks(M)][J], G: [H][S][J],
+// ystar: [H][S][K], fit: [H][S][8], bests: [H][S]; hyp as launch_mes takes it
+int mes_fant_sum_blocks(int64_t M);
+int mes_fant_bound_blocks(int64_t M);
+void launch_mes_fant_means(hipStream_t s, const double* part_ss, const double* part_bgS, const double* htab, int nrb, int Mc, int nh,
+                           int S, int64_t c0, int64_t M, int64_t Mp, int h0, double* mu, double* v);
+void launch_mes_fant(hipStream_t s, const double* mu, const double* v, const double* hyp, int hs, const double* bests, int64_t M,
+                     int64_t Mp, int H, int S, int J, int K, double* bpart, double* bnd, double* part, double* G, double* ystar,
+                     double* fit, double* ei_draw);
+
 // ts_grad_kernels.hip: value and gradient of sample paths at points x [P][D], point p under path path_of[p] = draw S + s (null:
 // path 0 of draw 0) (spx.h: spx_thompson_grad_batch).  The prior and its gradient into prior [P] and gp [P][D]; then, one
 // workgroup per point, the update term against alpha [H S][Np] and the combine into out [P][2 + D] = {value, prior, grad};

@@ -115,3 +115,70 @@ SPX_MES_FN void mes_h_terms(double g, double& h, double& hp)
     h = (g * r) / 2.0 - lcdf;
     if (GRAD) hp = -(r / 2.0) * ((1.0 + g * g) + g * r);
 }
+
+#ifndef SPX_MES_HOST
+// ---- shared by the kernels of the plain pass (mes_kernels.hip) and of the pass over fantasies (mes_fant_kernels.hip) ----
+SPX_MES_FN bool mes_valid(double mu, double v) { return isfinite(mu) && v > 0.0 && isfinite(v); }
+
+// s += x, compensated
+SPX_MES_FN void mes_add(double& s, double& comp, double x)
+{
+#pragma clang fp contract(off)
+    const double t = s + x;
+    if (fabs(s) >= fabs(x)) comp += (s - t) + x;
+    else comp += (x - t) + s;
+    s = t;
+}
+
+// One fit record by one workgroup of 256 threads, from its bracket and its partial sums part [nb][J]: G_j = the partial sums in
+// block order, the quartiles of the minimum by linear interpolation of G on the probe grid, the reflected-Gumbel fit, K levels
+// y*_k = min(a + b w_k, cap).  fit = {lo, hi, y25, y50, y75, a, b, cap}.  sg [J], sh_q [3], sh_ab [3]: LDS of the caller.
+SPX_MES_FN void mes_fit_record(double lo, double hi, bool any_valid, const double* __restrict__ part, int nb, int J, int K,
+                               double noise, double best, double* __restrict__ G, double* __restrict__ ystar,
+                               double* __restrict__ fit, double* sg, double* sh_q, double* sh_ab)
+{
+#pragma clang fp contract(off)
+    const int tid = threadIdx.x;
+    for (int j = tid; j < J; j += 256) {
+        double s = 0.0, comp = 0.0;
+        for (int b = 0; b < nb; ++b) mes_add(s, comp, part[(size_t)b * J + j]);
+        const double g = any_valid ? s + comp : __builtin_nan("");
+        G[j] = g;
+        sg[j] = g;
+    }
+    __syncthreads();
+    const double step = (hi - lo) / (double)(J - 1);
+    if (tid < 3) {
+        // t_p = log(1 - p) for p = 0.25, 0.5, 0.75
+        const double tp = tid == 0 ? -0.2876820724517809 : tid == 1 ? -0.6931471805599453 : -1.3862943611198906;
+        int j = 0;
+        while (j < J && !(sg[j] <= tp)) ++j;
+        double yp = __builtin_nan("");
+        if (j > 0 && j < J) {
+            const double y0 = lo + (double)(j - 1) * step, y1 = lo + (double)j * step;
+            const double g0 = sg[j - 1], g1 = sg[j];
+            yp = y0 + (y1 - y0) * (g0 - tp) / (g0 - g1);
+        }
+        sh_q[tid] = yp;
+    }
+    __syncthreads();
+    if (tid == 0) {
+        const double bb = (sh_q[2] - sh_q[0]) / 1.5725335836855194;     // log(log 4) - log(log(4/3))
+        const double aa = sh_q[1] - bb * -0.36651292058166435;          // log(log 2)
+        const double c5 = 5.0 * sqrt(noise);
+        const double cap = best - c5;
+        sh_ab[0] = aa; sh_ab[1] = bb; sh_ab[2] = cap;
+        fit[0] = lo; fit[1] = hi; fit[2] = sh_q[0]; fit[3] = sh_q[1]; fit[4] = sh_q[2]; fit[5] = aa; fit[6] = bb; fit[7] = cap;
+    }
+    __syncthreads();
+    const double aa = sh_ab[0], bb = sh_ab[1], cap = sh_ab[2];
+    for (int k = tid; k < K; k += 256) {
+        const double u = ((double)k + 0.5) / (double)K;
+        const double w = log(-log1p(-u));
+        const double bw = bb * w;
+        double y = aa + bw;
+        y = (y < cap || y != y) ? y : cap;          // np.minimum: NaN on either side stays
+        ystar[k] = y;
+    }
+}
+#endif

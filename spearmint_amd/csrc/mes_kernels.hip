@@ -16,18 +16,6 @@
 int mes_sum_blocks(int64_t M) { return (int)((M + MES_CT - 1) / MES_CT); }
 int mes_bound_blocks(int64_t M) { return (int)((M + MES_BT - 1) / MES_BT); }
 
-__device__ __forceinline__ bool mes_valid(double mu, double v) { return isfinite(mu) && v > 0.0 && isfinite(v); }
-
-// s += x, compensated
-__device__ __forceinline__ void mes_add(double& s, double& comp, double x)
-{
-#pragma clang fp contract(off)
-    const double t = s + x;
-    if (fabs(s) >= fabs(x)) comp += (s - t) + x;
-    else comp += (x - t) + s;
-    s = t;
-}
-
 // min over the block of two values and the "or" of a flag; every thread returns with the results
 __device__ __forceinline__ void mes_block_min2(double& lo, double& hi, double& any, double (*red)[4])
 {
@@ -140,53 +128,12 @@ __global__ __launch_bounds__(256) void k_mes_fit(const double* __restrict__ bpar
     extern __shared__ double sg[];     // [J]
     __shared__ double red[3][4];
     __shared__ double sh_q[3], sh_ab[3];
-    const int h = blockIdx.x, tid = threadIdx.x;
+    const int h = blockIdx.x;
     double lo, hi;
     bool any_valid;
     mes_draw_bounds(bpart, h, nbb, red, lo, hi, any_valid);
-    for (int j = tid; j < J; j += 256) {
-        double s = 0.0, comp = 0.0;
-        for (int b = 0; b < nb; ++b) mes_add(s, comp, part[((size_t)h * nb + b) * J + j]);
-        const double g = any_valid ? s + comp : __builtin_nan("");
-        G[(size_t)h * J + j] = g;
-        sg[j] = g;
-    }
-    __syncthreads();
-    const double step = (hi - lo) / (double)(J - 1);
-    if (tid < 3) {
-        // t_p = log(1 - p) for p = 0.25, 0.5, 0.75
-        const double tp = tid == 0 ? -0.2876820724517809 : tid == 1 ? -0.6931471805599453 : -1.3862943611198906;
-        int j = 0;
-        while (j < J && !(sg[j] <= tp)) ++j;
-        double yp = __builtin_nan("");
-        if (j > 0 && j < J) {
-            const double y0 = lo + (double)(j - 1) * step, y1 = lo + (double)j * step;
-            const double g0 = sg[j - 1], g1 = sg[j];
-            yp = y0 + (y1 - y0) * (g0 - tp) / (g0 - g1);
-        }
-        sh_q[tid] = yp;
-    }
-    __syncthreads();
-    if (tid == 0) {
-        const double noise = hyp[(size_t)h * hs + 1];
-        const double bb = (sh_q[2] - sh_q[0]) / 1.5725335836855194;     // log(log 4) - log(log(4/3))
-        const double aa = sh_q[1] - bb * -0.36651292058166435;          // log(log 2)
-        const double c5 = 5.0 * sqrt(noise);
-        const double cap = best - c5;
-        sh_ab[0] = aa; sh_ab[1] = bb; sh_ab[2] = cap;
-        double* f = fit + (size_t)h * 8;
-        f[0] = lo; f[1] = hi; f[2] = sh_q[0]; f[3] = sh_q[1]; f[4] = sh_q[2]; f[5] = aa; f[6] = bb; f[7] = cap;
-    }
-    __syncthreads();
-    const double aa = sh_ab[0], bb = sh_ab[1], cap = sh_ab[2];
-    for (int k = tid; k < K; k += 256) {
-        const double u = ((double)k + 0.5) / (double)K;
-        const double w = log(-log1p(-u));
-        const double bw = bb * w;
-        double y = aa + bw;
-        y = (y < cap || y != y) ? y : cap;          // np.minimum: NaN on either side stays
-        ystar[(size_t)h * K + k] = y;
-    }
+    mes_fit_record(lo, hi, any_valid, part + (size_t)h * nb * J, nb, J, K, hyp[(size_t)h * hs + 1], best, G + (size_t)h * J,
+                   ystar + (size_t)h * K, fit + (size_t)h * 8, sg, sh_q, sh_ab);
 }
 
 // one thread per (candidate, draw); pad columns c >= M are not written, as k_ei_finalize leaves them

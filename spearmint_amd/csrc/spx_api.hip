@@ -212,6 +212,13 @@ static int opt_mes_grid(spx_handle* h, int64_t value)
     h->opt.mes_grid = (int)value;
     return SPX_OK;
 }
+// SPX_ACQ_MES with fantasies held: over the fantasies (1) or refused (0); the tables of the last pass belong to the old setting
+static int opt_mes_fantasies(spx_handle* h, int64_t value)
+{
+    spx_drop(h, Held::RESULTS);
+    h->opt.mes_fantasies = value > 0;
+    return SPX_OK;
+}
 static int opt_timing(spx_handle* h, int64_t value)
 {
     h->opt.timing = value != 0;
@@ -256,6 +263,7 @@ static const OptRow kOptions[] = {
     OPT_CLAMP("kstar_ring", ring_opt, 0, 4096),         // streams = 3: staging slots of the ring (0, default: as many as the byte budget holds)
     OPT_TRI("kstar_corun", corun_opt),                  // streams = 3: K(X*,X) launches beside a GEMM in the form that fits there (1, default) or as k_cov_flat (0); same bits
     OPT_CALL("mes_grid", opt_mes_grid),                 // SPX_ACQ_MES: probe values J of the log-survival grid (default 256, 8 .. 4096); drops the last pass's results
+    OPT_CALL("mes_fantasies", opt_mes_fantasies),       // SPX_ACQ_MES while fantasies are held: MES per (draw, fantasy), averaged (1) or refused (0, default); drops the last pass's results
     OPT_CALL("timing", opt_timing),                     // per-launch HIP events on the handle's stream; (re)starts the accumulators
 };
 
@@ -314,7 +322,7 @@ void spx_destroy(spx_handle* h)
                           &h->am_out_val, &h->am_out_idx, &h->scratch, &h->sobol_dirs, &h->sobol_out, &h->rhs, &h->diagL, &h->ps_flags, &h->flow_flags,
                           &h->alphaS, &h->pt_u, &h->rec_send, &h->rec_recv, &h->rec_out, &h->ei_sum_full,
                           &h->con_tab, &h->mom_c, &h->rhs_rows, &h->eff_in, &h->eff_m, &h->eff_out, &h->loo_out,
-                          &h->mes_bpart, &h->mes_part, &h->mes_G, &h->mes_ystar, &h->mes_fit, &h->front_dev,
+                          &h->mes_bpart, &h->mes_part, &h->mes_G, &h->mes_ystar, &h->mes_fit, &h->mesf_mu, &h->mesf_v, &h->mesf_bpart, &h->mesf_bnd, &h->front_dev,
                           &h->ts_par, &h->ts_w, &h->ts_eps, &h->ts_pobs, &h->ts_rhs, &h->ts_gammaS, &h->ts_pcand, &h->ts_path,
                           &h->ts_am_val, &h->ts_am_idx, &h->ts_out_val, &h->ts_out_idx,
                           &h->ts_alpha, &h->ts_gin, &h->ts_gwork, &h->ts_gout,
@@ -1106,6 +1114,20 @@ static int check_run_flags(const spx_handle* h, int32_t flags, int nmodels)
     if (h->acq == SPX_ACQ_MES && (h->comm || h->part_ph > 1 || h->part_M > 0))
         return fail(SPX_ERR_ARG, "spx_ei_run: SPX_ACQ_MES is single-device only: y* of a draw needs every shard's moments "
                                  "(communicator attached or 2-D partition set)");
+    // MES over fantasies (option "mes_fantasies"): the resident means and the partial sums, from the host's record alone
+    if (h->acq == SPX_ACQ_MES && h->S > 0 && h->opt.mes_fantasies && h->held.has(Held::CAND) && h->held.has(Held::HYP)) {
+        const double rec = (double)h->H * h->S;
+        const double mu_bytes = rec * (double)round_up(h->M, SPX_BN) * 8.0;
+        const double part_bytes = rec * mes_fant_sum_blocks(h->M) * (double)h->opt.mes_grid * 8.0;
+        if (mu_bytes > (double)SPX_KG_MAX_LINE_BYTES)
+            return fail(SPX_ERR_ARG, "spx_ei_run: H S Mp 8 = %d x %d x %lld x 8 = %.0f bytes of means per (draw, fantasy) (SPX_ACQ_MES "
+                                     "over fantasies allows up to %lld bytes)", h->H, h->S, (long long)round_up(h->M, SPX_BN), mu_bytes,
+                        (long long)SPX_KG_MAX_LINE_BYTES);
+        if (part_bytes > (double)SPX_KG_MAX_LINE_BYTES)
+            return fail(SPX_ERR_ARG, "spx_ei_run: H S ceil(M / 512) J 8 = %.0f bytes of partial log-survival sums (SPX_ACQ_MES over "
+                                     "fantasies allows up to %lld bytes; a smaller mes_grid or fewer fantasies)", part_bytes,
+                        (long long)SPX_KG_MAX_LINE_BYTES);
+    }
     if (time_only && !(per_sec && keep_mom))
         return fail(SPX_ERR_ARG, "spx_ei_run: SPX_FLAG_TIME_ONLY needs SPX_FLAG_PER_SEC | SPX_FLAG_KEEP_MOMENTS");
     if (time_only && h->comm) return fail(SPX_ERR_ARG, "spx_ei_run: SPX_FLAG_TIME_ONLY has no winner to exchange (communicator attached)");
@@ -1294,13 +1316,14 @@ static int ei_run_impl(spx_handle* h, int32_t flags, bool factor_pending, PassRh
     // setting is not touched: the pass's kernels are handed pass_acq), then the MES stages on the same stream, which
     // overwrite the per-draw values before the mean and the argmax -- still ONE synchronisation.
     const bool mes = !ts && h->acq == SPX_ACQ_MES;
-    if (mes && h->S > 0)
+    const bool mesf = mes && h->S > 0 && h->opt.mes_fantasies;     // ... over the fantasies: the S > 0 branch, mes_fant_kernels.hip
+    if (mes && h->S > 0 && !mesf)
         return fail(SPX_ERR_ARG, "spx_ei_run: SPX_ACQ_MES is not defined over fantasies (clear them, or score the call with "
                                  "SPX_ACQ_EI)");
     // Expected hypervolume improvement: the same shape -- the pass as EI with the moments kept, k_ehvi behind it on the same
     // stream -- after the second GP's pass over the same candidates (ehvi_second, below)
     const bool ehvi = !ts && h->acq == SPX_ACQ_EHVI;
-    if (mes || ehvi) flags |= SPX_FLAG_KEEP_MOMENTS;
+    if ((mes && !mesf) || ehvi) flags |= SPX_FLAG_KEEP_MOMENTS;
     // Knowledge gradient: the S > 0 branch over gamma | Gamma_a (column 0 gives func_m, the others q(c, a)), the lines and the
     // values per work item in place of the acquisition; then the mean and the argmax of every pass (check_kg passed above)
     const bool kg = !ts && h->acq == SPX_ACQ_KG;
@@ -1371,12 +1394,19 @@ static int ei_run_impl(spx_handle* h, int32_t flags, bool factor_pending, PassRh
     // (read AFTER the reservations above: a buffer that grows moves)
     const double* gammaS_all = ts ? h->ts_gammaS.d() : kg ? h->kg_gammaS.d() : h->gammaS.d();
     const int mesK = mes ? (int)h->acq_par : 0, mesJ = h->opt.mes_grid;
+    const size_t mes_rec = mesf ? (size_t)H * S : (size_t)H;      // fit records: per draw, or per (draw, fantasy)
     if (mes) {
-        if ((rc = h->mes_bpart.reserve((size_t)H * mes_bound_blocks(M) * 3 * 8))) return rc;
-        if ((rc = h->mes_part.reserve((size_t)H * mes_sum_blocks(M) * mesJ * 8))) return rc;
-        if ((rc = h->mes_G.reserve((size_t)H * mesJ * 8))) return rc;
-        if ((rc = h->mes_ystar.reserve((size_t)H * mesK * 8))) return rc;
-        if ((rc = h->mes_fit.reserve((size_t)H * 8 * 8))) return rc;
+        if (!mesf && (rc = h->mes_bpart.reserve((size_t)H * mes_bound_blocks(M) * 3 * 8))) return rc;
+        if ((rc = h->mes_part.reserve(mes_rec * (mesf ? mes_fant_sum_blocks(M) : mes_sum_blocks(M)) * mesJ * 8))) return rc;
+        if ((rc = h->mes_G.reserve(mes_rec * mesJ * 8))) return rc;
+        if ((rc = h->mes_ystar.reserve(mes_rec * mesK * 8))) return rc;
+        if ((rc = h->mes_fit.reserve(mes_rec * 8 * 8))) return rc;
+    }
+    if (mesf) {
+        if ((rc = h->mesf_mu.reserve(mes_rec * Mp * 8))) return rc;
+        if ((rc = h->mesf_v.reserve((size_t)H * Mp * 8))) return rc;
+        if ((rc = h->mesf_bpart.reserve(mes_rec * mes_fant_bound_blocks(M) * 3 * 8))) return rc;
+        if ((rc = h->mesf_bnd.reserve(mes_rec * 3 * 8))) return rc;
     }
     h->corun_launches = 0;
 
@@ -1519,6 +1549,9 @@ static int ei_run_impl(spx_handle* h, int32_t flags, bool factor_pending, PassRh
             } else if (ts)
                 TIMED_S(ST_TS_FINISH, G, launch_ts_finish(G, bgS_k, h->htab.d() + (size_t)h0 * SPX_HT, h->ts_pcand.d(), nrb, mc, nhb, S,
                                                           c0, M, Mp, h0, h->ts_path.d()));
+            else if (mesf)    // the means of the work item in place of its EI values: the stages behind the last chunk read them
+                TIMED_S(ST_MES, G, launch_mes_fant_means(G, h->part_ss.d(), bgS_k, h->htab.d() + (size_t)h0 * SPX_HT, nrb, mc, nhb, S,
+                                                         c0, M, Mp, h0, h->mesf_mu.d(), h->mesf_v.d()));
             else if (S > 0)
                 TIMED_S(ST_EI_FINALIZE, G, launch_ei_finalize_fant(G, h->part_ss.d(), bgS_k,
                                                                    h->htab.d() + (size_t)h0 * SPX_HT,
@@ -1542,7 +1575,11 @@ static int ei_run_impl(spx_handle* h, int32_t flags, bool factor_pending, PassRh
     const int n_info = p.n_info;
     if ((rc = h->pin_res.reserve(16 + (size_t)n_info * sizeof(int)))) return rc;
     double* mirror = (double*)h->pin_res.p;
-    if (mes)   // behind the last finalize on the main stream: every draw's moments are complete
+    if (mesf)  // behind the last chunk on the main stream: the means of every (draw, fantasy) are complete
+        TIMED(ST_MES, launch_mes_fant(s, h->mesf_mu.d(), h->mesf_v.d(), h->htab.d(), SPX_HT, h->bests.d(), M, Mp, H, S, mesJ, mesK,
+                                      h->mesf_bpart.d(), h->mesf_bnd.d(), h->mes_part.d(), h->mes_G.d(), h->mes_ystar.d(),
+                                      h->mes_fit.d(), h->ei_draw.d()));
+    else if (mes)   // behind the last finalize on the main stream: every draw's moments are complete
         TIMED(ST_MES, launch_mes(s, h->mom_m.d(), h->mom_v.d(), h->htab.d(), SPX_HT, h->best, M, Mp, H, mesJ, mesK, h->mes_bpart.d(),
                                  h->mes_part.d(), h->mes_G.d(), h->mes_ystar.d(), h->mes_fit.d(), h->ei_draw.d()));
     if (ehvi) {   // likewise; the second GP's moments were complete (and synchronised) before this pass began
@@ -1588,7 +1625,8 @@ static int ei_run_impl(spx_handle* h, int32_t flags, bool factor_pending, PassRh
     r.con = constrained && keep_mom && !time_only;
     r.ehvi = ehvi;
     r.mes = mes;
-    if (mes) { h->mes_K = mesK; h->mes_J = mesJ; }
+    r.mes_fant = mesf;
+    if (mes) { h->mes_K = mesK; h->mes_J = mesJ; h->mes_S = mesf ? S : 0; }
     if (h->comm && (rc = spx_comm_exchange(h, &r.global2d))) return rc;   // one process per GPU: the winner over all ranks
     return spx_hold(h, Held::RESULTS, r);
 }
@@ -1656,6 +1694,9 @@ int spx_get_mes(spx_handle* h, int32_t draw, double* ystar, double* fit, double*
     if (!h) return fail(SPX_ERR_ARG, "spx_get_mes: null handle");
     if (h->multi) return fail(SPX_ERR_ARG, "spx_get_mes: SPX_ACQ_MES is single-device only (multi-device handle)");
     if (!h->held.results.mes) return fail(SPX_ERR_ARG, "spx_get_mes: no max-value entropy search results (run a pass with SPX_ACQ_MES set)");
+    if (h->held.results.mes_fant)
+        return fail(SPX_ERR_ARG, "spx_get_mes: the held tables are per (draw, fantasy) (a pass over fantasies, option mes_fantasies): "
+                                 "spx_get_mes_fantasy serves them");
     if (draw < 0 || draw >= h->H) return fail(SPX_ERR_ARG, "spx_get_mes: draw out of range");
     int rc = ensure_init(h);
     if (rc) return rc;
@@ -1663,6 +1704,43 @@ int spx_get_mes(spx_handle* h, int32_t draw, double* ystar, double* fit, double*
     if (ystar) HIPCHK(hipMemcpy(ystar, h->mes_ystar.d() + (size_t)draw * K, K * 8, hipMemcpyDeviceToHost));
     if (fit) HIPCHK(hipMemcpy(fit, h->mes_fit.d() + (size_t)draw * 8, 8 * 8, hipMemcpyDeviceToHost));
     if (G) HIPCHK(hipMemcpy(G, h->mes_G.d() + (size_t)draw * J, J * 8, hipMemcpyDeviceToHost));
+    return SPX_OK;
+}
+
+// what both getters of a pass over fantasies check; r: the record draw * S + s
+static int mes_fantasy_record(spx_handle* h, const char* who, int32_t draw, int32_t s, size_t* r)
+{
+    if (!h) return fail(SPX_ERR_ARG, "%s: null handle", who);
+    if (h->multi) return fail(SPX_ERR_ARG, "%s: SPX_ACQ_MES is single-device only (multi-device handle)", who);
+    if (!h->held.results.mes_fant)
+        return fail(SPX_ERR_ARG, "%s: no max-value entropy search results over fantasies (run a pass with SPX_ACQ_MES set, fantasies "
+                                 "held and option mes_fantasies on)", who);
+    if (draw < 0 || draw >= h->H) return fail(SPX_ERR_ARG, "%s: draw out of range", who);
+    if (s < 0 || s >= h->mes_S) return fail(SPX_ERR_ARG, "%s: fantasy out of range (the held table has %d)", who, h->mes_S);
+    *r = (size_t)draw * h->mes_S + s;
+    return ensure_init(h);
+}
+
+int spx_get_mes_fantasy(spx_handle* h, int32_t draw, int32_t s, double* ystar, double* fit, double* G)
+{
+    size_t r = 0;
+    int rc = mes_fantasy_record(h, "spx_get_mes_fantasy", draw, s, &r);
+    if (rc) return rc;
+    const size_t K = (size_t)h->mes_K, J = (size_t)h->mes_J;
+    if (ystar) HIPCHK(hipMemcpy(ystar, h->mes_ystar.d() + r * K, K * 8, hipMemcpyDeviceToHost));
+    if (fit) HIPCHK(hipMemcpy(fit, h->mes_fit.d() + r * 8, 8 * 8, hipMemcpyDeviceToHost));
+    if (G) HIPCHK(hipMemcpy(G, h->mes_G.d() + r * J, J * 8, hipMemcpyDeviceToHost));
+    return SPX_OK;
+}
+
+int spx_get_mes_fantasy_moments(spx_handle* h, int32_t draw, int32_t s, double* func_m, double* func_v)
+{
+    size_t r = 0;
+    int rc = mes_fantasy_record(h, "spx_get_mes_fantasy_moments", draw, s, &r);
+    if (rc) return rc;
+    const int64_t Mp = round_up(h->M, SPX_BN);
+    if (func_m) HIPCHK(hipMemcpy(func_m, h->mesf_mu.d() + r * Mp, (size_t)h->M * 8, hipMemcpyDeviceToHost));
+    if (func_v) HIPCHK(hipMemcpy(func_v, h->mesf_v.d() + (size_t)draw * Mp, (size_t)h->M * 8, hipMemcpyDeviceToHost));
     return SPX_OK;
 }
 
@@ -2128,6 +2206,9 @@ int spx_ei_grad_batch(spx_handle* h, const double* points, int32_t P, double* ne
         return fail(SPX_ERR_ARG, "spx_ei_grad_batch: fantasies with a time model are not defined "
                     "(the reference's per-second refinement ignores pending jobs)");
     // MES: against the y* table of the last MES pass, held fixed (a reader of it: nothing is dropped)
+    if (h->acq == SPX_ACQ_MES && h->held.results.mes_fant)
+        return fail(SPX_ERR_ARG, "spx_ei_grad_batch: the held y* tables are per (draw, fantasy) (a pass over fantasies, option "
+                                 "mes_fantasies): refinement against them is not defined");
     if (h->acq == SPX_ACQ_MES && !h->held.results.mes)
         return fail(SPX_ERR_ARG, "spx_ei_grad_batch: SPX_ACQ_MES needs the y* table of a max-value entropy search pass "
                                  "(spx_ei_run / spx_ei_step / spx_ei_grid with SPX_ACQ_MES set)");
@@ -2569,6 +2650,7 @@ int spx_get_stat(spx_handle* h, const char* name, int64_t* value)
     else if (!strcmp(name, "last_effects_passes")) *value = h->effects_plan.npass;   // grid passes the last spx_main_effects ran its rows in
     else if (!strcmp(name, "last_effects_rows")) *value = h->effects_plan.rows;      // ... and how many rows that were
     else if (!strcmp(name, "last_mes_samples")) *value = h->held.results.mes ? h->mes_K : 0;   // K and
+    else if (!strcmp(name, "last_mes_fantasies")) *value = h->held.results.mes_fant ? h->mes_S : 0;   // S of a held table over fantasies (0: none)
     else if (!strcmp(name, "last_mes_grid")) *value = h->held.results.mes ? h->mes_J : 0;      // ... J of the held MES results (0: none)
     else if (!strcmp(name, "last_ts_paths")) *value = h->held.results.ts ? h->ts_S : 0;        // S and
     else if (!strcmp(name, "last_ts_features")) *value = h->held.results.ts ? h->ts_F : 0;     // ... F of the held sample paths (0: none)

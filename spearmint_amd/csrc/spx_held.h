@@ -18,6 +18,8 @@ struct HeldResults {
     bool global2d = false;     // spx_get_ei_mean serves the all-reduced vector of a 2-D partition
     bool mes = false;          // the pass was a max-value entropy search: its y* table, fit and G are resident (spx_get_mes,
                                // spx_ei_grad_batch under SPX_ACQ_MES); gone with the results, so with everything that drops them
+    bool mes_fant = false;     // ... over the fantasies (option "mes_fantasies"): the tables are per (draw, fantasy) -- spx_get_mes_fantasy
+                               // serves them, spx_get_mes and spx_ei_grad_batch refuse; gone with the fantasies too (RESULTS uses FANT)
     bool ehvi = false;         // the pass was an expected-hypervolume-improvement pass: the second GP's func_m / func_v of the same
                                // candidates are resident on its internal handle (spx_get_moments, draws H .. 2H-1)
     bool ts = false;           // the "pass" was spx_thompson: what is resident are posterior sample paths and their priors

@@ -175,6 +175,10 @@ struct spx_handle {
     // last MES pass and its sizes; part of RESULTS (held.results.mes)
     DevBuf mes_bpart, mes_part, mes_G, mes_ystar, mes_fit;
     int mes_K = 0, mes_J = 0;
+    // ... over fantasies (option "mes_fantasies", held.results.mes_fant): the means [H][S][Mp] and the shared variance [H][Mp], the
+    // partial minima and the brackets per (draw, fantasy); the sums, G, y* and fit go into the buffers above, S times their size
+    DevBuf mesf_mu, mesf_v, mesf_bpart, mesf_bnd;
+    int mes_S = 0;
     // two objectives (SPX_ACQ_EHVI): the front as spx_set_pareto_front received it (FRONT held: front_n >= 0) and as k_ehvi reads
     // it -- [2][front_n + 1]: the strips' upper edges a_1 .. a_n, r1, then their heights' levels r2, b_1 .. b_n; the second GP's
     // internal handle on the same device (SEC / SEC_CAND: what of the caller's data it holds), its moments are the pass's

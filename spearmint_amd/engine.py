@@ -110,6 +110,8 @@ ABI = {
     "spx_set_acquisition": (ctypes.c_int, [_vp, ctypes.c_int32, ctypes.c_double]),
     "spx_get_acquisition": (ctypes.c_int, [_vp, _c_int32_p, _c_double_p]),
     "spx_get_mes": (ctypes.c_int, [_vp, ctypes.c_int32, _c_double_p, _c_double_p, _c_double_p]),
+    "spx_get_mes_fantasy": (ctypes.c_int, [_vp, ctypes.c_int32, ctypes.c_int32, _c_double_p, _c_double_p, _c_double_p]),
+    "spx_get_mes_fantasy_moments": (ctypes.c_int, [_vp, ctypes.c_int32, ctypes.c_int32, _c_double_p, _c_double_p]),
     "spx_set_pareto_front": (ctypes.c_int, [_vp, _c_double_p, _c_double_p, ctypes.c_int32, ctypes.c_double, ctypes.c_double]),
     "spx_get_pareto_front": (ctypes.c_int, [_vp, _c_double_p, _c_double_p, _c_int32_p, _c_double_p, _c_double_p]),
     "spx_set_kg_points": (ctypes.c_int, [_vp, _c_double_p, ctypes.c_int32]),
@@ -558,6 +560,32 @@ class Engine(object):
         out = {"ystar": ystar, "fit": fit, "G": G}
         out.update(zip(MES_FIT_FIELDS, (float(v) for v in fit)))
         return out
+
+    def mes_fantasy_info(self, draw, s):
+        """mes_info for one (draw, fantasy) of a max-value entropy search pass over fantasies (option "mes_fantasies";
+        include/spx.h: spx_get_mes_fantasy).  ValueError when no such table is held."""
+        K, J = self.stat("last_mes_samples"), self.stat("last_mes_grid")
+        if self.stat("last_mes_fantasies") < 1 or K < 1 or J < 1:
+            raise ValueError("mes_fantasy_info: no max-value entropy search results over fantasies (run a pass with ACQ_MES set, "
+                             "fantasies held and option mes_fantasies on)")
+        ystar = np.empty(K)
+        fit = np.empty(8)
+        G = np.empty(J)
+        self._check(self._lib.spx_get_mes_fantasy(self._h, int(draw), int(s), _dp(ystar), _dp(fit), _dp(G)))
+        out = {"ystar": ystar, "fit": fit, "G": G}
+        out.update(zip(MES_FIT_FIELDS, (float(v) for v in fit)))
+        return out
+
+    def mes_fantasy_moments(self, draw, s):
+        """(func_m (M,), func_v (M,)) of the candidates under fantasy s of draw `draw`, as that pass formed them: the mean depends
+        on the fantasy, the variance on the draw alone (include/spx.h: spx_get_mes_fantasy_moments)."""
+        if self.stat("last_mes_fantasies") < 1:
+            raise ValueError("mes_fantasy_moments: no max-value entropy search results over fantasies (run a pass with ACQ_MES "
+                             "set, fantasies held and option mes_fantasies on)")
+        m = np.empty(self.M)
+        v = np.empty(self.M)
+        self._check(self._lib.spx_get_mes_fantasy_moments(self._h, int(draw), int(s), _dp(m), _dp(v)))
+        return m, v
 
     # -- hot path ---------------------------------------------------------
     def factor(self):
