@@ -393,6 +393,45 @@ int spx_set_kg_points(spx_handle* h, const double* pts /* A x D */, int32_t A);
 int spx_get_kg_points(spx_handle* h, double* pts /* A x D */, int32_t* A);
 int spx_get_kg_lines(spx_handle* h, int32_t draw, double* mu_a /* A */, double* cov /* A x M */);
 
+/* ---- ... while jobs are pending: KG over the fantasies (option "kg_fantasies") -----------------------------------------------
+ * spx_set_option(h, "kg_fantasies", 1) (default 0: the refusal "with fantasies held" above stands): with SPX_ACQ_KG set, points
+ * held and fantasies held (spx_set_fantasies / spx_draw_fantasies, S per draw; `bests` is not read), spx_ei_run / spx_ei_step run
+ * the S > 0 branch ONCE over S + A right-hand sides per draw -- columns 0 .. S-1 the held Gamma of the fantasies, columns S ..
+ * S+A-1 Gamma_a, formed as the plain pass forms them -- and value a candidate by plain KG on a handle that was given (X, y_s) as
+ * its observations, averaged over s.  X = [completed; pending] are the resident rows; conditioned on the pending INPUTS every
+ * posterior covariance is the same under every fantasy, so per draw d:
+ *   independent of the fantasy   func_v(c), s_c, Gamma_a, C(c, a) and the SLOPES b_0 = func_v(c) / s_c, b_a = C(c, a) / s_c: the
+ *                                plain contract's expressions
+ *   per fantasy, the intercepts  mu_c[s] = func_m(c) under fantasy s: the sum the EI branch forms for that column, bit for bit;
+ *                                mu_a[s] = mean_d + sum_i Gamma_a[i] gamma_s[i], summed per (a, s) in the plain pass's order (lane
+ *                                i mod 64 takes row i, then the butterfly)
+ *   KG_ds(c) = sum_k (b_k - b_{k+1}) f(-|z_k|) over the lower envelope of the n = A + 1 lines (mu_.[s], b_.); the value of (d, c) is
+ *   the mean of KG_ds(c) over s in numpy's pairwise order (np.mean); then the mean over the draws, the argmax rule and the result
+ *   getters of every pass.
+ * The ENVELOPE RULE of this path (csrc/kg_fant_device.h states it operation for operation): the lines are ordered by falling
+ * slope, ties by rising index, once per (d, c); per fantasy one scan in that order with one expression per breakpoint, z = (mu_k -
+ * mu_j) / (b_j - b_k), j the top of a stack and k the visited line; a line whose slope equals the top's replaces it only when its
+ * intercept is strictly lower (the plain tie rule: lowest intercept, then lowest index); the top is popped while z <= z_top; the
+ * terms are added in envelope order from +0.0 with the plain f.  Where the rounding of a breakpoint decides whether a line
+ * touches the envelope, this rule and the plain all-pairs rule may keep different lines: the values then differ by that rounding.
+ * EXACT cases as for plain KG: all slopes equal: +0.0; no value is negative; func_v(c) + noise_d not > 0 or a non-finite slope: NaN
+ * for (d, c) alone; a non-finite mu_c[s]: NaN for (d, c) alone; a non-finite mu_a[s]: NaN for every candidate of draw d.
+ * Same bits for every chunking, draw grouping, "streams", "gemm_partial", and spx_ei_step against spx_factor + spx_ei_run: the
+ * value of (d, c) depends on its own lines, the order of the points and S alone.  Option "timing": the stages belong to "kg".
+ * The lines are results of the pass: they go with the fantasies, with the points, with everything that drops plain KG results,
+ * and whenever the option is set (an unchanged value included).  spx_get_stat "last_kg_fantasies": S of held results over
+ * fantasies (0: none, or plain results).
+ * spx_get_kg_fantasy_lines: of (draw, s), mu_c (M; needs SPX_FLAG_KEEP_MOMENTS -- without it the pass writes KG_ds over the
+ * intercepts it has consumed) and mu_a (A; always kept).  spx_get_kg_fantasy_var: func_v[draw][.] (M; always kept).
+ * spx_get_kg_lines keeps serving cov under SPX_FLAG_KEEP_MOMENTS and refuses mu_a != NULL while such results are held, naming
+ * spx_get_kg_fantasy_lines.  Any pointer may be NULL.
+ * REFUSED with SPX_ERR_ARG from the host's record alone, before any device is touched: everything plain KG refuses (flags,
+ * multi-device handles, communicators, partitions, the three refinement entry points); S + A > 4096, the width the S-column
+ * branch is held to; H S Mp 8 bytes of intercepts (Mp = M rounded up to 128; twice that with SPX_FLAG_KEEP_MOMENTS, which keeps
+ * KG_ds beside them) or H (A + 1) Mp 9 bytes of ordered slopes above SPX_KG_MAX_LINE_BYTES, the message naming the size.                                                                       */
+int spx_get_kg_fantasy_lines(spx_handle* h, int32_t draw, int32_t s, double* mu_c /* M */, double* mu_a /* A */);
+int spx_get_kg_fantasy_var(spx_handle* h, int32_t draw, double* func_v /* M */);
+
 /* ---- Thompson sampling: posterior sample paths over the candidates (pathwise conditioning) ---------------------------------
  * Wilson et al. (2020): a draw from the GP posterior is a draw from the prior plus a data-dependent update,
  *     f_s(x) = mean + p_s(x) + k(x, X)' (K + sig^2 I)^-1 (y - mean - p_s(X) - sig eps_s),      sig^2 = noise + 1e-6 amp2

@@ -57,6 +57,9 @@ class GPEIChooser(GPEIBase):
                 best = self._thompson_gpu(comp, cand, vals, self.current_hyper_row()[None, :])
             elif self.acq == "KG" and pend.shape[0] == 0:
                 best = self._kg_gpu(grid, comp, cand, vals, self.current_hyper_row()[None, :])
+            elif self.acq == "KG" and self.kg_pending:   # KG over the fantasies; the normals as the EI call below draws them
+                randn = [npr.randn(pend.shape[0], self.pending_samples)]
+                best = self._kg_pending_gpu(grid, comp, pend, cand, vals, self.current_hyper_row()[None, :], randn)
             else:
                 randn = [npr.randn(pend.shape[0], self.pending_samples)] if pend.shape[0] > 0 else []
                 best, _, _ = self.ei_over_hypers_gpu(comp, pend, cand, vals, self.current_hyper_row()[None, :],
@@ -91,6 +94,8 @@ class GPEIChooser(GPEIBase):
             best = self._thompson_gpu(comp, cand, vals, np.array(rows))
         elif self.acq == "KG" and pend.shape[0] == 0:   # (with pending jobs: EI over the fantasies, below -- the MES rule)
             best = self._kg_gpu(grid, comp, cand, vals, np.array(rows))
+        elif self.acq == "KG" and self.kg_pending:      # kg_pending=1: KG over the fantasies (_base.py: _kg_pending_gpu)
+            best = self._kg_pending_gpu(grid, comp, pend, cand, vals, np.array(rows), randn)
         else:
             best, _, _ = self.ei_over_hypers_gpu(comp, pend, cand, vals, np.array(rows), randn=randn)
         if self.recommend:         # (the proposal is fixed; no random numbers from here on)

@@ -296,6 +296,19 @@ class GPEIOptChooser(GPEIBase):
                 self._loo(complete, comp, vals, rows)
             return job
 
+        if self.acq == "KG" and self.kg_pending and pend.shape[0] > 0:
+            # KG over the fantasies of the pending jobs (kg_pending=1): the grid point of the highest value, as without pending
+            # jobs.  The fantasy normals leave the generator where an acq=EI call's first pass leaves it.
+            randn = self._fantasy_normals(pend)
+            job = int(candidates[self._kg_pending_gpu(grid, comp, pend, cand, vals, rows, randn)])
+            if self.recommend:
+                self._recommend(grid, comp, vals, rows, refine_count=self.grid_subset)
+            if self.importance:
+                self._importance(grid, comp, vals, rows)
+            if self.loo:
+                self._loo(complete, comp, vals, rows)
+            return job
+
         if self.acq == "MES" and self.mes_pending and pend.shape[0] > 0:
             # MES over the fantasies of the pending jobs: the grid point of the highest value.  One pass over the grid alone (y* is
             # a property of the candidate set; the sprayed points' normals above are drawn all the same) and no refinement: the

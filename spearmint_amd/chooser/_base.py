@@ -63,7 +63,7 @@ class GPEIBase(object):
                  noiseless=False, device=0, ndev=1, lib=None, gpu_logprob="auto", gpu_refine="auto",
                  lookahead="auto", follow="auto", sampler="native", gpu_sobol=0, gpu_fantasies="auto", acq="EI", acq_par=0,
                  recommend=0, importance=0, importance_levels=16, importance_points=256, loo=0, ts_refine=0, mes_pending=0,
-                 **unused):
+                 kg_pending=0, **unused):
         if covar not in hostgp.COVARS:
             # the reference does getattr(gp, covar) here (GPEIChooser.py:52)
             raise AttributeError("no covariance function %r (gp.py has %s)" % (covar, ", ".join(hostgp.COVARS)))
@@ -84,6 +84,12 @@ class GPEIBase(object):
         if self.mes_pending and self.acq != "MES":
             raise ValueError("mes_pending=1 is max-value entropy search over the fantasies of pending jobs (allowed with acq=%s: "
                              "mes_pending=0)" % self.acq)
+        # kg_pending=1: acq=KG scores a call with pending jobs itself, over the fantasies (include/spx.h: option "kg_fantasies");
+        # 0: such a call is scored with EI over the fantasies
+        self.kg_pending = _as_bool(kg_pending)
+        if self.kg_pending and self.acq != "KG":
+            raise ValueError("kg_pending=1 is the knowledge gradient over the fantasies of pending jobs (allowed with acq=%s: "
+                             "kg_pending=0)" % self.acq)
         self.last_kg = None            # acq=KG: {"points_index", "points", "grid_index", "value"} of the last call scored with KG
         self.ts_refine = _as_bool(ts_refine)
         if self.ts_refine and not self.ts_refine_allowed:
@@ -217,15 +223,18 @@ class GPEIBase(object):
             par = float(int(par) or cls.ts_default_features)
         return name, par
 
-    def _apply_acquisition(self, eng, pending=False):
+    def _apply_acquisition(self, eng, pending=False, kg_over_fantasies=True):
         """Before a pass: the handle scores with this chooser's acquisition.  EI is the handle's default and is left
         untouched, so an engine that knows nothing else is never asked.  acq=MES while jobs are pending: by default the
         library refuses MES over fantasies, so the call is scored with EI over the fantasies, exactly as an acq=EI chooser
         scores it (last_acq_used says which one it was); with mes_pending=1 the handle's option "mes_fantasies" is set and
-        the pass is MES per (draw, fantasy), averaged over the fantasies."""
+        the pass is MES per (draw, fantasy), averaged over the fantasies; acq=KG with kg_pending=1 and option "kg_fantasies"
+        likewise (kg_over_fantasies=False: such a call found no representer point and is scored with EI)."""
         acq, par = self.acq, self.acq_par
         if acq == "MES" and pending and self.mes_pending:
             eng.set_option("mes_fantasies", 1)
+        elif acq == "KG" and pending and self.kg_pending and kg_over_fantasies:
+            eng.set_option("kg_fantasies", 1)
         elif acq in ("MES", "KG") and pending:   # (KG likewise: the library refuses it over fantasies -- the MES rule)
             acq, par = "EI", 0.0
         if acq == "KG":                          # (A is the chooser's; the handle's acquisition takes no parameter)
@@ -321,6 +330,39 @@ class GPEIBase(object):
         self.last_acq_used = "KG"
         self.last_kg = {"points_index": np.array(pidx, dtype=int), "points": np.array(grid[pidx, :], dtype=float),
                         "grid_index": int(idx), "value": float(val)}
+        return int(idx)
+
+    def _kg_pending_gpu(self, grid, comp, pend, cand, vals, hyper_rows, randn):
+        """The proposal of an acq=KG call with pending jobs and kg_pending=1: _kg_gpu's model-mean pass over the COMPLETED points
+        and its representer rows, then the pending branch exactly as an acq=EI call runs it -- [comp; pend] resident, the
+        fantasies from `randn` (gpu_fantasies on or off) -- with the handle's option "kg_fantasies" set, so that the pass is KG
+        per (draw, fantasy) averaged over the fantasies.  Draws no random numbers of its own.  Leaves self.last_kg; returns the
+        index of the winner among the candidates.  No grid row with a mean: the call is scored with EI over the fantasies."""
+        eng = self.engine()
+        grid = np.ascontiguousarray(grid, dtype=np.float64)
+        rows = np.ascontiguousarray(np.atleast_2d(hyper_rows), dtype=np.float64)
+        prev = eng.get_acquisition()
+        self._lp_key = None
+        self._factor_covers = None
+        self._kg_mean_pass = None
+        try:
+            mean = -np.asarray(self._neg_mean_over_grid(eng, grid, comp, vals, rows), dtype=np.float64)
+            order = np.argsort(mean, kind="stable")
+            pidx = order[~np.isnan(mean[order])][:int(self.acq_par)]
+            self._factor_covers = None          # (the pending branch below factors [comp; pend])
+            if pidx.size == 0:
+                self.last_kg = None
+                eng.set_acquisition(*prev)
+                return self._ei_with_pending_gpu(comp, pend, cand, vals, rows, randn, False, kg_over_fantasies=False)[0]
+            eng.set_kg_points(grid[pidx, :])
+            idx, mean_kg, _ = self._ei_with_pending_gpu(comp, pend, cand, vals, rows, randn, True)
+        finally:
+            eng.set_acquisition(*prev)
+        warning = eng.last_warning()
+        if warning:
+            log("libspx " + warning)
+        self.last_kg = {"points_index": np.array(pidx, dtype=int), "points": np.array(grid[pidx, :], dtype=float),
+                        "grid_index": int(idx), "value": float(mean_kg[int(idx)])}
         return int(idx)
 
     # -- the model-mean recommendation (recommend=1) ---------------------------------
@@ -903,7 +945,7 @@ class GPEIBase(object):
         self.last_ei_mean = mean
         return idx, mean, draws
 
-    def _ei_with_pending_gpu(self, comp, pend, cand, vals, hyper_rows, randn, want_draws):
+    def _ei_with_pending_gpu(self, comp, pend, cand, vals, hyper_rows, randn, want_draws, kg_over_fantasies=True):
         """Pending experiments: fantasise their outcomes (GPEIChooser.py:209-266).
         GPU: factorisation of cov([comp; pend]) for every draw, K(X*,X), the solve,
         Sigma beta^2 and the S fantasy means, EI averaged over fantasies -- and, unless
@@ -914,7 +956,7 @@ class GPEIBase(object):
         n_comp, n_pend = comp.shape[0], pend.shape[0]
         eng = self.engine()
         self._lp_key = None
-        self._apply_acquisition(eng, pending=True)
+        self._apply_acquisition(eng, pending=True, kg_over_fantasies=kg_over_fantasies)
         comp_pend = np.concatenate((comp, pend))
         eng.set_observations(comp_pend, np.concatenate((vals, np.zeros(n_pend))))
         eng.set_candidates(cand)

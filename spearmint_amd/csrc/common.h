@@ -241,6 +241,20 @@ void launch_kg_value(hipStream_t s, const double* slope, const double* muc, cons
                      int64_t M, int64_t Mp, int h0, double* ei_draw);
 int kg_tile_candidates(int n);
 
+// kg_fant_kernels.hip: the knowledge gradient over the fantasies of the S > 0 GEMM branch with S + A columns per draw (spx.h: option
+// "kg_fantasies"; columns 0 .. S-1 the fantasies' Gamma, S .. S+A-1 Gamma_a).  mua [H][A][S] once per pass;  per work item the
+// resident intercepts muc [H][S][Mp], func_v fv [H][Mp], with cov given C [H][A][Mp], the slopes [nh][A + 1][Mc] and from them the
+// slope order of every (draw, candidate): bsort / perm [H][A + 1][Mp] by rank;  behind the last chunk KG_ds into val [H][S][Mp]
+// (val may be muc) and its numpy-order mean over s into ei_draw
+void launch_kgf_mu(hipStream_t s, const double* gammaS, const double* htab, int Np, int S, int A, int H, double* mua);
+void launch_kgf_lines(hipStream_t s, const double* part_ss, const double* part_bgS, const double* htab, const double* Kac, int nrb,
+                      int Mc, int nh, int S, int A, int Ap, int64_t c0, int64_t M, int64_t Mp, int h0, double* slope, double* muc,
+                      double* fv, double* cov, double* bsort, unsigned char* perm);
+void launch_kgf_value(hipStream_t s, const double* bsort, const unsigned char* perm, const double* mua, const double* muc, double* val,
+                      int n, int S, int H, int64_t M, int64_t Mp, double* ei_draw);
+void kgf_tile(int n, int S, int* TC, int* SB);
+size_t kgf_lds_bytes(int n, int TC, int SB);
+
 // predict_kernels.hip
 void launch_predict_gemm(hipStream_t s, int variant, const double* WT, const double* Kst, const double* gamma,
                          double* part_ss, double* part_bg, int Np, int Mc, int nh, int part_nh, int part_h0,

@@ -219,6 +219,13 @@ static int opt_mes_fantasies(spx_handle* h, int64_t value)
     h->opt.mes_fantasies = value > 0;
     return SPX_OK;
 }
+// SPX_ACQ_KG with fantasies held: over the fantasies (1) or refused (0); the lines of the last pass belong to the old setting
+static int opt_kg_fantasies(spx_handle* h, int64_t value)
+{
+    spx_drop(h, Held::RESULTS);
+    h->opt.kg_fantasies = value > 0;
+    return SPX_OK;
+}
 static int opt_timing(spx_handle* h, int64_t value)
 {
     h->opt.timing = value != 0;
@@ -264,6 +271,7 @@ static const OptRow kOptions[] = {
     OPT_TRI("kstar_corun", corun_opt),                  // streams = 3: K(X*,X) launches beside a GEMM in the form that fits there (1, default) or as k_cov_flat (0); same bits
     OPT_CALL("mes_grid", opt_mes_grid),                 // SPX_ACQ_MES: probe values J of the log-survival grid (default 256, 8 .. 4096); drops the last pass's results
     OPT_CALL("mes_fantasies", opt_mes_fantasies),       // SPX_ACQ_MES while fantasies are held: MES per (draw, fantasy), averaged (1) or refused (0, default); drops the last pass's results
+    OPT_CALL("kg_fantasies", opt_kg_fantasies),         // SPX_ACQ_KG while fantasies are held: KG per (draw, fantasy), averaged (1) or refused (0, default); drops the last pass's results
     OPT_CALL("timing", opt_timing),                     // per-launch HIP events on the handle's stream; (re)starts the accumulators
 };
 
@@ -326,7 +334,8 @@ void spx_destroy(spx_handle* h)
                           &h->ts_par, &h->ts_w, &h->ts_eps, &h->ts_pobs, &h->ts_rhs, &h->ts_gammaS, &h->ts_pcand, &h->ts_path,
                           &h->ts_am_val, &h->ts_am_idx, &h->ts_out_val, &h->ts_out_idx,
                           &h->ts_alpha, &h->ts_gin, &h->ts_gwork, &h->ts_gout,
-                          &h->kg_pts, &h->kg_As, &h->kg_sA, &h->kg_kxa, &h->kg_gammaS, &h->kg_mua, &h->kg_Kac, &h->kg_muc, &h->kg_cov};
+                          &h->kg_pts, &h->kg_As, &h->kg_sA, &h->kg_kxa, &h->kg_gammaS, &h->kg_mua, &h->kg_Kac, &h->kg_muc, &h->kg_cov,
+                          &h->kgf_muc, &h->kgf_mua, &h->kgf_v, &h->kgf_bsort, &h->kgf_perm, &h->kgf_val};
         for (DevBuf* b : bufs) b->release();
         h->pin_up.release();
         h->pin_res.release();
@@ -1070,8 +1079,27 @@ static int check_kg(const spx_handle* h, int32_t flags, const char* who)
         return fail(SPX_ERR_ARG, "%s: SPX_ACQ_KG is single-device only (communicator attached or 2-D partition set)", who);
     if (!h->held.has(Held::KGPTS))
         return fail(SPX_ERR_ARG, "%s: SPX_ACQ_KG needs representer points (spx_set_kg_points)", who);
-    if (h->S > 0)
+    if (h->S > 0 && !h->opt.kg_fantasies)
         return fail(SPX_ERR_ARG, "%s: SPX_ACQ_KG is not defined over fantasies (clear them, or score the call with SPX_ACQ_EI)", who);
+    if (h->S > 0) {   // over the fantasies (option "kg_fantasies"): the GEMM branch's width and the resident tables
+        if (h->S + h->kg_A > 4096)
+            return fail(SPX_ERR_ARG, "%s: S + A = %d + %d right-hand sides per draw (SPX_ACQ_KG over fantasies allows up to 4096)", who,
+                        h->S, h->kg_A);
+        if (h->held.has(Held::CAND) && h->held.has(Held::HYP)) {
+            const double Mp = (double)round_up(h->M, SPX_BN);
+            // (with the moments kept KG_ds has a table of its own beside the intercepts: twice the bytes)
+            const int tabs = (flags & SPX_FLAG_KEEP_MOMENTS) ? 2 : 1;
+            const double mu_bytes = (double)tabs * h->H * h->S * Mp * 8.0, ord_bytes = (double)h->H * (h->kg_A + 1) * Mp * 9.0;
+            if (mu_bytes > (double)SPX_KG_MAX_LINE_BYTES)
+                return fail(SPX_ERR_ARG, "%s: H S Mp 8 = %d x %d x %.0f x 8 = %.0f bytes of means per (draw, fantasy)%s (SPX_ACQ_KG over "
+                                         "fantasies allows up to %lld bytes)", who, h->H, h->S, Mp, mu_bytes / tabs,
+                            tabs == 2 ? ", twice with SPX_FLAG_KEEP_MOMENTS" : "", (long long)SPX_KG_MAX_LINE_BYTES);
+            if (ord_bytes > (double)SPX_KG_MAX_LINE_BYTES)
+                return fail(SPX_ERR_ARG, "%s: H (A + 1) Mp 9 = %d x %d x %.0f x 9 = %.0f bytes of ordered slopes (SPX_ACQ_KG over "
+                                         "fantasies allows up to %lld bytes)", who, h->H, h->kg_A + 1, Mp, ord_bytes,
+                            (long long)SPX_KG_MAX_LINE_BYTES);
+        }
+    }
     if ((flags & SPX_FLAG_KEEP_MOMENTS) && h->held.has(Held::CAND) && h->held.has(Held::HYP)
         && (double)h->H * h->kg_A * (double)round_up(h->M, SPX_BN) * 8.0 > (double)SPX_KG_MAX_LINE_BYTES)
         return fail(SPX_ERR_ARG, "%s: H A Mp 8 = %d x %d x %lld x 8 bytes of kept covariances (SPX_FLAG_KEEP_MOMENTS under SPX_ACQ_KG "
@@ -1327,7 +1355,10 @@ static int ei_run_impl(spx_handle* h, int32_t flags, bool factor_pending, PassRh
     // Knowledge gradient: the S > 0 branch over gamma | Gamma_a (column 0 gives func_m, the others q(c, a)), the lines and the
     // values per work item in place of the acquisition; then the mean and the argmax of every pass (check_kg passed above)
     const bool kg = !ts && h->acq == SPX_ACQ_KG;
-    if (kg) rhs = PassRhs{PassRhs::KG, h->kg_A + 1};
+    // ... over the fantasies (option "kg_fantasies"; check_kg passed): the fantasies' Gamma in place of column 0, kg_fant_kernels.hip
+    const bool kgf = kg && h->S > 0;
+    const int kgS = kgf ? h->S : 1;                 // columns in front of Gamma_a
+    if (kg) rhs = PassRhs{PassRhs::KG, kgS + h->kg_A};
     const int pass_acq = (mes || ehvi || kg) ? SPX_ACQ_EI : h->acq;
     const double pass_par = (mes || ehvi || kg) ? 0.0 : h->acq_par;
     if ((rc = ensure_init(h))) return rc;
@@ -1391,6 +1422,14 @@ static int ei_run_impl(spx_handle* h, int32_t flags, bool factor_pending, PassRh
         if ((rc = h->kg_muc.reserve((size_t)Hb * Mc * 8))) return rc;
         if (keep_mom && (rc = h->kg_cov.reserve((size_t)H * kgA * Mp * 8))) return rc;
     }
+    if (kgf) {
+        if ((rc = h->kgf_muc.reserve((size_t)H * kgS * Mp * 8))) return rc;
+        if ((rc = h->kgf_mua.reserve((size_t)H * kgA * kgS * 8))) return rc;
+        if ((rc = h->kgf_v.reserve((size_t)H * Mp * 8))) return rc;
+        if ((rc = h->kgf_bsort.reserve((size_t)H * (kgA + 1) * Mp * 8))) return rc;
+        if ((rc = h->kgf_perm.reserve((size_t)H * (kgA + 1) * Mp))) return rc;
+        if (keep_mom && (rc = h->kgf_val.reserve((size_t)H * kgS * Mp * 8))) return rc;   // (mu_c stays for its getter)
+    }
     // (read AFTER the reservations above: a buffer that grows moves)
     const double* gammaS_all = ts ? h->ts_gammaS.d() : kg ? h->kg_gammaS.d() : h->gammaS.d();
     const int mesK = mes ? (int)h->acq_par : 0, mesJ = h->opt.mes_grid;
@@ -1449,12 +1488,14 @@ static int ei_run_impl(spx_handle* h, int32_t flags, bool factor_pending, PassRh
         TIMED_S(ST_SCALE, G, launch_scale_rows(G, h->kg_pts.d(), kgA, kgAp, D, Dp, ls, hs, H, 1.0, h->kg_As.d(), h->kg_sA.d()));
         TIMED_S(ST_COV_CROSS, G, launch_cov_cross(G, h->kg_As.d(), h->kg_sA.d(), h->X2s.d(), h->s1.d(), h->htab.d(), h->kg_kxa.d(), kgA,
                                                   kgAp, Np, Dp, H, dev_kind(h)));
-        HIPCHK(hipMemcpy2DAsync(h->kg_gammaS.d(), (size_t)S * Np * 8, h->gamma.d(), (size_t)Np * 8, (size_t)Np * 8, (size_t)H,
-                                hipMemcpyDeviceToDevice, G));
+        // (over fantasies: the kgS held columns of every draw in place of gamma)
+        HIPCHK(hipMemcpy2DAsync(h->kg_gammaS.d(), (size_t)S * Np * 8, kgf ? h->gammaS.d() : h->gamma.d(), (size_t)kgS * Np * 8,
+                                (size_t)kgS * Np * 8, (size_t)H, hipMemcpyDeviceToDevice, G));
         for (int d = 0; d < H; ++d)
             TIMED_S(ST_GAMMA_ALPHA, G, launch_gamma_cols(G, h->WT.d() + (size_t)d * nn, h->kg_kxa.d() + (size_t)d * kgAp * Np, (size_t)Np,
-                                                         h->kg_gammaS.d() + ((size_t)d * S + 1) * Np, (int)N, Np, kgA));
-        TIMED_S(ST_KG, G, launch_kg_mu(G, h->kg_gammaS.d(), h->htab.d(), Np, S, H, h->kg_mua.d()));
+                                                         h->kg_gammaS.d() + ((size_t)d * S + kgS) * Np, (int)N, Np, kgA));
+        if (kgf) TIMED_S(ST_KG, G, launch_kgf_mu(G, h->kg_gammaS.d(), h->htab.d(), Np, kgS, kgA, H, h->kgf_mua.d()));
+        else TIMED_S(ST_KG, G, launch_kg_mu(G, h->kg_gammaS.d(), h->htab.d(), Np, S, H, h->kg_mua.d()));
     }
     int item = 0, chunk = 0;
     for (int64_t c0 = 0; c0 < Mp; c0 += Mc, ++chunk) {
@@ -1539,7 +1580,12 @@ static int ei_run_impl(spx_handle* h, int32_t flags, bool factor_pending, PassRh
                                                           Cs + (size_t)h0 * mc * Dp, s2 + (size_t)h0 * mc,
                                                           h->htab.d() + (size_t)h0 * SPX_HT, h->kg_Kac.d(), kgA, kgAp, mc, Dp, nhb,
                                                           dev_kind(h)));
-                TIMED_S(ST_KG, G, {
+                if (kgf)   // the intercepts, the slopes and their order; the scans run behind the last chunk
+                    TIMED_S(ST_KG, G, launch_kgf_lines(G, h->part_ss.d(), bgS_k, h->htab.d() + (size_t)h0 * SPX_HT, h->kg_Kac.d(), nrb, mc,
+                                                       nhb, kgS, kgA, kgAp, c0, M, Mp, h0, h->scratch.d(), h->kgf_muc.d(), h->kgf_v.d(),
+                                                       keep_mom ? h->kg_cov.d() : nullptr, h->kgf_bsort.d(),
+                                                       (unsigned char*)h->kgf_perm.p));
+                else TIMED_S(ST_KG, G, {
                     launch_kg_lines(G, h->part_ss.d(), bgS_k, h->htab.d() + (size_t)h0 * SPX_HT, h->kg_Kac.d(), nrb, mc, nhb, S, kgAp, c0, M,
                                     Mp, h0, h->scratch.d(), h->kg_muc.d(), keep_mom ? h->mom_m.d() : nullptr,
                                     keep_mom ? h->mom_v.d() : nullptr, keep_mom ? h->kg_cov.d() : nullptr);
@@ -1575,6 +1621,9 @@ static int ei_run_impl(spx_handle* h, int32_t flags, bool factor_pending, PassRh
     const int n_info = p.n_info;
     if ((rc = h->pin_res.reserve(16 + (size_t)n_info * sizeof(int)))) return rc;
     double* mirror = (double*)h->pin_res.p;
+    if (kgf)   // behind the last chunk on the main stream: the lines of every (draw, fantasy, candidate) are complete
+        TIMED(ST_KG, launch_kgf_value(s, h->kgf_bsort.d(), (const unsigned char*)h->kgf_perm.p, h->kgf_mua.d(), h->kgf_muc.d(),
+                                      keep_mom ? h->kgf_val.d() : h->kgf_muc.d(), kgA + 1, kgS, H, M, Mp, h->ei_draw.d()));
     if (mesf)  // behind the last chunk on the main stream: the means of every (draw, fantasy) are complete
         TIMED(ST_MES, launch_mes_fant(s, h->mesf_mu.d(), h->mesf_v.d(), h->htab.d(), SPX_HT, h->bests.d(), M, Mp, H, S, mesJ, mesK,
                                       h->mesf_bpart.d(), h->mesf_bnd.d(), h->mes_part.d(), h->mes_G.d(), h->mes_ystar.d(),
@@ -1617,10 +1666,11 @@ static int ei_run_impl(spx_handle* h, int32_t flags, bool factor_pending, PassRh
     Held::Results r;
     r.time_only = time_only;         // (a time-only pass has no EI results: spx_get_best & co. refuse)
     r.ts = ts;                       // (paths and priors, nothing else: every EI getter refuses)
-    r.moments = keep_mom && (S == 0 || kg) && !time_only;   // (KG: k_kg_lines wrote func_m / func_v from column 0)
+    r.moments = keep_mom && (S == 0 || (kg && !kgf)) && !time_only;   // (KG: k_kg_lines wrote func_m / func_v from column 0)
     r.kg = kg;
     r.kg_lines = kg && keep_mom;
-    if (kg) h->kg_last_A = kgA;
+    r.kg_fant = kgf;
+    if (kg) { h->kg_last_A = kgA; h->kg_last_S = kgf ? kgS : 0; }
     r.tmean = keep_mom && per_sec;   // (with fantasies the pass keeps no func_m / func_v, but mom_t is written all the same)
     r.con = constrained && keep_mom && !time_only;
     r.ehvi = ehvi;
@@ -1750,6 +1800,9 @@ int spx_get_kg_lines(spx_handle* h, int32_t draw, double* mu_a, double* cov)
     if (h->multi) return fail(SPX_ERR_ARG, "spx_get_kg_lines: SPX_ACQ_KG is single-device only (multi-device handle)");
     if (!h->held.results.kg) return fail(SPX_ERR_ARG, "spx_get_kg_lines: no knowledge-gradient results (run a pass with SPX_ACQ_KG set)");
     if (draw < 0 || draw >= h->H) return fail(SPX_ERR_ARG, "spx_get_kg_lines: draw out of range");
+    if (mu_a && h->held.results.kg_fant)
+        return fail(SPX_ERR_ARG, "spx_get_kg_lines: the held intercepts are per (draw, fantasy) (a pass over fantasies, option "
+                                 "kg_fantasies): spx_get_kg_fantasy_lines serves them");
     if (cov && !h->held.results.kg_lines)
         return fail(SPX_ERR_ARG, "spx_get_kg_lines: the covariances are kept by a pass with SPX_FLAG_KEEP_MOMENTS");
     int rc = ensure_init(h);
@@ -1760,6 +1813,44 @@ int spx_get_kg_lines(spx_handle* h, int32_t draw, double* mu_a, double* cov)
     if (cov)
         HIPCHK(hipMemcpy2D(cov, (size_t)h->M * 8, h->kg_cov.d() + (size_t)draw * A * Mp, (size_t)Mp * 8, (size_t)h->M * 8, A,
                            hipMemcpyDeviceToHost));
+    return SPX_OK;
+}
+
+// what both getters of a KG pass over fantasies check
+static int kg_fantasy_results(spx_handle* h, const char* who, int32_t draw)
+{
+    if (!h) return fail(SPX_ERR_ARG, "%s: null handle", who);
+    if (h->multi) return fail(SPX_ERR_ARG, "%s: SPX_ACQ_KG is single-device only (multi-device handle)", who);
+    if (!h->held.results.kg_fant)
+        return fail(SPX_ERR_ARG, "%s: no knowledge-gradient results over fantasies (run a pass with SPX_ACQ_KG set, fantasies held "
+                                 "and option kg_fantasies on)", who);
+    if (draw < 0 || draw >= h->H) return fail(SPX_ERR_ARG, "%s: draw out of range", who);
+    return ensure_init(h);
+}
+
+int spx_get_kg_fantasy_lines(spx_handle* h, int32_t draw, int32_t s, double* mu_c, double* mu_a)
+{
+    int rc = kg_fantasy_results(h, "spx_get_kg_fantasy_lines", draw);
+    if (rc) return rc;
+    const size_t S = (size_t)h->kg_last_S, A = (size_t)h->kg_last_A;
+    if (s < 0 || (size_t)s >= S)
+        return fail(SPX_ERR_ARG, "spx_get_kg_fantasy_lines: fantasy out of range (the held results have %d)", h->kg_last_S);
+    if (mu_c && !h->held.results.kg_lines)
+        return fail(SPX_ERR_ARG, "spx_get_kg_fantasy_lines: the candidates' intercepts are kept by a pass with SPX_FLAG_KEEP_MOMENTS "
+                                 "(without it the pass writes its values over them)");
+    const int64_t Mp = round_up(h->M, SPX_BN);
+    if (mu_c) HIPCHK(hipMemcpy(mu_c, h->kgf_muc.d() + ((size_t)draw * S + s) * Mp, (size_t)h->M * 8, hipMemcpyDeviceToHost));
+    if (mu_a)   // resident as [H][A][S]: column s of draw's block
+        HIPCHK(hipMemcpy2D(mu_a, 8, h->kgf_mua.d() + (size_t)draw * A * S + s, S * 8, 8, A, hipMemcpyDeviceToHost));
+    return SPX_OK;
+}
+
+int spx_get_kg_fantasy_var(spx_handle* h, int32_t draw, double* func_v)
+{
+    int rc = kg_fantasy_results(h, "spx_get_kg_fantasy_var", draw);
+    if (rc) return rc;
+    const int64_t Mp = round_up(h->M, SPX_BN);
+    if (func_v) HIPCHK(hipMemcpy(func_v, h->kgf_v.d() + (size_t)draw * Mp, (size_t)h->M * 8, hipMemcpyDeviceToHost));
     return SPX_OK;
 }
 
@@ -2656,6 +2747,7 @@ int spx_get_stat(spx_handle* h, const char* name, int64_t* value)
     else if (!strcmp(name, "last_ts_features")) *value = h->held.results.ts ? h->ts_F : 0;     // ... F of the held sample paths (0: none)
     else if (!strcmp(name, "kg_points")) *value = h->held.has(Held::KGPTS) ? h->kg_A : 0;       // A of the held representer points (0: none)
     else if (!strcmp(name, "last_kg_points")) *value = h->held.results.kg ? h->kg_last_A : 0;  // ... and of the held KG results
+    else if (!strcmp(name, "last_kg_fantasies")) *value = h->held.results.kg_fant ? h->kg_last_S : 0;   // S of held KG results over fantasies (0: none or plain)
     else if (!strcmp(name, "last_kg_lines")) *value = h->held.results.kg_lines ? 1 : 0;        // ... whose covariances are kept
     else if (!strcmp(name, "gemm_lds_bytes")) *value = (int64_t)predict_gemm_lds_bytes();   // dynamic LDS of a predict-GEMM workgroup (two are resident per CU)
     else if (!strcmp(name, "hip_runtime_version") || !strcmp(name, "hip_driver_version")) {

@@ -208,6 +208,11 @@ struct spx_handle {
     DevBuf kg_pts, kg_As, kg_sA, kg_kxa, kg_gammaS, kg_mua, kg_Kac, kg_muc, kg_cov;
     int64_t kg_fant_budget = 0;    // the per-column partial means' byte budget, as fant_budget / fant_budget_S are the fantasies'
     int kg_fant_budget_S = -1;
+    // ... over fantasies (option "kg_fantasies", held.results.kg_fant): the intercepts mu_c [H][S][Mp] and mu_a [H][A][S], func_v
+    // [H][Mp], the slopes by rank and the lines' indices by rank [H][A + 1][Mp], and -- with the moments kept, so that mu_c stays
+    // readable -- KG_ds [H][S][Mp].  kg_last_S: S of the held results
+    DevBuf kgf_muc, kgf_mua, kgf_v, kgf_bsort, kgf_perm, kgf_val;
+    int kg_last_S = 0;
     DevBuf loo_out;                                                 // spx_loo: loo_mean | loo_var | kinv_diag, [3][H][N]; scratch of that call, not part of `held`
     // probit constraint model (spx_set_constraint_model): an internal handle on the same device factors
     // (amp2_c (K_c + 1e-6 I) + noise_c I) alpha_c = ff over its own Nc points; the EI pass reads its scaled rows and alpha_c

@@ -28,6 +28,7 @@ struct Options {
     int64_t effects_pass_rows = 0;      // "effects_pass_rows": rows per pass of spx_main_effects (0 = default)
     int mes_grid = 256;                 // "mes_grid": probe values J of a max-value entropy search pass (8 .. 4096)
     int mes_fantasies = 0;              // "mes_fantasies": SPX_ACQ_MES with fantasies held runs over them (1) or refuses (0, default)
+    int kg_fantasies = 0;               // "kg_fantasies": SPX_ACQ_KG with fantasies held runs over them (1) or refuses (0, default)
     bool timing = false;
     int lean_lazy = -1, step_overlap = -1, ei_fused = -1, ei_flow = -1, lean_flow_cov = -1, lean_flow_yield = -1,
         lean_flow_cu = -1, lean_flow = -1, lean_ps = -1, lean_merge = -1, lean_one = -1, lean_poll = -1, lean_zc = -1,

@@ -117,6 +117,8 @@ ABI = {
     "spx_set_kg_points": (ctypes.c_int, [_vp, _c_double_p, ctypes.c_int32]),
     "spx_get_kg_points": (ctypes.c_int, [_vp, _c_double_p, _c_int32_p]),
     "spx_get_kg_lines": (ctypes.c_int, [_vp, ctypes.c_int32, _c_double_p, _c_double_p]),
+    "spx_get_kg_fantasy_lines": (ctypes.c_int, [_vp, ctypes.c_int32, ctypes.c_int32, _c_double_p, _c_double_p]),
+    "spx_get_kg_fantasy_var": (ctypes.c_int, [_vp, ctypes.c_int32, _c_double_p]),
     "spx_main_effects": (ctypes.c_int, [_vp, _c_double_p, ctypes.c_int32, _c_double_p, ctypes.c_int32, _c_double_p, _c_double_p]),
     "spx_loo": (ctypes.c_int, [_vp, ctypes.c_int32, _c_double_p, _c_double_p, _c_double_p]),
     "spx_ei_run": (ctypes.c_int, [_vp, ctypes.c_int32]),
@@ -541,10 +543,34 @@ class Engine(object):
         A = self.stat("last_kg_points")
         if A < 1:
             raise ValueError("kg_lines: no knowledge-gradient results (run a pass with ACQ_KG set)")
-        mu = np.empty(A)
+        mu = None if self.stat("last_kg_fantasies") > 0 else np.empty(A)    # (over fantasies: None -- kg_fantasy_lines serves mu_a[s])
         cov = np.empty((A, self.M)) if want_cov else None
         self._check(self._lib.spx_get_kg_lines(self._h, int(draw), _dp(mu), _dp(cov)))
         return mu, cov
+
+    def kg_fantasy_lines(self, draw, s, want_mu_c=True):
+        """The intercepts of (draw, fantasy s) of the last ACQ_KG pass over fantasies (option "kg_fantasies"; include/spx.h:
+        spx_get_kg_fantasy_lines): (mu_c (M,), mu_a (A,)).  mu_c needs a pass with FLAG_KEEP_MOMENTS (want_mu_c=False: None in
+        its place); the slopes come from kg_lines(draw)'s cov and kg_fantasy_var(draw).  ValueError when no such results are
+        held."""
+        A = self.stat("last_kg_points")
+        if self.stat("last_kg_fantasies") < 1 or A < 1:
+            raise ValueError("kg_fantasy_lines: no knowledge-gradient results over fantasies (run a pass with ACQ_KG set, "
+                             "fantasies held and option kg_fantasies on)")
+        mu_c = np.empty(self.M) if want_mu_c else None
+        mu_a = np.empty(A)
+        self._check(self._lib.spx_get_kg_fantasy_lines(self._h, int(draw), int(s), _dp(mu_c), _dp(mu_a)))
+        return mu_c, mu_a
+
+    def kg_fantasy_var(self, draw):
+        """func_v (M,) of the candidates under `draw` as the last ACQ_KG pass over fantasies formed it: it does not depend on the
+        fantasy (include/spx.h: spx_get_kg_fantasy_var)."""
+        if self.stat("last_kg_fantasies") < 1:
+            raise ValueError("kg_fantasy_var: no knowledge-gradient results over fantasies (run a pass with ACQ_KG set, "
+                             "fantasies held and option kg_fantasies on)")
+        v = np.empty(self.M)
+        self._check(self._lib.spx_get_kg_fantasy_var(self._h, int(draw), _dp(v)))
+        return v
 
     def mes_info(self, draw):
         """What the last max-value entropy search pass fitted for one draw (include/spx.h: spx_get_mes): a dict with ystar
@@ -1012,6 +1038,12 @@ class MultiEngine(Engine):
         raise ValueError("the knowledge gradient is not available on a multi-device engine (include/spx.h: SPX_ACQ_KG)")
 
     def kg_lines(self, draw, want_cov=True):
+        raise ValueError("the knowledge gradient is not available on a multi-device engine (include/spx.h: SPX_ACQ_KG)")
+
+    def kg_fantasy_lines(self, draw, s, want_mu_c=True):
+        raise ValueError("the knowledge gradient is not available on a multi-device engine (include/spx.h: SPX_ACQ_KG)")
+
+    def kg_fantasy_var(self, draw):
         raise ValueError("the knowledge gradient is not available on a multi-device engine (include/spx.h: SPX_ACQ_KG)")
 
     def thompson_grad_batch(self, points, path_of=None, want_prior=False):
