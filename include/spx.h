@@ -347,7 +347,8 @@ int spx_get_pareto_front(spx_handle* h, double* a, double* b, int32_t* n, double
  * Frazier, Powell & Dayanik (2009); Scott, Frazier & Powell (2011), the discrete form: a candidate c is valued by the expected
  * drop of the minimum of the posterior MEAN -- over c itself and A representer points -- after one more noisy evaluation at c.
  * (EI, PI and MES measure against `best`, the minimum OBSERVED value: on a noisy objective the luckiest draw.)
- * Everything is per hyper draw d.  A = number of representer points, 1 .. SPX_KG_MAX_POINTS; a contract:
+ * Everything is per hyper draw d.  A = number of representer points, 1 .. SPX_KG_MAX_POINTS (option "kg_scan", below: 1 ..
+ * SPX_KG_SCAN_MAX_POINTS); a contract:
  *   mu_c      = func_m(c) of the pass;   func_v(c) its variance;   s_c = sqrt(func_v(c) + noise_d), the standard deviation of a
  *               new OBSERVATION at c
  *   Gamma_a   = L^-1 k(X, a), no mean subtracted; k(X, a) from the library's own cross-covariance launch with the points as rows
@@ -388,6 +389,7 @@ int spx_get_pareto_front(spx_handle* h, double* a, double* b, int32_t* n, double
  * of the envelope: out of scope); a non-finite coordinate in the points, A out of range.                                    */
 #define SPX_ACQ_KG 5
 #define SPX_KG_MAX_POINTS 255
+#define SPX_KG_SCAN_MAX_POINTS 1023
 #define SPX_KG_MAX_LINE_BYTES (4ll << 30)
 int spx_set_kg_points(spx_handle* h, const double* pts /* A x D */, int32_t A);
 int spx_get_kg_points(spx_handle* h, double* pts /* A x D */, int32_t* A);
@@ -431,6 +433,29 @@ int spx_get_kg_lines(spx_handle* h, int32_t draw, double* mu_a /* A */, double* 
  * KG_ds beside them) or H (A + 1) Mp 9 bytes of ordered slopes above SPX_KG_MAX_LINE_BYTES, the message naming the size.                                                                       */
 int spx_get_kg_fantasy_lines(spx_handle* h, int32_t draw, int32_t s, double* mu_c /* M */, double* mu_a /* A */);
 int spx_get_kg_fantasy_var(spx_handle* h, int32_t draw, double* func_v /* M */);
+
+/* ---- ... by slope order and one scan, up to 1023 points (option "kg_scan") --------------------------------------------------------
+ * spx_set_option(h, "kg_scan", 1) (default 0; any other value is SPX_ERR_ARG): spx_set_kg_points takes A in 1 ..
+ * SPX_KG_SCAN_MAX_POINTS, and a pass with SPX_ACQ_KG set, points held and no fantasies runs the plain pass up to and including its
+ * lines -- mu_c, func_v, s_c, Gamma_a, mu_a, q(c, a), C(c, a) exactly as the plain contract forms them, nothing in the GEMM changed
+ * -- and values them by the ENVELOPE RULE of the pending path above (csrc/kg_fant_device.h), one line set per (d, c): the lines
+ * ordered by falling slope, ties by rising index; one scan with one expression per breakpoint; the same tie rule; the terms added
+ * in envelope order from +0.0 with the plain f.  About 3 n divisions per (d, c) where the all-pairs rule spends n^2, which is
+ * what lets n = A + 1 reach 1024: the discrete KG of Scott, Frazier & Powell over every point sampled so far.  The order is found
+ * by a bitonic network in LDS and kept as 16-bit line indices (csrc/kg_scan_kernels.hip).
+ * EXACT cases, the plain pass's: all slopes equal: +0.0; no value is negative; func_v(c) + noise_d not > 0 or a non-finite line:
+ * NaN for that (d, c) alone (a non-finite mu_a: for every candidate of draw d).  The value of (d, c) depends on its own lines and on
+ * the order of the points only: same bits for every chunking, draw grouping, "streams", "gemm_partial", spx_ei_step against
+ * spx_factor + spx_ei_run, with or without SPX_FLAG_KEEP_MOMENTS.  Against the all-pairs rule the values may differ where the
+ * rounding of a breakpoint decides whether a line touches the envelope, by that rounding.
+ * spx_get_kg_lines, spx_get_moments, the mean over the draws, the argmax and every result getter behave as after a plain pass;
+ * spx_get_stat "last_kg_points" reports A, "last_kg_scan" is 1 when the held KG results came from this path (0: none, or another).
+ * Setting the option, an unchanged value included, drops the results of the last pass and nothing else.
+ * With the option 0, A > SPX_KG_MAX_POINTS is refused as before, and a pass while more points than that are held (set while the
+ * option was 1) is refused with SPX_ERR_ARG before any device is touched, naming the option.  Everything plain KG refuses stays
+ * refused.  With option "kg_fantasies" and fantasies held the pending path runs as it does, for A up to SPX_KG_MAX_POINTS; more
+ * points held: SPX_ERR_ARG from the host's record.  The ordered slopes and indices are tables of one work item, 10 bytes per line
+ * beside the 8 of the slopes the plain pass holds there, under the same byte budget: they add no refusal of their own.       */
 
 /* ---- Thompson sampling: posterior sample paths over the candidates (pathwise conditioning) ---------------------------------
  * Wilson et al. (2020): a draw from the GP posterior is a draw from the prior plus a data-dependent update,

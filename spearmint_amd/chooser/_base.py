@@ -63,12 +63,26 @@ class GPEIBase(object):
                  noiseless=False, device=0, ndev=1, lib=None, gpu_logprob="auto", gpu_refine="auto",
                  lookahead="auto", follow="auto", sampler="native", gpu_sobol=0, gpu_fantasies="auto", acq="EI", acq_par=0,
                  recommend=0, importance=0, importance_levels=16, importance_points=256, loo=0, ts_refine=0, mes_pending=0,
-                 kg_pending=0, **unused):
+                 kg_pending=0, kg_scan=0, kg_points="grid", **unused):
         if covar not in hostgp.COVARS:
             # the reference does getattr(gp, covar) here (GPEIChooser.py:52)
             raise AttributeError("no covariance function %r (gp.py has %s)" % (covar, ", ".join(hostgp.COVARS)))
         self.covar = covar        # every kernel of gp.py runs on the GPU: option "covar" of the handle
-        self.acq, self.acq_par = self._parse_acquisition(acq, acq_par)
+        # kg_scan=1: acq=KG values its lines by slope order and one scan (include/spx.h: option "kg_scan"), acq_par up to 1023, and
+        # kg_points=observed takes the completed points themselves as the representer set (Scott, Frazier & Powell's discrete KG)
+        # in place of the acq_par grid rows of lowest mean (kg_points=grid)
+        if str(kg_scan).strip() not in ("0", "1"):
+            raise ValueError("kg_scan=%r (allowed: 0, 1)" % (kg_scan,))
+        self.kg_scan = int(str(kg_scan).strip())
+        self.kg_points = str(kg_points).strip().lower()
+        if self.kg_points not in ("grid", "observed"):
+            raise ValueError("kg_points=%r (allowed: grid, observed)" % (kg_points,))
+        if self.kg_points == "observed" and not self.kg_scan:
+            raise ValueError("kg_points=observed needs kg_scan=1: the all-pairs pass takes 255 points (allowed with kg_scan=0: "
+                             "kg_points=grid)")
+        self.acq, self.acq_par = self._parse_acquisition(acq, acq_par, 1023 if self.kg_scan else 255)
+        if self.kg_scan and self.acq != "KG":
+            raise ValueError("kg_scan=1 is a form of the knowledge gradient (allowed with acq=%s: kg_scan=0)" % self.acq)
         if self.acq == "MES" and int(ndev) > 1:
             raise ValueError("acq=MES is not available with ndev=%d: y* of a draw needs the moments of every candidate on one "
                              "device (allowed: ndev=1, or acq=EI, PI, LCB)" % int(ndev))
@@ -90,6 +104,9 @@ class GPEIBase(object):
         if self.kg_pending and self.acq != "KG":
             raise ValueError("kg_pending=1 is the knowledge gradient over the fantasies of pending jobs (allowed with acq=%s: "
                              "kg_pending=0)" % self.acq)
+        if self.kg_pending and (self.acq_par > 255 or self.kg_points == "observed"):
+            raise ValueError("kg_pending=1 takes up to 255 grid rows as representer points (allowed: acq_par in 1 .. 255 and "
+                             "kg_points=grid, or kg_pending=0)")
         self.last_kg = None            # acq=KG: {"points_index", "points", "grid_index", "value"} of the last call scored with KG
         self.ts_refine = _as_bool(ts_refine)
         if self.ts_refine and not self.ts_refine_allowed:
@@ -189,7 +206,7 @@ class GPEIBase(object):
 
     # -- acquisition -----------------------------------------------------------
     @classmethod
-    def _parse_acquisition(cls, acq, acq_par):
+    def _parse_acquisition(cls, acq, acq_par, kg_max=255):
         """acq=EI|PI|LCB|MES|TS and acq_par=<xi, kappa, K or F>: finite, >= 0, 0 for EI, an integer in 0 .. 1024 for MES (0: the
         default of 10 levels), a multiple of 16 in 16 .. 8192 for TS (0: the default of 1024 features) (include/spx.h:
         spx_set_acquisition, spx_thompson)."""
@@ -212,9 +229,9 @@ class GPEIBase(object):
                                  "the default of %d)" % (acq_par, cls.mes_default_levels))
             par = float(int(par) or cls.mes_default_levels)
         if name == "KG":
-            if par != int(par) or par > 255:
-                raise ValueError("acq_par=%r is not a number of representer points (allowed with acq=KG: an integer in 1 .. 255, "
-                                 "or 0 for the default of %d)" % (acq_par, cls.kg_default_points))
+            if par != int(par) or par > kg_max:
+                raise ValueError("acq_par=%r is not a number of representer points (allowed with acq=KG: an integer in 1 .. %d, "
+                                 "or 0 for the default of %d)" % (acq_par, kg_max, cls.kg_default_points))
             par = float(int(par) or cls.kg_default_points)
         if name == "TS":
             if par != int(par) or int(par) % 16 or (par != 0 and not 16 <= par <= 8192):
@@ -295,7 +312,9 @@ class GPEIBase(object):
         """The proposal of an acq=KG call without pending jobs: the model-mean pass over the grid (which holds the completed
         points), the A = acq_par grid rows of the lowest mean over the draws as representer points -- a stable argsort, NaN rows
         skipped, fewer if fewer exist -- then the KG pass over the candidates against the factor the first pass left.  Draws no
-        random numbers.  Leaves self.last_kg; returns the index of the winner among the candidates.  No grid row with a mean:
+        random numbers.  kg_scan=1: the handle's option "kg_scan" is set first; kg_points=observed: the representer points are
+        the completed points themselves in the order of `comp`, the first 1023, and last_kg["points_index"] counts along `comp`.
+        Leaves self.last_kg; returns the index of the winner among the candidates.  No grid row with a mean:
         nothing to represent the minimum, and the call is scored with EI (last_acq_used says so)."""
         from ..engine import ACQ_KG
         eng = self.engine()
@@ -314,7 +333,13 @@ class GPEIBase(object):
                 self.last_kg = None
                 eng.set_acquisition(*prev)
                 return self.ei_over_hypers_gpu(comp, np.zeros((0, grid.shape[1])), cand, vals, rows)[0]
-            eng.set_kg_points(grid[pidx, :])
+            points = grid[pidx, :]
+            if self.kg_scan:     # (kg_scan=0 never names the option: an engine that does not know it is never asked)
+                eng.set_option("kg_scan", 1)
+            if self.kg_points == "observed":     # the completed points in the order of `comp`; points_index counts along comp
+                pidx = np.arange(min(comp.shape[0], 1023))
+                points = np.ascontiguousarray(comp[pidx, :], dtype=np.float64)
+            eng.set_kg_points(points)
             eng.set_candidates(cand)
             eng.set_acquisition(ACQ_KG, 0.0)
             eng.ei_run()
@@ -328,7 +353,7 @@ class GPEIBase(object):
         if warning:
             log("libspx " + warning)
         self.last_acq_used = "KG"
-        self.last_kg = {"points_index": np.array(pidx, dtype=int), "points": np.array(grid[pidx, :], dtype=float),
+        self.last_kg = {"points_index": np.array(pidx, dtype=int), "points": np.array(points, dtype=float),
                         "grid_index": int(idx), "value": float(val)}
         return int(idx)
 

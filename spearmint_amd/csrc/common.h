@@ -241,6 +241,11 @@ void launch_kg_value(hipStream_t s, const double* slope, const double* muc, cons
                      int64_t M, int64_t Mp, int h0, double* ei_draw);
 int kg_tile_candidates(int n);
 
+// kg_scan_kernels.hip: the values of a plain knowledge-gradient work item by slope order and one scan (spx.h: option "kg_scan"),
+// in place of launch_kg_value behind the same launch_kg_lines; n = A + 1 up to 1024.  bsort / perm: nh n Mc entries, the work item's.
+void launch_kgs_value(hipStream_t s, const double* slope, const double* muc, const double* mua, int Mc, int nh, int n, int64_t c0,
+                      int64_t M, int64_t Mp, int h0, double* bsort, unsigned short* perm, double* ei_draw);
+
 // kg_fant_kernels.hip: the knowledge gradient over the fantasies of the S > 0 GEMM branch with S + A columns per draw (spx.h: option
 // "kg_fantasies"; columns 0 .. S-1 the fantasies' Gamma, S .. S+A-1 Gamma_a).  mua [H][A][S] once per pass;  per work item the
 // resident intercepts muc [H][S][Mp], func_v fv [H][Mp], with cov given C [H][A][Mp], the slopes [nh][A + 1][Mc] and from them the

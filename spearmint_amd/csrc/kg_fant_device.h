@@ -57,12 +57,15 @@ __device__ __forceinline__ int kgf_below(const unsigned* stk, int ss, int k)
 }
 
 // Lines by rank k: index p = perm[k * ps] (0: the candidate, a >= 1: representer point a - 1), intercept p ? mua[(p - 1) * ms] : mu0,
-// slope bsort[k * bs].  stk: (n + 31) / 32 words at stride ss, the scan's own.
-struct KgfLines {
+// slope bsort[k * bs].  stk: (n + 31) / 32 words at stride ss, the scan's own.  The index type is the caller's: a byte holds
+// n <= 256 (KgfLines, the pending path), 16 bits n <= 65536 (KgsLines: option "kg_scan", kg_scan_kernels.hip); the strides are
+// size_t there because its tables live in memory, a chunk of candidates apart.  kgf_value is the same text for every such type.
+template <class Index, class Stride>
+struct KgfLinesOf {
     double mu0;
     const double* mua; int ms;
-    const unsigned char* perm; int ps;
-    const double* bsort; int bs;
+    const Index* perm; Stride ps;
+    const double* bsort; Stride bs;
     __device__ __forceinline__ double m(int k) const
     {
         const int p = perm[(size_t)k * ps];
@@ -70,8 +73,11 @@ struct KgfLines {
     }
     __device__ __forceinline__ double b(int k) const { return bsort[(size_t)k * bs]; }
 };
+typedef KgfLinesOf<unsigned char, int> KgfLines;
+typedef KgfLinesOf<unsigned short, size_t> KgsLines;
 
-__device__ __forceinline__ double kgf_value(const KgfLines& L, int n, unsigned* stk, int ss)
+template <class Lines>
+__device__ __forceinline__ double kgf_value(const Lines& L, int n, unsigned* stk, int ss)
 {
 #pragma clang fp contract(off)
     const int nw = (n + 31) >> 5;

@@ -226,6 +226,15 @@ static int opt_kg_fantasies(spx_handle* h, int64_t value)
     h->opt.kg_fantasies = value > 0;
     return SPX_OK;
 }
+// a plain SPX_ACQ_KG pass: slope order and one scan, A up to 1023 (1), or all pairs, A up to 255 (0); the results of the last pass
+// belong to the old setting
+static int opt_kg_scan(spx_handle* h, int64_t value)
+{
+    if (value != 0 && value != 1) return fail(SPX_ERR_ARG, "spx_set_option: kg_scan=%lld (allowed: 0, 1)", (long long)value);
+    spx_drop(h, Held::RESULTS);
+    h->opt.kg_scan = (int)value;
+    return SPX_OK;
+}
 static int opt_timing(spx_handle* h, int64_t value)
 {
     h->opt.timing = value != 0;
@@ -272,6 +281,7 @@ static const OptRow kOptions[] = {
     OPT_CALL("mes_grid", opt_mes_grid),                 // SPX_ACQ_MES: probe values J of the log-survival grid (default 256, 8 .. 4096); drops the last pass's results
     OPT_CALL("mes_fantasies", opt_mes_fantasies),       // SPX_ACQ_MES while fantasies are held: MES per (draw, fantasy), averaged (1) or refused (0, default); drops the last pass's results
     OPT_CALL("kg_fantasies", opt_kg_fantasies),         // SPX_ACQ_KG while fantasies are held: KG per (draw, fantasy), averaged (1) or refused (0, default); drops the last pass's results
+    OPT_CALL("kg_scan", opt_kg_scan),                   // plain SPX_ACQ_KG: slope order and one scan, A up to 1023 (1), or all pairs, A up to 255 (0, default); drops the last pass's results
     OPT_CALL("timing", opt_timing),                     // per-launch HIP events on the handle's stream; (re)starts the accumulators
 };
 
@@ -335,7 +345,8 @@ void spx_destroy(spx_handle* h)
                           &h->ts_am_val, &h->ts_am_idx, &h->ts_out_val, &h->ts_out_idx,
                           &h->ts_alpha, &h->ts_gin, &h->ts_gwork, &h->ts_gout,
                           &h->kg_pts, &h->kg_As, &h->kg_sA, &h->kg_kxa, &h->kg_gammaS, &h->kg_mua, &h->kg_Kac, &h->kg_muc, &h->kg_cov,
-                          &h->kgf_muc, &h->kgf_mua, &h->kgf_v, &h->kgf_bsort, &h->kgf_perm, &h->kgf_val};
+                          &h->kgf_muc, &h->kgf_mua, &h->kgf_v, &h->kgf_bsort, &h->kgf_perm, &h->kgf_val,
+                          &h->kgs_bsort, &h->kgs_perm};
         for (DevBuf* b : bufs) b->release();
         h->pin_up.release();
         h->pin_res.release();
@@ -616,8 +627,9 @@ int spx_set_kg_points(spx_handle* h, const double* pts, int32_t A)
     if (!h) return fail(SPX_ERR_ARG, "spx_set_kg_points: null handle");
     if (h->multi) return fail(SPX_ERR_ARG, "spx_set_kg_points: SPX_ACQ_KG is single-device only (multi-device handle)");
     if (A < 0) { spx_drop(h, Held::KGPTS); h->kg_A = -1; h->kg_pts_host.clear(); return SPX_OK; }
-    if (A < 1 || A > SPX_KG_MAX_POINTS)
-        return fail(SPX_ERR_ARG, "spx_set_kg_points: A=%d representer points (allowed: 1 .. %d)", (int)A, SPX_KG_MAX_POINTS);
+    const int maxA = h->opt.kg_scan ? SPX_KG_SCAN_MAX_POINTS : SPX_KG_MAX_POINTS;       // (option "kg_scan")
+    if (A < 1 || A > maxA)
+        return fail(SPX_ERR_ARG, "spx_set_kg_points: A=%d representer points (allowed: 1 .. %d)", (int)A, maxA);
     if (!pts) return fail(SPX_ERR_ARG, "spx_set_kg_points: null points with A=%d", (int)A);
     if (!h->held.has(Held::OBS) && !h->held.has(Held::CAND))
         return fail(SPX_ERR_ARG, "spx_set_kg_points: set observations or candidates first (they give the dimension)");
@@ -1079,6 +1091,13 @@ static int check_kg(const spx_handle* h, int32_t flags, const char* who)
         return fail(SPX_ERR_ARG, "%s: SPX_ACQ_KG is single-device only (communicator attached or 2-D partition set)", who);
     if (!h->held.has(Held::KGPTS))
         return fail(SPX_ERR_ARG, "%s: SPX_ACQ_KG needs representer points (spx_set_kg_points)", who);
+    // (points set while option "kg_scan" was on)
+    if (h->kg_A > SPX_KG_MAX_POINTS && !h->opt.kg_scan)
+        return fail(SPX_ERR_ARG, "%s: %d representer points are held and the all-pairs pass takes up to %d (option kg_scan = 1 values "
+                                 "them by slope order and one scan)", who, h->kg_A, SPX_KG_MAX_POINTS);
+    if (h->kg_A > SPX_KG_MAX_POINTS && h->S > 0 && h->opt.kg_fantasies)
+        return fail(SPX_ERR_ARG, "%s: %d representer points are held and SPX_ACQ_KG over fantasies (option kg_fantasies) takes up "
+                                 "to %d", who, h->kg_A, SPX_KG_MAX_POINTS);
     if (h->S > 0 && !h->opt.kg_fantasies)
         return fail(SPX_ERR_ARG, "%s: SPX_ACQ_KG is not defined over fantasies (clear them, or score the call with SPX_ACQ_EI)", who);
     if (h->S > 0) {   // over the fantasies (option "kg_fantasies"): the GEMM branch's width and the resident tables
@@ -1357,6 +1376,7 @@ static int ei_run_impl(spx_handle* h, int32_t flags, bool factor_pending, PassRh
     const bool kg = !ts && h->acq == SPX_ACQ_KG;
     // ... over the fantasies (option "kg_fantasies"; check_kg passed): the fantasies' Gamma in place of column 0, kg_fant_kernels.hip
     const bool kgf = kg && h->S > 0;
+    const bool kgs = kg && !kgf && h->opt.kg_scan;  // ... its lines valued by slope order and one scan (option "kg_scan"), kg_scan_kernels.hip
     const int kgS = kgf ? h->S : 1;                 // columns in front of Gamma_a
     if (kg) rhs = PassRhs{PassRhs::KG, kgS + h->kg_A};
     const int pass_acq = (mes || ehvi || kg) ? SPX_ACQ_EI : h->acq;
@@ -1421,6 +1441,10 @@ static int ei_run_impl(spx_handle* h, int32_t flags, bool factor_pending, PassRh
         if ((rc = h->kg_Kac.reserve((size_t)Hb * kgAp * Mc * 8))) return rc;
         if ((rc = h->kg_muc.reserve((size_t)Hb * Mc * 8))) return rc;
         if (keep_mom && (rc = h->kg_cov.reserve((size_t)H * kgA * Mp * 8))) return rc;
+    }
+    if (kgs) {
+        if ((rc = h->kgs_bsort.reserve((size_t)Hb * S * Mc * 8))) return rc;
+        if ((rc = h->kgs_perm.reserve((size_t)Hb * S * Mc * 2))) return rc;
     }
     if (kgf) {
         if ((rc = h->kgf_muc.reserve((size_t)H * kgS * Mp * 8))) return rc;
@@ -1589,8 +1613,12 @@ static int ei_run_impl(spx_handle* h, int32_t flags, bool factor_pending, PassRh
                     launch_kg_lines(G, h->part_ss.d(), bgS_k, h->htab.d() + (size_t)h0 * SPX_HT, h->kg_Kac.d(), nrb, mc, nhb, S, kgAp, c0, M,
                                     Mp, h0, h->scratch.d(), h->kg_muc.d(), keep_mom ? h->mom_m.d() : nullptr,
                                     keep_mom ? h->mom_v.d() : nullptr, keep_mom ? h->kg_cov.d() : nullptr);
-                    launch_kg_value(G, h->scratch.d(), h->kg_muc.d(), h->kg_mua.d() + (size_t)h0 * kgA, mc, nhb, S, c0, M, Mp, h0,
-                                    h->ei_draw.d());
+                    if (kgs)
+                        launch_kgs_value(G, h->scratch.d(), h->kg_muc.d(), h->kg_mua.d() + (size_t)h0 * kgA, mc, nhb, S, c0, M, Mp, h0,
+                                         h->kgs_bsort.d(), (unsigned short*)h->kgs_perm.p, h->ei_draw.d());
+                    else
+                        launch_kg_value(G, h->scratch.d(), h->kg_muc.d(), h->kg_mua.d() + (size_t)h0 * kgA, mc, nhb, S, c0, M, Mp, h0,
+                                        h->ei_draw.d());
                 });
             } else if (ts)
                 TIMED_S(ST_TS_FINISH, G, launch_ts_finish(G, bgS_k, h->htab.d() + (size_t)h0 * SPX_HT, h->ts_pcand.d(), nrb, mc, nhb, S,
@@ -1669,6 +1697,7 @@ static int ei_run_impl(spx_handle* h, int32_t flags, bool factor_pending, PassRh
     r.moments = keep_mom && (S == 0 || (kg && !kgf)) && !time_only;   // (KG: k_kg_lines wrote func_m / func_v from column 0)
     r.kg = kg;
     r.kg_lines = kg && keep_mom;
+    r.kg_scan = kgs;
     r.kg_fant = kgf;
     if (kg) { h->kg_last_A = kgA; h->kg_last_S = kgf ? kgS : 0; }
     r.tmean = keep_mom && per_sec;   // (with fantasies the pass keeps no func_m / func_v, but mom_t is written all the same)
@@ -2748,6 +2777,7 @@ int spx_get_stat(spx_handle* h, const char* name, int64_t* value)
     else if (!strcmp(name, "kg_points")) *value = h->held.has(Held::KGPTS) ? h->kg_A : 0;       // A of the held representer points (0: none)
     else if (!strcmp(name, "last_kg_points")) *value = h->held.results.kg ? h->kg_last_A : 0;  // ... and of the held KG results
     else if (!strcmp(name, "last_kg_fantasies")) *value = h->held.results.kg_fant ? h->kg_last_S : 0;   // S of held KG results over fantasies (0: none or plain)
+    else if (!strcmp(name, "last_kg_scan")) *value = (h->held.results.kg && h->held.results.kg_scan) ? 1 : 0;   // ... valued by slope order and one scan (option "kg_scan")
     else if (!strcmp(name, "last_kg_lines")) *value = h->held.results.kg_lines ? 1 : 0;        // ... whose covariances are kept
     else if (!strcmp(name, "gemm_lds_bytes")) *value = (int64_t)predict_gemm_lds_bytes();   // dynamic LDS of a predict-GEMM workgroup (two are resident per CU)
     else if (!strcmp(name, "hip_runtime_version") || !strcmp(name, "hip_driver_version")) {

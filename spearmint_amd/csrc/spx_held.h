@@ -28,6 +28,7 @@ struct HeldResults {
                                // spx_thompson_grad_batch after a spx_thompson); gone with the paths, so with everything that drops them
     bool kg = false;           // the pass was a knowledge-gradient pass: mu_a of its representer points is resident
     bool kg_lines = false;     // ... and, kept with the moments, the covariances C[d][a][c] (spx_get_kg_lines)
+    bool kg_scan = false;      // ... valued by slope order and one scan (option "kg_scan"; spx_get_stat "last_kg_scan")
     bool kg_fant = false;      // ... over the fantasies (option "kg_fantasies"): the intercepts are per (draw, fantasy) -- spx_get_kg_fantasy_lines
                                // serves them, spx_get_kg_lines refuses mu_a; gone with the fantasies too (RESULTS uses FANT)
 };

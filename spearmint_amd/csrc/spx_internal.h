@@ -213,6 +213,9 @@ struct spx_handle {
     // readable -- KG_ds [H][S][Mp].  kg_last_S: S of the held results
     DevBuf kgf_muc, kgf_mua, kgf_v, kgf_bsort, kgf_perm, kgf_val;
     int kg_last_S = 0;
+    // ... by slope order and one scan (option "kg_scan", held.results.kg_scan): the work item's ordered slopes and line indices,
+    // [Hb][A + 1][Mc] of 8 and 2 bytes
+    DevBuf kgs_bsort, kgs_perm;
     DevBuf loo_out;                                                 // spx_loo: loo_mean | loo_var | kinv_diag, [3][H][N]; scratch of that call, not part of `held`
     // probit constraint model (spx_set_constraint_model): an internal handle on the same device factors
     // (amp2_c (K_c + 1e-6 I) + noise_c I) alpha_c = ff over its own Nc points; the EI pass reads its scaled rows and alpha_c

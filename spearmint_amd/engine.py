@@ -42,6 +42,7 @@ ACQ_EHVI = 4          # expected hypervolume improvement over (objective, second
 ACQ_KG = 5            # knowledge gradient over representer points (set_kg_points); par 0; single-GPU handles only
 ACQ = {"EI": ACQ_EI, "PI": ACQ_PI, "LCB": ACQ_LCB, "MES": ACQ_MES, "EHVI": ACQ_EHVI, "KG": ACQ_KG}
 KG_MAX_POINTS = 255   # include/spx.h SPX_KG_MAX_POINTS: representer points spx_set_kg_points takes
+KG_SCAN_MAX_POINTS = 1023   # ... SPX_KG_SCAN_MAX_POINTS: with set_option("kg_scan", 1), slope order and one scan; stat("last_kg_scan")
 MAX_FRONT = 4096      # include/spx.h SPX_MAX_FRONT: front points spx_set_pareto_front takes
 MES_FIT_FIELDS = ("lo", "hi", "y25", "y50", "y75", "a", "b", "cap")    # include/spx.h: the fit record of spx_get_mes
 
@@ -516,7 +517,7 @@ class Engine(object):
         return np.stack((a, b), axis=1), (float(r1.value), float(r2.value))
 
     def set_kg_points(self, points):
-        """The representer points of an ACQ_KG pass (include/spx.h: spx_set_kg_points): points (A, D), A in 1 .. KG_MAX_POINTS,
+        """The representer points of an ACQ_KG pass (include/spx.h: spx_set_kg_points): points (A, D), A in 1 .. KG_MAX_POINTS (KG_SCAN_MAX_POINTS while option "kg_scan" is 1),
         D the resident observations' / candidates'.  None clears them.  Drops the results of the last pass and nothing else."""
         if points is None:
             self._check(self._lib.spx_set_kg_points(self._h, None, -1))
