@@ -430,7 +430,13 @@ int spx_get_kg_lines(spx_handle* h, int32_t draw, double* mu_a /* A */, double* 
  * REFUSED with SPX_ERR_ARG from the host's record alone, before any device is touched: everything plain KG refuses (flags,
  * multi-device handles, communicators, partitions, the three refinement entry points); S + A > 4096, the width the S-column
  * branch is held to; H S Mp 8 bytes of intercepts (Mp = M rounded up to 128; twice that with SPX_FLAG_KEEP_MOMENTS, which keeps
- * KG_ds beside them) or H (A + 1) Mp 9 bytes of ordered slopes above SPX_KG_MAX_LINE_BYTES, the message naming the size.                                                                       */
+ * KG_ds beside them) or H (A + 1) Mp 9 bytes of ordered slopes above SPX_KG_MAX_LINE_BYTES, the message naming the size.
+ * VALUE 2, the wide form (csrc/kg_fant_scan_kernels.hip): the same rule on the same lines, operation for operation -- every result
+ * agrees with value 1 bit for bit -- for A up to SPX_KG_SCAN_MAX_POINTS (points that many can only have been set while option
+ * "kg_scan" was 1; the pass itself does not ask for it).  The order is found by the bitonic network of "kg_scan" and kept as
+ * 16-bit indices, so the ordered slopes are H (A + 1) Mp 10 bytes under the same budget, and the scans read mu_a where it lies.
+ * Value 2 takes these kernels at every A.  spx_get_stat "last_kg_scan" is 1 for results of this form, "last_kg_fantasies" is S.
+ * Every other value > 0 means 1, which refuses more than SPX_KG_MAX_POINTS points as before.                                 */
 int spx_get_kg_fantasy_lines(spx_handle* h, int32_t draw, int32_t s, double* mu_c /* M */, double* mu_a /* A */);
 int spx_get_kg_fantasy_var(spx_handle* h, int32_t draw, double* func_v /* M */);
 

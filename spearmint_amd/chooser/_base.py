@@ -100,11 +100,17 @@ class GPEIBase(object):
                              "mes_pending=0)" % self.acq)
         # kg_pending=1: acq=KG scores a call with pending jobs itself, over the fantasies (include/spx.h: option "kg_fantasies");
         # 0: such a call is scored with EI over the fantasies
-        self.kg_pending = _as_bool(kg_pending)
+        # 2: likewise in the wide form (option "kg_fantasies" = 2), which takes what kg_scan=1 takes: acq_par up to 1023 and
+        # kg_points=observed
+        self.kg_pending = int(kg_pending)
+        if self.kg_pending not in (0, 1, 2):
+            raise ValueError("kg_pending=%r (allowed: 0, 1, 2)" % (kg_pending,))
         if self.kg_pending and self.acq != "KG":
-            raise ValueError("kg_pending=1 is the knowledge gradient over the fantasies of pending jobs (allowed with acq=%s: "
-                             "kg_pending=0)" % self.acq)
-        if self.kg_pending and (self.acq_par > 255 or self.kg_points == "observed"):
+            raise ValueError("kg_pending=%d is the knowledge gradient over the fantasies of pending jobs (allowed with acq=%s: "
+                             "kg_pending=0)" % (self.kg_pending, self.acq))
+        if self.kg_pending == 2 and not self.kg_scan:
+            raise ValueError("kg_pending=2 is the pending form of kg_scan=1 (allowed with kg_scan=0: kg_pending=0, 1)")
+        if self.kg_pending == 1 and (self.acq_par > 255 or self.kg_points == "observed"):
             raise ValueError("kg_pending=1 takes up to 255 grid rows as representer points (allowed: acq_par in 1 .. 255 and "
                              "kg_points=grid, or kg_pending=0)")
         self.last_kg = None            # acq=KG: {"points_index", "points", "grid_index", "value"} of the last call scored with KG
@@ -251,7 +257,7 @@ class GPEIBase(object):
         if acq == "MES" and pending and self.mes_pending:
             eng.set_option("mes_fantasies", 1)
         elif acq == "KG" and pending and self.kg_pending and kg_over_fantasies:
-            eng.set_option("kg_fantasies", 1)
+            eng.set_option("kg_fantasies", self.kg_pending)     # (2: the wide form; _kg_pending_gpu has set "kg_scan")
         elif acq in ("MES", "KG") and pending:   # (KG likewise: the library refuses it over fantasies -- the MES rule)
             acq, par = "EI", 0.0
         if acq == "KG":                          # (A is the chooser's; the handle's acquisition takes no parameter)
@@ -379,14 +385,20 @@ class GPEIBase(object):
                 self.last_kg = None
                 eng.set_acquisition(*prev)
                 return self._ei_with_pending_gpu(comp, pend, cand, vals, rows, randn, False, kg_over_fantasies=False)[0]
-            eng.set_kg_points(grid[pidx, :])
+            points = grid[pidx, :]
+            if self.kg_pending == 2:             # as _kg_gpu takes them under kg_scan=1; pending points are never representer points
+                eng.set_option("kg_scan", 1)
+                if self.kg_points == "observed":
+                    pidx = np.arange(min(comp.shape[0], 1023))
+                    points = np.ascontiguousarray(comp[pidx, :], dtype=np.float64)
+            eng.set_kg_points(points)
             idx, mean_kg, _ = self._ei_with_pending_gpu(comp, pend, cand, vals, rows, randn, True)
         finally:
             eng.set_acquisition(*prev)
         warning = eng.last_warning()
         if warning:
             log("libspx " + warning)
-        self.last_kg = {"points_index": np.array(pidx, dtype=int), "points": np.array(grid[pidx, :], dtype=float),
+        self.last_kg = {"points_index": np.array(pidx, dtype=int), "points": np.array(points, dtype=float),
                         "grid_index": int(idx), "value": float(mean_kg[int(idx)])}
         return int(idx)
 

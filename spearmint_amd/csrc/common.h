@@ -245,6 +245,9 @@ int kg_tile_candidates(int n);
 // in place of launch_kg_value behind the same launch_kg_lines; n = A + 1 up to 1024.  bsort / perm: nh n Mc entries, the work item's.
 void launch_kgs_value(hipStream_t s, const double* slope, const double* muc, const double* mua, int Mc, int nh, int n, int64_t c0,
                       int64_t M, int64_t Mp, int h0, double* bsort, unsigned short* perm, double* ei_draw);
+// ... its order alone, into tables of row stride orow at column oc0 of draw oh0 + h (the plain pass: Mc, 0, 0)
+void launch_kgs_order(hipStream_t s, const double* slope, int Mc, int nh, int n, int64_t c0, int64_t M, size_t orow, int64_t oc0, int oh0,
+                      double* bsort, unsigned short* perm);
 
 // kg_fant_kernels.hip: the knowledge gradient over the fantasies of the S > 0 GEMM branch with S + A columns per draw (spx.h: option
 // "kg_fantasies"; columns 0 .. S-1 the fantasies' Gamma, S .. S+A-1 Gamma_a).  mua [H][A][S] once per pass;  per work item the
@@ -259,6 +262,20 @@ void launch_kgf_value(hipStream_t s, const double* bsort, const unsigned char* p
                       int n, int S, int H, int64_t M, int64_t Mp, double* ei_draw);
 void kgf_tile(int n, int S, int* TC, int* SB);
 size_t kgf_lds_bytes(int n, int TC, int SB);
+// (its pieces, for kg_fant_scan_kernels.hip: k_kgf_lines without the order, k_kgf_mean)
+void launch_kgf_lines_only(hipStream_t s, const double* part_ss, const double* part_bgS, const double* htab, const double* Kac, int nrb,
+                           int Mc, int nh, int S, int A, int Ap, int64_t c0, int64_t M, int64_t Mp, int h0, double* slope, double* muc,
+                           double* fv, double* cov);
+void launch_kgf_mean(hipStream_t s, const double* val, int S, int H, int64_t M, int64_t Mp, double* ei_draw);
+
+// kg_fant_scan_kernels.hip: KG over the fantasies by the bitonic slope order and a scan that reads mu_a where it lies (spx.h: option
+// "kg_fantasies" = 2), n = A + 1 up to 1024.  As launch_kgf_lines / launch_kgf_value with 16-bit indices in perm; badcol: H S ints.
+void launch_kgw_lines(hipStream_t s, const double* part_ss, const double* part_bgS, const double* htab, const double* Kac, int nrb,
+                      int Mc, int nh, int S, int A, int Ap, int64_t c0, int64_t M, int64_t Mp, int h0, double* slope, double* muc,
+                      double* fv, double* cov, double* bsort, unsigned short* perm);
+void launch_kgw_value(hipStream_t s, const double* bsort, const unsigned short* perm, const double* mua, const double* muc, double* val,
+                      int* badcol, int n, int S, int H, int64_t M, int64_t Mp, double* ei_draw);
+size_t kgw_lds_bytes(int n, bool staged);
 
 // predict_kernels.hip
 void launch_predict_gemm(hipStream_t s, int variant, const double* WT, const double* Kst, const double* gamma,

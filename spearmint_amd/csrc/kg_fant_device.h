@@ -76,6 +76,31 @@ struct KgfLinesOf {
 typedef KgfLinesOf<unsigned char, int> KgfLines;
 typedef KgfLinesOf<unsigned short, size_t> KgsLines;
 
+// the terms of the envelope a scan left on the stack, from bottom to top (shared by kgf_value and kg_fant_scan_kernels.hip's scan)
+template <class Lines>
+__device__ __forceinline__ double kgf_terms(const Lines& L, int n, const unsigned* stk, int ss)
+{
+#pragma clang fp contract(off)
+    const int nw = (n + 31) >> 5;
+    double acc = 0.0, mj = 0.0, bj = 0.0;
+    bool first = true;
+    for (int w = 0; w < nw; ++w) {
+        unsigned m = stk[(size_t)w * ss];
+        while (m) {
+            const int k = (w << 5) + __builtin_ctz(m);
+            m &= m - 1u;
+            const double mk = L.m(k), bk = L.b(k);
+            if (!first) {
+                const double db = bj - bk;
+                acc = acc + db * kg_f((mk - mj) / db);
+            }
+            first = false;
+            mj = mk; bj = bk;
+        }
+    }
+    return acc;
+}
+
 template <class Lines>
 __device__ __forceinline__ double kgf_value(const Lines& L, int n, unsigned* stk, int ss)
 {
@@ -110,21 +135,5 @@ __device__ __forceinline__ double kgf_value(const Lines& L, int n, unsigned* stk
         top = k; mt = mk; bt = bk;
         stk[(size_t)(k >> 5) * ss] |= 1u << (k & 31);
     }
-    double acc = 0.0, mj = 0.0, bj = 0.0;
-    bool first = true;
-    for (int w = 0; w < nw; ++w) {
-        unsigned m = stk[(size_t)w * ss];
-        while (m) {
-            const int k = (w << 5) + __builtin_ctz(m);
-            m &= m - 1u;
-            const double mk = L.m(k), bk = L.b(k);
-            if (!first) {
-                const double db = bj - bk;
-                acc = acc + db * kg_f((mk - mj) / db);
-            }
-            first = false;
-            mj = mk; bj = bk;
-        }
-    }
-    return acc;
+    return kgf_terms(L, n, stk, ss);
 }

@@ -193,13 +193,21 @@ __global__ __launch_bounds__(256) void k_kgf_order(const double* __restrict__ sl
     }
 }
 
+// k_kgf_lines alone (kg_fant_scan_kernels.hip orders the slopes it leaves with a kernel of its own)
+void launch_kgf_lines_only(hipStream_t s, const double* part_ss, const double* part_bgS, const double* htab, const double* Kac, int nrb,
+                           int Mc, int nh, int S, int A, int Ap, int64_t c0, int64_t M, int64_t Mp, int h0, double* slope, double* muc,
+                           double* fv, double* cov)
+{
+    hipLaunchKernelGGL(k_kgf_lines, dim3((Mc + 255) / 256, nh * (S + A)), dim3(256), 0, s, part_ss, part_bgS, htab, Kac, nrb, Mc, nh, S, A,
+                       Ap, c0, M, Mp, h0, slope, muc, fv, cov);
+}
+
 void launch_kgf_lines(hipStream_t s, const double* part_ss, const double* part_bgS, const double* htab, const double* Kac, int nrb,
                       int Mc, int nh, int S, int A, int Ap, int64_t c0, int64_t M, int64_t Mp, int h0, double* slope, double* muc,
                       double* fv, double* cov, double* bsort, unsigned char* perm)
 {
     const int n = A + 1, TC = kg_tile_candidates(n);
-    hipLaunchKernelGGL(k_kgf_lines, dim3((Mc + 255) / 256, nh * (S + A)), dim3(256), 0, s, part_ss, part_bgS, htab, Kac, nrb, Mc, nh, S, A,
-                       Ap, c0, M, Mp, h0, slope, muc, fv, cov);
+    launch_kgf_lines_only(s, part_ss, part_bgS, htab, Kac, nrb, Mc, nh, S, A, Ap, c0, M, Mp, h0, slope, muc, fv, cov);
     hipLaunchKernelGGL(k_kgf_order, dim3((Mc + TC - 1) / TC, nh), dim3(256), 0, s, slope, Mc, n, TC, c0, M, Mp, h0, bsort, perm);
 }
 
@@ -305,6 +313,11 @@ __global__ __launch_bounds__(256) void k_kgf_mean(const double* __restrict__ val
     ei_draw[(size_t)h * Mp + c] = (0.0 + res) / (double)S;
 }
 
+void launch_kgf_mean(hipStream_t s, const double* val, int S, int H, int64_t M, int64_t Mp, double* ei_draw)
+{
+    hipLaunchKernelGGL(k_kgf_mean, dim3((unsigned)((M + 255) / 256), H), dim3(256), 0, s, val, S, ei_draw, M, Mp);
+}
+
 void launch_kgf_value(hipStream_t s, const double* bsort, const unsigned char* perm, const double* mua, const double* muc, double* val,
                       int n, int S, int H, int64_t M, int64_t Mp, double* ei_draw)
 {
@@ -319,5 +332,5 @@ void launch_kgf_value(hipStream_t s, const double* bsort, const unsigned char* p
     runs = (S + sper - 1) / sper;
     hipLaunchKernelGGL(k_kgf_value, dim3((unsigned)ntiles, runs, H), dim3(256), kgf_lds_bytes(n, TC, SB), s, bsort, perm, mua, muc, val,
                        n, S, TC, SB, sper, M, Mp);
-    hipLaunchKernelGGL(k_kgf_mean, dim3((unsigned)((M + 255) / 256), H), dim3(256), 0, s, val, S, ei_draw, M, Mp);
+    launch_kgf_mean(s, val, S, H, M, Mp, ei_draw);
 }

@@ -58,8 +58,9 @@ static int kgs_tile_candidates(int P) { return KGS_SLOTS / P < 256 ? KGS_SLOTS /
 __device__ __forceinline__ bool kgs_before(double bi, unsigned i, double bj, unsigned j) { return bi > bj || (bi == bj && i < j); }
 
 __global__ __launch_bounds__(256) void k_kgs_order(const double* __restrict__ slope /*[nh][n][Mc]*/, int Mc, int n, int P, int TC,
-                                                   int64_t c0, int64_t M, double* __restrict__ bsort /*[nh][n][Mc]*/,
-                                                   unsigned short* __restrict__ perm /*[nh][n][Mc]*/)
+                                                   int64_t c0, int64_t M, size_t orow, int64_t oc0, int oh0,
+                                                   double* __restrict__ bsort /*[.][n][orow]*/,
+                                                   unsigned short* __restrict__ perm /*[.][n][orow]*/)
 {
     extern __shared__ double kgs_lds[];
     double* s_b = kgs_lds;                                         // [P][TC]
@@ -110,7 +111,8 @@ __global__ __launch_bounds__(256) void k_kgs_order(const double* __restrict__ sl
     for (int idx = tid; idx < n * TC; idx += 256) {
         const int k = idx >> tsh, ct = idx & (TC - 1), c = cbase + ct;
         if (c >= Mc || c0 + c >= M) continue;
-        const size_t o = ((size_t)h * n + k) * Mc + c;
+        // (the work item's own tables: orow = Mc, oc0 = oh0 = 0; resident [H][n][Mp] ones: orow = Mp, oc0 = c0, oh0 = h0)
+        const size_t o = ((size_t)(oh0 + h) * n + k) * orow + oc0 + c;
         bsort[o] = s_bad[ct] ? __builtin_nan("") : s_b[idx];
         perm[o] = s_i[idx];
     }
@@ -153,13 +155,21 @@ __global__ __launch_bounds__(256) void k_kgs_value(const double* __restrict__ bs
     ei_draw[(size_t)(h0 + h) * Mp + c0 + c] = v;
 }
 
+// the slope order of a work item's (d, c) into tables of row stride orow, the work item at column oc0 of draw oh0 + h (the plain
+// pass: its own [nh][n][Mc]; KG over fantasies, kg_fant_scan_kernels.hip: the resident [H][n][Mp])
+void launch_kgs_order(hipStream_t s, const double* slope, int Mc, int nh, int n, int64_t c0, int64_t M, size_t orow, int64_t oc0, int oh0,
+                      double* bsort, unsigned short* perm)
+{
+    const int P = kgs_pow2(n), TC = kgs_tile_candidates(P);
+    hipLaunchKernelGGL(k_kgs_order, dim3((Mc + TC - 1) / TC, nh), dim3(256), (size_t)10 * P * TC + 4 * TC, s, slope, Mc, n, P, TC, c0, M,
+                       orow, oc0, oh0, bsort, perm);
+}
+
 // slope / muc as launch_kg_lines left them for the work item, mua the draws' [nh][n - 1]; bsort / perm: nh n Mc entries each
 void launch_kgs_value(hipStream_t s, const double* slope, const double* muc, const double* mua, int Mc, int nh, int n, int64_t c0,
                       int64_t M, int64_t Mp, int h0, double* bsort, unsigned short* perm, double* ei_draw)
 {
-    const int P = kgs_pow2(n), TC = kgs_tile_candidates(P);
-    hipLaunchKernelGGL(k_kgs_order, dim3((Mc + TC - 1) / TC, nh), dim3(256), (size_t)10 * P * TC + 4 * TC, s, slope, Mc, n, P, TC, c0, M,
-                       bsort, perm);
+    launch_kgs_order(s, slope, Mc, nh, n, c0, M, (size_t)Mc, 0, 0, bsort, perm);
     hipLaunchKernelGGL(k_kgs_value, dim3((Mc + 255) / 256, nh), dim3(256), (size_t)8 * (n - 1) + 1024 * (size_t)((n + 31) / 32) + 4, s,
                        bsort, perm, muc, mua, Mc, n, c0, M, Mp, h0, ei_draw);
 }

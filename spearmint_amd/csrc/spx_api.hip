@@ -219,11 +219,12 @@ static int opt_mes_fantasies(spx_handle* h, int64_t value)
     h->opt.mes_fantasies = value > 0;
     return SPX_OK;
 }
-// SPX_ACQ_KG with fantasies held: over the fantasies (1) or refused (0); the lines of the last pass belong to the old setting
+// SPX_ACQ_KG with fantasies held: over the fantasies (1; 2: the wide form, kg_fant_scan_kernels.hip) or refused (0); the lines of
+// the last pass belong to the old setting
 static int opt_kg_fantasies(spx_handle* h, int64_t value)
 {
     spx_drop(h, Held::RESULTS);
-    h->opt.kg_fantasies = value > 0;
+    h->opt.kg_fantasies = value == 2 ? 2 : value > 0;
     return SPX_OK;
 }
 // a plain SPX_ACQ_KG pass: slope order and one scan, A up to 1023 (1), or all pairs, A up to 255 (0); the results of the last pass
@@ -346,7 +347,7 @@ void spx_destroy(spx_handle* h)
                           &h->ts_alpha, &h->ts_gin, &h->ts_gwork, &h->ts_gout,
                           &h->kg_pts, &h->kg_As, &h->kg_sA, &h->kg_kxa, &h->kg_gammaS, &h->kg_mua, &h->kg_Kac, &h->kg_muc, &h->kg_cov,
                           &h->kgf_muc, &h->kgf_mua, &h->kgf_v, &h->kgf_bsort, &h->kgf_perm, &h->kgf_val,
-                          &h->kgs_bsort, &h->kgs_perm};
+                          &h->kgs_bsort, &h->kgs_perm, &h->kgw_badcol};
         for (DevBuf* b : bufs) b->release();
         h->pin_up.release();
         h->pin_res.release();
@@ -1092,10 +1093,12 @@ static int check_kg(const spx_handle* h, int32_t flags, const char* who)
     if (!h->held.has(Held::KGPTS))
         return fail(SPX_ERR_ARG, "%s: SPX_ACQ_KG needs representer points (spx_set_kg_points)", who);
     // (points set while option "kg_scan" was on)
-    if (h->kg_A > SPX_KG_MAX_POINTS && !h->opt.kg_scan)
+    // (option "kg_fantasies" = 2: the wide form over fantasies orders its lines itself, whatever "kg_scan" says now)
+    const bool wide = h->S > 0 && h->opt.kg_fantasies == 2;
+    if (h->kg_A > SPX_KG_MAX_POINTS && !h->opt.kg_scan && !wide)
         return fail(SPX_ERR_ARG, "%s: %d representer points are held and the all-pairs pass takes up to %d (option kg_scan = 1 values "
                                  "them by slope order and one scan)", who, h->kg_A, SPX_KG_MAX_POINTS);
-    if (h->kg_A > SPX_KG_MAX_POINTS && h->S > 0 && h->opt.kg_fantasies)
+    if (h->kg_A > SPX_KG_MAX_POINTS && h->S > 0 && h->opt.kg_fantasies && !wide)
         return fail(SPX_ERR_ARG, "%s: %d representer points are held and SPX_ACQ_KG over fantasies (option kg_fantasies) takes up "
                                  "to %d", who, h->kg_A, SPX_KG_MAX_POINTS);
     if (h->S > 0 && !h->opt.kg_fantasies)
@@ -1108,14 +1111,15 @@ static int check_kg(const spx_handle* h, int32_t flags, const char* who)
             const double Mp = (double)round_up(h->M, SPX_BN);
             // (with the moments kept KG_ds has a table of its own beside the intercepts: twice the bytes)
             const int tabs = (flags & SPX_FLAG_KEEP_MOMENTS) ? 2 : 1;
-            const double mu_bytes = (double)tabs * h->H * h->S * Mp * 8.0, ord_bytes = (double)h->H * (h->kg_A + 1) * Mp * 9.0;
+            const int ord = wide ? 10 : 9;                    // a slope and an index of 16 or 8 bits per line
+            const double mu_bytes = (double)tabs * h->H * h->S * Mp * 8.0, ord_bytes = (double)h->H * (h->kg_A + 1) * Mp * ord;
             if (mu_bytes > (double)SPX_KG_MAX_LINE_BYTES)
                 return fail(SPX_ERR_ARG, "%s: H S Mp 8 = %d x %d x %.0f x 8 = %.0f bytes of means per (draw, fantasy)%s (SPX_ACQ_KG over "
                                          "fantasies allows up to %lld bytes)", who, h->H, h->S, Mp, mu_bytes / tabs,
                             tabs == 2 ? ", twice with SPX_FLAG_KEEP_MOMENTS" : "", (long long)SPX_KG_MAX_LINE_BYTES);
             if (ord_bytes > (double)SPX_KG_MAX_LINE_BYTES)
-                return fail(SPX_ERR_ARG, "%s: H (A + 1) Mp 9 = %d x %d x %.0f x 9 = %.0f bytes of ordered slopes (SPX_ACQ_KG over "
-                                         "fantasies allows up to %lld bytes)", who, h->H, h->kg_A + 1, Mp, ord_bytes,
+                return fail(SPX_ERR_ARG, "%s: H (A + 1) Mp %d = %d x %d x %.0f x %d = %.0f bytes of ordered slopes (SPX_ACQ_KG over "
+                                         "fantasies allows up to %lld bytes)", who, ord, h->H, h->kg_A + 1, Mp, ord, ord_bytes,
                             (long long)SPX_KG_MAX_LINE_BYTES);
         }
     }
@@ -1376,6 +1380,7 @@ static int ei_run_impl(spx_handle* h, int32_t flags, bool factor_pending, PassRh
     const bool kg = !ts && h->acq == SPX_ACQ_KG;
     // ... over the fantasies (option "kg_fantasies"; check_kg passed): the fantasies' Gamma in place of column 0, kg_fant_kernels.hip
     const bool kgf = kg && h->S > 0;
+    const bool kgw = kgf && h->opt.kg_fantasies == 2;   // ... in the wide form: 16-bit indices, A up to 1023, kg_fant_scan_kernels.hip
     const bool kgs = kg && !kgf && h->opt.kg_scan;  // ... its lines valued by slope order and one scan (option "kg_scan"), kg_scan_kernels.hip
     const int kgS = kgf ? h->S : 1;                 // columns in front of Gamma_a
     if (kg) rhs = PassRhs{PassRhs::KG, kgS + h->kg_A};
@@ -1451,7 +1456,8 @@ static int ei_run_impl(spx_handle* h, int32_t flags, bool factor_pending, PassRh
         if ((rc = h->kgf_mua.reserve((size_t)H * kgA * kgS * 8))) return rc;
         if ((rc = h->kgf_v.reserve((size_t)H * Mp * 8))) return rc;
         if ((rc = h->kgf_bsort.reserve((size_t)H * (kgA + 1) * Mp * 8))) return rc;
-        if ((rc = h->kgf_perm.reserve((size_t)H * (kgA + 1) * Mp))) return rc;
+        if ((rc = h->kgf_perm.reserve((size_t)H * (kgA + 1) * Mp * (kgw ? 2 : 1)))) return rc;
+        if (kgw && (rc = h->kgw_badcol.reserve((size_t)H * kgS * sizeof(int)))) return rc;
         if (keep_mom && (rc = h->kgf_val.reserve((size_t)H * kgS * Mp * 8))) return rc;   // (mu_c stays for its getter)
     }
     // (read AFTER the reservations above: a buffer that grows moves)
@@ -1604,7 +1610,12 @@ static int ei_run_impl(spx_handle* h, int32_t flags, bool factor_pending, PassRh
                                                           Cs + (size_t)h0 * mc * Dp, s2 + (size_t)h0 * mc,
                                                           h->htab.d() + (size_t)h0 * SPX_HT, h->kg_Kac.d(), kgA, kgAp, mc, Dp, nhb,
                                                           dev_kind(h)));
-                if (kgf)   // the intercepts, the slopes and their order; the scans run behind the last chunk
+                if (kgw)   // likewise, the order by the bitonic network with 16-bit indices
+                    TIMED_S(ST_KG, G, launch_kgw_lines(G, h->part_ss.d(), bgS_k, h->htab.d() + (size_t)h0 * SPX_HT, h->kg_Kac.d(), nrb, mc,
+                                                       nhb, kgS, kgA, kgAp, c0, M, Mp, h0, h->scratch.d(), h->kgf_muc.d(), h->kgf_v.d(),
+                                                       keep_mom ? h->kg_cov.d() : nullptr, h->kgf_bsort.d(),
+                                                       (unsigned short*)h->kgf_perm.p));
+                else if (kgf)   // the intercepts, the slopes and their order; the scans run behind the last chunk
                     TIMED_S(ST_KG, G, launch_kgf_lines(G, h->part_ss.d(), bgS_k, h->htab.d() + (size_t)h0 * SPX_HT, h->kg_Kac.d(), nrb, mc,
                                                        nhb, kgS, kgA, kgAp, c0, M, Mp, h0, h->scratch.d(), h->kgf_muc.d(), h->kgf_v.d(),
                                                        keep_mom ? h->kg_cov.d() : nullptr, h->kgf_bsort.d(),
@@ -1649,7 +1660,11 @@ static int ei_run_impl(spx_handle* h, int32_t flags, bool factor_pending, PassRh
     const int n_info = p.n_info;
     if ((rc = h->pin_res.reserve(16 + (size_t)n_info * sizeof(int)))) return rc;
     double* mirror = (double*)h->pin_res.p;
-    if (kgf)   // behind the last chunk on the main stream: the lines of every (draw, fantasy, candidate) are complete
+    if (kgw)
+        TIMED(ST_KG, launch_kgw_value(s, h->kgf_bsort.d(), (const unsigned short*)h->kgf_perm.p, h->kgf_mua.d(), h->kgf_muc.d(),
+                                      keep_mom ? h->kgf_val.d() : h->kgf_muc.d(), (int*)h->kgw_badcol.p, kgA + 1, kgS, H, M, Mp,
+                                      h->ei_draw.d()));
+    else if (kgf)   // behind the last chunk on the main stream: the lines of every (draw, fantasy, candidate) are complete
         TIMED(ST_KG, launch_kgf_value(s, h->kgf_bsort.d(), (const unsigned char*)h->kgf_perm.p, h->kgf_mua.d(), h->kgf_muc.d(),
                                       keep_mom ? h->kgf_val.d() : h->kgf_muc.d(), kgA + 1, kgS, H, M, Mp, h->ei_draw.d()));
     if (mesf)  // behind the last chunk on the main stream: the means of every (draw, fantasy) are complete
@@ -1697,7 +1712,7 @@ static int ei_run_impl(spx_handle* h, int32_t flags, bool factor_pending, PassRh
     r.moments = keep_mom && (S == 0 || (kg && !kgf)) && !time_only;   // (KG: k_kg_lines wrote func_m / func_v from column 0)
     r.kg = kg;
     r.kg_lines = kg && keep_mom;
-    r.kg_scan = kgs;
+    r.kg_scan = kgs || kgw;
     r.kg_fant = kgf;
     if (kg) { h->kg_last_A = kgA; h->kg_last_S = kgf ? kgS : 0; }
     r.tmean = keep_mom && per_sec;   // (with fantasies the pass keeps no func_m / func_v, but mom_t is written all the same)

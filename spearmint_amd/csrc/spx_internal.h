@@ -211,7 +211,8 @@ struct spx_handle {
     // ... over fantasies (option "kg_fantasies", held.results.kg_fant): the intercepts mu_c [H][S][Mp] and mu_a [H][A][S], func_v
     // [H][Mp], the slopes by rank and the lines' indices by rank [H][A + 1][Mp], and -- with the moments kept, so that mu_c stays
     // readable -- KG_ds [H][S][Mp].  kg_last_S: S of the held results
-    DevBuf kgf_muc, kgf_mua, kgf_v, kgf_bsort, kgf_perm, kgf_val;
+    // "kg_fantasies" = 2 (kg_fant_scan_kernels.hip): the indices are 16 bits wide; kgw_badcol [H][S]: a mu_a[.][s] is not finite
+    DevBuf kgf_muc, kgf_mua, kgf_v, kgf_bsort, kgf_perm, kgf_val, kgw_badcol;
     int kg_last_S = 0;
     // ... by slope order and one scan (option "kg_scan", held.results.kg_scan): the work item's ordered slopes and line indices,
     // [Hb][A + 1][Mc] of 8 and 2 bytes

@@ -28,7 +28,7 @@ struct Options {
     int64_t effects_pass_rows = 0;      // "effects_pass_rows": rows per pass of spx_main_effects (0 = default)
     int mes_grid = 256;                 // "mes_grid": probe values J of a max-value entropy search pass (8 .. 4096)
     int mes_fantasies = 0;              // "mes_fantasies": SPX_ACQ_MES with fantasies held runs over them (1) or refuses (0, default)
-    int kg_fantasies = 0;               // "kg_fantasies": SPX_ACQ_KG with fantasies held runs over them (1) or refuses (0, default)
+    int kg_fantasies = 0;               // "kg_fantasies": SPX_ACQ_KG with fantasies held runs over them (1; 2: the wide form, A up to 1023) or refuses (0, default)
     int kg_scan = 0;                    // "kg_scan": a plain SPX_ACQ_KG pass values its lines by slope order and one scan, A up to 1023 (1), or by all pairs, A up to 255 (0, default)
     bool timing = false;
     int lean_lazy = -1, step_overlap = -1, ei_fused = -1, ei_flow = -1, lean_flow_cov = -1, lean_flow_yield = -1,
