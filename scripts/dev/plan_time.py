@@ -3,9 +3,11 @@
 label, which gives the spread of the machine on the day: a difference between builds means something only beyond it.
 Call sets: `host` -- spx_gp_logprob at N = 64 x 1 draw and N = 256 x 10 draws, spx_ei_step at N = 128, 20 000 candidates,
 10 draws; `staging` -- spx_ei_step at N = 256, 20 000 candidates, 10 draws through a 1 MiB K(X*,X) staging buffer (40 chunks
-x 10 draws = 400 work items a pass: the event traffic of the hand-off dominates) under streams = 1, 2 and 3.
-   python scripts/dev/plan_time.py _variants/libspx_parent.so [rounds] [host|staging|all]
-(profiles/plan_refactor_time.log: the host set; profiles/staging_ring_time.log: all)"""
+x 10 draws = 400 work items a pass: the event traffic of the hand-off dominates) under streams = 1, 2 and 3; `pass` -- the
+step at N = 128, 20 000 candidates, 10 draws as EI, under SPX_ACQ_KG (16 representer points) and under SPX_ACQ_MES, and
+spx_gp_logprob at N = 64 x 1 draw (option key "acq": the acquisition, its parameter, the number of points).
+   python scripts/dev/plan_time.py _variants/libspx_parent.so [rounds] [host|staging|pass|all]
+(profiles/plan_refactor_time.log: the host set; profiles/staging_ring_time.log: all; profiles/pass_refactor_time.log: pass)"""
 import json
 import os
 import subprocess
@@ -21,6 +23,10 @@ SETS = {"host": {"logprob N=64 H=1": (64, 16, 1, 400, {}), "logprob N=256 H=10":
         "staging": {"ei_step N=256 M=20000 H=10 1MiB streams=%d" % ns: (256, 20000, 10, 12, {"kstar_budget_bytes": 1 << 20, "streams": ns})
                     for ns in (1, 2, 3)}}
 SETS["all"] = dict(SETS["host"], **SETS["staging"])
+SETS["pass"] = {"ei_step N=128 M=20000 H=10": (128, 20000, 10, 150, {}),
+                "ei_step N=128 M=20000 H=10 KG A=16": (128, 20000, 10, 40, {"acq": ("KG", 0.0, 16)}),
+                "ei_step N=128 M=20000 H=10 MES K=8": (128, 20000, 10, 100, {"acq": ("MES", 8, 0)}),
+                "logprob N=64 H=1": (64, 16, 1, 400, {})}
 
 if len(sys.argv) > 1 and sys.argv[1] == "--child":
     sys.path.insert(0, root)
@@ -31,11 +37,14 @@ if len(sys.argv) > 1 and sys.argv[1] == "--child":
     out = {}
     for name, (N, Mc, H, reps, opts) in SETS[sys.argv[3]].items():
         comp, cand, vals, hypers = synthetic_problem(N, Mc, 6, H, 5)
-        for k, v in dict(DEFAULTS, **opts).items():
+        acq, par, A = opts.get("acq", ("EI", 0.0, 0))
+        for k, v in dict(DEFAULTS, **{k: v for k, v in opts.items() if k != "acq"}).items():
             eng.set_option(k, v)
         eng.set_observations(comp, vals)
         eng.set_candidates(cand)
         eng.set_hypers(hypers)
+        eng.set_kg_points(np.random.RandomState(1).uniform(0.0, 1.0, (A, 6)) if A else None)
+        eng.set_acquisition(acq, par)
         if name.startswith("logprob"):
             def call():
                 eng.set_hypers(hypers)

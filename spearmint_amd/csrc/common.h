@@ -177,9 +177,7 @@ void launch_loo_diag(hipStream_t s, const double* WT, const double* alpha, const
 
 // mes_kernels.hip: max-value entropy search behind a pass that kept its moments ([H][Mp]) -- bounds, log-survival sums for J probe
 // values, quartiles + Gumbel fit + the y* table [H][K], and the values into ei_draw.  bpart: [H][mes_bound_blocks(M)][3],
-// part: [H][mes_sum_blocks(M)][J], G: [H][J], fit: [H][8]; hyp: a row per draw with the noise at +1, hs doubles apart (htab)
-int mes_sum_blocks(int64_t M);
-int mes_bound_blocks(int64_t M);
+// part: [H][mes_sum_blocks(M)][J], G: [H][J], fit: [H][8]; hyp: a row per draw with the noise at +1, hs doubles apart (htab); the block counts: spx_geom.h
 void launch_mes(hipStream_t s, const double* mom_m, const double* mom_v, const double* hyp, int hs, double best, int64_t M,
                 int64_t Mp, int H, int J, int K, double* bpart, double* part, double* G, double* ystar, double* fit,
                 double* ei_draw);
@@ -210,8 +208,6 @@ void launch_ts_argmin(hipStream_t s, const double* path, int64_t M, int64_t Mp, 
 // the log-survival sums, the fit per (draw, fantasy) and the values, their mean over the fantasies into ei_draw.
 // bpart: [H][S][mes_fant_bound_blocks(M)][3], bnd: [H][S][3], part: [H][S][mes_fant_sum_blocks(M)][J], G: [H][S][J],
 // ystar: [H][S][K], fit: [H][S][8], bests: [H][S]; hyp as launch_mes takes it
-int mes_fant_sum_blocks(int64_t M);
-int mes_fant_bound_blocks(int64_t M);
 void launch_mes_fant_means(hipStream_t s, const double* part_ss, const double* part_bgS, const double* htab, int nrb, int Mc, int nh,
                            int S, int64_t c0, int64_t M, int64_t Mp, int h0, double* mu, double* v);
 void launch_mes_fant(hipStream_t s, const double* mu, const double* v, const double* hyp, int hs, const double* bests, int64_t M,

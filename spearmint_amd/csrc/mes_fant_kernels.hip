@@ -39,15 +39,11 @@
 #include "mes_device.h"
 #include "np_sum.h"
 
-#define MESF_CT 512        // candidates per partial sum of k_mes_fant_logsurv (MES_CT of the plain pass)
+// (MESF_CT / MESF_BT, candidates per partial sum / minimum, and mes_fant_sum_blocks / mes_fant_bound_blocks: spx_geom.h)
 #define MESF_SB 8          // fantasies whose means a workgroup of k_mes_fant_logsurv holds in LDS at a time
 #define MESF_JW 256        // probe values per workgroup of k_mes_fant_logsurv
-#define MESF_BT 1024       // candidates per partial minimum of k_mes_fant_bounds
 #define MESF_LV 2048       // y* levels a workgroup of k_mes_fant_values holds in LDS at a time (K <= 1024: at least two fantasies)
 #define MESF_DBL_MAX 1.79769313486231570815e308
-
-int mes_fant_sum_blocks(int64_t M) { return (int)((M + MESF_CT - 1) / MESF_CT); }
-int mes_fant_bound_blocks(int64_t M) { return (int)((M + MESF_BT - 1) / MESF_BT); }
 
 __global__ __launch_bounds__(256) void k_mes_fant_means(const double* __restrict__ part_ss, const double* __restrict__ part_bgS,
                                                         const double* __restrict__ htab, int nrb, int Mc, int nh, int S, int64_t c0,

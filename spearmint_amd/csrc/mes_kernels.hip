@@ -10,11 +10,7 @@
 // draw's moments, M and J alone and its summation error stays under two ulp whatever M is.
 #include "mes_device.h"
 
-#define MES_CT 512        // candidates per partial sum of k_mes_logsurv
-#define MES_BT 1024       // candidates per partial minimum of k_mes_bounds
-
-int mes_sum_blocks(int64_t M) { return (int)((M + MES_CT - 1) / MES_CT); }
-int mes_bound_blocks(int64_t M) { return (int)((M + MES_BT - 1) / MES_BT); }
+// (MES_CT / MES_BT, candidates per partial sum / minimum, and mes_sum_blocks / mes_bound_blocks: spx_geom.h)
 
 // min over the block of two values and the "or" of a flag; every thread returns with the results
 __device__ __forceinline__ void mes_block_min2(double& lo, double& hi, double& any, double (*red)[4])

@@ -1065,13 +1065,13 @@ int spx_get_pending_fantasies(spx_handle* h, int32_t draw, double* pend_fant, do
 
 // factor_pending (spx_ei_step): the factorisation is queued on the stream but not yet checked -- its not-PD flags travel
 // home with the winner, and ONE synchronisation ends the step
-// rhs: what the pass's S > 0 GEMM branch runs over when it is not the handle's fantasies (FANT, S = h->S):
-//   TS (spx_thompson)  the rhs.S right-hand sides per draw in h->ts_gammaS, k_ts_prior per chunk, k_ts_finish in place of the
-//                      acquisition, a per-path argmin in place of the mean and argmax
-//   KG (decided inside, from the handle's acquisition: no caller passes it)  gamma | Gamma_a of the A representer points in
-//                      h->kg_gammaS, S = A + 1; k(A, c) per work item and the two kg kernels in place of the acquisition
-struct PassRhs { enum Kind { FANT, TS, KG } kind = FANT; int S = 0; };
-static int ei_run_impl(spx_handle* h, int32_t flags, bool factor_pending, PassRhs rhs = PassRhs());
+// req: what a caller other than spx_ei_run / spx_ei_step asks of the pass (such a caller made every check of its own):
+//   rhs = EI_RHS_TS (spx_thompson)  the S right-hand sides per draw in h->ts_gammaS through the S > 0 GEMM branch, k_ts_prior per
+//                      chunk, k_ts_finish in place of the acquisition, a per-path argmin in place of the mean and argmax
+//   plain_ei (spx_main_effects)     the pass scored as SPX_ACQ_EI whatever the handle is set to; the setting is not touched
+// (SPX_ACQ_KG's columns gamma | Gamma_a in h->kg_gammaS are no request: plan_ei reads them off the acquisition, spx_plan.h)
+struct PassRequest { int rhs = EI_RHS_FANT; int S = 0; bool plain_ei = false; };
+static int ei_run_impl(spx_handle* h, int32_t flags, bool factor_pending, PassRequest req = PassRequest());
 static int ehvi_second(spx_handle* h);
 
 // what an EI pass refuses because of its flags alone (nmodels: 2 when a time model is / will be factored)
@@ -1081,15 +1081,31 @@ static const char* acq_name(int acq)
          : acq == SPX_ACQ_KG ? "KG" : "EI";
 }
 
-// what a pass under SPX_ACQ_KG refuses, decided from the host's record alone (who: the entry point's name)
-static int check_kg(const spx_handle* h, int32_t flags, const char* who)
+// What a pass refuses because of the acquisition it is scored with -- SPX_ACQ_EHVI's and SPX_ACQ_KG's own conditions -- decided
+// from the host's record alone (who: the entry point's name).  A step makes these before its factorisation.
+static int refuse_ei_flags(const char* who, int acq)
 {
-    if (h->acq != SPX_ACQ_KG) return SPX_OK;
-    if (flags & (SPX_FLAG_PER_SEC | SPX_FLAG_CONSTRAINED | SPX_FLAG_TIME_ONLY))
-        return fail(SPX_ERR_ARG, "%s: SPX_FLAG_PER_SEC / SPX_FLAG_CONSTRAINED / SPX_FLAG_TIME_ONLY are defined for "
-                                 "SPX_ACQ_EI only (spx_set_acquisition chose KG)", who);
+    return fail(SPX_ERR_ARG, "%s: SPX_FLAG_PER_SEC / SPX_FLAG_CONSTRAINED / SPX_FLAG_TIME_ONLY are defined for "
+                             "SPX_ACQ_EI only (spx_set_acquisition chose %s)", who, acq_name(acq));
+}
+
+static int check_acq(const spx_handle* h, int32_t flags, const char* who)
+{
+    const bool ehvi = h->acq == SPX_ACQ_EHVI, kg = h->acq == SPX_ACQ_KG;
+    if (!ehvi && !kg) return SPX_OK;
+    if (flags & (SPX_FLAG_PER_SEC | SPX_FLAG_CONSTRAINED | SPX_FLAG_TIME_ONLY)) return refuse_ei_flags(who, h->acq);
     if (h->comm || h->part_ph > 1 || h->part_M > 0)
-        return fail(SPX_ERR_ARG, "%s: SPX_ACQ_KG is single-device only (communicator attached or 2-D partition set)", who);
+        return fail(SPX_ERR_ARG, "%s: SPX_ACQ_%s is single-device only (communicator attached or 2-D partition set)", who,
+                    acq_name(h->acq));
+    if (ehvi) {
+        if (!h->held.has(Held::TIME))
+            return fail(SPX_ERR_ARG, "%s: SPX_ACQ_EHVI needs the second objective's GP (spx_set_time_model)", who);
+        if (!h->held.has(Held::FRONT))
+            return fail(SPX_ERR_ARG, "%s: SPX_ACQ_EHVI needs a front (spx_set_pareto_front)", who);
+        if (h->S > 0)
+            return fail(SPX_ERR_ARG, "%s: SPX_ACQ_EHVI is not defined over fantasies (clear them first)", who);
+        return SPX_OK;
+    }
     if (!h->held.has(Held::KGPTS))
         return fail(SPX_ERR_ARG, "%s: SPX_ACQ_KG needs representer points (spx_set_kg_points)", who);
     // (points set while option "kg_scan" was on)
@@ -1103,80 +1119,52 @@ static int check_kg(const spx_handle* h, int32_t flags, const char* who)
                                  "to %d", who, h->kg_A, SPX_KG_MAX_POINTS);
     if (h->S > 0 && !h->opt.kg_fantasies)
         return fail(SPX_ERR_ARG, "%s: SPX_ACQ_KG is not defined over fantasies (clear them, or score the call with SPX_ACQ_EI)", who);
-    if (h->S > 0) {   // over the fantasies (option "kg_fantasies"): the GEMM branch's width and the resident tables
-        if (h->S + h->kg_A > 4096)
-            return fail(SPX_ERR_ARG, "%s: S + A = %d + %d right-hand sides per draw (SPX_ACQ_KG over fantasies allows up to 4096)", who,
-                        h->S, h->kg_A);
-        if (h->held.has(Held::CAND) && h->held.has(Held::HYP)) {
-            const double Mp = (double)round_up(h->M, SPX_BN);
-            // (with the moments kept KG_ds has a table of its own beside the intercepts: twice the bytes)
-            const int tabs = (flags & SPX_FLAG_KEEP_MOMENTS) ? 2 : 1;
-            const int ord = wide ? 10 : 9;                    // a slope and an index of 16 or 8 bits per line
-            const double mu_bytes = (double)tabs * h->H * h->S * Mp * 8.0, ord_bytes = (double)h->H * (h->kg_A + 1) * Mp * ord;
-            if (mu_bytes > (double)SPX_KG_MAX_LINE_BYTES)
-                return fail(SPX_ERR_ARG, "%s: H S Mp 8 = %d x %d x %.0f x 8 = %.0f bytes of means per (draw, fantasy)%s (SPX_ACQ_KG over "
-                                         "fantasies allows up to %lld bytes)", who, h->H, h->S, Mp, mu_bytes / tabs,
-                            tabs == 2 ? ", twice with SPX_FLAG_KEEP_MOMENTS" : "", (long long)SPX_KG_MAX_LINE_BYTES);
-            if (ord_bytes > (double)SPX_KG_MAX_LINE_BYTES)
-                return fail(SPX_ERR_ARG, "%s: H (A + 1) Mp %d = %d x %d x %.0f x %d = %.0f bytes of ordered slopes (SPX_ACQ_KG over "
-                                         "fantasies allows up to %lld bytes)", who, ord, h->H, h->kg_A + 1, Mp, ord, ord_bytes,
-                            (long long)SPX_KG_MAX_LINE_BYTES);
-        }
-    }
-    if ((flags & SPX_FLAG_KEEP_MOMENTS) && h->held.has(Held::CAND) && h->held.has(Held::HYP)
-        && (double)h->H * h->kg_A * (double)round_up(h->M, SPX_BN) * 8.0 > (double)SPX_KG_MAX_LINE_BYTES)
+    if (h->S > 0 && h->S + h->kg_A > 4096)   // over the fantasies (option "kg_fantasies"): the GEMM branch's width
+        return fail(SPX_ERR_ARG, "%s: S + A = %d + %d right-hand sides per draw (SPX_ACQ_KG over fantasies allows up to 4096)", who,
+                    h->S, h->kg_A);
+    if (!(h->held.has(Held::CAND) && h->held.has(Held::HYP))) return SPX_OK;
+    // ... and the resident tables (acq_tables, spx_plan.h: what plan_ei will size them)
+    const AcqTables t = acq_tables(h->H, h->S, h->kg_A, h->M, (flags & SPX_FLAG_KEEP_MOMENTS) != 0, wide, h->opt.mes_grid);
+    const long long Mp = (long long)round_up(h->M, SPX_BN), lim = (long long)SPX_KG_MAX_LINE_BYTES;
+    if (h->S > 0 && (double)t.mu_tabs * (double)t.mu > (double)lim)
+        return fail(SPX_ERR_ARG, "%s: H S Mp 8 = %d x %d x %.0f x 8 = %.0f bytes of means per (draw, fantasy)%s (SPX_ACQ_KG over "
+                                 "fantasies allows up to %lld bytes)", who, h->H, h->S, (double)Mp, (double)t.mu,
+                    t.mu_tabs == 2 ? ", twice with SPX_FLAG_KEEP_MOMENTS" : "", lim);
+    if (h->S > 0 && (double)(t.slopes + t.perm) > (double)lim)
+        return fail(SPX_ERR_ARG, "%s: H (A + 1) Mp %d = %d x %d x %.0f x %d = %.0f bytes of ordered slopes (SPX_ACQ_KG over "
+                                 "fantasies allows up to %lld bytes)", who, t.ord_width, h->H, h->kg_A + 1, (double)Mp, t.ord_width,
+                    (double)(t.slopes + t.perm), lim);
+    if ((flags & SPX_FLAG_KEEP_MOMENTS) && (double)t.cov > (double)lim)
         return fail(SPX_ERR_ARG, "%s: H A Mp 8 = %d x %d x %lld x 8 bytes of kept covariances (SPX_FLAG_KEEP_MOMENTS under SPX_ACQ_KG "
-                                 "allows up to %lld bytes)", who, h->H, h->kg_A, (long long)round_up(h->M, SPX_BN),
-                    (long long)SPX_KG_MAX_LINE_BYTES);
+                                 "allows up to %lld bytes)", who, h->H, h->kg_A, Mp, lim);
     return SPX_OK;
 }
 
-// what a pass under SPX_ACQ_EHVI refuses, decided from the host's record alone (who: the entry point's name)
-static int check_ehvi(const spx_handle* h, int32_t flags, const char* who)
+// Everything a pass refuses before anything is reserved or queued: check_acq under `who`, then what the flags, the handle's
+// attachments and the sizes rule out -- these name spx_ei_run whoever asks (nmodels: 2 when a time model is / will be factored)
+static int check_pass(const spx_handle* h, int32_t flags, const char* who, int nmodels)
 {
-    if (h->acq != SPX_ACQ_EHVI) return SPX_OK;
-    if (flags & (SPX_FLAG_PER_SEC | SPX_FLAG_CONSTRAINED | SPX_FLAG_TIME_ONLY))
-        return fail(SPX_ERR_ARG, "%s: SPX_FLAG_PER_SEC / SPX_FLAG_CONSTRAINED / SPX_FLAG_TIME_ONLY are defined for "
-                                 "SPX_ACQ_EI only (spx_set_acquisition chose EHVI)", who);
-    if (h->comm || h->part_ph > 1 || h->part_M > 0)
-        return fail(SPX_ERR_ARG, "%s: SPX_ACQ_EHVI is single-device only (communicator attached or 2-D partition set)", who);
-    if (!h->held.has(Held::TIME))
-        return fail(SPX_ERR_ARG, "%s: SPX_ACQ_EHVI needs the second objective's GP (spx_set_time_model)", who);
-    if (!h->held.has(Held::FRONT))
-        return fail(SPX_ERR_ARG, "%s: SPX_ACQ_EHVI needs a front (spx_set_pareto_front)", who);
-    if (h->S > 0)
-        return fail(SPX_ERR_ARG, "%s: SPX_ACQ_EHVI is not defined over fantasies (clear them first)", who);
-    return SPX_OK;
-}
-
-static int check_run_flags(const spx_handle* h, int32_t flags, int nmodels)
-{
-    int rc_ehvi = check_ehvi(h, flags, "spx_ei_run");
-    if (rc_ehvi) return rc_ehvi;
-    if ((rc_ehvi = check_kg(h, flags, "spx_ei_run"))) return rc_ehvi;
+    int rc = check_acq(h, flags, who);
+    if (rc) return rc;
     const bool per_sec = (flags & SPX_FLAG_PER_SEC) != 0;
     const bool keep_mom = (flags & SPX_FLAG_KEEP_MOMENTS) != 0;
     const bool time_only = (flags & SPX_FLAG_TIME_ONLY) != 0;
     if (h->acq != SPX_ACQ_EI && (flags & (SPX_FLAG_PER_SEC | SPX_FLAG_CONSTRAINED | SPX_FLAG_TIME_ONLY)))
-        return fail(SPX_ERR_ARG, "spx_ei_run: SPX_FLAG_PER_SEC / SPX_FLAG_CONSTRAINED / SPX_FLAG_TIME_ONLY are defined for "
-                                 "SPX_ACQ_EI only (spx_set_acquisition chose %s)",
-                    acq_name(h->acq));
+        return refuse_ei_flags("spx_ei_run", h->acq);
     // (a communicator or a partition attached after spx_set_acquisition accepted MES)
     if (h->acq == SPX_ACQ_MES && (h->comm || h->part_ph > 1 || h->part_M > 0))
         return fail(SPX_ERR_ARG, "spx_ei_run: SPX_ACQ_MES is single-device only: y* of a draw needs every shard's moments "
                                  "(communicator attached or 2-D partition set)");
     // MES over fantasies (option "mes_fantasies"): the resident means and the partial sums, from the host's record alone
     if (h->acq == SPX_ACQ_MES && h->S > 0 && h->opt.mes_fantasies && h->held.has(Held::CAND) && h->held.has(Held::HYP)) {
-        const double rec = (double)h->H * h->S;
-        const double mu_bytes = rec * (double)round_up(h->M, SPX_BN) * 8.0;
-        const double part_bytes = rec * mes_fant_sum_blocks(h->M) * (double)h->opt.mes_grid * 8.0;
-        if (mu_bytes > (double)SPX_KG_MAX_LINE_BYTES)
+        const AcqTables t = acq_tables(h->H, h->S, 0, h->M, keep_mom, false, h->opt.mes_grid);
+        if ((double)t.mu > (double)SPX_KG_MAX_LINE_BYTES)
             return fail(SPX_ERR_ARG, "spx_ei_run: H S Mp 8 = %d x %d x %lld x 8 = %.0f bytes of means per (draw, fantasy) (SPX_ACQ_MES "
-                                     "over fantasies allows up to %lld bytes)", h->H, h->S, (long long)round_up(h->M, SPX_BN), mu_bytes,
+                                     "over fantasies allows up to %lld bytes)", h->H, h->S, (long long)round_up(h->M, SPX_BN), (double)t.mu,
                         (long long)SPX_KG_MAX_LINE_BYTES);
-        if (part_bytes > (double)SPX_KG_MAX_LINE_BYTES)
+        if ((double)t.mes_part > (double)SPX_KG_MAX_LINE_BYTES)
             return fail(SPX_ERR_ARG, "spx_ei_run: H S ceil(M / 512) J 8 = %.0f bytes of partial log-survival sums (SPX_ACQ_MES over "
-                                     "fantasies allows up to %lld bytes; a smaller mes_grid or fewer fantasies)", part_bytes,
+                                     "fantasies allows up to %lld bytes; a smaller mes_grid or fewer fantasies)", (double)t.mes_part,
                         (long long)SPX_KG_MAX_LINE_BYTES);
     }
     if (time_only && !(per_sec && keep_mom))
@@ -1218,17 +1206,14 @@ int spx_ei_step(spx_handle* h, int32_t flags)
         int rc = spx_multi_factor(h->multi);
         return rc ? rc : spx_multi_ei_run(h->multi, flags & ~SPX_FLAG_TIME_ONLY);
     }
-    {   // EHVI's refusals come before the factorisation in either form below (which would drop the fantasies it refuses)
-        int rc = check_ehvi(h, flags, "spx_ei_step");
-        if (rc) return rc;
-        if ((rc = check_kg(h, flags, "spx_ei_step"))) return rc;   // (likewise)
-    }
+    // The pass's refusals BEFORE anything is queued (ei_run_impl makes them for spx_ei_run).  EHVI's and KG's come before the
+    // factorisation in either form below (which would drop the fantasies they refuse).
     if (h->opt.timing || (flags & SPX_FLAG_TIMING) || !h->held.has(Held::CAND)) {   // stage timers bracket each call: keep the two-call form
-        int rc = spx_factor(h);
+        int rc = check_acq(h, flags, "spx_ei_step");
+        if (!rc) rc = spx_factor(h);
         return rc ? rc : ei_run_impl(h, flags, false);
     }
-    // the pass's argument checks BEFORE anything is queued (ei_run_impl repeats them for spx_ei_run)
-    int rc = check_run_flags(h, flags, h->held.has(Held::TIME) ? 2 : 1);
+    int rc = check_pass(h, flags, "spx_ei_step", h->held.has(Held::TIME) ? 2 : 1);
     if (rc) return rc;
     if ((rc = factor_constraint(h))) return rc;
     // EHVI: the second GP's factorisation and pass run to their end first, as the constraint model's factorisation does -- one
@@ -1259,10 +1244,10 @@ int spx_ei_step(spx_handle* h, int32_t flags)
 }
 
 // everything an EI pass writes on the device, reserved as its plan says before anything is queued
-static int ei_reserve(spx_handle* h, const EiPlan& p, int S)
+static int ei_reserve(spx_handle* h, const EiPlan& p)
 {
     int rc;
-    const bool fant = S > 0, con_gp = p.constrained && h->con_n > 0;
+    const bool fant = p.rhs_S > 0, con_gp = p.constrained && h->con_n > 0;
     if (p.ns == 3 && (rc = ensure_stream3(h))) return rc;   // (a time-only pass too: it stages nothing, but produces there)
     // the staging slots: K(X*,X) of a work item and, with fantasies, its partial means; the buffers of slots that the pass
     // does not use go back to the device first
@@ -1299,7 +1284,20 @@ static int ei_reserve(spx_handle* h, const EiPlan& p, int S)
     if ((rc = h->am_val.reserve((size_t)nab * 8))) return rc;
     if ((rc = h->am_idx.reserve((size_t)nab * 8))) return rc;
     if ((rc = h->am_out_val.reserve(8))) return rc;
-    return h->am_out_idx.reserve(8);
+    if ((rc = h->am_out_idx.reserve(8))) return rc;
+    // the acquisition's tables (0 bytes: the pass does not use the buffer)
+    const struct { DevBuf& buf; size_t bytes; } acq_bufs[] = {
+        {h->kg_As, p.kg_As_bytes}, {h->kg_sA, p.kg_sA_bytes}, {h->kg_kxa, p.kg_kxa_bytes}, {h->kg_gammaS, p.kg_gammaS_bytes},
+        {h->kg_mua, p.kg_mua_bytes}, {h->kg_Kac, p.kg_Kac_bytes}, {h->kg_muc, p.kg_muc_bytes}, {h->kg_cov, p.kg_cov_bytes},
+        {h->kgs_bsort, p.kgs_bsort_bytes}, {h->kgs_perm, p.kgs_perm_bytes}, {h->kgf_muc, p.kgf_muc_bytes},
+        {h->kgf_mua, p.kgf_mua_bytes}, {h->kgf_v, p.kgf_v_bytes}, {h->kgf_bsort, p.kgf_bsort_bytes}, {h->kgf_perm, p.kgf_perm_bytes},
+        {h->kgw_badcol, p.kgw_badcol_bytes}, {h->kgf_val, p.kgf_val_bytes}, {h->mes_bpart, p.mes_bpart_bytes},
+        {h->mes_part, p.mes_part_bytes}, {h->mes_G, p.mes_G_bytes}, {h->mes_ystar, p.mes_ystar_bytes}, {h->mes_fit, p.mes_fit_bytes},
+        {h->mesf_mu, p.mesf_mu_bytes}, {h->mesf_v, p.mesf_v_bytes}, {h->mesf_bpart, p.mesf_bpart_bytes},
+        {h->mesf_bnd, p.mesf_bnd_bytes}};
+    for (auto& b : acq_bufs)
+        if (b.bytes && (rc = b.buf.reserve(b.bytes))) return rc;
+    return SPX_OK;
 }
 
 // The second GP of an EHVI pass (spx.h): an internal handle on the same device holds (comp, second values, second hypers) and
@@ -1356,132 +1354,182 @@ static int ehvi_second(spx_handle* h)
     return rc;
 }
 
-static int ei_run_impl(spx_handle* h, int32_t flags, bool factor_pending, PassRhs rhs)
+// a share of the device's free memory plus what the handle already holds of it, within [lo, hi]; hi when the device does not say
+static int64_t budget_share(int64_t lo, int64_t hi, int div, int64_t held)
+{
+    size_t mem_free = 0, mem_total = 0;
+    if (hipMemGetInfo(&mem_free, &mem_total) != hipSuccess) { (void)hipGetLastError(); return hi; }
+    return std::max<int64_t>(lo, std::min<int64_t>(hi, (int64_t)(mem_free / div) + held));
+}
+
+// SPX_ACQ_KG, once per pass on the consumer stream (in a step: behind the factorisation queued there): the points scaled per
+// draw; k(A, X) with the points as the rows and the observations -- the factorisation's pre-doubled rows -- as the columns of
+// the library's own cross-covariance launch, [H][Ap][Np]; Gamma_a = W k(X, a), no mean subtracted, behind the kgS columns in
+// front of it (gamma, or over fantasies the held columns of every draw); mu_a
+static int kg_prologue(spx_handle* h, const EiPlan& p, hipStream_t G)
+{
+    const int H = h->H, D = h->D, Dp = p.Dp, Np = h->Np, hs = 3 + D, S = p.rhs_S, kgS = p.kgS, kgA = p.kgA, kgAp = p.kgAp;
+    const size_t nn = (size_t)Np * Np;
+    TIMED_S(ST_SCALE, G, launch_scale_rows(G, h->kg_pts.d(), kgA, kgAp, D, Dp, h->hyp.d() + 3, hs, H, 1.0, h->kg_As.d(), h->kg_sA.d()));
+    TIMED_S(ST_COV_CROSS, G, launch_cov_cross(G, h->kg_As.d(), h->kg_sA.d(), h->X2s.d(), h->s1.d(), h->htab.d(), h->kg_kxa.d(), kgA,
+                                              kgAp, Np, Dp, H, dev_kind(h)));
+    HIPCHK(hipMemcpy2DAsync(h->kg_gammaS.d(), (size_t)S * Np * 8, p.kg_fant() ? h->gammaS.d() : h->gamma.d(), (size_t)kgS * Np * 8,
+                            (size_t)kgS * Np * 8, (size_t)H, hipMemcpyDeviceToDevice, G));
+    for (int d = 0; d < H; ++d)
+        TIMED_S(ST_GAMMA_ALPHA, G, launch_gamma_cols(G, h->WT.d() + (size_t)d * nn, h->kg_kxa.d() + (size_t)d * kgAp * Np, (size_t)Np,
+                                                     h->kg_gammaS.d() + ((size_t)d * S + kgS) * Np, (int)h->N, Np, kgA));
+    if (p.kg_fant()) TIMED_S(ST_KG, G, launch_kgf_mu(G, h->kg_gammaS.d(), h->htab.d(), Np, kgS, kgA, H, h->kgf_mua.d()));
+    else TIMED_S(ST_KG, G, launch_kg_mu(G, h->kg_gammaS.d(), h->htab.d(), Np, S, H, h->kg_mua.d()));
+    return SPX_OK;
+}
+
+// one work item of the GEMM path: draws h0 .. h0 + nhb of the mc candidates from c0 on
+struct EiItem {
+    int h0, nhb, mc;
+    int64_t c0;
+    const double *Cs, *s2;      // the chunk's scaled candidates and norms, all draws
+    const double *tm, *cp;      // its predicted durations / P(feasible), all draws (null: not asked for)
+    const double* bgS;          // the item's partial means per right-hand side (its staging slot's)
+};
+
+// what a work item of the S > 0 branch runs behind its predict GEMM, on the consumer stream (the plan's `finish`)
+static int ei_finish_item(spx_handle* h, const EiPlan& p, hipStream_t G, const EiItem& it)
+{
+    const int nrb = p.nrb, S = p.rhs_S, kgS = p.kgS, kgA = p.kgA, kgAp = p.kgAp, h0 = it.h0, nhb = it.nhb, mc = it.mc, Dp = p.Dp;
+    const int64_t c0 = it.c0, M = h->M, Mp = p.Mp;
+    const bool keep_mom = p.keep_mom;
+    const double* htab = h->htab.d() + (size_t)h0 * SPX_HT;
+    if (p.kg())   // k(A, c) of the work item (the points as rows: the pass's own K(X*,X) launch over A rows); then its lines, its values
+        TIMED_S(ST_COV_CROSS, G, launch_cov_cross(G, h->kg_As.d() + (size_t)h0 * kgAp * Dp, h->kg_sA.d() + (size_t)h0 * kgAp,
+                                                  it.Cs + (size_t)h0 * mc * Dp, it.s2 + (size_t)h0 * mc, htab, h->kg_Kac.d(), kgA, kgAp,
+                                                  mc, Dp, nhb, dev_kind(h)));
+    switch (p.finish) {
+    case EI_FIN_KGF_LINES16:   // as EI_FIN_KGF_LINES8, the order by the bitonic network with 16-bit indices
+        TIMED_S(ST_KG, G, launch_kgw_lines(G, h->part_ss.d(), it.bgS, htab, h->kg_Kac.d(), nrb, mc, nhb, kgS, kgA, kgAp, c0, M, Mp, h0,
+                                           h->scratch.d(), h->kgf_muc.d(), h->kgf_v.d(), keep_mom ? h->kg_cov.d() : nullptr,
+                                           h->kgf_bsort.d(), (unsigned short*)h->kgf_perm.p));
+        break;
+    case EI_FIN_KGF_LINES8:    // the intercepts, the slopes and their order; the scans run behind the last chunk
+        TIMED_S(ST_KG, G, launch_kgf_lines(G, h->part_ss.d(), it.bgS, htab, h->kg_Kac.d(), nrb, mc, nhb, kgS, kgA, kgAp, c0, M, Mp, h0,
+                                           h->scratch.d(), h->kgf_muc.d(), h->kgf_v.d(), keep_mom ? h->kg_cov.d() : nullptr,
+                                           h->kgf_bsort.d(), (unsigned char*)h->kgf_perm.p));
+        break;
+    case EI_FIN_KG_PAIRS:
+    case EI_FIN_KG_SCAN:
+        TIMED_S(ST_KG, G, {
+            launch_kg_lines(G, h->part_ss.d(), it.bgS, htab, h->kg_Kac.d(), nrb, mc, nhb, S, kgAp, c0, M, Mp, h0, h->scratch.d(),
+                            h->kg_muc.d(), keep_mom ? h->mom_m.d() : nullptr, keep_mom ? h->mom_v.d() : nullptr,
+                            keep_mom ? h->kg_cov.d() : nullptr);
+            if (p.finish == EI_FIN_KG_SCAN)
+                launch_kgs_value(G, h->scratch.d(), h->kg_muc.d(), h->kg_mua.d() + (size_t)h0 * kgA, mc, nhb, S, c0, M, Mp, h0,
+                                 h->kgs_bsort.d(), (unsigned short*)h->kgs_perm.p, h->ei_draw.d());
+            else
+                launch_kg_value(G, h->scratch.d(), h->kg_muc.d(), h->kg_mua.d() + (size_t)h0 * kgA, mc, nhb, S, c0, M, Mp, h0,
+                                h->ei_draw.d());
+        });
+        break;
+    case EI_FIN_TS:
+        TIMED_S(ST_TS_FINISH, G, launch_ts_finish(G, it.bgS, htab, h->ts_pcand.d(), nrb, mc, nhb, S, c0, M, Mp, h0, h->ts_path.d()));
+        break;
+    case EI_FIN_MES_FANT_MEANS:   // the means of the work item in place of its EI values: the stages behind the last chunk read them
+        TIMED_S(ST_MES, G, launch_mes_fant_means(G, h->part_ss.d(), it.bgS, htab, nrb, mc, nhb, S, c0, M, Mp, h0, h->mesf_mu.d(),
+                                                 h->mesf_v.d()));
+        break;
+    case EI_FIN_PER_FANTASY:
+        TIMED_S(ST_EI_FINALIZE, G, launch_ei_finalize_fant(G, h->part_ss.d(), it.bgS, htab, h->bests.d() + (size_t)h0 * S,
+                                                           it.tm ? it.tm + (size_t)h0 * mc : nullptr,
+                                                           it.cp ? it.cp + (size_t)h0 * mc : nullptr, h->ei_draw.d(), nrb, mc, nhb, S,
+                                                           c0, M, Mp, h0, h->scratch.d(), p.pass_acq, p.pass_par));
+        break;
+    default: break;               // EI_FIN_ALL_DRAWS: one finalize per chunk, behind its last item
+    }
+    return SPX_OK;
+}
+
+// what a pass leaves held beside its buffers, read off its plan
+static Held::Results pass_results(const EiPlan& p)
+{
+    Held::Results r;
+    r.time_only = p.time_only;       // (a time-only pass has no EI results: spx_get_best & co. refuse)
+    r.ts = p.rhs == EI_RHS_TS;       // (paths and priors, nothing else: every EI getter refuses)
+    r.moments = p.keep_mom && (p.rhs_S == 0 || (p.kg() && !p.kg_fant())) && !p.time_only;   // (KG: k_kg_lines wrote func_m / func_v from column 0)
+    r.kg = p.kg();
+    r.kg_lines = p.kg() && p.keep_mom;
+    r.kg_scan = p.kg_scan();
+    r.kg_fant = p.kg_fant();
+    r.tmean = p.keep_mom && p.per_sec;   // (with fantasies the pass keeps no func_m / func_v, but mom_t is written all the same)
+    r.con = p.constrained && p.keep_mom && !p.time_only;
+    r.ehvi = p.tail == EI_TAIL_EHVI;
+    r.mes = p.mes();
+    r.mes_fant = p.tail == EI_TAIL_MES_FANT;
+    return r;
+}
+
+// checks, shape, budgets, plan, reservations, timers, prologue, chunk loop, tail, closing launch, ONE synchronisation, results
+static int ei_run_impl(spx_handle* h, int32_t flags, bool factor_pending, PassRequest req)
 {
     if (!h->held.has(Held::FACTOR) && !factor_pending) return fail(SPX_ERR_ARG, "spx_ei_run: call spx_factor first");
     if (!h->held.has(Held::CAND)) return fail(SPX_ERR_ARG, "spx_ei_run: no candidates set");
-    const bool ts = rhs.kind == PassRhs::TS;       // (spx_thompson made every check of its own; the acquisition setting is not read)
-    int rc = ts ? (int)SPX_OK : check_run_flags(h, flags, h->nmodels);
+    const bool asked = req.rhs == EI_RHS_TS || req.plain_ei;     // (a caller with a request made every check of its own)
+    int rc = asked ? (int)SPX_OK : check_pass(h, flags, "spx_ei_run", h->nmodels);
     if (rc) return rc;
-    // Max-value entropy search: the ordinary pass as EI with the moments kept (the way spx_main_effects runs it; the handle's
-    // setting is not touched: the pass's kernels are handed pass_acq), then the MES stages on the same stream, which
-    // overwrite the per-draw values before the mean and the argmax -- still ONE synchronisation.
-    const bool mes = !ts && h->acq == SPX_ACQ_MES;
-    const bool mesf = mes && h->S > 0 && h->opt.mes_fantasies;     // ... over the fantasies: the S > 0 branch, mes_fant_kernels.hip
-    if (mes && h->S > 0 && !mesf)
+    EiShape sh;
+    sh.acq = asked ? SPX_ACQ_EI : h->acq;
+    sh.acq_par = asked ? 0.0 : h->acq_par;
+    // (not part of check_pass: a step makes that before its factorisation, which drops the fantasies -- and then runs MES without them)
+    if (sh.acq == SPX_ACQ_MES && h->S > 0 && !h->opt.mes_fantasies)
         return fail(SPX_ERR_ARG, "spx_ei_run: SPX_ACQ_MES is not defined over fantasies (clear them, or score the call with "
                                  "SPX_ACQ_EI)");
-    // Expected hypervolume improvement: the same shape -- the pass as EI with the moments kept, k_ehvi behind it on the same
-    // stream -- after the second GP's pass over the same candidates (ehvi_second, below)
-    const bool ehvi = !ts && h->acq == SPX_ACQ_EHVI;
-    if ((mes && !mesf) || ehvi) flags |= SPX_FLAG_KEEP_MOMENTS;
-    // Knowledge gradient: the S > 0 branch over gamma | Gamma_a (column 0 gives func_m, the others q(c, a)), the lines and the
-    // values per work item in place of the acquisition; then the mean and the argmax of every pass (check_kg passed above)
-    const bool kg = !ts && h->acq == SPX_ACQ_KG;
-    // ... over the fantasies (option "kg_fantasies"; check_kg passed): the fantasies' Gamma in place of column 0, kg_fant_kernels.hip
-    const bool kgf = kg && h->S > 0;
-    const bool kgw = kgf && h->opt.kg_fantasies == 2;   // ... in the wide form: 16-bit indices, A up to 1023, kg_fant_scan_kernels.hip
-    const bool kgs = kg && !kgf && h->opt.kg_scan;  // ... its lines valued by slope order and one scan (option "kg_scan"), kg_scan_kernels.hip
-    const int kgS = kgf ? h->S : 1;                 // columns in front of Gamma_a
-    if (kg) rhs = PassRhs{PassRhs::KG, kgS + h->kg_A};
-    const int pass_acq = (mes || ehvi || kg) ? SPX_ACQ_EI : h->acq;
-    const double pass_par = (mes || ehvi || kg) ? 0.0 : h->acq_par;
     if ((rc = ensure_init(h))) return rc;
     if ((flags & SPX_FLAG_CONSTRAINED) && h->con_n > 0 && !h->held.has(Held::CON_FACTOR))
         return fail(SPX_ERR_ARG, "spx_ei_run: the constraint model is not factored (spx_factor after spx_set_constraint_model)");
     spx_drop(h, Held::RESULTS);     // the pass overwrites them; a failed one keeps the factor and the fantasies
-    if (ehvi && !factor_pending && (rc = ehvi_second(h))) return rc;     // (a pending step ran it before its own factorisation)
-    EiShape sh;
-    sh.N = h->N; sh.M = h->M; sh.Np = h->Np; sh.D = h->D; sh.H = h->H; sh.S = (ts || kg) ? rhs.S : h->S; sh.nmodels = h->nmodels;
+    // Expected hypervolume improvement: the second GP's pass over the same candidates first (a pending step ran it before its
+    // own factorisation)
+    if (sh.acq == SPX_ACQ_EHVI && !factor_pending && (rc = ehvi_second(h))) return rc;
+    sh.N = h->N; sh.M = h->M; sh.Np = h->Np; sh.D = h->D; sh.H = h->H; sh.S = h->S; sh.nmodels = h->nmodels;
+    sh.mesK = sh.acq == SPX_ACQ_MES ? (int)h->acq_par : 0;
+    sh.rhs = req.rhs; sh.ts_S = req.S; sh.A = sh.acq == SPX_ACQ_KG ? h->kg_A : 0;
     sh.flags = flags; sh.factor_pending = factor_pending; sh.kst_budget = h->opt.kst_budget;
     // The byte budgets of the plan are shares of what the device has free (a smaller or fuller GPU takes smaller chunks
-    // instead of an allocation failure).  They are queried when the number of fantasies / the size of a ring slot changes, not
-    // per pass: the plan -- buffer sizes, launch counts -- then stays what it was from pass to pass and across ranks that
-    // share a device.  Fantasies: an eighth of free memory, at most 2 GB.
-    // (spx_thompson's paths keep a budget of their own: the one cached for the fantasies, and with it the chunking of a later
-    // fantasy pass, is what it is on a handle that never drew a path)
-    int64_t& fant_budget = ts ? h->ts_fant_budget : kg ? h->kg_fant_budget : h->fant_budget;
-    int& fant_budget_S = ts ? h->ts_fant_budget_S : kg ? h->kg_fant_budget_S : h->fant_budget_S;
-    if (sh.S > 0 && fant_budget_S != sh.S) {
-        size_t mem_free = 0, mem_total = 0;
-        int64_t b = 2048ll << 20;
-        if (hipMemGetInfo(&mem_free, &mem_total) == hipSuccess) {
-            size_t held = h->scratch.cap;
-            for (auto& sl : h->ring) held += sl.part_bgS.cap;
-            b = std::max<int64_t>(64ll << 20, std::min<int64_t>(b, (int64_t)(mem_free / 8) + (int64_t)held / 2));
-        } else (void)hipGetLastError();
-        fant_budget = b;
-        fant_budget_S = sh.S;
+    // instead of an allocation failure).  They are queried when the number of right-hand sides / the size of a ring slot
+    // changes, not per pass: the plan -- buffer sizes, launch counts -- then stays what it was from pass to pass and across
+    // ranks that share a device.  Right-hand sides: an eighth of free memory, 64 MB to 2 GB, a budget per kind of
+    // them (spx_thompson's paths and KG's columns keep their own: the one cached for the fantasies, and with it the chunking
+    // of a later fantasy pass, is what it is on a handle that never drew a path).
+    const EiRhs rhs = ei_rhs(sh);
+    spx_handle::RhsBudget& fb = h->fant_budget[rhs.kind];
+    if (rhs.S > 0 && fb.S != rhs.S) {
+        size_t held = h->scratch.cap;
+        for (auto& sl : h->ring) held += sl.part_bgS.cap;
+        fb.bytes = budget_share(64ll << 20, 2048ll << 20, 8, (int64_t)held / 2);
+        fb.S = rhs.S;
     }
-    sh.fant_budget = fant_budget;
+    sh.fant_budget = fb.bytes;
     sh.ring_budget = h->ring_budget;
     EiPlan& p = h->ei_plan;
     p = plan_ei(h->opt, sh);                  // every decision of this pass (spx_plan.h); below: reserve and launch
     // The ring: a sixteenth of free memory, at most 10 GiB.  Its slot size comes out of the plan, so a new size means a new
     // budget and the plan again.
     if (p.ringed && h->ring_budget_slot != p.slot_bytes) {
-        size_t mem_free = 0, mem_total = 0;
-        int64_t b = 10ll << 30;
-        if (hipMemGetInfo(&mem_free, &mem_total) == hipSuccess) {
-            int64_t held = 0;
-            for (auto& sl : h->ring) held += (int64_t)(sl.Kst.cap + sl.part_bgS.cap);
-            b = std::min<int64_t>(b, (int64_t)(mem_free / 16) + held);
-        } else (void)hipGetLastError();
-        h->ring_budget = b;
+        int64_t held = 0;
+        for (auto& sl : h->ring) held += (int64_t)(sl.Kst.cap + sl.part_bgS.cap);
+        h->ring_budget = budget_share(0, 10ll << 30, 16, held);
         h->ring_budget_slot = p.slot_bytes;
-        sh.ring_budget = b;
+        sh.ring_budget = h->ring_budget;
         p = plan_ei(h->opt, sh);
     }
     const bool per_sec = p.per_sec, keep_mom = p.keep_mom, time_only = p.time_only, constrained = p.constrained, fused = p.fused;
-    const int H = h->H, D = h->D, Dp = p.Dp, Np = h->Np, hs = 3 + D, nrb = p.nrb, Hb = p.Hb, S = sh.S, ns = p.ns;
+    const int H = h->H, D = h->D, Dp = p.Dp, Np = h->Np, hs = 3 + D, nrb = p.nrb, Hb = p.Hb, S = p.rhs_S, ns = p.ns;
     const int64_t N = h->N, M = h->M, Mp = p.Mp, Mc = p.Mc;
-    if ((rc = ei_reserve(h, p, S))) return rc;
-    const int kgA = kg ? h->kg_A : 0, kgAp = (int)round_up(kgA, SPX_PADN);     // (rows of a K(A, .) launch: padded as N is)
-    if (kg) {
-        if ((rc = h->kg_As.reserve((size_t)H * kgAp * Dp * 8))) return rc;
-        if ((rc = h->kg_sA.reserve((size_t)H * kgAp * 8))) return rc;
-        if ((rc = h->kg_kxa.reserve((size_t)H * kgAp * Np * 8))) return rc;
-        if ((rc = h->kg_gammaS.reserve((size_t)H * S * Np * 8))) return rc;
-        if ((rc = h->kg_mua.reserve((size_t)H * kgA * 8))) return rc;
-        if ((rc = h->kg_Kac.reserve((size_t)Hb * kgAp * Mc * 8))) return rc;
-        if ((rc = h->kg_muc.reserve((size_t)Hb * Mc * 8))) return rc;
-        if (keep_mom && (rc = h->kg_cov.reserve((size_t)H * kgA * Mp * 8))) return rc;
-    }
-    if (kgs) {
-        if ((rc = h->kgs_bsort.reserve((size_t)Hb * S * Mc * 8))) return rc;
-        if ((rc = h->kgs_perm.reserve((size_t)Hb * S * Mc * 2))) return rc;
-    }
-    if (kgf) {
-        if ((rc = h->kgf_muc.reserve((size_t)H * kgS * Mp * 8))) return rc;
-        if ((rc = h->kgf_mua.reserve((size_t)H * kgA * kgS * 8))) return rc;
-        if ((rc = h->kgf_v.reserve((size_t)H * Mp * 8))) return rc;
-        if ((rc = h->kgf_bsort.reserve((size_t)H * (kgA + 1) * Mp * 8))) return rc;
-        if ((rc = h->kgf_perm.reserve((size_t)H * (kgA + 1) * Mp * (kgw ? 2 : 1)))) return rc;
-        if (kgw && (rc = h->kgw_badcol.reserve((size_t)H * kgS * sizeof(int)))) return rc;
-        if (keep_mom && (rc = h->kgf_val.reserve((size_t)H * kgS * Mp * 8))) return rc;   // (mu_c stays for its getter)
-    }
-    // (read AFTER the reservations above: a buffer that grows moves)
-    const double* gammaS_all = ts ? h->ts_gammaS.d() : kg ? h->kg_gammaS.d() : h->gammaS.d();
-    const int mesK = mes ? (int)h->acq_par : 0, mesJ = h->opt.mes_grid;
-    const size_t mes_rec = mesf ? (size_t)H * S : (size_t)H;      // fit records: per draw, or per (draw, fantasy)
-    if (mes) {
-        if (!mesf && (rc = h->mes_bpart.reserve((size_t)H * mes_bound_blocks(M) * 3 * 8))) return rc;
-        if ((rc = h->mes_part.reserve(mes_rec * (mesf ? mes_fant_sum_blocks(M) : mes_sum_blocks(M)) * mesJ * 8))) return rc;
-        if ((rc = h->mes_G.reserve(mes_rec * mesJ * 8))) return rc;
-        if ((rc = h->mes_ystar.reserve(mes_rec * mesK * 8))) return rc;
-        if ((rc = h->mes_fit.reserve(mes_rec * 8 * 8))) return rc;
-    }
-    if (mesf) {
-        if ((rc = h->mesf_mu.reserve(mes_rec * Mp * 8))) return rc;
-        if ((rc = h->mesf_v.reserve((size_t)H * Mp * 8))) return rc;
-        if ((rc = h->mesf_bpart.reserve(mes_rec * mes_fant_bound_blocks(M) * 3 * 8))) return rc;
-        if ((rc = h->mesf_bnd.reserve(mes_rec * 3 * 8))) return rc;
-    }
+    if ((rc = ei_reserve(h, p))) return rc;
+    // (read AFTER the reservations: a buffer that grows moves)
+    const double* gammaS_all = p.rhs == EI_RHS_TS ? h->ts_gammaS.d() : p.kg() ? h->kg_gammaS.d() : h->gammaS.d();
     h->corun_launches = 0;
 
     hipStream_t s = h->stream;
-    if (flags & SPX_FLAG_TIMING) h->opt.timing = true;
-    if (!ts) h->ev_used = 0;         // (spx_thompson's own stages in front of the pass are in the pool already)
+    if (p.flags & SPX_FLAG_TIMING) h->opt.timing = true;
+    if (p.rhs != EI_RHS_TS) h->ev_used = 0;      // (spx_thompson's own stages in front of the pass are in the pool already)
     hipEvent_t t0 = h->ev_t0, t1 = h->ev_t1;
     HIPCHK(hipEventRecord(t0, s));
     const int gemm_nlive = p.gemm_nlive;
@@ -1510,23 +1558,7 @@ static int ei_run_impl(spx_handle* h, int32_t flags, bool factor_pending, PassRh
     // factorisation's first kernel: ev_obs); a time model's predicted durations read alpha of the duration GP -- the END of
     // the factorisation (ev_fac).
     if (factor_pending && ns >= 2) HIPCHK(hipStreamWaitEvent(P, per_sec ? h->ev_fac : h->ev_obs, 0));
-    if (kg) {
-        // Once per pass, on the consumer stream (in a step: behind the factorisation queued there): the points scaled per draw;
-        // k(A, X) with the points as the rows and the observations -- the factorisation's pre-doubled rows -- as the columns of
-        // the library's own cross-covariance launch, [H][Ap][Np]; Gamma_a = W k(X, a), no mean subtracted, behind column 0 =
-        // the ordinary gamma; mu_a
-        TIMED_S(ST_SCALE, G, launch_scale_rows(G, h->kg_pts.d(), kgA, kgAp, D, Dp, ls, hs, H, 1.0, h->kg_As.d(), h->kg_sA.d()));
-        TIMED_S(ST_COV_CROSS, G, launch_cov_cross(G, h->kg_As.d(), h->kg_sA.d(), h->X2s.d(), h->s1.d(), h->htab.d(), h->kg_kxa.d(), kgA,
-                                                  kgAp, Np, Dp, H, dev_kind(h)));
-        // (over fantasies: the kgS held columns of every draw in place of gamma)
-        HIPCHK(hipMemcpy2DAsync(h->kg_gammaS.d(), (size_t)S * Np * 8, kgf ? h->gammaS.d() : h->gamma.d(), (size_t)kgS * Np * 8,
-                                (size_t)kgS * Np * 8, (size_t)H, hipMemcpyDeviceToDevice, G));
-        for (int d = 0; d < H; ++d)
-            TIMED_S(ST_GAMMA_ALPHA, G, launch_gamma_cols(G, h->WT.d() + (size_t)d * nn, h->kg_kxa.d() + (size_t)d * kgAp * Np, (size_t)Np,
-                                                         h->kg_gammaS.d() + ((size_t)d * S + kgS) * Np, (int)N, Np, kgA));
-        if (kgf) TIMED_S(ST_KG, G, launch_kgf_mu(G, h->kg_gammaS.d(), h->htab.d(), Np, kgS, kgA, H, h->kgf_mua.d()));
-        else TIMED_S(ST_KG, G, launch_kg_mu(G, h->kg_gammaS.d(), h->htab.d(), Np, S, H, h->kg_mua.d()));
-    }
+    if (p.kg() && (rc = kg_prologue(h, p, G))) return rc;
     int item = 0, chunk = 0;
     for (int64_t c0 = 0; c0 < Mp; c0 += Mc, ++chunk) {
         const int mc = (int)std::min<int64_t>(Mc, Mp - c0);       // multiple of 128
@@ -1574,7 +1606,7 @@ static int ei_run_impl(spx_handle* h, int32_t flags, bool factor_pending, PassRh
         // 2 * cand / ls and |cand / ls|^2 for every draw (one launch per chunk)
         hipStream_t Pc = (chunk == 0) ? P0 : P;       // (the first chunk's producer work of a step: beside the factorisation)
         TIMED_S(ST_SCALE, Pc, launch_scale_rows(Pc, xc, nreal, mc, D, Dp, ls, hs, H, 2.0, Cs, s2));
-        if (ts) {   // the prior of the chunk's rows under every draw and path, on the consumer stream in front of the finishes that read it
+        if (p.rhs == EI_RHS_TS) {   // the prior of the chunk's rows under every draw and path, on the consumer stream in front of the finishes that read it
             const double* par = h->ts_par.d();
             const size_t nnu = (size_t)H * h->ts_F * Dp;
             TIMED_S(ST_TS_PRIOR, G, launch_ts_prior(G, xc, nreal, D, Dp, par, par + nnu, h->ts_w.d(), h->ts_w_stride, par + nnu + h->ts_F,
@@ -1585,7 +1617,7 @@ static int ei_run_impl(spx_handle* h, int32_t flags, bool factor_pending, PassRh
             TIMED_S(ST_PREDICT_GEMM, G, launch_ei_fused128(G, dev_kind(h), h->WT.d(), h->gamma.d(), h->Xs.d(), h->s1.d(), Cs, s2,
                                                            h->htab.d(), tm, cp, h->best, h->ei_draw.d(), keep_mom ? h->mom_m.d() : nullptr,
                                                            keep_mom ? h->mom_v.d() : nullptr, (int)N, mc, Dp, H, c0, M, Mp, h->n_cu,
-                                                           pass_acq, pass_par));
+                                                           p.pass_acq, p.pass_par));
         for (int h0 = 0; h0 < (fused ? 0 : H); h0 += Hb, ++item) {
             const int nhb = std::min(Hb, H - h0);
             spx_handle::RingSlot& sl = h->ring[item % p.slots];
@@ -1599,59 +1631,20 @@ static int ei_run_impl(spx_handle* h, int32_t flags, bool factor_pending, PassRh
                                                       h->htab.d() + (size_t)h0 * SPX_HT, Kst_k, (int)N, Np, mc, Dp, nhb, dev_kind(h),
                                                       p.cov_live_rows, p.cov_flat, corun));
             if ((rc = hand_off(Pi, G, sl.ready))) return rc;
-            // with fantasies the launch's partial sums are consumed right away and sit at draws 0 .. nhb-1
+            // with right-hand sides of its own the launch's partial sums are consumed right away and sit at draws 0 .. nhb-1
             TIMED_S(ST_PREDICT_GEMM, G, launch_predict_gemm(G, h->opt.gemm_variant, h->WT.d() + (size_t)h0 * nn, Kst_k,
                                                             h->gamma.d() + (size_t)h0 * Np, h->part_ss.d(),
                                                             h->part_bg.d(), Np, mc, nhb, S > 0 ? nhb : H, S > 0 ? 0 : h0,
                                                             S > 0 ? gammaS_all + (size_t)h0 * S * Np : nullptr, S,
                                                             bgS_k, gemm_nlive));
-            if (kg) {   // k(A, c) of the work item (the points as rows: the pass's own K(X*,X) launch over A rows), its lines, its values
-                TIMED_S(ST_COV_CROSS, G, launch_cov_cross(G, h->kg_As.d() + (size_t)h0 * kgAp * Dp, h->kg_sA.d() + (size_t)h0 * kgAp,
-                                                          Cs + (size_t)h0 * mc * Dp, s2 + (size_t)h0 * mc,
-                                                          h->htab.d() + (size_t)h0 * SPX_HT, h->kg_Kac.d(), kgA, kgAp, mc, Dp, nhb,
-                                                          dev_kind(h)));
-                if (kgw)   // likewise, the order by the bitonic network with 16-bit indices
-                    TIMED_S(ST_KG, G, launch_kgw_lines(G, h->part_ss.d(), bgS_k, h->htab.d() + (size_t)h0 * SPX_HT, h->kg_Kac.d(), nrb, mc,
-                                                       nhb, kgS, kgA, kgAp, c0, M, Mp, h0, h->scratch.d(), h->kgf_muc.d(), h->kgf_v.d(),
-                                                       keep_mom ? h->kg_cov.d() : nullptr, h->kgf_bsort.d(),
-                                                       (unsigned short*)h->kgf_perm.p));
-                else if (kgf)   // the intercepts, the slopes and their order; the scans run behind the last chunk
-                    TIMED_S(ST_KG, G, launch_kgf_lines(G, h->part_ss.d(), bgS_k, h->htab.d() + (size_t)h0 * SPX_HT, h->kg_Kac.d(), nrb, mc,
-                                                       nhb, kgS, kgA, kgAp, c0, M, Mp, h0, h->scratch.d(), h->kgf_muc.d(), h->kgf_v.d(),
-                                                       keep_mom ? h->kg_cov.d() : nullptr, h->kgf_bsort.d(),
-                                                       (unsigned char*)h->kgf_perm.p));
-                else TIMED_S(ST_KG, G, {
-                    launch_kg_lines(G, h->part_ss.d(), bgS_k, h->htab.d() + (size_t)h0 * SPX_HT, h->kg_Kac.d(), nrb, mc, nhb, S, kgAp, c0, M,
-                                    Mp, h0, h->scratch.d(), h->kg_muc.d(), keep_mom ? h->mom_m.d() : nullptr,
-                                    keep_mom ? h->mom_v.d() : nullptr, keep_mom ? h->kg_cov.d() : nullptr);
-                    if (kgs)
-                        launch_kgs_value(G, h->scratch.d(), h->kg_muc.d(), h->kg_mua.d() + (size_t)h0 * kgA, mc, nhb, S, c0, M, Mp, h0,
-                                         h->kgs_bsort.d(), (unsigned short*)h->kgs_perm.p, h->ei_draw.d());
-                    else
-                        launch_kg_value(G, h->scratch.d(), h->kg_muc.d(), h->kg_mua.d() + (size_t)h0 * kgA, mc, nhb, S, c0, M, Mp, h0,
-                                        h->ei_draw.d());
-                });
-            } else if (ts)
-                TIMED_S(ST_TS_FINISH, G, launch_ts_finish(G, bgS_k, h->htab.d() + (size_t)h0 * SPX_HT, h->ts_pcand.d(), nrb, mc, nhb, S,
-                                                          c0, M, Mp, h0, h->ts_path.d()));
-            else if (mesf)    // the means of the work item in place of its EI values: the stages behind the last chunk read them
-                TIMED_S(ST_MES, G, launch_mes_fant_means(G, h->part_ss.d(), bgS_k, h->htab.d() + (size_t)h0 * SPX_HT, nrb, mc, nhb, S,
-                                                         c0, M, Mp, h0, h->mesf_mu.d(), h->mesf_v.d()));
-            else if (S > 0)
-                TIMED_S(ST_EI_FINALIZE, G, launch_ei_finalize_fant(G, h->part_ss.d(), bgS_k,
-                                                                   h->htab.d() + (size_t)h0 * SPX_HT,
-                                                                   h->bests.d() + (size_t)h0 * S,
-                                                                   per_sec ? tm + (size_t)h0 * mc : nullptr,
-                                                                   constrained ? cp + (size_t)h0 * mc : nullptr,
-                                                                   h->ei_draw.d(), nrb, mc, nhb, S, c0, M, Mp, h0,
-                                                                   h->scratch.d(), pass_acq, pass_par));
+            if ((rc = ei_finish_item(h, p, G, EiItem{h0, nhb, mc, c0, Cs, s2, tm, cp, bgS_k}))) return rc;
             if (P != G && (int64_t)item + p.slots < p.ring_items) HIPCHK(hipEventRecord(sl.consumed, G));   // (only where an item waits for it)
         }
-        if (S == 0 && !fused)   // every draw of the chunk in one launch
+        if (p.finish == EI_FIN_ALL_DRAWS)   // every draw of the chunk in one launch
             TIMED_S(ST_EI_FINALIZE, G, launch_ei_finalize(G, h->part_ss.d(), h->part_bg.d(), h->htab.d(), tm, cp, h->best,
                                                           h->ei_draw.d(), keep_mom ? h->mom_m.d() : nullptr,
-                                                          keep_mom ? h->mom_v.d() : nullptr, nrb, mc, H, c0, M, Mp, 0, pass_acq,
-                                                          pass_par));
+                                                          keep_mom ? h->mom_v.d() : nullptr, nrb, mc, H, c0, M, Mp, 0, p.pass_acq,
+                                                          p.pass_par));
         if (P != G) HIPCHK(hipEventRecord(cb.consumed, G));
     }
     // the duration / probability copies ran on P
@@ -1660,29 +1653,39 @@ static int ei_run_impl(spx_handle* h, int32_t flags, bool factor_pending, PassRh
     const int n_info = p.n_info;
     if ((rc = h->pin_res.reserve(16 + (size_t)n_info * sizeof(int)))) return rc;
     double* mirror = (double*)h->pin_res.p;
-    if (kgw)
+    // behind the last chunk on the main stream: the lines / the means of every (draw, fantasy, candidate), every draw's moments
+    // are complete
+    switch (p.tail) {
+    case EI_TAIL_KGW_VALUE:
         TIMED(ST_KG, launch_kgw_value(s, h->kgf_bsort.d(), (const unsigned short*)h->kgf_perm.p, h->kgf_mua.d(), h->kgf_muc.d(),
-                                      keep_mom ? h->kgf_val.d() : h->kgf_muc.d(), (int*)h->kgw_badcol.p, kgA + 1, kgS, H, M, Mp,
+                                      keep_mom ? h->kgf_val.d() : h->kgf_muc.d(), (int*)h->kgw_badcol.p, p.kgA + 1, p.kgS, H, M, Mp,
                                       h->ei_draw.d()));
-    else if (kgf)   // behind the last chunk on the main stream: the lines of every (draw, fantasy, candidate) are complete
+        break;
+    case EI_TAIL_KGF_VALUE:
         TIMED(ST_KG, launch_kgf_value(s, h->kgf_bsort.d(), (const unsigned char*)h->kgf_perm.p, h->kgf_mua.d(), h->kgf_muc.d(),
-                                      keep_mom ? h->kgf_val.d() : h->kgf_muc.d(), kgA + 1, kgS, H, M, Mp, h->ei_draw.d()));
-    if (mesf)  // behind the last chunk on the main stream: the means of every (draw, fantasy) are complete
-        TIMED(ST_MES, launch_mes_fant(s, h->mesf_mu.d(), h->mesf_v.d(), h->htab.d(), SPX_HT, h->bests.d(), M, Mp, H, S, mesJ, mesK,
+                                      keep_mom ? h->kgf_val.d() : h->kgf_muc.d(), p.kgA + 1, p.kgS, H, M, Mp, h->ei_draw.d()));
+        break;
+    case EI_TAIL_MES_FANT:
+        TIMED(ST_MES, launch_mes_fant(s, h->mesf_mu.d(), h->mesf_v.d(), h->htab.d(), SPX_HT, h->bests.d(), M, Mp, H, S, p.mesJ, p.mesK,
                                       h->mesf_bpart.d(), h->mesf_bnd.d(), h->mes_part.d(), h->mes_G.d(), h->mes_ystar.d(),
                                       h->mes_fit.d(), h->ei_draw.d()));
-    else if (mes)   // behind the last finalize on the main stream: every draw's moments are complete
-        TIMED(ST_MES, launch_mes(s, h->mom_m.d(), h->mom_v.d(), h->htab.d(), SPX_HT, h->best, M, Mp, H, mesJ, mesK, h->mes_bpart.d(),
+        break;
+    case EI_TAIL_MES:
+        TIMED(ST_MES, launch_mes(s, h->mom_m.d(), h->mom_v.d(), h->htab.d(), SPX_HT, h->best, M, Mp, H, p.mesJ, p.mesK, h->mes_bpart.d(),
                                  h->mes_part.d(), h->mes_G.d(), h->mes_ystar.d(), h->mes_fit.d(), h->ei_draw.d()));
-    if (ehvi) {   // likewise; the second GP's moments were complete (and synchronised) before this pass began
+        break;
+    case EI_TAIL_EHVI: {   // the second GP's moments were complete (and synchronised) before this pass began
         const spx_handle* c = h->sec;
         if (c->M != M || c->H != H || c->ei_plan.Mp != Mp)
             return fail(SPX_ERR_ARG, "internal error: the second GP's pass does not match the objective's (M, H, Mp)");
         const int nstrips = h->front_n + 1;
         TIMED(ST_EHVI, launch_ehvi(s, h->mom_m.d(), h->mom_v.d(), c->mom_m.d(), c->mom_v.d(), h->front_dev.d(),
                                    h->front_dev.d() + nstrips, nstrips, M, Mp, H, h->ei_draw.d()));
+        break;
     }
-    if (ts)
+    default: break;
+    }
+    if (p.closing == EI_CLOSE_TS_ARGMIN)
         TIMED(ST_TS_FINISH, launch_ts_argmin(s, h->ts_path.d(), M, Mp, H * S, h->ts_am_val.d(), (int64_t*)h->ts_am_idx.p,
                                              h->ts_out_val.d(), (int64_t*)h->ts_out_idx.p, h->index_base));
     else TIMED(ST_MEAN_ARGMAX, {
@@ -1692,7 +1695,7 @@ static int ei_run_impl(spx_handle* h, int32_t flags, bool factor_pending, PassRh
     HIPCHK(hipEventRecord(t1, s));
     HIPCHK(hipStreamSynchronize(s));
     LAUNCHCHK();
-    if (!ts) {
+    if (p.closing == EI_CLOSE_MEAN_ARGMAX) {
         h->best_val = mirror[0];
         h->best_idx = ((const int64_t*)mirror)[1];
     }
@@ -1706,21 +1709,9 @@ static int ei_run_impl(spx_handle* h, int32_t flags, bool factor_pending, PassRh
         ev_collect(h);
         h->st_ms[ST_EI_RUN_TOTAL] += ms; h->st_n[ST_EI_RUN_TOTAL] += 1;
     }
-    Held::Results r;
-    r.time_only = time_only;         // (a time-only pass has no EI results: spx_get_best & co. refuse)
-    r.ts = ts;                       // (paths and priors, nothing else: every EI getter refuses)
-    r.moments = keep_mom && (S == 0 || (kg && !kgf)) && !time_only;   // (KG: k_kg_lines wrote func_m / func_v from column 0)
-    r.kg = kg;
-    r.kg_lines = kg && keep_mom;
-    r.kg_scan = kgs || kgw;
-    r.kg_fant = kgf;
-    if (kg) { h->kg_last_A = kgA; h->kg_last_S = kgf ? kgS : 0; }
-    r.tmean = keep_mom && per_sec;   // (with fantasies the pass keeps no func_m / func_v, but mom_t is written all the same)
-    r.con = constrained && keep_mom && !time_only;
-    r.ehvi = ehvi;
-    r.mes = mes;
-    r.mes_fant = mesf;
-    if (mes) { h->mes_K = mesK; h->mes_J = mesJ; h->mes_S = mesf ? S : 0; }
+    Held::Results r = pass_results(p);
+    if (r.kg) { h->kg_last_A = p.kgA; h->kg_last_S = r.kg_fant ? p.kgS : 0; }
+    if (r.mes) { h->mes_K = p.mesK; h->mes_J = p.mesJ; h->mes_S = r.mes_fant ? S : 0; }
     if (h->comm && (rc = spx_comm_exchange(h, &r.global2d))) return rc;   // one process per GPU: the winner over all ranks
     return spx_hold(h, Held::RESULTS, r);
 }
@@ -2430,7 +2421,7 @@ int spx_constrained_ei_grad_batch(spx_handle* h, const double* points, int32_t P
 // Main effects of the posterior mean (spx.h).  The (D T + 1) Q structured rows are formed on the device (k_effects_rows) and
 // scored by the ordinary pass with the moments kept -- ei_run_impl, one call per plan_effects pass, so a row's func_m is the
 // bits spx_ei_run + spx_get_moments give for it -- and the kept means are reduced on the device (k_effects_mean).  The pass
-// runs as SPX_ACQ_EI whatever the handle is set to (the moments do not depend on it; the setting is put back), and its own
+// runs as SPX_ACQ_EI whatever the handle is set to (the moments do not depend on it; the setting is not touched: PassRequest::plain_ei), and its own
 // results (the winner, the EI values) are not kept: the call drops CAND, and with it RESULTS, before its first mutation and
 // leaves them dropped.
 int spx_main_effects(spx_handle* h, const double* base, int32_t Q, const double* levels, int32_t T, double* curves,
@@ -2469,9 +2460,6 @@ int spx_main_effects(spx_handle* h, const double* base, int32_t Q, const double*
     stage_begin(h);
     if ((rc = stage_h2d(h, d_base, base, (size_t)Q * D * 8, h->stream))) return rc;
     if ((rc = stage_h2d(h, d_levels, levels, (size_t)T * 8, h->stream))) return rc;
-    const int acq = h->acq;
-    const double acq_par = h->acq_par;
-    h->acq = SPX_ACQ_EI; h->acq_par = 0.0;
     h->index_base = 0;
     for (int64_t r0 = 0; r0 < p.rows && !rc; r0 += p.pass_rows) {
         const int64_t m = std::min<int64_t>(p.pass_rows, p.rows - r0);
@@ -2482,7 +2470,7 @@ int spx_main_effects(spx_handle* h, const double* base, int32_t Q, const double*
         if (e != hipSuccess) { rc = fail(SPX_ERR_HIP, "spx_main_effects: k_effects_rows failed: %s", hipGetErrorString(e)); break; }
         h->M = m;
         if ((rc = spx_hold(h, Held::CAND))) break;
-        if ((rc = ei_run_impl(h, SPX_FLAG_KEEP_MOMENTS, false))) break;
+        if ((rc = ei_run_impl(h, SPX_FLAG_KEEP_MOMENTS, false, PassRequest{EI_RHS_FANT, 0, true}))) break;
         if (p.gather) {
             const int64_t Mp = h->ei_plan.Mp;
             e = hipMemcpy2DAsync(h->eff_m.d() + r0, (size_t)p.rows * 8, h->mom_m.d(), (size_t)Mp * 8, (size_t)m * 8, (size_t)H,
@@ -2490,7 +2478,6 @@ int spx_main_effects(spx_handle* h, const double* base, int32_t Q, const double*
             if (e != hipSuccess) { (void)hipGetLastError(); rc = fail(SPX_ERR_HIP, "spx_main_effects: hipMemcpy2DAsync failed: %s", hipGetErrorString(e)); }
         }
     }
-    h->acq = acq; h->acq_par = acq_par;
     if (!rc) {
         launch_effects_mean(h->stream, p, p.gather ? h->eff_m.d() : h->mom_m.d(), p.gather ? p.rows : h->ei_plan.Mp, Q, H, d_curves,
                             d_bmean);
@@ -2643,7 +2630,7 @@ int spx_thompson(spx_handle* h, int32_t F, int32_t S, const double* omega_z, con
     for (int d = 0; d < H; ++d)      // Gamma_d = W_d (rhs_d - mean_d): what spx_set_fantasies does with its fantasy columns
         TIMED(ST_GAMMA_ALPHA, launch_gamma_multi(s, h->WT.d() + (size_t)d * Np * Np, h->ts_rhs.d() + (size_t)d * S * N,
                                                  h->htab.d() + (size_t)d * SPX_HT, h->ts_gammaS.d() + (size_t)d * S * Np, (int)N, Np, S));
-    if ((rc = ei_run_impl(h, 0, false, PassRhs{PassRhs::TS, S}))) {
+    if ((rc = ei_run_impl(h, 0, false, PassRequest{EI_RHS_TS, S}))) {
         (void)hipStreamSynchronize(h->stream);
         (void)hipStreamSynchronize(h->stream2);
         if (h->stream3) (void)hipStreamSynchronize(h->stream3);

@@ -20,3 +20,15 @@ static inline int padded_dim(int D)
     if (D <= 16) return 16;
     return (int)round_up(D, 32);
 }
+
+// Max-value entropy search: candidates per partial log-survival sum / per partial minimum of the plain pass (mes_kernels.hip)
+// and of the pass over fantasies (mes_fant_kernels.hip), and the block counts their tables are sized by (plan_ei, spx_plan.h)
+#define MES_CT 512        // candidates per partial sum of k_mes_logsurv
+#define MES_BT 1024       // candidates per partial minimum of k_mes_bounds
+#define MESF_CT 512       // candidates per partial sum of k_mes_fant_logsurv (MES_CT of the plain pass)
+#define MESF_BT 1024      // candidates per partial minimum of k_mes_fant_bounds
+
+static inline int mes_sum_blocks(int64_t M) { return (int)((M + MES_CT - 1) / MES_CT); }
+static inline int mes_bound_blocks(int64_t M) { return (int)((M + MES_BT - 1) / MES_BT); }
+static inline int mes_fant_sum_blocks(int64_t M) { return (int)((M + MESF_CT - 1) / MESF_CT); }
+static inline int mes_fant_bound_blocks(int64_t M) { return (int)((M + MESF_BT - 1) / MESF_BT); }

@@ -136,8 +136,9 @@ struct spx_handle {
     int acq = 0;              // SPX_ACQ_*: what the EI pass and the refinement objective compute (spx_set_acquisition) ...
     double acq_par = 0.0;     // ... and its parameter: xi (PI) / kappa (LCB)
     int not_pd_draw = -1, not_pd_pivot = -1;
-    int64_t fant_budget = 0;            // bytes the per-fantasy partial means may take (an eighth of free memory, <= 2 GB) ...
-    int fant_budget_S = -1;             // ... as found when the number of fantasies last changed
+    // bytes the partial means per right-hand side may take (an eighth of free memory, <= 2 GB), as found when the number of
+    // right-hand sides last changed; one per EiRhsKind -- the fantasies', spx_thompson's paths', SPX_ACQ_KG's columns'
+    struct RhsBudget { int64_t bytes = 0; int S = -1; } fant_budget[EI_RHS_KINDS];
     double* fused_lp = nullptr;         // (spx_gp_logprob -> do_factor: pinned destinations of the fused form's results)
     int* fused_info = nullptr;
     const void* info_clean_ptr = nullptr;   // the not-PD flags at this address ...
@@ -172,7 +173,7 @@ struct spx_handle {
     DevBuf eff_in, eff_m, eff_out;
     EffectsPlan effects_plan;                                       // the last spx_main_effects (spx_plan.h)
     // max-value entropy search (SPX_ACQ_MES): partial minima, partial log-survival sums, G [H][J], y* [H][K], fit [H][8] of the
-    // last MES pass and its sizes; part of RESULTS (held.results.mes)
+    // last MES pass and its sizes; part of RESULTS (held.results.mes).  Sized by plan_ei (EiPlan::mes_*_bytes, mesf_*_bytes)
     DevBuf mes_bpart, mes_part, mes_G, mes_ystar, mes_fit;
     int mes_K = 0, mes_J = 0;
     // ... over fantasies (option "mes_fantasies", held.results.mes_fant): the means [H][S][Mp] and the shared variance [H][Mp], the
@@ -196,18 +197,15 @@ struct spx_handle {
     // [P] as uploaded; prior [P] | its gradient [P][D] | dk/dr^2 [P][Np] between the two kernels; {value, prior, grad[D]} per point
     DevBuf ts_alpha, ts_gin, ts_gwork, ts_gout;
     int ts_S = 0, ts_F = 0;
-    int64_t ts_fant_budget = 0;    // the per-path partial means' byte budget, as fant_budget / fant_budget_S are the fantasies'
-    int ts_fant_budget_S = -1;
     size_t ts_w_stride = 0;        // doubles between the draws' blocks of w (0: shared)
     // knowledge gradient (SPX_ACQ_KG): the representer points as spx_set_kg_points received them (KGPTS held: kg_A >= 1) and on
     // the device; per pass: the points scaled per draw [H][Ap][Dp] and their norms [H][Ap], k(A, X) [H][Ap][Np], the columns
     // gamma | Gamma_a [H][A + 1][Np], mu_a [H][A]; per work item: k(A, c) [Hb][Ap][Mc] and mu_c [Hb][Mc] (the slopes take `scratch`);
-    // with the moments kept C [H][A][Mp].  kg_last_A: A of the held KG results (held.results.kg)
+    // with the moments kept C [H][A][Mp].  kg_last_A: A of the held KG results (held.results.kg).  All of these, and the
+    // tables over fantasies / by scan below, are sized by plan_ei (EiPlan::kg_*_bytes, kgf_*, kgs_*) and reserved by ei_reserve
     int kg_A = -1, kg_last_A = 0;
     std::vector<double> kg_pts_host;
     DevBuf kg_pts, kg_As, kg_sA, kg_kxa, kg_gammaS, kg_mua, kg_Kac, kg_muc, kg_cov;
-    int64_t kg_fant_budget = 0;    // the per-column partial means' byte budget, as fant_budget / fant_budget_S are the fantasies'
-    int kg_fant_budget_S = -1;
     // ... over fantasies (option "kg_fantasies", held.results.kg_fant): the intercepts mu_c [H][S][Mp] and mu_a [H][A][S], func_v
     // [H][Mp], the slopes by rank and the lines' indices by rank [H][A + 1][Mp], and -- with the moments kept, so that mu_c stays
     // readable -- KG_ds [H][S][Mp].  kg_last_S: S of the held results

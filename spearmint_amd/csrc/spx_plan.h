@@ -1,7 +1,9 @@
 // What a call will run, decided before anything is reserved or queued: the options of a handle and two pure functions,
 // plan_factor (do_factor) and plan_ei (ei_run_impl), of the options and the call's shape.  Host-only, plain C++17, no HIP and
 // no handle: spx_api.hip executes a plan and keeps it for spx_get_stat & co.; tests/c/plan_client.cpp prints plans on a
-// machine without a GPU.  A new path decision is a field of a plan, set here, read there.
+// machine without a GPU.  A new path decision is a field of a plan, set here, read there.  That includes the acquisition of an
+// EI pass: which launches score it (EiFinish / EiTail / EiClosing), what its own kernels are handed, and the size of every
+// buffer it reserves; and the sizes a pass is refused for (acq_tables), which the refusals read before a plan exists.
 #pragma once
 #include <math.h>
 #include <stdint.h>
@@ -185,10 +187,39 @@ inline int predict_gemm_padding_plan(int variant, int N, int Np)
     return (25 * (8 - lt) >= 12 * (nrb + 1)) ? nlive : 0;
 }
 
+// who supplies the right-hand sides of the pass's S > 0 GEMM branch
+enum EiRhsKind {
+    EI_RHS_FANT = 0,    // the held fantasies (none: the S = 0 pass)
+    EI_RHS_TS,          // spx_thompson's paths per draw; the acquisition setting is not read
+    EI_RHS_KG,          // gamma (or the fantasies' Gamma) | Gamma_a of the representer points: never asked for, follows from SPX_ACQ_KG
+    EI_RHS_KINDS
+};
+// what runs per work item in place of / as the acquisition
+enum EiFinish {
+    EI_FIN_FUSED = 0,       // nothing: k_ei_fused128 is the chunk's whole pass
+    EI_FIN_ALL_DRAWS,       // nothing per item: one EI finalize per chunk for all its draws
+    EI_FIN_PER_FANTASY,     // EI per (draw, fantasy)
+    EI_FIN_MES_FANT_MEANS,  // the means per (draw, fantasy): the MES stages behind the last chunk read them
+    EI_FIN_TS,              // path = posterior mean + prior
+    EI_FIN_KG_PAIRS,        // KG lines, valued by all pairs
+    EI_FIN_KG_SCAN,         // KG lines, valued by slope order and one scan
+    EI_FIN_KGF_LINES8,      // KG lines over the fantasies, ordered with 8-bit indices; valued behind the last chunk
+    EI_FIN_KGF_LINES16      // ... in the wide form: 16-bit indices
+};
+// what runs once behind the last chunk, in front of the closing launch
+enum EiTail { EI_TAIL_NONE = 0, EI_TAIL_MES, EI_TAIL_MES_FANT, EI_TAIL_EHVI, EI_TAIL_KGF_VALUE, EI_TAIL_KGW_VALUE };
+enum EiClosing { EI_CLOSE_MEAN_ARGMAX = 0, EI_CLOSE_TS_ARGMIN };
+
 struct EiShape {
     int64_t N = 0, M = 0;
     int Np = 0, D = 0, H = 0;
-    int S = 0;                      // fantasies per draw
+    int S = 0;                      // held fantasies per draw
+    int acq = SPX_ACQ_EI;           // what the pass is scored with (not read under EI_RHS_TS)
+    double acq_par = 0.0;           // ... and its parameter: xi (PI) / kappa (LCB)
+    int mesK = 0;                   // ... the y* samples per fit (MES)
+    int rhs = EI_RHS_FANT;          // EI_RHS_FANT or EI_RHS_TS
+    int ts_S = 0;                   // Thompson paths per draw (EI_RHS_TS)
+    int A = 0;                      // held representer points (read under SPX_ACQ_KG)
     int nmodels = 1;
     int32_t flags = 0;              // SPX_FLAG_*
     bool factor_pending = false;    // spx_ei_step: the factorisation is queued on the stream but not yet checked
@@ -218,18 +249,90 @@ struct EiPlan {
     int n_info = 0;                 // not-PD flags that travel home with the winner
     size_t cs_bytes = 0, s2_bytes = 0, kst_bytes = 0, bgS_bytes = 0, part_bytes = 0, scratch_bytes = 0, draw_bytes = 0,
            mean_bytes = 0;
+    // the acquisition: which launches score the pass, and what the pass's own kernels are handed
+    int rhs = EI_RHS_FANT;          // EiRhsKind: whose columns the S > 0 branch runs over
+    int rhs_S = 0;                  // ... and how many per draw (0: the S = 0 branch); KG: kgS + kgA
+    int finish = EI_FIN_ALL_DRAWS, tail = EI_TAIL_NONE, closing = EI_CLOSE_MEAN_ARGMAX;
+    int pass_acq = SPX_ACQ_EI;      // MES, EHVI and KG run the pass as EI (MES without fantasies and EHVI with the moments kept)
+    double pass_par = 0.0;
+    int32_t flags = 0;              // the flags as the pass runs them (keep_mom & co. above are read off these)
+    int kgS = 0, kgA = 0, kgAp = 0; // KG: columns in front of Gamma_a (the fantasies, or 1 = gamma), the points, padded as N is
+    int mesK = 0, mesJ = 0;         // MES: y* samples per fit and probe values
+    // the acquisition's buffers (spx_handle's members of these names); 0: the pass does not use the buffer
+    size_t kg_As_bytes = 0, kg_sA_bytes = 0, kg_kxa_bytes = 0, kg_gammaS_bytes = 0, kg_mua_bytes = 0, kg_Kac_bytes = 0,
+           kg_muc_bytes = 0, kg_cov_bytes = 0, kgs_bsort_bytes = 0, kgs_perm_bytes = 0, kgf_muc_bytes = 0, kgf_mua_bytes = 0,
+           kgf_v_bytes = 0, kgf_bsort_bytes = 0, kgf_perm_bytes = 0, kgw_badcol_bytes = 0, kgf_val_bytes = 0, mes_bpart_bytes = 0,
+           mes_part_bytes = 0, mes_G_bytes = 0, mes_ystar_bytes = 0, mes_fit_bytes = 0, mesf_mu_bytes = 0, mesf_v_bytes = 0,
+           mesf_bpart_bytes = 0, mesf_bnd_bytes = 0;
+    bool kg() const { return rhs == EI_RHS_KG; }
+    bool kg_fant() const { return tail == EI_TAIL_KGF_VALUE || tail == EI_TAIL_KGW_VALUE; }
+    bool kg_scan() const { return finish == EI_FIN_KG_SCAN || finish == EI_FIN_KGF_LINES16; }
+    bool mes() const { return tail == EI_TAIL_MES || tail == EI_TAIL_MES_FANT; }
 };
 
-// With `ringed` and no kstar_ring option, R is read off s.ring_budget, which the caller finds when slot_bytes changes: it
+// Whose columns the S > 0 branch of a pass runs over and how many: read by the caller for the byte budget it keeps per kind
+// (the plan's chunks depend on it) and by plan_ei.  KG over fantasies puts the S held columns in front of Gamma_a, plain KG gamma.
+struct EiRhs { int kind = EI_RHS_FANT, S = 0, kgS = 0; };
+inline EiRhs ei_rhs(const EiShape& s)
+{
+    EiRhs r;
+    if (s.rhs == EI_RHS_TS) { r.kind = EI_RHS_TS; r.S = s.ts_S; }
+    else if (s.acq == SPX_ACQ_KG) { r.kind = EI_RHS_KG; r.kgS = s.S > 0 ? s.S : 1; r.S = r.kgS + s.A; }
+    else r.S = s.S;
+    return r;
+}
+
+// The resident tables of a pass that SPX_KG_MAX_LINE_BYTES bounds.  The refusals (check_pass, spx_api.hip) run before a plan
+// exists, from the host's record alone, so the sizes are a function of their own; plan_ei sizes the buffers from it.
+struct AcqTables {
+    size_t mu = 0;          // means per (draw, fantasy), [H][S][Mp] doubles: kgf_muc, mesf_mu -- mu_tabs of them under KG
+    int mu_tabs = 1;        // ... (with the moments kept KG_ds has a table of its own beside the intercepts: kgf_val)
+    size_t slopes = 0;      // the slopes by rank, [H][A + 1][Mp] doubles: kgf_bsort
+    size_t perm = 0;        // ... and the lines' indices by rank, 8 bits or (wide) 16: kgf_perm
+    int ord_width = 9;      // bytes per line of the two: a slope and an index
+    size_t cov = 0;         // kept covariances, [H][A][Mp] doubles: kg_cov
+    size_t mes_part = 0;    // partial log-survival sums over fantasies, [H][S][mes_fant_sum_blocks(M)][J] doubles: mes_part
+};
+inline AcqTables acq_tables(int H, int S, int A, int64_t M, bool keep_mom, bool wide, int J)
+{
+    AcqTables t;
+    const size_t Mp = (size_t)round_up(M, SPX_BN);
+    t.mu = (size_t)H * S * Mp * 8;
+    t.mu_tabs = keep_mom ? 2 : 1;
+    t.slopes = (size_t)H * (A + 1) * Mp * 8;
+    t.perm = (size_t)H * (A + 1) * Mp * (wide ? 2 : 1);
+    t.ord_width = wide ? 10 : 9;
+    t.cov = (size_t)H * A * Mp * 8;
+    t.mes_part = (size_t)H * S * mes_fant_sum_blocks(M) * J * 8;
+    return t;
+}
+
+// The KG column count kgS + A is computed here (ei_rhs), so every chunk, Hb and buffer decision of a KG pass follows from
+// (options, shape) alone.  With `ringed` and no kstar_ring option, R is read off s.ring_budget, which the caller finds when slot_bytes changes: it
 // plans, compares slot_bytes with the slot its budget was found for, and plans again with the new budget if they differ.
 inline EiPlan plan_ei(const Options& o, const EiShape& s)
 {
     EiPlan p;
-    p.per_sec = (s.flags & SPX_FLAG_PER_SEC) != 0;
-    p.keep_mom = (s.flags & SPX_FLAG_KEEP_MOMENTS) != 0;
-    p.time_only = (s.flags & SPX_FLAG_TIME_ONLY) != 0;
-    p.constrained = (s.flags & SPX_FLAG_CONSTRAINED) != 0;
-    const int H = s.H, Np = s.Np, S = s.S;
+    // The acquisition.  MES, EHVI and KG run the ordinary pass as EI and score it with stages of their own: MES (without
+    // fantasies) and EHVI behind the last chunk from the kept moments, so they force SPX_FLAG_KEEP_MOMENTS; MES over the
+    // fantasies (option "mes_fantasies") and KG in the S > 0 branch.  A Thompson pass reads no acquisition.
+    const EiRhs rhs = ei_rhs(s);
+    const bool ts = rhs.kind == EI_RHS_TS, kg = rhs.kind == EI_RHS_KG;
+    const bool mes = !ts && s.acq == SPX_ACQ_MES, mesf = mes && s.S > 0 && o.mes_fantasies;
+    const bool ehvi = !ts && s.acq == SPX_ACQ_EHVI;
+    const bool kgf = kg && s.S > 0;                         // over the fantasies (option "kg_fantasies"), kg_fant_kernels.hip
+    const bool kgw = kgf && o.kg_fantasies == 2;            // ... in the wide form, kg_fant_scan_kernels.hip: orders its lines itself
+    const bool kgs = kg && !kgf && o.kg_scan;               // plain KG valued by slope order and one scan, kg_scan_kernels.hip
+    p.flags = s.flags | (((mes && !mesf) || ehvi) ? SPX_FLAG_KEEP_MOMENTS : 0);
+    p.pass_acq = (mes || ehvi || kg) ? SPX_ACQ_EI : s.acq;
+    p.pass_par = (mes || ehvi || kg) ? 0.0 : s.acq_par;
+    p.rhs = rhs.kind;
+    p.rhs_S = rhs.S;
+    p.per_sec = (p.flags & SPX_FLAG_PER_SEC) != 0;
+    p.keep_mom = (p.flags & SPX_FLAG_KEEP_MOMENTS) != 0;
+    p.time_only = (p.flags & SPX_FLAG_TIME_ONLY) != 0;
+    p.constrained = (p.flags & SPX_FLAG_CONSTRAINED) != 0;
+    const int H = s.H, Np = s.Np, S = rhs.S;
     const int64_t Mp = round_up(s.M, SPX_BN);
     p.Mp = Mp;
     p.Dp = padded_dim(s.D);
@@ -323,6 +426,59 @@ inline EiPlan plan_ei(const Options& o, const EiShape& s)
     p.scratch_bytes = (size_t)p.Hb * S * Mc * 8;
     p.draw_bytes = (size_t)H * Mp * 8;
     p.mean_bytes = (size_t)Mp * 8;
+    p.finish = p.fused ? EI_FIN_FUSED : kgw ? EI_FIN_KGF_LINES16 : kgf ? EI_FIN_KGF_LINES8 : kgs ? EI_FIN_KG_SCAN
+             : kg ? EI_FIN_KG_PAIRS : ts ? EI_FIN_TS : mesf ? EI_FIN_MES_FANT_MEANS : S > 0 ? EI_FIN_PER_FANTASY : EI_FIN_ALL_DRAWS;
+    p.tail = kgw ? EI_TAIL_KGW_VALUE : kgf ? EI_TAIL_KGF_VALUE : mesf ? EI_TAIL_MES_FANT : mes ? EI_TAIL_MES
+           : ehvi ? EI_TAIL_EHVI : EI_TAIL_NONE;
+    p.closing = ts ? EI_CLOSE_TS_ARGMIN : EI_CLOSE_MEAN_ARGMAX;
+    // The acquisition's buffers.  KG: the points scaled per draw [H][Ap][Dp] and their norms, k(A, X) [H][Ap][Np], the columns
+    // [H][S][Np], mu_a [H][A]; per work item k(A, c) [Hb][Ap][Mc] and mu_c [Hb][Mc] (the slopes take `scratch`); with the
+    // moments kept C [H][A][Mp].  By scan: the item's ordered slopes and 16-bit line indices [Hb][S][Mc].  Over fantasies: the
+    // intercepts [H][kgS][Mp] and mu_a [H][A][kgS], func_v [H][Mp], the lines by rank [H][A + 1][Mp], a flag per (draw, column)
+    // in the wide form, and KG_ds beside the intercepts with the moments kept (mu_c stays for its getter).
+    const AcqTables t = acq_tables(H, s.S, kg ? s.A : 0, s.M, p.keep_mom, kgw, o.mes_grid);
+    if (kg) {
+        p.kgS = rhs.kgS; p.kgA = s.A; p.kgAp = (int)round_up(s.A, SPX_PADN);   // (rows of a K(A, .) launch: padded as N is)
+        p.kg_As_bytes = (size_t)H * p.kgAp * p.Dp * 8;
+        p.kg_sA_bytes = (size_t)H * p.kgAp * 8;
+        p.kg_kxa_bytes = (size_t)H * p.kgAp * Np * 8;
+        p.kg_gammaS_bytes = (size_t)H * S * Np * 8;
+        p.kg_mua_bytes = (size_t)H * p.kgA * 8;
+        p.kg_Kac_bytes = (size_t)p.Hb * p.kgAp * Mc * 8;
+        p.kg_muc_bytes = (size_t)p.Hb * Mc * 8;
+        p.kg_cov_bytes = p.keep_mom ? t.cov : 0;
+    }
+    if (kgs) {
+        p.kgs_bsort_bytes = (size_t)p.Hb * S * Mc * 8;
+        p.kgs_perm_bytes = (size_t)p.Hb * S * Mc * 2;
+    }
+    if (kgf) {
+        p.kgf_muc_bytes = t.mu;
+        p.kgf_mua_bytes = (size_t)H * p.kgA * p.kgS * 8;
+        p.kgf_v_bytes = (size_t)H * Mp * 8;
+        p.kgf_bsort_bytes = t.slopes;
+        p.kgf_perm_bytes = t.perm;
+        p.kgw_badcol_bytes = kgw ? (size_t)H * p.kgS * sizeof(int) : 0;
+        p.kgf_val_bytes = p.keep_mom ? t.mu : 0;
+    }
+    // MES: partial minima [H][blocks][3], partial log-survival sums [rec][blocks][J], G [rec][J], y* [rec][K], fit [rec][8], a
+    // record per draw or (over fantasies) per (draw, fantasy); there also the means [rec][Mp], the shared variance [H][Mp],
+    // and the partial minima and brackets per record
+    if (mes) {
+        const size_t rec = mesf ? (size_t)H * S : (size_t)H;
+        p.mesK = s.mesK; p.mesJ = o.mes_grid;
+        p.mes_bpart_bytes = mesf ? 0 : (size_t)H * mes_bound_blocks(s.M) * 3 * 8;
+        p.mes_part_bytes = mesf ? t.mes_part : (size_t)H * mes_sum_blocks(s.M) * p.mesJ * 8;
+        p.mes_G_bytes = rec * p.mesJ * 8;
+        p.mes_ystar_bytes = rec * p.mesK * 8;
+        p.mes_fit_bytes = rec * 8 * 8;
+        if (mesf) {
+            p.mesf_mu_bytes = t.mu;
+            p.mesf_v_bytes = (size_t)H * Mp * 8;
+            p.mesf_bpart_bytes = rec * mes_fant_bound_blocks(s.M) * 3 * 8;
+            p.mesf_bnd_bytes = rec * 3 * 8;
+        }
+    }
     return p;
 }
 

@@ -1,9 +1,12 @@
 // Stand-alone host program over csrc/spx_plan.h alone (no HIP, no library): reads one case per line from stdin and prints
 // the plan as one JSON line (tests/test_plan.py, tests/test_gpu_r_plan_runs.py).
 //   factor N= D= H= [time=1] [lean=1] [defer=1] [dest=1] [demoted=1] [rhs_rows=1] [Np=] [OPTION=value ...]
-//   ei     N= M= D= H= [S=] [nmodels=] [flags=] [pending=1] [fant_budget=] [ring_budget=] [Np=] [OPTION=value ...]
+//   ei     N= M= D= H= [S=] [nmodels=] [flags=] [pending=1] [fant_budget=] [ring_budget=] [Np=] [acq=] [rhs=] [ts_S=] [A=]
+//          [mesK=] [OPTION=value ...]
 // OPTION is a name spx_set_option takes, the value what it stores (tri-states -1 / 0 / 1).  Np defaults to the handle's
-// (N padded to 128), the K(X*,X) budget to option kstar_budget_bytes.
+// (N padded to 128), the K(X*,X) budget to option kstar_budget_bytes.  S: the held fantasies; acq: SPX_ACQ_* (0 = EI); rhs: 1 =
+// a Thompson pass over ts_S paths per draw (EiRhsKind); A: the held KG points; mesK: the y* samples of a MES pass.  The plan's
+// enums (finish, tail, closing, rhs) print as their numbers: EiFinish, EiTail, EiClosing, EiRhsKind of spx_plan.h.
 #include <stdio.h>
 #include <stdlib.h>
 #include <string.h>
@@ -26,7 +29,9 @@ static bool set_option(Options& o, const std::string& k, int64_t v)
         {"lean_flow_yield", &Options::lean_flow_yield}, {"lean_flow_cu", &Options::lean_flow_cu},
         {"lean_flow", &Options::lean_flow}, {"lean_ps", &Options::lean_ps}, {"lean_merge", &Options::lean_merge},
         {"lean_one", &Options::lean_one}, {"lean_poll", &Options::lean_poll}, {"lean_zc", &Options::lean_zc},
-        {"stage_copies", &Options::stage_copies}, {"cov_flat", &Options::cov_flat}, {"gemm_partial", &Options::gemm_partial}};
+        {"stage_copies", &Options::stage_copies}, {"cov_flat", &Options::cov_flat}, {"gemm_partial", &Options::gemm_partial},
+        {"mes_grid", &Options::mes_grid}, {"mes_fantasies", &Options::mes_fantasies}, {"kg_fantasies", &Options::kg_fantasies},
+        {"kg_scan", &Options::kg_scan}};
     if (k == "kstar_budget_bytes") { o.kst_budget = v; return true; }
     if (k == "timing") { o.timing = v != 0; return true; }
     auto it = ints.find(k);
@@ -73,12 +78,26 @@ int main()
             s.Np = (int)get("Np", round_up(s.N, SPX_PADN));
             s.nmodels = (int)get("nmodels", 1); s.flags = (int32_t)get("flags", 0); s.factor_pending = get("pending", 0);
             s.kst_budget = o.kst_budget; s.fant_budget = get("fant_budget", 0); s.ring_budget = get("ring_budget", 0);
+            s.acq = (int)get("acq", SPX_ACQ_EI); s.rhs = (int)get("rhs", EI_RHS_FANT); s.ts_S = (int)get("ts_S", 0);
+            s.A = (int)get("A", 0); s.mesK = (int)get("mesK", 0);
             const EiPlan p = plan_ei(o, s);
             printf("{");
             J(per_sec); J(keep_mom); J(time_only); J(constrained); J(Mp); J(Mc); J(Hb); J(nrb); J(Dp); J(fused); J(gemm_path);
             J(timing_on); J(ns); J(kst_bufs); J(slots); J(ringed); J(slot_bytes); J(R); J(ring_items); J(trim_ring); J(overlap);
             J(cov_flat); J(corun); J(gemm_nlive); J(cov_live_rows); J(n_info); J(cs_bytes); J(s2_bytes); J(kst_bytes);
             J(bgS_bytes); J(part_bytes); J(scratch_bytes); J(draw_bytes); J(mean_bytes);
+            J(rhs); J(rhs_S); J(finish); J(tail); J(closing); J(pass_acq); J(flags); J(kgS); J(kgA); J(kgAp); J(mesK); J(mesJ);
+            J(kg_As_bytes); J(kg_sA_bytes); J(kg_kxa_bytes); J(kg_gammaS_bytes); J(kg_mua_bytes); J(kg_Kac_bytes); J(kg_muc_bytes);
+            J(kg_cov_bytes); J(kgs_bsort_bytes); J(kgs_perm_bytes); J(kgf_muc_bytes); J(kgf_mua_bytes); J(kgf_v_bytes);
+            J(kgf_bsort_bytes); J(kgf_perm_bytes); J(kgw_badcol_bytes); J(kgf_val_bytes); J(mes_bpart_bytes); J(mes_part_bytes);
+            J(mes_G_bytes); J(mes_ystar_bytes); J(mes_fit_bytes); J(mesf_mu_bytes); J(mesf_v_bytes); J(mesf_bpart_bytes);
+            J(mesf_bnd_bytes);
+            {   // the bytes SPX_KG_MAX_LINE_BYTES bounds, as the refusals compute them before a plan exists (acq_tables)
+                const AcqTables t = acq_tables(s.H, s.S, s.A, s.M, p.keep_mom, s.S > 0 && o.kg_fantasies == 2, o.mes_grid);
+                printf("\"lim_mu_bytes\": %zu, \"lim_mu_tabs\": %d, \"lim_ord_bytes\": %zu, \"lim_ord_width\": %d, \"lim_cov_bytes\": "
+                       "%zu, \"lim_mes_part_bytes\": %zu, \"lim_bytes\": %lld, ", t.mu, t.mu_tabs, t.slopes + t.perm, t.ord_width, t.cov,
+                       t.mes_part, (long long)SPX_KG_MAX_LINE_BYTES);
+            }
             printf("\"kind\": \"ei\"}\n");
         } else {
             fprintf(stderr, "plan_client: unknown case kind '%s'\n", kind.c_str());

@@ -1,7 +1,9 @@
 """What plan_factor / plan_ei (csrc/spx_plan.h) say will run is what runs: for the shapes of tests/test_plan.py that sit on
 either side of a decision below N = 300 (and M <= 2000), the call is made and the library's statistics -- and, with option
 timing, the per-stage launch counts of the factorisation -- are compared with the plan that tests/c/plan_client.cpp prints for
-the same shape and options.  The plans of all cases come from one run of the client."""
+the same shape and options.  The plans of all cases come from one run of the client.  The acquisition rows of
+tests/plan_helpers.py (ACQ_ROWS) run the same way: the statistics of the held results and, with option timing, the launches of
+the acquisition's stages against counts read off the plan."""
 import numpy as np
 import pytest
 
@@ -153,3 +155,113 @@ def test_ei_pass_runs_its_plan(eng, plans, case, step):
     assert got == dict(_plan_stats(pf), step_fused=pe["fused"], step_skipped_padding=int(pe["gemm_nlive"] > 0), kstar_ring=pe["R"])
     if counts is not None:
         assert {k: counts[k] for k in ("scale_rows", "cov_self", "chol_diag", "chol_panel")} == _factor_counts(pf, False)
+
+
+# ---- the acquisition rows: which launches score the pass -------------------------------------------------------------------
+ACQ_STATS = ("last_kg_points", "last_kg_fantasies", "last_kg_scan", "last_kg_lines", "last_mes_samples", "last_mes_fantasies",
+             "last_mes_grid", "last_ts_paths", "last_step_fused", "last_kstar_ring")
+ACQ_STAGES = ("kg", "mes", "ehvi", "ts_prior", "ts_finish", "ei_finalize", "cov_cross", "mean_argmax")
+ACQ_OPTS = ("mes_fantasies", "kg_fantasies", "kg_scan")
+
+
+@pytest.fixture(scope="module")
+def acq_plans():
+    names = list(ph.ACQ_ROWS)
+    return dict(zip(names, ph.plans([ph.acq_case(n) for n in names])))
+
+
+def _acq_stats(p):
+    """What spx_get_stat reports of the results a pass with plan p leaves held."""
+    F, T = ph.FINISH, ph.TAIL
+    kg = p["rhs"] == ph.RHS["kg"]
+    kgf = p["tail"] in (T["kgf_value"], T["kgw_value"])
+    mes, mesf = p["tail"] in (T["mes"], T["mes_fant"]), p["tail"] == T["mes_fant"]
+    return {"last_kg_points": p["kgA"] if kg else 0, "last_kg_fantasies": p["kgS"] if kgf else 0,
+            "last_kg_scan": int(p["finish"] in (F["kg_scan"], F["kgf_lines16"])), "last_kg_lines": int(kg and p["keep_mom"]),
+            "last_mes_samples": p["mesK"] if mes else 0, "last_mes_fantasies": p["rhs_S"] if mesf else 0,
+            "last_mes_grid": p["mesJ"] if mes else 0, "last_ts_paths": p["rhs_S"] if p["rhs"] == ph.RHS["ts"] else 0,
+            "last_step_fused": p["fused"], "last_kstar_ring": p["R"]}
+
+
+def _acq_counts(p):
+    """Launches per stage of one pass, read off its plan (ei_run_impl's TIMED launches; spx_thompson's own in front of a TS pass).
+    items: work items of the GEMM path (chunks x draw groups); chunks: candidate chunks."""
+    F, T = ph.FINISH, ph.TAIL
+    items, chunks = p["ring_items"], (p["Mp"] + p["Mc"] - 1) // p["Mc"]
+    kg, ts = p["rhs"] == ph.RHS["kg"], p["rhs"] == ph.RHS["ts"]
+    return {
+        # K(X*,X) per item; KG: k(A, X) once in the prologue and k(A, c) per item
+        "cov_cross": items + (1 + items if kg else 0),
+        # mu_a once, the lines (with their values in the same bracket, where they are valued per item) per item, and over
+        # fantasies one valuing launch behind the last chunk
+        "kg": (1 + items + (1 if p["tail"] in (T["kgf_value"], T["kgw_value"]) else 0)) if kg else 0,
+        # over fantasies the means per item and the stages behind the last chunk; else those stages alone
+        "mes": items + 1 if p["tail"] == T["mes_fant"] else 1 if p["tail"] == T["mes"] else 0,
+        "ehvi": int(p["tail"] == T["ehvi"]),
+        # spx_thompson: the prior at the observations (with the right-hand sides, one bracket), then per chunk the prior at its rows
+        "ts_prior": 1 + chunks if ts else 0,
+        "ts_finish": items + 1 if ts else 0,                             # per item, and the argmin
+        "ei_finalize": chunks if p["finish"] == F["all_draws"] else items if p["finish"] == F["per_fantasy"] else 0,
+        "mean_argmax": 0 if ts else 1}
+
+
+def _run_acq_row(e, name, p, step, timing):
+    N, kv, _ = ph.ACQ_ROWS[name]
+    H, S, A = 3, kv.get("S", 0), kv.get("A", 0)
+    comp, cand, vals, hypers, log_durs, th = synthetic_problem(N, 1000, 2, H, 13, per_sec=True)
+    rs = np.random.RandomState(7)
+    acq = {v: k for k, v in ph.ACQ.items()}[kv.get("acq", 0)]
+    opts = dict({k: kv[k] for k in ACQ_OPTS if k in kv}, kstar_budget_bytes=1 << 20, timing=timing)
+    e.set_observations(comp, vals)
+    e.set_candidates(cand)
+    e.set_hypers(hypers)
+    e.set_time_model(log_durs, th) if acq == "EHVI" else e.set_time_model(None, None)
+    if acq == "EHVI":
+        e.set_pareto_front([[-1.0, 0.5], [0.0, -0.5]], (5.0, 5.0))
+    if A:
+        e.set_kg_points(rs.uniform(0.0, 1.0, (A, 2)))
+    _set(e, opts)
+    e.set_acquisition(acq, {"MES": kv.get("mesK", 0), "PI": 0.01, "LCB": 2.0}.get(acq, 0.0))
+    try:
+        if step:
+            e.ei_step(0)
+            before = None
+        else:
+            e.factor()
+            before = {k: v[1] for k, v in e.timings().items()}
+            if S:
+                fant = rs.randn(H, N, S)
+                e.set_fantasies(fant, np.min(fant, axis=1) - 0.1)
+            if name == "TS":
+                e.thompson(S=kv["ts_S"], F=32, rng=np.random.RandomState(3))
+            else:
+                e.ei_run(0)
+        stats = {k: e.stat(k) for k in ACQ_STATS}
+        after = {k: v[1] for k, v in e.timings().items()}
+        assert e.get_acquisition()[0] == ph.ACQ[acq]
+    finally:
+        e.set_fantasies(None, None)
+        e.set_acquisition("EI")
+        e.set_kg_points(None)
+        e.set_pareto_front(None, None)
+        e.set_time_model(None, None)
+        _reset(e, {"kstar_budget_bytes": 0, "timing": 0})
+        for k in ACQ_OPTS:                      # (0 / 1 options: their default is 0)
+            e.set_option(k, 0)
+    counts = None if before is None else {k: after[k] - before[k] for k in ACQ_STAGES}
+    print(name, step, timing, stats, counts)
+    assert stats == _acq_stats(p)
+    if timing:
+        assert counts == _acq_counts(p)
+
+
+@pytest.mark.parametrize("name", list(ph.ACQ_ROWS))
+def test_acquisition_pass_runs_its_plan(eng, acq_plans, name):
+    """spx_factor + spx_ei_run (spx_thompson for the TS row) with option timing: the statistics and the launches per stage."""
+    _run_acq_row(eng, name, acq_plans[name], 0, 1)
+
+
+@pytest.mark.parametrize("name", [n for n, (_, kv, _) in ph.ACQ_ROWS.items() if not kv.get("S") and n != "TS"])
+def test_acquisition_step_runs_its_plan(eng, acq_plans, name):
+    """spx_ei_step (one synchronisation; a step's factorisation drops fantasies, so the rows without them): the statistics."""
+    _run_acq_row(eng, name, acq_plans[name], 1, 0)

@@ -2,7 +2,7 @@
 is reserved or queued.  Every "same bits in every form" test forces a form through options and trusts that decision; here
 it is pinned without a GPU, through tests/c/plan_client.cpp (a stand-alone host program over the header alone, built with
 the address and undefined-behaviour sanitizers).  Each expected value carries its derivation from the rules of do_factor /
-ei_run_impl as they stood before the planner existed.  The option table is checked through the real library
+ei_run_impl as they stood before the planner existed (the acquisition's decisions: before they moved into plan_ei).  The option table is checked through the real library
 (spx_create touches no device)."""
 import itertools
 import os
@@ -248,6 +248,126 @@ def test_ei_pass_padding_skip():
     assert ei(20, 1000, 3)["gemm_nlive"] == 0
 
 
+# ---- the EI pass's acquisition: which launches score it, what its kernels are handed, what it reserves -------------------------
+@needs_cxx
+def test_acquisition_truth_table():
+    # The parent's ei_run_impl: mes = acq == MES, mesf = mes and S > 0 and mes_fantasies, ehvi = acq == EHVI, kg = acq == KG,
+    # kgf = kg and S > 0, kgw = kgf and kg_fantasies == 2, kgs = kg and not kgf and kg_scan (all false in a Thompson pass);
+    # flags |= KEEP_MOMENTS if (mes and not mesf) or ehvi; pass_acq = EI if mes or ehvi or kg else acq; the S of the pass is
+    # rhs.S of a Thompson pass, kgS + A under KG (kgS = S if kgf else 1), else the fantasies.  Per item: kg -> kgw / kgf /
+    # (lines + kgs ? scan : pairs), else ts, else mesf, else S > 0 -> per-fantasy EI; S == 0 and not fused: one finalize per chunk;
+    # fused = Np == 128 and S == 0.  Behind the last chunk: kgw / kgf value, mesf / mes, ehvi; then ts ? argmin : mean + argmax.
+    names = list(ph.ACQ_ROWS)
+    for name, p in zip(names, ph.plans([ph.acq_case(n) for n in names])):
+        finish, tail, closing, pass_acq, keep, rhs_S = ph.ACQ_ROWS[name][2]
+        got = (p["finish"], p["tail"], p["closing"], p["pass_acq"], p["keep_mom"], p["rhs_S"])
+        assert got == (ph.FINISH[finish], ph.TAIL[tail], ph.CLOSING[closing], ph.ACQ[pass_acq], keep, rhs_S), name
+        assert p["flags"] == (KEEP_MOMENTS if keep else 0), name
+        assert bool(p["fused"]) == (finish == "fused") and not (p["fused"] and p["rhs_S"] > 0), name
+        assert p["rhs"] == (ph.RHS["ts"] if name == "TS" else ph.RHS["kg"] if name.startswith("KG") else ph.RHS["fant"]), name
+        # two chunks x three draws through the GEMM path, or nothing staged (fused)
+        assert (p["gemm_path"], p["ring_items"]) == ((0, 0) if finish == "fused" else (1, 6)), name
+    # KG's columns put a pass at N = 128 on the GEMM path (S = 1 + A > 0: never fused), with or without fantasies
+    for name, cols in (("KG-pairs", 1 + ph.ACQ_A), ("KG-scan", 1 + ph.ACQ_A), ("KG-fant", ph.ACQ_S + ph.ACQ_A)):
+        p = ph.plans([ph.acq_case(name, N=128)])[0]
+        assert (p["fused"], p["gemm_path"], p["rhs_S"], p["kgS"], p["kgA"], p["kgAp"]) == (0, 1, cols, cols - ph.ACQ_A, ph.ACQ_A, 128), name
+    # the caller's KEEP_MOMENTS stays what it is where the acquisition does not force it
+    assert ph.plans([ph.acq_case("MES-fant", flags=KEEP_MOMENTS)])[0]["keep_mom"] == 1
+    assert ph.plans([ph.acq_case("KG-fant", flags=0)])[0]["keep_mom"] == 0
+    # PI / LCB over fantasies: per-fantasy values of that acquisition
+    p = ph.plans([ph.acq_case("PI-130", S=3)])[0]
+    assert (p["finish"], p["pass_acq"], p["rhs_S"]) == (ph.FINISH["per_fantasy"], ph.ACQ["PI"], 3)
+    # a Thompson pass reads no acquisition: the handle may be set to anything
+    p = ph.plans([ph.acq_case("TS", acq=ph.ACQ["KG"], A=5)])[0]
+    assert (p["finish"], p["rhs"], p["rhs_S"], p["kgA"]) == (ph.FINISH["ts"], ph.RHS["ts"], 3, 0)
+
+
+ACQ_BUFS = ("kg_As", "kg_sA", "kg_kxa", "kg_gammaS", "kg_mua", "kg_Kac", "kg_muc", "kg_cov", "kgs_bsort", "kgs_perm", "kgf_muc",
+            "kgf_mua", "kgf_v", "kgf_bsort", "kgf_perm", "kgw_badcol", "kgf_val", "mes_bpart", "mes_part", "mes_G", "mes_ystar",
+            "mes_fit", "mesf_mu", "mesf_v", "mesf_bpart", "mesf_bnd")
+
+
+@needs_cxx
+def test_acquisition_buffer_sizes():
+    # N = 130: Np = 256, Mp = 1024, two chunks Mc = 512 of Hb = 1 draw (test_ei_pass_chunks; the 64 MiB right-hand-side budget
+    # holds far more), Dp = 4, Ap = round_up(5, 128) = 128; J = 256 (option mes_grid's default), K = 4.  Each size: the
+    # reserve() line of the parent's ei_run_impl between ei_reserve(...) and h->corun_launches = 0.
+    H, Np, Mp, Mc, Hb, Dp, A, Ap, S, J, K, M = 3, 256, 1024, 512, 1, 4, ph.ACQ_A, 128, ph.ACQ_S, 256, ph.ACQ_K, 1000
+
+    def sizes(name, **kw):
+        p = ph.plans([ph.acq_case(name, **kw)])[0]
+        assert (p["Mp"], p["Mc"], p["Hb"], p["Dp"]) == (Mp, Mc, Hb, Dp) or kw.get("M", M) != M
+        return {b: p[b + "_bytes"] for b in ACQ_BUFS}
+
+    def only(**kw):
+        return dict({b: 0 for b in ACQ_BUFS}, **kw)
+
+    def kg(cols, keep):          # if (kg): the points per draw, k(A, X), the columns, mu_a; per item k(A, c) and mu_c; C if keep_mom
+        return dict(kg_As=H * Ap * Dp * 8, kg_sA=H * Ap * 8, kg_kxa=H * Ap * Np * 8, kg_gammaS=H * cols * Np * 8, kg_mua=H * A * 8,
+                    kg_Kac=Hb * Ap * Mc * 8, kg_muc=Hb * Mc * 8, kg_cov=H * A * Mp * 8 if keep else 0)
+
+    for keep in (0, KEEP_MOMENTS):
+        assert sizes("KG-pairs", flags=keep) == only(**kg(1 + A, keep))
+        # if (kgs): Hb S Mc 8 and ... 2 with S = 1 + A the pass's columns
+        assert sizes("KG-scan", flags=keep) == only(kgs_bsort=Hb * (1 + A) * Mc * 8, kgs_perm=Hb * (1 + A) * Mc * 2, **kg(1 + A, keep))
+        for opt, width in ((1, 1), (2, 2)):
+            # if (kgf): H kgS Mp 8, H A kgS 8, H Mp 8, H (A + 1) Mp 8, H (A + 1) Mp (kgw ? 2 : 1), kgw: H kgS sizeof(int),
+            # keep_mom: H kgS Mp 8 -- kgS = S
+            want = only(kgf_muc=H * S * Mp * 8, kgf_mua=H * A * S * 8, kgf_v=H * Mp * 8, kgf_bsort=H * (A + 1) * Mp * 8,
+                        kgf_perm=H * (A + 1) * Mp * width, kgw_badcol=H * S * 4 if opt == 2 else 0,
+                        kgf_val=H * S * Mp * 8 if keep else 0, **kg(S + A, keep))
+            assert sizes("KG-fant", flags=keep, kg_fantasies=opt) == want
+    # if (mes): bpart H ceil(M / 1024) 3 8 unless mesf; part rec ceil(M / 512) J 8; G rec J 8; y* rec K 8; fit rec 8 8, rec = H or
+    # (mesf) H S; if (mesf): mu rec Mp 8, v H Mp 8, bpart rec ceil(M / 1024) 3 8, bnd rec 3 8
+    assert sizes("MES") == only(mes_bpart=H * 1 * 3 * 8, mes_part=H * 2 * J * 8, mes_G=H * J * 8, mes_ystar=H * K * 8, mes_fit=H * 64)
+    assert sizes("MES", mes_grid=64, M=1025, mesK=7) == only(mes_bpart=H * 2 * 3 * 8, mes_part=H * 3 * 64 * 8, mes_G=H * 64 * 8,
+                                                              mes_ystar=H * 7 * 8, mes_fit=H * 64)
+    rec = H * S
+    assert sizes("MES-fant") == only(mes_part=rec * 2 * J * 8, mes_G=rec * J * 8, mes_ystar=rec * K * 8, mes_fit=rec * 64,
+                                     mesf_mu=rec * Mp * 8, mesf_v=H * Mp * 8, mesf_bpart=rec * 1 * 3 * 8, mesf_bnd=rec * 3 * 8)
+    for name in ("EI-130", "EI-fant", "PI-130", "EHVI", "TS"):
+        assert sizes(name, M=M) == only(), name
+
+
+@needs_cxx
+def test_acquisition_limits_at_their_boundaries():
+    # What check_kg / check_run_flags compared with SPX_KG_MAX_LINE_BYTES = 4 GiB (refused when greater), from the helper that
+    # sizes the plan's buffers.  tests/test_gpu_zz_kg_pending_scan.py's shape -- H = 2, A + 1 = 257 lines, Mp = 1 100 032, the
+    # wide form: 2 x 257 x 1 100 032 x 10 = 5 654 164 480 > 4 294 967 296.  A candidate tile is 2 x 257 x 128 x 10 = 657 920
+    # bytes, so one tile less stays refused; the nearest pair that straddles the limit is 6528 tiles (Mp = 835 584:
+    # 4 294 901 760, accepted) and 6529 (Mp = 835 712: 4 295 559 680, refused).
+    lim = 4 << 30
+
+    def t(M, **kw):
+        return ph.plans([("ei", dict(dict(N=130, M=M, D=2, H=2, S=3, A=256, acq=ph.ACQ["KG"], kg_fantasies=2, fant_budget=64 << 20), **kw))])[0]
+
+    p = t(1100032)
+    assert (p["lim_ord_bytes"], p["lim_ord_width"], p["lim_bytes"]) == (2 * 257 * 1100032 * 10, 10, lim) and p["lim_ord_bytes"] > lim
+    assert t(1100032 - 128)["lim_ord_bytes"] == 2 * 257 * 1099904 * 10 > lim
+    lo, hi = t(835584), t(835584 + 1)                                   # (M = 835 585 pads to the next tile)
+    assert (lo["Mp"], hi["Mp"]) == (835584, 835712)
+    assert lo["lim_ord_bytes"] == 4294901760 <= lim < hi["lim_ord_bytes"] == 4295559680
+    assert lo["lim_ord_bytes"] == lo["kgf_bsort_bytes"] + lo["kgf_perm_bytes"]        # the plan's two buffers are those bytes
+    # the narrow form: 9 bytes a line, a tile 2 x 256 x 128 x 9 = 589 824 = 2^16 x 9: 7281 tiles 4 294 508 544, 7282 tiles 4 295 098 368
+    lo, hi = t(7281 * 128, A=255, kg_fantasies=1), t(7282 * 128, A=255, kg_fantasies=1)
+    assert (lo["lim_ord_width"], lo["lim_ord_bytes"], hi["lim_ord_bytes"]) == (9, 4294508544, 4295098368) and lo["lim_ord_bytes"] <= lim < hi["lim_ord_bytes"]
+    # means per (draw, fantasy): H S Mp 8, twice with the moments kept (KG_ds beside the intercepts).  H = 2, S = 256: a tile is
+    # 2 x 256 x 128 x 8 = 2^19 bytes, so 8192 tiles are exactly 4 GiB (accepted: not greater), 8193 are beyond; kept, 4096 / 4097
+    for keep, tiles in ((0, 8192), (KEEP_MOMENTS, 4096)):
+        lo, hi = t(tiles * 128, S=256, A=5, flags=keep), t((tiles + 1) * 128, S=256, A=5, flags=keep)
+        assert lo["lim_mu_tabs"] == hi["lim_mu_tabs"] == (2 if keep else 1)
+        assert lo["lim_mu_bytes"] * lo["lim_mu_tabs"] == lim < hi["lim_mu_bytes"] * hi["lim_mu_tabs"] == lim + (2 if keep else 1) * (1 << 19)
+        assert lo["kgf_muc_bytes"] == lo["lim_mu_bytes"] and lo["kgf_val_bytes"] == (lo["lim_mu_bytes"] if keep else 0)
+    # kept covariances H A Mp 8 (plain KG, KEEP_MOMENTS): H = 2, A = 256: the same 2^19 a tile
+    lo, hi = t(8192 * 128, S=0, kg_fantasies=0, kg_scan=1, flags=KEEP_MOMENTS), t(8193 * 128, S=0, kg_fantasies=0, kg_scan=1, flags=KEEP_MOMENTS)
+    assert lo["lim_cov_bytes"] == lo["kg_cov_bytes"] == lim < hi["lim_cov_bytes"] == lim + (1 << 19)
+    # MES over fantasies: partial sums H S ceil(M / 512) J 8.  H = 2, S = 256, J = 4096: 2^24 bytes a block of 512 candidates
+    def m(M):
+        return ph.plans([("ei", dict(N=130, M=M, D=2, H=2, S=256, acq=ph.ACQ["MES"], mesK=4, mes_fantasies=1, mes_grid=4096, fant_budget=64 << 20))])[0]
+    lo, hi = m(256 * 512), m(256 * 512 + 1)
+    assert lo["lim_mes_part_bytes"] == lo["mes_part_bytes"] == lim < hi["lim_mes_part_bytes"] == lim + (1 << 24)
+
+
 # ---- invariants over a lattice ------------------------------------------------------------------------------------------
 TRI = ("lean_lazy", "ei_flow", "lean_flow_cov", "lean_flow_yield", "lean_flow_cu", "lean_flow", "lean_ps", "lean_merge",
        "lean_one", "lean_poll", "lean_zc", "step_overlap", "ei_fused", "stage_copies", "cov_flat", "gemm_partial", "kstar_corun")
@@ -281,6 +401,29 @@ def test_invariants_over_the_lattice():
         if not (is_lean and p["nh"] <= 32):
             assert p["Np"] % 128 == 0, key
         assert p["Np"] - N < (64 if is_lean and p["nh"] <= 32 else 128), key
+
+
+@needs_cxx
+def test_acquisition_invariants_over_the_lattice():
+    cases, keys = [], []
+    for name, N, H, streams, flags in itertools.product(ph.ACQ_ROWS, (17, 128, 130, 300), (1, 3), (1, 2, 3), (0, KEEP_MOMENTS)):
+        for budget in (1 << 20, 512 << 20):
+            cases.append(ph.acq_case(name, N=N, H=H, streams=streams, flags=flags, kstar_budget_bytes=budget, ring_budget=6 << 20))
+            keys.append((name, N, H, streams, flags, budget))
+    F, T, C = ph.FINISH, ph.TAIL, ph.CLOSING
+    for key, p in zip(keys, ph.plans(cases)):
+        assert (p["tail"] == T["kgf_value"]) == (p["finish"] == F["kgf_lines8"]), key
+        assert (p["tail"] == T["kgw_value"]) == (p["finish"] == F["kgf_lines16"]), key
+        assert (p["tail"] == T["mes_fant"]) == (p["finish"] == F["mes_fant_means"]), key
+        assert (p["closing"] == C["ts_argmin"]) == (p["rhs"] == ph.RHS["ts"]) == (p["finish"] == F["ts"]), key
+        assert (p["scratch_bytes"] > 0) == (p["rhs_S"] > 0) == (p["bgS_bytes"] > 0), key
+        assert not (p["fused"] and p["rhs_S"] > 0) and (p["finish"] == F["fused"]) == bool(p["fused"]), key
+        assert (p["rhs"] == ph.RHS["kg"]) == (p["kg_As_bytes"] > 0) == (p["kgA"] > 0) == (p["finish"] in (F["kg_pairs"], F["kg_scan"], F["kgf_lines8"], F["kgf_lines16"])), key
+        if p["rhs"] == ph.RHS["kg"]:
+            assert p["rhs_S"] == p["kgS"] + p["kgA"], key
+        if p["tail"] in (T["mes"], T["ehvi"]):
+            assert p["keep_mom"] and p["rhs_S"] == 0, key
+        assert p["pass_acq"] in (ph.ACQ["EI"], ph.ACQ["PI"], ph.ACQ["LCB"]), key
 
 
 # ---- the option table, through the library ---------------------------------------------------------------------------------
